@@ -15,7 +15,7 @@ keys marked `_orc` and every *reference* operator downstream consumes them, so t
 divergence after `correc` (reference `chkdiv`) certifies them independently.
 
 Usage:  python tests/golden/gen_golden.py            # all cases (one subprocess per case)
-        python tests/golden/gen_golden.py --case NAME
+        python tests/golden/gen_golden.py --case NAME      # NAME: a case of CASES, grids, outstats or initflow
 """
 import argparse
 import json
@@ -350,6 +350,37 @@ ref.finalize()
     np.savez_compressed(out, **G)
 
 
+# initial fields of the pressure-driven kinds no golden case starts from (tests/test_host_side.py): the half-channel case with inivel and
+# is_wallturb replaced and no forcing, run through the reference's own initflow (one case per process: it reads input.nml from the working directory)
+INIFLOW = [("hdc", "F"), ("hdc", "T"), ("pdc", "T"), ("hcp", "F")]
+
+
+def initflow_nml(base, inivel, wallturb):
+    text = re.sub(r"inivel = .*", f"inivel = '{inivel}'", base)
+    text = re.sub(r"is_wallturb = .*", f"is_wallturb = {wallturb}", text)
+    text = re.sub(r"bforce\(1:3\) = .*", "bforce(1:3) = 0.7, 0., 0.", text)
+    return re.sub(r"is_forced\(1:3\) = .*", "is_forced(1:3) = F, F, F", text)
+
+
+def run_initflow(out):
+    base = str(np.load(os.path.join(HERE, "halfchan_imp1d.npz"))["input_nml"])
+    G = {}
+    for inivel, wallturb in INIFLOW:
+        tmp = tempfile.mkdtemp(prefix="inif_")
+        text = initflow_nml(base, inivel, wallturb)
+        open(os.path.join(tmp, "input.nml"), "w").write(text)
+        code = (f"import sys, numpy as np; sys.path.insert(0, {ROOT!r}); from oracle.ref.refpy import Ref; "
+                "u, v, w, p = Ref(0).initflow(); np.savez('out.npz', u=u, v=v, w=w, p=p)")
+        subprocess.check_call([sys.executable, "-c", code], cwd=tmp)
+        r = np.load(os.path.join(tmp, "out.npz"))
+        key = f"{inivel}_{wallturb}"
+        G[key + "_input_nml"] = np.array(text)
+        for k in "uvwp":
+            G[key + "_" + k] = r[k]
+        print("initflow:", key, "ok")
+    np.savez_compressed(out, **G)
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--case", default=None)
@@ -358,6 +389,8 @@ if __name__ == "__main__":
         run_grids(os.path.join(HERE, "grids.npz"))
     elif a.case == "outstats":
         run_outstats(os.path.join(HERE, "outstats.npz"))
+    elif a.case == "initflow":
+        run_initflow(os.path.join(HERE, "initflow.npz"))
     elif a.case:
         run_case(a.case, os.path.join(HERE, a.case + ".npz"))
     else:
@@ -365,6 +398,7 @@ if __name__ == "__main__":
             subprocess.check_call([sys.executable, os.path.abspath(__file__), "--case", name])
         subprocess.check_call([sys.executable, os.path.abspath(__file__), "--case", "grids"])
         subprocess.check_call([sys.executable, os.path.abspath(__file__), "--case", "outstats"])
+        subprocess.check_call([sys.executable, os.path.abspath(__file__), "--case", "initflow"])
     # the manifest follows whatever was (re)generated: case list, grid list and a digest of every vector file
     import hashlib
     json.dump({"cases": list(CASES), "grids": GRIDS,

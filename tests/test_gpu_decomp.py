@@ -313,7 +313,7 @@ def test_bench_two_processes_one_gpu():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr", "127.0.0.1",
                         "--master-port", "29611", os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "10", "--warmup", "2",
-                        "--ng", "64", "64", "32", "--backend", "gloo", "--no-cpu"], capture_output=True, text=True, timeout=900, cwd=root)
+                        "--ng", "64", "64", "32", "--backend", "gloo", "--full", "--no-cpu"], capture_output=True, text=True, timeout=900, cwd=root)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]                      # rank 0 prints ONE line
@@ -332,7 +332,7 @@ def test_bench_eight_processes_one_gpu_bare_form():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "8", "--steps", "4", "--warmup", "1", "--ng", "64", "64", "32",
-                        "--backend", "gloo", "--no-cpu"], capture_output=True, text=True, timeout=1500, cwd=root, env=env)
+                        "--backend", "gloo", "--full", "--no-cpu"], capture_output=True, text=True, timeout=1500, cwd=root, env=env)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]
@@ -390,7 +390,7 @@ def test_bench_reports_both_exchange_orders():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "CALES_OVERLAP")}
     n = torch.cuda.device_count()
     backend = ["--backend", "gloo"] if n < 2 else []
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "1", "--ng", "64", "64", "32", "--no-cpu"] + backend,
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "1", "--ng", "64", "64", "32", "--full", "--no-cpu"] + backend,
                        capture_output=True, text=True, timeout=900, cwd=root, env=env)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
@@ -412,7 +412,7 @@ def test_bench_second_order_cannot_cost_the_first():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "CALES_OVERLAP")}
     env["CALES_BENCH_TEST_BOTH"] = "1"
-    args = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "1", "--ng", "64", "64", "32", "--backend", "gloo", "--no-cpu"]
+    args = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "1", "--ng", "64", "64", "32", "--backend", "gloo", "--full", "--no-cpu"]
     r = subprocess.run(args, capture_output=True, text=True, timeout=900, cwd=root, env=env)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])

@@ -245,7 +245,7 @@ def test_manifest_lists_every_golden_file():
     man = json.load(open(os.path.join(here, "manifest.json")))
     files = sorted(f for f in os.listdir(here) if f.endswith(".npz"))
     assert sorted(man["files"]) == files
-    assert set(c + ".npz" for c in man["cases"]) | {"grids.npz", "outstats.npz"} == set(files)
+    assert set(c + ".npz" for c in man["cases"]) | {"grids.npz", "outstats.npz", "initflow.npz"} == set(files)
     for f in files:
         assert hashlib.sha256(open(os.path.join(here, f), "rb").read()).hexdigest()[:16] == man["files"][f], f
 

@@ -1,7 +1,7 @@
 #!/bin/bash
 # kernel stats + two SQ counter passes of a short bench run:  bash tools/sq_bench.sh TAG [bench args]   (results in gpurun_out/TAG_*)
 TAG=$1; shift
-ARGS=${@:-"--steps 3 --warmup 1 --no-cpu --configs none"}
+ARGS="--full ${*:---steps 3 --warmup 1 --no-cpu --configs none}"
 export TMPDIR=/tmp
 O=$PWD/gpurun_out
 rocprofv3 --output-format csv --kernel-trace --stats -d $O/${TAG}_stats -- python3 bench.py $ARGS > $O/${TAG}_bench_under_rocprof.json 2> $O/${TAG}_stats.log
