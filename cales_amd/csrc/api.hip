@@ -174,7 +174,7 @@ int cales_create(const cales_case *cs, void *stream, cales_ctx **out) {
   DBound *bs[11] = {&c->bcu, &c->bcv, &c->bcw, &c->bcp, &c->bcs, &c->bcuf, &c->bcvf, &c->bcwf, &c->bcu_mag, &c->bcv_mag, &c->bcw_mag};
   for (auto *b : bs) b->x = b->y = b->z = nullptr;
   for (int d = 0; d < 3; ++d) { c->rhsbp[d] = nullptr; c->d_av[d] = c->d_bv[d] = c->d_cv[d] = nullptr; }
-  c->rhsbz_vel = c->d_lamx = c->d_lamy = c->d_a = c->d_b = c->d_c = c->d_twx = c->d_twy = c->d_twx_post = c->d_twy_post = nullptr;
+  c->rhsbz_vel = c->d_a = c->d_b = c->d_c = nullptr;
   c->scr1 = c->scr2 = c->d_red = c->h_red = c->d_force = nullptr;
   c->s0 = c->uc = c->vc = c->wc = c->uf = c->vf = c->wf = c->alph2 = c->d_p1d = nullptr;
   for (int m = 0; m < 6; ++m) c->wk[m] = c->sij[m] = c->mij[m] = nullptr;
@@ -475,7 +475,7 @@ static void make_plan(cales_ctx *c) {
   // periodic x, explicit diffusion, no wall model, the fused passes everywhere: every kernel of the step wraps around instead of reading x ghost
   // columns, which are then left alone until the step returns (common.hpp, step_xskip)
   pl.xskip = !fl.xghosts_in_step && CBP(c, 0, 1) == 'P' && CBP(c, 1, 1) == 'P' && c->C.impdiff == 0 && !fl.unfused_rk && !fl.unfused_correc &&
-             pl.fuse_fill && c->xkind == 0 && sgs_wraps_x(c) && !pl.any_wm;
+             pl.fuse_fill && sgs_wraps_x(c) && !pl.any_wm;
   // dynamic model, x and y periodic (|S|Sij as pair fields), z periodic or two no-slip walls, explicit diffusion, no wall model: the projection
   // u = u* - dtrk grad(pp) (+ the deferred forcing) and p += pp are folded into the strain-rate pass of cmpt_sgs, which reads the velocity anyway --
   // the correction pass (9 words per cell) disappears (dsmag_fast, k_corr_strain_tile)
@@ -548,7 +548,7 @@ int cales_describe_plan(cales_ctx *c, char *buf, int buflen) {
   s += std::string(";momentum=") + (c->fl.unfused_rk ? "mom+rk_update" : "fused_mom_rk");
   s += std::string(";sgs=") + sgs_path_name(c);
   s += std::string(";solver=") + solver_path_name(c);
-  if (c->P > 1) s += ";mode_columns_per_rank=" + std::to_string(c->nyq_ok ? c->cw_nyq : c->cw);      // of the pressure solve (padded to whole 128-B lines where that costs 6 % or less: solver_setup)
+  if (c->P > 1) s += ";mode_columns_per_rank=" + std::to_string(solver_mode_columns(c));      // of the pressure solve (padded to whole 128-B lines where that costs 6 % or less: solver_setup)
   s += ";ranks=" + std::to_string(c->P) + ";exchanges=" + (c->P == 1 ? "none" : !c->comm.on ? "unset" : (c->comm_stream && (c->comm.halo_s || c->comm.a2a_part)) ? "second_stream" : "in_order");
   std::snprintf(buf, buflen, "%s", s.c_str());
   return (int)s.size() < buflen ? 0 : 2;      // 2: truncated

@@ -141,6 +141,7 @@ struct StepPlan {
 };
 
 struct KernelStat { std::string name; int64_t calls = 0; real ms = 0.; };
+struct Solver;      // k_solver.hip
 
 struct cales_ctx {
   cales_case C;
@@ -169,15 +170,9 @@ struct cales_ctx {
   real *rhsbp[3];        // (na,nb,0:1)
   real *rhsbz_vel;       // scratch (n1,n2,0:1) for z-implicit Helmholtz r.h.s.
   // solver
-  real *d_lamx, *d_lamy;     // eigenvalues per stored spectral index
+  Solver *solver = nullptr;  // k_solver.hip: plans, tables and the path of every solved field (solver_setup / solver_teardown)
   real *d_a, *d_b, *d_c;     // tridiagonal (n3)
   real *d_av[3], *d_bv[3], *d_cv[3];
-  real normfft;
-  int xkind, ykind;            // 0: periodic (r2c / c2c), 1: Neumann-Neumann cell-centred (DCT-II/III)
-  bool nyq_ok = false; int cw_nyq = 0;      // the pressure solve packs the modes 0 and n1/2 into one column (solver_setup: periodic x and y, walls in z, radix-8 transforms, the z tile); mode columns per rank then
-  real *d_twx, *d_twy;       // twiddle tables
-  real *d_twx_post, *d_twy_post;    // d_twy_post: DCT weights of the x direction
-  real *scr_twyd = nullptr;           // DCT weights of the y direction
   real *scr1, *scr2;         // solver scratch (haloed size)
   // reductions
   real *d_red; real *h_red;       // partial sums / results (pinned host)
@@ -198,15 +193,12 @@ struct cales_ctx {
   std::vector<KernelStat> stats;
   std::vector<std::pair<int, std::pair<hipEvent_t, hipEvent_t>>> pending;
   std::vector<std::pair<hipEvent_t, hipEvent_t>> evpool;
-  real *d_tw4x = nullptr;  // DCT-IV weights of the x transform (pressure ND / DN)
-  real *d_tw4y = nullptr, *d_twy4 = nullptr;      // the same for y, and the twiddles of its N/2-point lines
   real *d_del = nullptr;   // Smagorinsky filter width per plane (fast path)
   void *native_comm = nullptr;   // RCCL communicator + staging buffers when the library does the exchanges itself (comm_rccl.cpp)
   bool visct_zero = true;  // CALES_VISCT still holds the zeros it was created / reset with (no SGS model: lets kernels skip it)
   // dynamic model, fast path: the eddy-viscosity field holds |S| and d_cs(0:n3+1) the clipped plane coefficients <LM>/<MM> until somebody
   // other than the fused momentum kernel reads it (materialize_visct); visct = |S| * cs(k) is the same product either way
   bool visct_lazy = false; real *d_cs = nullptr;
-  void *cur_velset = nullptr;       // k_solver.hip: transform set of the velocity component being solved by op_helmholtz
   bool in_step = false;             // inside cales_step: the operator order is known, dead ghost work can be dropped
   bool skip_rhs_store = false;      // cales_step, third substep: see MomRkArgs::wr_new
   real *d_stat2 = nullptr;
@@ -348,6 +340,7 @@ int op_out1d(cales_ctx *c, int field, int idir, int use_dzc, real *buf);
 int op_out1d_chan(cales_ctx *c, real *buf);
 int op_out2d_duct(cales_ctx *c, real *buf);
 bool solver_can_fuse_fillps(cales_ctx *c);
+int solver_mode_columns(cales_ctx *c);      // complex mode columns per rank of the pressure solve
 std::string solver_path_name(cales_ctx *c);      // which transform / tridiagonal kernels the pressure solve of this context takes (cales_describe_plan)
 const char *sgs_path_name(const cales_ctx *c);      // likewise for cmpt_sgs
 int op_force_from_partials(cales_ctx *c, int mask, const real *part, int nblk);

@@ -12,8 +12,6 @@
 // Spectral layout differs from FFTW's half-complex order; eigenvalues are laid out to match, so the
 // solution p = solver(rhs) is the same discrete function (checked against the oracle).
 #include "common.hpp"
-#include <list>
-#include <mutex>
 
 // (aligned to its own size: LDS and global accesses of a complex value are ONE 128-bit operation -- ds_read_b128 at 256 B/clk instead of ds_read2_b64 at
 //  128, MI355X_MICROARCH.md "LDS"; every cpx array here starts on a 16-byte boundary: hipMalloc'ed tables, the __align__(16) dynamic LDS block)
@@ -1458,10 +1456,17 @@ __global__ __launch_bounds__(256) void k_gaussel_nyq(Geom g, int nz, int N, int 
   }
 }
 template <int M>
-static void launch_gaussel_nyq(cales_ctx *c, int nz, int N, int nh, real lscale, const real *da, const real *db, const real *dc, real2 *p, int fixnull, const Spec &S, const real *tab) {
+static void launch_gaussel_nyq(cales_ctx *c, bool herm, int nz, int N, int nh, real lscale, const real *da, const real *db, const real *dc, const real *lamx, const real *lamy, real2 *p, int fixnull, const Spec &S, const real *tab) {
   constexpr int lds = 4 * (64 * (M + 1) + GT_PAD) * 8;
-  if (c->ykind == 0) LAUNCH(c, (k_gaussel_nyq<M, 1>), dim3(N / 2 + 1), dim3(256), lds, c->stream, c->g, nz, N, nh, lscale, tab, c->d_lamx, c->d_lamy, p, fixnull, S, da, db, dc);
-  else LAUNCH(c, (k_gaussel_nyq<M, 0>), dim3(N / 2), dim3(256), lds, c->stream, c->g, nz, N, nh, lscale, tab, c->d_lamx, c->d_lamy, p, fixnull, S, da, db, dc);
+  if (herm) LAUNCH(c, (k_gaussel_nyq<M, 1>), dim3(N / 2 + 1), dim3(256), lds, c->stream, c->g, nz, N, nh, lscale, tab, lamx, lamy, p, fixnull, S, da, db, dc);
+  else LAUNCH(c, (k_gaussel_nyq<M, 0>), dim3(N / 2), dim3(256), lds, c->stream, c->g, nz, N, nh, lscale, tab, lamx, lamy, p, fixnull, S, da, db, dc);
+}
+// the packed column of the modes 0 and n1/2 (periodic y: Hermitian pairing of the rows); reads the coefficient table the tile of this nz built
+static void gaussel_nyq(cales_ctx *c, bool herm, int nz, int N, int nh, real lscale, const real *da, const real *db, const real *dc, const real *lamx, const real *lamy, real2 *p, int fixnull, const Spec &S) {
+  if (nz <= 128) launch_gaussel_nyq<2>(c, herm, nz, N, nh, lscale, da, db, dc, lamx, lamy, p, fixnull, S, c->d_abct);
+  else if (nz <= 256) launch_gaussel_nyq<4>(c, herm, nz, N, nh, lscale, da, db, dc, lamx, lamy, p, fixnull, S, c->d_abct);
+  else if (nz <= 512) launch_gaussel_nyq<8>(c, herm, nz, N, nh, lscale, da, db, dc, lamx, lamy, p, fixnull, S, c->d_abct);
+  else launch_gaussel_nyq<16>(c, herm, nz, N, nh, lscale, da, db, dc, lamx, lamy, p, fixnull, S, c->d_abct);
 }
 // The same tile PERSISTENT over `tpb` neighbouring tiles of a segment, for nz = 1024 planes in chunks of sixteen (the 1024^3 cavity): the
 // classic form holds one block of 1024 threads and 140 KB of LDS per CU, so the load of a tile, its solve and its store run one after the other (5.6 ms
@@ -1671,8 +1676,8 @@ __global__ __launch_bounds__(512, 2) void k_gaussel_tile_p(Geom g, int nz, int n
   for (int tile = tile0 + 1; tile < tend; ++tile) one_tile(tile);
 }
 template <int M, int NV, int PER = 0>
-static void launch_gaussel_tile(cales_ctx *c, int nz, int ndbl, int nrow, real lscale, const real *da, const real *db, const real *dc,
-                                real *p, int fixnull, const TileMap &T, real *tab_of_caller = nullptr, bool tab_ready = false) {
+static void launch_gaussel_tile(cales_ctx *c, int nz, int ndbl, int nrow, real lscale, const real *da, const real *db, const real *dc, const real *lamx,
+                               const real *lamy, real *p, int fixnull, const TileMap &T, real *tab_of_caller, bool tab_ready) {
   constexpr int W = gt_width(M, NV), lds = W * (64 * (M + 1) + GT_PAD) * 8 + (GT_TL && M == 16 ? 2 * 64 * M * 8 : 0);
   static bool once = false;
   if (!once) {
@@ -1689,15 +1694,15 @@ static void launch_gaussel_tile(cales_ctx *c, int nz, int ndbl, int nrow, real l
   if (tab_of_caller ? !tab_ready : (!pressure || !c->abct_ready)) LAUNCH(c, k_abc_chunked, dim3((64 * M + 255) / 256), dim3(256), 0, c->stream, PER ? nz - 1 : nz, M, da, db, dc, tab);
   if (pressure && !tab_of_caller) c->abct_ready = true;
   if constexpr (NV == 2 && PER == 0) {
-    if (T.dud) { LAUNCH(c, (k_gaussel_tile<M, NV, PER, 1>), dim3((ndbl + W - 1) / W, nrow), dim3(64 * W / NV), lds, c->stream, c->g, nz, ndbl, lscale, tab, c->d_lamx, c->d_lamy, p, fixnull, T, da, db, dc); return; }
+    if (T.dud) { LAUNCH(c, (k_gaussel_tile<M, NV, PER, 1>), dim3((ndbl + W - 1) / W, nrow), dim3(64 * W / NV), lds, c->stream, c->g, nz, ndbl, lscale, tab, lamx, lamy, p, fixnull, T, da, db, dc); return; }
   }
   if (T.dud) { launch_failed(c, "k_gaussel_tile: the Helmholtz form exists for pairs of real columns and non-periodic z only", hipErrorInvalidValue); return; }
   LAUNCH(c, (k_gaussel_tile<M, NV, PER>), dim3((ndbl + W - 1) / W, nrow), dim3(64 * W / NV), lds, c->stream, c->g, nz, ndbl, lscale, tab,
-                     c->d_lamx, c->d_lamy, p, fixnull, T, da, db, dc);
+                     lamx, lamy, p, fixnull, T, da, db, dc);
 }
 // the persistent form (k_gaussel_tile_p): pressure operands only (their table is built once), tiles per block so that ~2048 blocks or more remain
 template <int NV>
-static void launch_gaussel_tile_p(cales_ctx *c, int nz, int ndbl, int nrow, real lscale, const real *da, const real *db, const real *dc, real *p, int fixnull, const TileMap &T) {
+static void launch_gaussel_tile_p(cales_ctx *c, int nz, int ndbl, int nrow, real lscale, const real *da, const real *db, const real *dc, const real *lamx, const real *lamy, real *p, int fixnull, const TileMap &T) {
   constexpr int M = 16, W = gt_width(M, NV), lds = W * (64 * (M + 1) + GT_PAD) * 8 + (GT_TL ? 2 * 64 * M * 8 : 0);
   static bool once = false;
   if (!once) { HIPSOFT(c, hipFuncSetAttribute((const void *)k_gaussel_tile_p<NV>, hipFuncAttributeMaxDynamicSharedMemorySize, lds)); once = true; }
@@ -1708,19 +1713,19 @@ static void launch_gaussel_tile_p(cales_ctx *c, int nz, int ndbl, int nrow, real
   if (pressure) c->abct_ready = true;
   const int ntile = ndbl / W;
   int tpb = 1; while (tpb * 2 <= ntile && tpb < 32 && (long)nrow * ((ntile + 2 * tpb - 1) / (2 * tpb)) >= 2048) tpb *= 2;
-  LAUNCH(c, (k_gaussel_tile_p<NV>), dim3((ntile + tpb - 1) / tpb, nrow), dim3(512), lds, c->stream, c->g, nz, ndbl, lscale, tab, c->d_lamx, c->d_lamy, p, fixnull, T, tpb, da, db, dc);
+  LAUNCH(c, (k_gaussel_tile_p<NV>), dim3((ntile + tpb - 1) / tpb, nrow), dim3(512), lds, c->stream, c->g, nz, ndbl, lscale, tab, lamx, lamy, p, fixnull, T, tpb, da, db, dc);
 }
+// whether the LDS tile solves nz planes (periodic: the cyclic closure inside the tile); the callers decide with it before they call gaussel_tile
+static bool tile_takes(const cales_ctx *c, int nz, bool periodic) { return nz >= (periodic ? 4 : 2) && nz <= 1024 && !c->fl.gaussel_march; }
 // one rank: ndbl doubles of each of the nrow rows; several ranks (T.blocked): nrow = peers, ndbl = 2 cw n2l doubles per plane of a peer block
 template <int NV, int PER = 0>
-static bool gaussel_tile(cales_ctx *c, int nz, int ndbl, int nrow, real lscale, const real *da, const real *db, const real *dc,
+static void gaussel_tile(cales_ctx *c, int nz, int ndbl, int nrow, real lscale, const real *da, const real *db, const real *dc, const real *lamx, const real *lamy,
                          real *p, int fixnull, const TileMap &T, real *tab = nullptr, bool tab_ready = false) {
-  if (nz < (PER ? 4 : 2) || nz > 1024 || c->fl.gaussel_march) return false;
-  if (nz <= 128) launch_gaussel_tile<2, NV, PER>(c, nz, ndbl, nrow, lscale, da, db, dc, p, fixnull, T, tab, tab_ready);
-  else if (nz <= 256) launch_gaussel_tile<4, NV, PER>(c, nz, ndbl, nrow, lscale, da, db, dc, p, fixnull, T, tab, tab_ready);
-  else if (nz <= 512) launch_gaussel_tile<8, NV, PER>(c, nz, ndbl, nrow, lscale, da, db, dc, p, fixnull, T, tab, tab_ready);
-  else if (!PER && NV == 1 && nz == 1024 && ndbl % 16 == 0 && !T.dud && !T.nolam && !tab) launch_gaussel_tile_p<1>(c, nz, ndbl, nrow, lscale, da, db, dc, p, fixnull, T);
-  else launch_gaussel_tile<16, NV, PER>(c, nz, ndbl, nrow, lscale, da, db, dc, p, fixnull, T, tab, tab_ready);
-  return true;
+  if (nz <= 128) launch_gaussel_tile<2, NV, PER>(c, nz, ndbl, nrow, lscale, da, db, dc, lamx, lamy, p, fixnull, T, tab, tab_ready);
+  else if (nz <= 256) launch_gaussel_tile<4, NV, PER>(c, nz, ndbl, nrow, lscale, da, db, dc, lamx, lamy, p, fixnull, T, tab, tab_ready);
+  else if (nz <= 512) launch_gaussel_tile<8, NV, PER>(c, nz, ndbl, nrow, lscale, da, db, dc, lamx, lamy, p, fixnull, T, tab, tab_ready);
+  else if (!PER && NV == 1 && nz == 1024 && ndbl % 16 == 0 && !T.dud && !T.nolam && !tab) launch_gaussel_tile_p<1>(c, nz, ndbl, nrow, lscale, da, db, dc, lamx, lamy, p, fixnull, T);
+  else launch_gaussel_tile<16, NV, PER>(c, nz, ndbl, nrow, lscale, da, db, dc, lamx, lamy, p, fixnull, T, tab, tab_ready);
 }
 
 // Non-periodic x (real modes r = 2m, 2m+1 paired into one complex column) with PERIODIC y: the y transform of the pair gives
@@ -1826,87 +1831,144 @@ __global__ __launch_bounds__(256) void k_gaussel(Geom g, int nz, int ncol, int n
 }
 
 // ------------------------------------------------------------------------------------------ host side
-struct SolverPlans { FftPlan py4; int CBy4; size_t shy4; FftPlan px, py; int Rx, CBy; size_t shx, shy; bool x8, y8, y16 = false; int x8_threads, y8_threads; size_t shx8, shy8, shy8r, shy16 = 0; };
-struct VelSet { bool ready = false; int xkind = 0, ykind = 0; real *lamx = nullptr, *lamy = nullptr; real normfft = 1.; FftPlan p1x, p1y; real *tw1x = nullptr, *tw1y = nullptr; };
-struct PlanSlot { cales_ctx *ctx; SolverPlans sp; VelSet vs[3]; };
-// one entry per context; a list (stable addresses) behind a mutex: contexts are created and destroyed from several host threads in the
-// loopback tests while others hold pointers to their own entry
-static std::list<PlanSlot> g_slots;
-static std::mutex g_slots_mx;
-static PlanSlot *find_slot(cales_ctx *c) { std::lock_guard<std::mutex> lk(g_slots_mx); for (auto &s : g_slots) if (s.ctx == c) return &s; return nullptr; }
-static SolverPlans *find_plans(cales_ctx *c) { PlanSlot *s = find_slot(c); return s ? &s->sp : nullptr; }
+// The path of one solved field: its transform kinds, the kernel of each direction, its eigenvalues and normalisation -- decided once (the pressure's
+// by solver_setup, a velocity component's of the 3-D implicit step by velocity_path on its first solve) and then only read: solve_field launches
+// it, solver_path_name prints it (cales_describe_plan).
+enum class XKernel { fft_x8, fft_x4, dst1, fft_x };                             // radix-8 | DCT-IV | face-centred | mixed radix
+enum class YKernel { fft_y16, fft_y8, fft_y8r, fft_y4, dst1, fft_y };          // radix-8 (16 | 8 per thread | register ends) | DCT-IV | face-centred | mixed radix
+enum class ZKernel { herm, tile, ri, periodic_real, periodic_cpx };            // k_gaussel_herm | gaussel_tile | k_gaussel_ri | k_gaussel<real, 1> | k_gaussel<real2, 1>
+static bool radix8_y(YKernel k) { return k == YKernel::fft_y16 || k == YKernel::fft_y8 || k == YKernel::fft_y8r; }
+struct SolvePath {
+  int xkind = 0, ykind = 0;      // 0 PP, 1 NN, 2 DD, 3 ND, 4 DN (cell-centred); 5..7 the face-centred kinds of a velocity component (velocity_path)
+  XKernel xk = XKernel::fft_x; YKernel yk = YKernel::fft_y; ZKernel zk = ZKernel::ri;
+  int nz = 0; bool periodic_z = false, poisson = false;
+  int fixnull = 0;               // pressure without a Dirichlet condition in z: the zero-eigenvalue mode (if x and y have one) is singular
+  bool refnull = false;          // CALES_KEEP_NULL_MODE: that column in the reference's sequential order (k_null_column)
+  bool nyq = false;              // the modes 0 and n1/2 share mode column 0 (Spec::nyq): k_gaussel_nyq solves it after the tile
+  int cw = 0;                    // complex mode columns per rank
+  int xrows = 1, ycols = 1;      // rows per block of k_fft_x8, columns per block of the radix-8 y kernels
+  real *lamx = nullptr, *lamy = nullptr; real normfft = 1.;      // eigenvalues per stored spectral index; scale of the inverse transforms
+  FftPlan p1x, p1y; real *tw1x = nullptr, *tw1y = nullptr;      // k_dst1 (face-centred kinds)
+};
+// the solver state a context owns (cales_ctx::solver): line plans and launch geometry of the transforms, their tables, the paths
+struct Solver {
+  FftPlan px, py, py4; int Rx, CBy, CBy4 = 0; size_t shx, shy, shy4 = 0;
+  bool x8, y8, y16 = false; int x8_threads, y8_threads; size_t shx8, shy8, shy8r, shy16 = 0;
+  real *twx = nullptr, *twx_post = nullptr, *twy = nullptr, *twy_post = nullptr, *twyd = nullptr;      // twiddle tables; twy_post, twyd: DCT weights of x, of y
+  real *tw4x = nullptr, *tw4y = nullptr, *twy4 = nullptr;         // DCT-IV weights of x and y, twiddles of the N/2-point y lines
+  SolvePath pres, vel[3]; bool vel_ready[3] = {false, false, false};
+};
 
-bool solver_can_fuse_fillps(cales_ctx *c) { SolverPlans *sp = find_plans(c); return sp && sp->x8; }
+bool solver_can_fuse_fillps(cales_ctx *c) { return c->solver && c->solver->x8; }
+int solver_mode_columns(cales_ctx *c) { return c->solver ? c->solver->pres.cw : c->cw; }
+
+// twiddles exp(-2 pi i q/N), q < cnt
+static int upload_twiddles(cales_ctx *c, int N, int cnt, real **dev) {
+  std::vector<real> t(2 * (size_t)cnt);
+  const real pi = std::acos(-1.0);
+  for (int q = 0; q < cnt; ++q) { const real ang = -2. * pi * q / N; t[2 * q] = std::cos(ang); t[2 * q + 1] = std::sin(ang); }
+  HIPCHK(c, hipMalloc(dev, t.size() * sizeof(real)));
+  HIPCHK(c, hipMemcpy(*dev, t.data(), t.size() * sizeof(real), hipMemcpyHostToDevice));
+  return 0;
+}
+// DCT-IV weights of n-point lines (k_fft_x4, k_fft_y4): e^{-i pi (4q+1)/(4n)}, then e^{-i pi q/n}, q < n/2
+static int upload_dct4_weights(cales_ctx *c, int n, real **dev) {
+  const int nh = n / 2; std::vector<real> t(4 * (size_t)nh); const real pi = std::acos(-1.0);
+  for (int q = 0; q < nh; ++q) { const real a1 = -pi * (4. * q + 1.) / (4. * n), a2 = -pi * q / (real)n;
+                                 t[2 * q] = std::cos(a1); t[2 * q + 1] = std::sin(a1); t[2 * (nh + q)] = std::cos(a2); t[2 * (nh + q) + 1] = std::sin(a2); }
+  HIPCHK(c, hipMalloc(dev, t.size() * sizeof(real)));
+  HIPCHK(c, hipMemcpy(*dev, t.data(), t.size() * sizeof(real), hipMemcpyHostToDevice));
+  return 0;
+}
+// DCT-IV / DST-IV in y (k_fft_y4): N/2-point lines, two per complex column -- plans and tables made by the first path that needs them
+static int dct4_y_setup(cales_ctx *c, Solver &s, const char *who) {
+  const int n2g = c->C.ng[1];
+  if (s.tw4y) return 0;
+  if (!make_plan(n2g / 2, s.py4)) { c->err = std::string(who) + ": ng(2)/2 must factor into primes <= 127"; return 1; }
+  s.CBy4 = 4; s.shy4 = (size_t)2 * s.CBy4 * 2 * (n2g / 2 + 1) * sizeof(cpx);
+  while (s.shy4 > 60 * 1024 && s.CBy4 > 1) { s.CBy4 /= 2; s.shy4 = (size_t)2 * s.CBy4 * 2 * (n2g / 2 + 1) * sizeof(cpx); }
+  if (s.shy4 > 64 * 1024) { c->err = std::string(who) + ": y line too long for the LDS-resident DCT-IV"; return 1; }
+  if (upload_dct4_weights(c, n2g, &s.tw4y)) return 1;
+  return s.twy4 ? 0 : upload_twiddles(c, n2g / 2, n2g / 2, &s.twy4);
+}
+
+// the kernels of a path whose kinds, nz, z condition and equation are set
+static void choose_kernels(cales_ctx *c, const Solver &s, SolvePath &P) {
+  const int nh = c->C.ng[0] / 2, n2g = c->C.ng[1];
+  // the radix-8 kernels know the periodic and the Neumann-Neumann transform; a velocity component of the 3-D implicit step may need others
+  const bool use8x = s.x8 && P.xkind <= 1, use8y = s.y8 && P.ykind <= 1;
+  P.xk = use8x ? XKernel::fft_x8 : P.xkind >= 5 ? XKernel::dst1 : P.xkind >= 3 ? XKernel::fft_x4 : XKernel::fft_x;
+  P.yk = P.ykind >= 5 ? YKernel::dst1 : P.ykind >= 3 ? YKernel::fft_y4 : !use8y ? YKernel::fft_y : s.y16 ? YKernel::fft_y16 : P.ykind ? YKernel::fft_y8 : YKernel::fft_y8r;
+  P.xrows = use8x ? s.x8_threads / (nh / 8) : 1;
+  P.ycols = P.yk == YKernel::fft_y16 ? 8 : use8y ? s.y8_threads / (n2g / 8) : 1;
+  const bool hasd = CBP(c, 0, 3) == 'D' || CBP(c, 1, 3) == 'D';
+  P.fixnull = (P.poisson && !hasd && !c->fl.keep_null_mode) ? 1 : 0;
+  P.refnull = P.poisson && !hasd && c->fl.keep_null_mode;
+  if (P.xkind && !P.ykind) P.zk = ZKernel::herm;      // real x modes paired into complex columns + periodic y: Hermitian separation of rows ky and N-ky
+  else if ((P.periodic_z || P.fixnull || !P.poisson || hasd) && tile_takes(c, P.nz, P.periodic_z)) P.zk = ZKernel::tile;
+  else if (P.xkind) P.zk = P.periodic_z ? ZKernel::periodic_real : ZKernel::ri;
+  else P.zk = P.periodic_z ? ZKernel::periodic_cpx : ZKernel::ri;
+}
 
 int solver_setup(cales_ctx *c) {
+  Solver &s = *(c->solver = new Solver());
+  SolvePath &P = s.pres;
   const int *n = c->n; const int n1 = c->C.ng[0], n2g = c->C.ng[1], n3 = n[2];
   const std::string bx = std::string(1, c->C.cbcpre[0]) + c->C.cbcpre[1], by = std::string(1, c->C.cbcpre[2]) + c->C.cbcpre[3];
   // transform kinds of the cell-centred pressure (fft.f90:192-245): 0 PP (R2HC/HC2R), 1 NN (REDFT10/01), 2 DD (RODFT10/01), 3 ND (REDFT11), 4 DN (RODFT11)
   auto kind_of = [](const std::string &b) { return b == "PP" ? 0 : b == "NN" ? 1 : b == "DD" ? 2 : b == "ND" ? 3 : b == "DN" ? 4 : -1; };
-  c->xkind = kind_of(bx); c->ykind = kind_of(by);
-  if (c->xkind < 0 || c->ykind < 0) { c->err = "solver: unknown pressure BC pair in x or y"; return 1; }
-  if (c->ykind >= 3 && (n2g % 2)) { c->err = "solver: ND/DN in y need an even ng(2)"; return 1; }
-  if (c->xkind && c->C.cbcpre[4] == 'P' && (!c->ykind || c->P > 1)) { c->err = "solver: a non-periodic x with periodic z needs a non-periodic y and one rank"; return 1; }
-  SolverPlans sp;
-  if (!make_plan(n1 / 2, sp.px) || !make_plan(n2g, sp.py)) { c->err = "solver: ng(1)/2 and ng(2) must factor into primes <= 127"; return 1; }
+  P.xkind = kind_of(bx); P.ykind = kind_of(by);
+  if (P.xkind < 0 || P.ykind < 0) { c->err = "solver: unknown pressure BC pair in x or y"; return 1; }
+  if (P.ykind >= 3 && (n2g % 2)) { c->err = "solver: ND/DN in y need an even ng(2)"; return 1; }
+  if (P.xkind && c->C.cbcpre[4] == 'P' && (!P.ykind || c->P > 1)) { c->err = "solver: a non-periodic x with periodic z needs a non-periodic y and one rank"; return 1; }
+  if (!make_plan(n1 / 2, s.px) || !make_plan(n2g, s.py)) { c->err = "solver: ng(1)/2 and ng(2) must factor into primes <= 127"; return 1; }
   // rows per block in x: aim at ~nh/4 threads per row, 256 threads per block
-  { int T = std::max(1, std::min(256, (n1 / 2) / 4)); int p2 = 1; while (p2 * 2 <= T) p2 *= 2; T = p2; sp.Rx = 256 / T; }
-  sp.shx = (size_t)sp.Rx * 2 * (n1 / 2 + 1) * sizeof(cpx);
-  while (sp.shx > 60 * 1024 && sp.Rx > 1) { sp.Rx /= 2; sp.shx = (size_t)sp.Rx * 2 * (n1 / 2 + 1) * sizeof(cpx); }
-  sp.CBy = 8;
-  sp.shy = (size_t)sp.CBy * 2 * (n2g + 1) * sizeof(cpx);
-  while (sp.shy > 60 * 1024 && sp.CBy > 1) { sp.CBy /= 2; sp.shy = (size_t)sp.CBy * 2 * (n2g + 1) * sizeof(cpx); }
-  if (sp.shx > 64 * 1024 || sp.shy > 64 * 1024) { c->err = "solver: line too long for the LDS-resident transform"; return 1; }
+  { int T = std::max(1, std::min(256, (n1 / 2) / 4)); int p2 = 1; while (p2 * 2 <= T) p2 *= 2; T = p2; s.Rx = 256 / T; }
+  s.shx = (size_t)s.Rx * 2 * (n1 / 2 + 1) * sizeof(cpx);
+  while (s.shx > 60 * 1024 && s.Rx > 1) { s.Rx /= 2; s.shx = (size_t)s.Rx * 2 * (n1 / 2 + 1) * sizeof(cpx); }
+  s.CBy = 8;
+  s.shy = (size_t)s.CBy * 2 * (n2g + 1) * sizeof(cpx);
+  while (s.shy > 60 * 1024 && s.CBy > 1) { s.CBy /= 2; s.shy = (size_t)s.CBy * 2 * (n2g + 1) * sizeof(cpx); }
+  if (s.shx > 64 * 1024 || s.shy > 64 * 1024) { c->err = "solver: line too long for the LDS-resident transform"; return 1; }
   // power-of-two lines take the radix-8 register kernels
   auto pow2 = [](int v) { return v >= 16 && (v & (v - 1)) == 0; };
-  sp.x8 = pow2(n1 / 2) && n1 / 2 <= 1024 && c->xkind <= 1; sp.y8 = pow2(n2g) && n2g <= 1024;
-  if (sp.x8) { const int T = (n1 / 2) / 8; sp.x8_threads = T >= 256 ? T : (256 / T) * T;
-               sp.shx8 = ((size_t)(sp.x8_threads / T) * (n1 / 2 + n1 / 16 + 2) + (n1 + 1) + (c->xkind ? n1 / 2 + 1 : 0)) * sizeof(cpx); }
-  if (sp.y8) { const int T = n2g / 8; int CB = std::max(1, std::min(std::max(8, 256 / T), 512 / T));
-               while (CB > 1 && ((size_t)CB * (n2g + n2g / 8 + 1) + n2g) * sizeof(cpx) > 150 * 1024) CB /= 2;
-               sp.y8_threads = CB * T; sp.shy8 = ((size_t)CB * (n2g + n2g / 8 + 1) + n2g) * sizeof(cpx);
-               sp.shy8r = ((size_t)CB * ((((n2g + n2g / 8) + 15) & ~15) + 4) + n2g) * sizeof(cpx);      // k_fft_y8r: line pitch = 4 (mod 16) slots
-               if (sp.shy8r > 64 * 1024) { HIPSOFT(c, hipFuncSetAttribute((const void *)k_fft_y8r<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sp.shy8r));
-                                           HIPSOFT(c, hipFuncSetAttribute((const void *)k_fft_y8r<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sp.shy8r)); }
-               if (sp.shy8 > 64 * 1024) {      // n2 = 1024: 4 columns (64-B row segments) need 90 KB of LDS
-                 HIPSOFT(c, hipFuncSetAttribute((const void *)k_fft_y8<0, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sp.shy8));
-                 HIPSOFT(c, hipFuncSetAttribute((const void *)k_fft_y8<1, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sp.shy8)); } }
+  s.x8 = pow2(n1 / 2) && n1 / 2 <= 1024 && P.xkind <= 1; s.y8 = pow2(n2g) && n2g <= 1024;
+  if (s.x8) { const int T = (n1 / 2) / 8; s.x8_threads = T >= 256 ? T : (256 / T) * T;
+              s.shx8 = ((size_t)(s.x8_threads / T) * (n1 / 2 + n1 / 16 + 2) + (n1 + 1) + (P.xkind ? n1 / 2 + 1 : 0)) * sizeof(cpx); }
+  if (s.y8) { const int T = n2g / 8; int CB = std::max(1, std::min(std::max(8, 256 / T), 512 / T));
+              while (CB > 1 && ((size_t)CB * (n2g + n2g / 8 + 1) + n2g) * sizeof(cpx) > 150 * 1024) CB /= 2;
+              s.y8_threads = CB * T; s.shy8 = ((size_t)CB * (n2g + n2g / 8 + 1) + n2g) * sizeof(cpx);
+              s.shy8r = ((size_t)CB * ((((n2g + n2g / 8) + 15) & ~15) + 4) + n2g) * sizeof(cpx);      // k_fft_y8r: line pitch = 4 (mod 16) slots
+              if (s.shy8r > 64 * 1024) { HIPSOFT(c, hipFuncSetAttribute((const void *)k_fft_y8r<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)s.shy8r));
+                                         HIPSOFT(c, hipFuncSetAttribute((const void *)k_fft_y8r<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)s.shy8r)); }
+              if (s.shy8 > 64 * 1024) {      // n2 = 1024: 4 columns (64-B row segments) need 90 KB of LDS
+                HIPSOFT(c, hipFuncSetAttribute((const void *)k_fft_y8<0, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)s.shy8));
+                HIPSOFT(c, hipFuncSetAttribute((const void *)k_fft_y8<1, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)s.shy8)); } }
   // eight columns per block, sixteen elements per thread (k_fft_y16): 1024-point lines of either kind, 256- and 512-point Neumann lines (where the
   // alternative is the staged k_fft_y8: 512 x 256 x 256 duct 0.39 / 0.42 -> 0.30 / 0.31 ms per step). Periodic 512-point lines stay with k_fft_y8r:
   // measured 1.49 / 1.55 against 1.45 / 1.52 ms per step at 512^3 -- both sit at the copy rate of that access pattern (128-B segments at a pitch of 4224 B)
-  sp.y16 = sp.y8 && c->ykind <= 1 && (n2g == 1024 || (c->ykind == 1 && (n2g == 512 || n2g == 256)));
-  if (sp.y16) {
-    sp.shy16 = ((size_t)n2g + 8 * ((size_t)n2g + 1)) * sizeof(cpx) + (size_t)n2g * sizeof(unsigned);
-    if (sp.shy16 > 64 * 1024) {
-#define Y16_ATTR(NN) do { HIPSOFT(c, hipFuncSetAttribute((const void *)k_fft_y16<NN, 0, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sp.shy16)); \
-                          HIPSOFT(c, hipFuncSetAttribute((const void *)k_fft_y16<NN, 1, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sp.shy16)); \
-                          HIPSOFT(c, hipFuncSetAttribute((const void *)k_fft_y16<NN, 0, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sp.shy16)); \
-                          HIPSOFT(c, hipFuncSetAttribute((const void *)k_fft_y16<NN, 1, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sp.shy16)); } while (0)
+  s.y16 = s.y8 && P.ykind <= 1 && (n2g == 1024 || (P.ykind == 1 && (n2g == 512 || n2g == 256)));
+  if (s.y16) {
+    s.shy16 = ((size_t)n2g + 8 * ((size_t)n2g + 1)) * sizeof(cpx) + (size_t)n2g * sizeof(unsigned);
+    if (s.shy16 > 64 * 1024) {
+#define Y16_ATTR(NN) do { HIPSOFT(c, hipFuncSetAttribute((const void *)k_fft_y16<NN, 0, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)s.shy16)); \
+                          HIPSOFT(c, hipFuncSetAttribute((const void *)k_fft_y16<NN, 1, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)s.shy16)); \
+                          HIPSOFT(c, hipFuncSetAttribute((const void *)k_fft_y16<NN, 0, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)s.shy16)); \
+                          HIPSOFT(c, hipFuncSetAttribute((const void *)k_fft_y16<NN, 1, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)s.shy16)); } while (0)
       if (n2g == 1024) Y16_ATTR(1024); else Y16_ATTR(512);
 #undef Y16_ATTR
     }
   }
-  if (c->ykind >= 3) {      // DCT-IV / DST-IV in y: N/2-point lines, two per complex column
-    if (!make_plan(n2g / 2, sp.py4)) { c->err = "solver: ng(2)/2 must factor into primes <= 127"; return 1; }
-    sp.CBy4 = 4; sp.shy4 = (size_t)2 * sp.CBy4 * 2 * (n2g / 2 + 1) * sizeof(cpx);
-    while (sp.shy4 > 60 * 1024 && sp.CBy4 > 1) { sp.CBy4 /= 2; sp.shy4 = (size_t)2 * sp.CBy4 * 2 * (n2g / 2 + 1) * sizeof(cpx); }
-    if (sp.shy4 > 64 * 1024) { c->err = "solver: y line too long for the LDS-resident DCT-IV"; return 1; }
-    sp.y8 = false;
-    std::vector<real> t(4 * (size_t)(n2g / 2)); const real pi = std::acos(-1.0); const int nh2 = n2g / 2;
-    for (int q = 0; q < nh2; ++q) { const real a1 = -pi * (4. * q + 1.) / (4. * n2g), a2 = -pi * q / (real)n2g;
-                                    t[2 * q] = std::cos(a1); t[2 * q + 1] = std::sin(a1); t[2 * (nh2 + q)] = std::cos(a2); t[2 * (nh2 + q) + 1] = std::sin(a2); }
-    HIPCHK(c, hipMalloc(&c->d_tw4y, t.size() * sizeof(real)));
-    HIPCHK(c, hipMemcpy(c->d_tw4y, t.data(), t.size() * sizeof(real), hipMemcpyHostToDevice));
-  }
-  if (c->ykind == 2) sp.y8 = false;      // the sign changes of the Dirichlet-Dirichlet transform live in the generic y kernel only
-  if (c->fl.fft_generic) sp.x8 = sp.y8 = false;
-  if (!sp.y8) sp.y16 = false;
+  if (P.ykind >= 3) { if (dct4_y_setup(c, s, "solver")) return 1; s.y8 = false; }
+  if (P.ykind == 2) s.y8 = false;      // the sign changes of the Dirichlet-Dirichlet transform live in the generic y kernel only
+  if (c->fl.fft_generic) s.x8 = s.y8 = false;
+  if (!s.y8) s.y16 = false;
   // eigenvalues (initsolver.f90:66-98); x: modes 0..n1/2 (half-complex symmetry), y: modes 0..n2-1
   std::vector<real> lx(n1 + 2, 0.), ly(n2g);
   hs_eigenvalues(n1, bx.c_str(), 'c', lx.data()); hs_eigenvalues(n2g, by.c_str(), 'c', ly.data());
   for (auto &v : lx) v = v * (c->dli[0] * c->dli[0]);
   for (auto &v : ly) v = v * (c->dli[1] * c->dli[1]);
-  if (c->ykind == 2) std::reverse(ly.begin(), ly.end());      // row r of the transformed field holds coefficient N-1-r (see k_fft_y)
+  if (P.ykind == 2) std::reverse(ly.begin(), ly.end());      // row r of the transformed field holds coefficient N-1-r (see k_fft_y)
   const int mh = n1 / 2 + 1;
   c->cw = (mh + c->P - 1) / c->P;                            // complex mode columns per rank (last block padded)
   // rows of the mode-block layout in whole 128-B lines (cw a multiple of 8) where the padding columns -- they travel in the all-to-all -- add 6 % or less: the y
@@ -1915,14 +1977,17 @@ int solver_setup(cales_ctx *c) {
   // on the links -- not padded there.
   if (c->P > 1) { const int cw8 = (c->cw + 7) / 8 * 8; if (100 * (cw8 - c->cw) <= 6 * c->cw && (size_t)cw8 * n2g * n3 <= c->ntot) c->cw = cw8; }
   if (c->P > 1 && (size_t)c->cw * n2g * n3 > c->ntot) { c->err = "solver: scratch too small for the mode-block layout"; return 1; }
+  P.nz = n3; P.periodic_z = CBP(c, 0, 3) == 'P' && CBP(c, 1, 3) == 'P'; P.poisson = true;
+  choose_kernels(c, s, P);
   // Nyquist packing of the pressure solve (k_gaussel_nyq): periodic x, periodic or Neumann y (the pair is separated by the Hermitian pairing of rows / by real and
   // imaginary part), radix-8 passes, the z solve in the LDS tile; n1/2 mode columns instead of n1/2 + 1
-  { const bool pz = CBP(c, 0, 3) == 'P' && CBP(c, 1, 3) == 'P', hasd = CBP(c, 0, 3) == 'D' || CBP(c, 1, 3) == 'D';
-    c->nyq_ok = c->xkind == 0 && c->ykind <= 1 && sp.x8 && sp.y8 && !pz && (hasd || !c->fl.keep_null_mode) && n3 >= 2 && n3 <= 1024 && !c->fl.gaussel_march && !c->fl.no_nyquist_packing;
-    c->cw_nyq = (n1 / 2 + c->P - 1) / c->P; }
-  HIPCHK(c, hipMalloc(&c->d_lamx, (n1 + 2) * sizeof(real))); HIPCHK(c, hipMalloc(&c->d_lamy, n2g * sizeof(real)));
-  HIPCHK(c, hipMemcpy(c->d_lamx, lx.data(), (n1 + 2) * sizeof(real), hipMemcpyHostToDevice));
-  HIPCHK(c, hipMemcpy(c->d_lamy, ly.data(), n2g * sizeof(real), hipMemcpyHostToDevice));
+  { const bool hasd = CBP(c, 0, 3) == 'D' || CBP(c, 1, 3) == 'D';
+    P.nyq = P.xkind == 0 && P.ykind <= 1 && s.x8 && s.y8 && !P.periodic_z && (hasd || !c->fl.keep_null_mode) && tile_takes(c, n3, false) && !c->fl.no_nyquist_packing;
+    if (P.nyq && P.zk != ZKernel::tile) { c->err = "solver: the packed mode column needs the z solve in the LDS tile"; return 1; }
+    P.cw = P.nyq ? (n1 / 2 + c->P - 1) / c->P : c->cw; }
+  HIPCHK(c, hipMalloc(&P.lamx, (n1 + 2) * sizeof(real))); HIPCHK(c, hipMalloc(&P.lamy, n2g * sizeof(real)));
+  HIPCHK(c, hipMemcpy(P.lamx, lx.data(), (n1 + 2) * sizeof(real), hipMemcpyHostToDevice));
+  HIPCHK(c, hipMemcpy(P.lamy, ly.data(), n2g * sizeof(real), hipMemcpyHostToDevice));
   // tridiagonal (initsolver.f90:127-169), pressure: cell-centred
   std::vector<real> a(n3), b(n3), cc(n3);
   hs_tridmatrix(&c->C.cbcpre[4], n3, c->dzci.data(), c->dzfi.data(), 'c', a.data(), b.data(), cc.data());
@@ -1930,29 +1995,13 @@ int solver_setup(cales_ctx *c) {
   HIPCHK(c, hipMemcpy(c->d_a, a.data(), n3 * sizeof(real), hipMemcpyHostToDevice));
   HIPCHK(c, hipMemcpy(c->d_b, b.data(), n3 * sizeof(real), hipMemcpyHostToDevice));
   HIPCHK(c, hipMemcpy(c->d_c, cc.data(), n3 * sizeof(real), hipMemcpyHostToDevice));
-  c->normfft = 1. / ((c->xkind ? 2. : 1.) * (real)n1 * (c->ykind ? 2. : 1.) * (real)n2g);   // fft.f90:99,136,142; find_fft norm = [1,0] (PP) / [2,0] (NN)
-  // twiddles: exp(-2 pi i q/N)
-  auto mk = [&](int N, int cnt, real **dev) -> int {
-    std::vector<real> t(2 * (size_t)cnt);
-    const real pi = std::acos(-1.0);
-    for (int q = 0; q < cnt; ++q) { const real ang = -2. * pi * q / N; t[2 * q] = std::cos(ang); t[2 * q + 1] = std::sin(ang); }
-    HIPCHK(c, hipMalloc(dev, t.size() * sizeof(real)));
-    HIPCHK(c, hipMemcpy(*dev, t.data(), t.size() * sizeof(real), hipMemcpyHostToDevice));
-    return 0;
-  };
-  if (mk(n1 / 2, n1 / 2, &c->d_twx)) return 1;
-  if (mk(n1, n1 / 2 + 1, &c->d_twx_post)) return 1;
-  if (mk(n2g, n2g, &c->d_twy)) return 1;
-  if (mk(4 * n1, n1 / 2 + 1, &c->d_twy_post)) return 1;      // DCT weights e^{-i pi k/(2 n1)}, k = 0..n1/2 (x)
-  if (mk(4 * n2g, n2g, &c->scr_twyd)) return 1;              // e^{-i pi k/(2 n2)}, k = 0..n2-1 (y)
-  if (c->ykind >= 3) { if (mk(n2g / 2, n2g / 2, &c->d_twy4)) return 1; }      // N/2-point lines of k_fft_y4
-  if (c->xkind >= 3) {            // DCT-IV weights (k_fft_x4)
-    const int nh = n1 / 2; std::vector<real> t(4 * (size_t)nh); const real pi = std::acos(-1.0);
-    for (int q = 0; q < nh; ++q) { const real a1 = -pi * (4. * q + 1.) / (4. * n1), a2 = -pi * q / (real)n1;
-                                   t[2 * q] = std::cos(a1); t[2 * q + 1] = std::sin(a1); t[2 * (nh + q)] = std::cos(a2); t[2 * (nh + q) + 1] = std::sin(a2); }
-    HIPCHK(c, hipMalloc(&c->d_tw4x, t.size() * sizeof(real)));
-    HIPCHK(c, hipMemcpy(c->d_tw4x, t.data(), t.size() * sizeof(real), hipMemcpyHostToDevice));
-  }
+  P.normfft = 1. / ((P.xkind ? 2. : 1.) * (real)n1 * (P.ykind ? 2. : 1.) * (real)n2g);   // fft.f90:99,136,142; find_fft norm = [1,0] (PP) / [2,0] (NN)
+  if (upload_twiddles(c, n1 / 2, n1 / 2, &s.twx)) return 1;
+  if (upload_twiddles(c, n1, n1 / 2 + 1, &s.twx_post)) return 1;
+  if (upload_twiddles(c, n2g, n2g, &s.twy)) return 1;
+  if (upload_twiddles(c, 4 * n1, n1 / 2 + 1, &s.twy_post)) return 1;      // DCT weights e^{-i pi k/(2 n1)}, k = 0..n1/2 (x)
+  if (upload_twiddles(c, 4 * n2g, n2g, &s.twyd)) return 1;               // e^{-i pi k/(2 n2)}, k = 0..n2-1 (y)
+  if (P.xkind >= 3 && upload_dct4_weights(c, n1, &s.tw4x)) return 1;    // DCT-IV weights (k_fft_x4)
   if (c->C.impdiff)
     for (int iv = 0; iv < 3; ++iv) {
       hs_tridmatrix(&c->cbcvel[6 * iv + 4], n3, c->dzci.data(), c->dzfi.data(), iv == 2 ? 'f' : 'c', a.data(), b.data(), cc.data());
@@ -1962,16 +2011,15 @@ int solver_setup(cales_ctx *c) {
       HIPCHK(c, hipMemcpy(c->d_bv[iv], b.data(), n3 * sizeof(real), hipMemcpyHostToDevice));
       HIPCHK(c, hipMemcpy(c->d_cv[iv], cc.data(), n3 * sizeof(real), hipMemcpyHostToDevice));
     }
-  { PlanSlot ps_; ps_.ctx = c; ps_.sp = sp; std::lock_guard<std::mutex> lk(g_slots_mx); g_slots.push_back(ps_); }
   return 0;
 }
 void solver_teardown(cales_ctx *c) {
-  { std::lock_guard<std::mutex> lk(g_slots_mx);
-    for (auto it = g_slots.begin(); it != g_slots.end(); ++it) if (it->ctx == c) {
-      for (auto &V : it->vs) { if (V.lamx) hipFree(V.lamx); if (V.lamy) hipFree(V.lamy); if (V.tw1x) hipFree(V.tw1x); if (V.tw1y) hipFree(V.tw1y); }
-      g_slots.erase(it); break; } }
-  hipFree(c->d_lamx); hipFree(c->d_lamy); hipFree(c->d_a); hipFree(c->d_b); hipFree(c->d_c);
-  hipFree(c->d_twx); hipFree(c->d_twx_post); hipFree(c->d_twy); hipFree(c->d_twy_post); hipFree(c->scr_twyd); hipFree(c->d_tw4x); if (c->d_tw4y) hipFree(c->d_tw4y); if (c->d_twy4) hipFree(c->d_twy4);
+  if (Solver *s = c->solver) {
+    for (const SolvePath *P : {&s->pres, &s->vel[0], &s->vel[1], &s->vel[2]}) { hipFree(P->lamx); hipFree(P->lamy); hipFree(P->tw1x); hipFree(P->tw1y); }
+    for (real *t : {s->twx, s->twx_post, s->twy, s->twy_post, s->twyd, s->tw4x, s->tw4y, s->twy4}) hipFree(t);
+    delete s; c->solver = nullptr;
+  }
+  hipFree(c->d_a); hipFree(c->d_b); hipFree(c->d_c);
   for (int iv = 0; iv < 3; ++iv) hipFree(c->d_av[iv]);
 }
 
@@ -2031,38 +2079,77 @@ __global__ void k_null_column(Geom g, Spec S, int nz, int periodic, const real *
   for (int l = 0; l < nz; ++l) p[S.at_mode(g, 0, 1, l + 1)].x = col[l];
 }
 
-// FFT x, FFT y, tridiagonal z, and back, in place on `pp`; (da,db,dc,nz,lscale) = (a,b,c,n3,1) for the pressure Poisson equation,
-// (alpha a, alpha b + 1, alpha c, n3 - q, alpha) for the Helmholtz equation of a velocity component (main.f90:435-445)
-static int solve_field(cales_ctx *c, real *pp, const real *da, const real *db, const real *dc, int nz, real lscale, bool periodic_z, bool poisson) {
-  SolverPlans *sp = find_plans(c);
-  if (!sp) { c->err = "solver not initialised"; return 1; }
+// The transform passes of a path. x: the rows [rb, re) of the (j,k) row list (re < 0: all), the radix-8 kernel in `blocks` blocks of `iters` row groups,
+// F (forward only): the pass forms pp = div(u*)/dtrk itself (fillps). y: the planes k0+1..k1 (k1 < 0: all), the radix-8 kernels `kchunk` planes per block.
+// The other kernels take the whole field in a geometry of their own.
+template <int INV, int KIND, int FILL>
+static void launch_x8(cales_ctx *c, const Solver &s, unsigned blocks, int iters, real *pp, real scale, const Spec &S, real2 *spec, const FillArgs &F, long rb, long re) {
+  LAUNCH(c, (k_fft_x8<INV, KIND, FILL>), dim3(blocks), dim3(s.x8_threads), s.shx8, c->stream, c->g, c->C.ng[0] / 2, iters, (const cpx *)s.twx, (const cpx *)s.twx_post,
+         (const cpx *)s.twy_post, pp, scale, S, spec, F, rb, re);
+}
+template <int INV>
+static void fft_x(cales_ctx *c, const SolvePath &P, real *pp, const Spec &S, real2 *spec, unsigned blocks, int iters, const FillArgs *F, long rb, long re) {
+  const Solver &s = *c->solver;
+  const real scale = INV ? P.normfft : (real)1.;
+  const long nrows = (long)c->n[1] * c->n[2];
+  const dim3 gx((unsigned)((nrows + s.Rx - 1) / s.Rx));
+  if (P.xk == XKernel::fft_x8) {
+    if constexpr (INV == 0) if (F) { if (P.xkind) launch_x8<0, 1, 1>(c, s, blocks, iters, pp, scale, S, spec, *F, rb, re); else launch_x8<0, 0, 1>(c, s, blocks, iters, pp, scale, S, spec, *F, rb, re); return; }
+    if (P.xkind) launch_x8<INV, 1, 0>(c, s, blocks, iters, pp, scale, S, spec, FillArgs{}, rb, re); else launch_x8<INV, 0, 0>(c, s, blocks, iters, pp, scale, S, spec, FillArgs{}, rb, re);
+  } else if (P.xk == XKernel::dst1)
+    LAUNCH(c, k_dst1<2 * INV>, dim3((unsigned)nrows), dim3(256), (size_t)2 * (P.p1x.N + 1) * sizeof(cpx), c->stream, c->g, P.p1x, 0, (const cpx *)P.tw1x, pp, scale, S, spec, P.xkind, INV);
+  else if (P.xk == XKernel::fft_x4 && P.xkind == 3) LAUNCH(c, (k_fft_x4<INV, 0>), gx, dim3(256), s.shx, c->stream, c->g, s.px, s.Rx, (const cpx *)s.twx, (const cpx *)s.tw4x, pp, scale, S, spec);
+  else if (P.xk == XKernel::fft_x4) LAUNCH(c, (k_fft_x4<INV, 1>), gx, dim3(256), s.shx, c->stream, c->g, s.px, s.Rx, (const cpx *)s.twx, (const cpx *)s.tw4x, pp, scale, S, spec);
+  else LAUNCH(c, k_fft_x<INV>, gx, dim3(256), s.shx, c->stream, c->g, s.px, s.Rx, P.xkind, (const cpx *)s.twx, (const cpx *)s.twx_post, (const cpx *)s.twy_post, pp, scale, S, spec);
+}
+template <int INV, int KIND, int N = 1024>      // N: the line length, 1024, 512 or 256 points
+static void fft_y16(cales_ctx *c, const Solver &s, dim3 gy, int ncols, int kchunk, const Spec &S, real2 *spec, int k0, int k1) {
+  if constexpr (N > 256) if (c->C.ng[1] < N) return fft_y16<INV, KIND, N / 2>(c, s, gy, ncols, kchunk, S, spec, k0, k1);
+  LAUNCH(c, (k_fft_y16<N, INV, KIND>), gy, dim3(N / 2), s.shy16, c->stream, c->g, ncols, kchunk, (const cpx *)s.twy, (const cpx *)s.twyd, S, spec, k0, k1);
+}
+// ncol_y: the columns the radix-8 y kernels transform (see solve_field)
+template <int INV>
+static void fft_y(cales_ctx *c, const SolvePath &P, real *pp, const Spec &S, real2 *spec, int ncol, int ncol_y, int kchunk, int k0, int k1) {
+  const Solver &s = *c->solver;
+  const int n2g = c->C.ng[1], n3 = c->n[2];
+  const dim3 gy((ncol_y + P.ycols - 1) / P.ycols, ((k1 < 0 ? n3 : k1) - k0 + kchunk - 1) / kchunk);
+  switch (P.yk) {
+  case YKernel::dst1:
+    LAUNCH(c, k_dst1<1>, dim3(ncol, n3), dim3(256), (size_t)2 * (P.p1y.N + 1) * sizeof(cpx), c->stream, c->g, P.p1y, ncol, (const cpx *)P.tw1y, pp, 1., S, spec, P.ykind, INV); break;
+  case YKernel::fft_y4:
+    if (P.ykind == 3) LAUNCH(c, k_fft_y4<0>, dim3((ncol + s.CBy4 - 1) / s.CBy4, n3), dim3(256), s.shy4, c->stream, c->g, s.py4, s.CBy4, ncol, (const cpx *)s.twy4, (const cpx *)s.tw4y, S, spec);
+    else LAUNCH(c, k_fft_y4<1>, dim3((ncol + s.CBy4 - 1) / s.CBy4, n3), dim3(256), s.shy4, c->stream, c->g, s.py4, s.CBy4, ncol, (const cpx *)s.twy4, (const cpx *)s.tw4y, S, spec);
+    break;
+  case YKernel::fft_y16:
+    if (P.ykind) fft_y16<INV, 1>(c, s, gy, ncol_y, kchunk, S, spec, k0, k1); else fft_y16<INV, 0>(c, s, gy, ncol_y, kchunk, S, spec, k0, k1);
+    break;
+  case YKernel::fft_y8:
+    LAUNCH(c, (k_fft_y8<INV, 1>), gy, dim3(s.y8_threads), s.shy8, c->stream, c->g, n2g, ncol_y, kchunk, (const cpx *)s.twy, (const cpx *)s.twyd, S, spec, k0, k1); break;
+  case YKernel::fft_y8r:
+    LAUNCH(c, (k_fft_y8r<INV>), dim3((ncol + P.ycols - 1) / P.ycols, gy.y), dim3(s.y8_threads), s.shy8r, c->stream, c->g, n2g, ncol, kchunk, (const cpx *)s.twy, S, spec, k0, k1); break;
+  case YKernel::fft_y:
+    LAUNCH(c, k_fft_y<INV>, dim3((ncol + s.CBy - 1) / s.CBy, n3), dim3(256), s.shy, c->stream, c->g, s.py, s.CBy, ncol, P.ykind, (const cpx *)s.twy, (const cpx *)s.twyd, S, spec); break;
+  }
+}
+
+// FFT x, FFT y, tridiagonal z, and back, in place on `pp` along path P; (da,db,dc,lscale) = (a,b,c,1) for the pressure Poisson equation,
+// (alpha a, alpha b + 1, alpha c, alpha) for the Helmholtz equation of a velocity component (main.f90:435-445)
+static int solve_field(cales_ctx *c, const SolvePath &P, real *pp, const real *da, const real *db, const real *dc, real lscale) {
   const int *n = c->n;
-  const int mh = n[0] / 2 + 1, n2g = c->C.ng[1];
+  const int mh = n[0] / 2 + 1, n2g = c->C.ng[1], nh = c->C.ng[0] / 2, nz = P.nz;
   const long nrows = (long)n[1] * n[2];
   const bool dist = c->P > 1;
-  // the radix-8 kernels know the periodic and the Neumann-Neumann transform; a velocity component of the 3-D implicit step may need others
-  const bool use8x = sp->x8 && c->xkind <= 1, use8y = sp->y8 && c->ykind <= 1;
-  const VelSet *VS = static_cast<const VelSet *>(c->cur_velset);      // transform set of the velocity component being solved (nullptr: the pressure's)
   if (dist && !c->comm.on) { c->err = "solver: nranks > 1 but no communication hooks registered (cales_set_comm)"; return 1; }
-  const bool nyq = poisson && !VS && c->nyq_ok && c->xkind == 0 && c->ykind <= 1;
-  const int cw = nyq ? c->cw_nyq : c->cw, nmodes = nyq ? n[0] / 2 : mh;      // complex mode columns: per rank, in all
-  Spec S; S.blocked = dist ? 1 : 0; S.cw = cw; S.n2l = n[1]; S.n3 = n[2]; S.nyq = nyq ? 1 : 0;
+  const int cw = P.cw, nmodes = P.nyq ? n[0] / 2 : mh;      // complex mode columns: per rank, in all
+  Spec S; S.blocked = dist ? 1 : 0; S.cw = cw; S.n2l = n[1]; S.n3 = n[2]; S.nyq = P.nyq ? 1 : 0;
   real2 *slab_spec = dist ? reinterpret_cast<real2 *>(c->comm.A) : reinterpret_cast<real2 *>(pp + 1);   // in place: modes of row (j,k) from i = 1
   real2 *mode_spec = dist ? reinterpret_cast<real2 *>(c->comm.B) : reinterpret_cast<real2 *>(pp + 1);
   const int ncol = dist ? cw : nmodes, mofs = dist ? c->rank * cw : 0;
   const int64_t a2a_count = (int64_t)n[2] * n[1] * cw * 2;
-  const int nh = c->C.ng[0] / 2;
-  const bool use16y = use8y && sp->y16;
-  const int Rx8 = use8x ? sp->x8_threads / (nh / 8) : 1, CB8 = use16y ? 8 : use8y ? sp->y8_threads / (n2g / 8) : 1;
+  const bool use8x = P.xk == XKernel::fft_x8, use8y = radix8_y(P.yk), use16y = P.yk == YKernel::fft_y16;
+  const int Rx8 = P.xrows, CB8 = P.ycols;
   // real x modes (Neumann in x) fill the complex columns 0 .. n1/2 - 1: the slot of "mode n1/2" is never written by the x pass nor read back by it
-  const int ncol_y = (!dist && c->xkind == 1 && use8y) ? nh : ncol;
-  auto launch_y16 = [&](int inv, dim3 gy, int kc, int ka, int kb) {
-#define Y16_GO(NN, IV, KD) LAUNCH(c, (k_fft_y16<NN, IV, KD>), gy, dim3(NN / 2), sp->shy16, c->stream, c->g, ncol_y, kc, (const cpx *)c->d_twy, (const cpx *)c->scr_twyd, S, mode_spec, ka, kb)
-#define Y16_N(NN) do { if (inv) { if (c->ykind) Y16_GO(NN, 1, 1); else Y16_GO(NN, 1, 0); } else { if (c->ykind) Y16_GO(NN, 0, 1); else Y16_GO(NN, 0, 0); } } while (0)
-    if (n2g == 1024) Y16_N(1024); else if (n2g == 512) Y16_N(512); else Y16_N(256);
-#undef Y16_N
-#undef Y16_GO
-  };
+  const int ncol_y = (!dist && P.xkind == 1 && use8y) ? nh : ncol;
   // persistent blocks: several row groups / planes per block so that the register prefetch overlaps the transforms
   const long xgroups = (nrows + Rx8 - 1) / Rx8;
   int xiters = 1; while (xiters < 8 && xgroups / (xiters * 2) >= 2048) xiters *= 2;
@@ -2071,7 +2158,7 @@ static int solve_field(cales_ctx *c, real *pp, const real *da, const real *db, c
   // 1.36 / 1.41 / 1.44 / 1.50 (one group per block), inverse Neumann pass 1024^3 12.6 / 12.0 / 11.4 / 10.8 (eight)
   if (xgroups <= 8192) xiters = 1;
   const unsigned xblocks = (unsigned)((xgroups + xiters - 1) / xiters);
-  const int xiters_b = (c->xkind == 0 && nh <= 256) ? 1 : xiters;
+  const int xiters_b = (P.xkind == 0 && nh <= 256) ? 1 : xiters;
   const unsigned xblocks_b = (unsigned)((xgroups + xiters_b - 1) / xiters_b);
   // planes per block of the eight-elements-per-thread y kernels: measured at 512^3 (round 6, in the step, planes per block 1 / 2 / 8): y passes 2.77 / 2.69 / 2.94 ms
   // per step -- many short blocks beat long persistent ones; from 8192 blocks on
@@ -2090,10 +2177,10 @@ static int solve_field(cales_ctx *c, real *pp, const real *da, const real *db, c
     return bk;
   };
   if (use16y) ykchunk = y16_chunk(n[2]);
-  const int ychunks = (n[2] + ykchunk - 1) / ykchunk;
   // ---- pipelined exchange (cales_set_comm_overlap): the spectrum travels in k-chunks on the second stream while the x transforms of
   // the next chunk and the y transforms of the previous one run on the context's stream (the reference's cuDecomp pipelined
-  // transposes, src/initmpi.f90:94-139). Radix-8 periodic / Neumann-Neumann transforms only; everything else keeps the single exchange.
+  // transposes, src/initmpi.f90:94-139). Radix-8 periodic / Neumann-Neumann transforms only; everything else keeps the single exchange,
+  // which is the same sequence with one chunk and the geometry above.
   int NCH = 1;
   if (dist && c->comm.a2a_part && c->comm_stream && use8x && use8y) { if (n[2] % 4 == 0 && n[2] >= 32) NCH = 4; else if (n[2] % 2 == 0 && n[2] >= 8) NCH = 2; }
   const bool pipe = NCH > 1;
@@ -2104,10 +2191,12 @@ static int solve_field(cales_ctx *c, real *pp, const real *da, const real *db, c
   const unsigned xblocks_c = (unsigned)((xgroups_c + xiters_c - 1) / xiters_c);
   int ykchunk_c = 1; { const long cg = (ncol + CB8 - 1) / CB8; while (ykchunk_c < 8 && cg * (kpc / (ykchunk_c * 2)) >= 2048 / NCH && kpc % (ykchunk_c * 2) == 0) ykchunk_c *= 2; }
   if (use16y) ykchunk_c = y16_chunk(kpc);
+  const unsigned xblk_f = pipe ? xblocks_c : xblocks, xblk_b = pipe ? xblocks_c : xblocks_b;
+  const int xit_f = pipe ? xiters_c : xiters, xit_b = pipe ? xiters_c : xiters_b, ykc = pipe ? ykchunk_c : ykchunk;
+  auto rows_of = [&](int ch, long &rb, long &re) { rb = pipe ? (long)n[1] * kpc * ch : 0; re = pipe ? rb + rows_c : -1; };
+  auto k0_of = [&](int ch) { return pipe ? kpc * ch : 0; };
+  auto k1_of = [&](int ch) { return pipe ? kpc * (ch + 1) : -1; };
   hipEvent_t ev_arrived[4];
-  // the bulk means summed by the fused fillps pass: several ranks all-reduce them on the context's stream, and RCCL orders the operations of
-  // one communicator across streams -- issued between the chunk exchanges it would hold the y transforms back, so it follows the z sweep
-  int pend_mean_mask = 0, pend_mean_nblk = 0; const real *pend_mean_part = nullptr;
   auto mark = [&](hipStream_t st, hipEvent_t &e) -> int {
     if (c->sync_ev.size() < 64) { hipEvent_t ne; HIPCHK(c, hipEventCreateWithFlags(&ne, hipEventDisableTiming)); c->sync_ev.push_back(ne); c->sync_next = c->sync_ev.size() - 1; }
     e = c->sync_ev[c->sync_next]; c->sync_next = (c->sync_next + 1) % c->sync_ev.size();
@@ -2117,180 +2206,108 @@ static int solve_field(cales_ctx *c, real *pp, const real *da, const real *db, c
     { ProfScope ps(c, "alltoall", c->comm_stream);
       if (c->comm.a2a_part(c->comm.user, dir, a2a_stride, (int64_t)ch * a2a_chunk, a2a_chunk, (void *)c->comm_stream)) { c->err = "alltoall_part callback failed"; return 1; } }
     return mark(c->comm_stream, ev_arrived[ch]); };
-  if (pipe) {
-    const bool fill = poisson && c->fuse_fillps_dti != 0. && sp->x8;
-    FillArgs F{};
-    if (fill) {
-      const real dti = c->fuse_fillps_dti;
-      F = FillArgs{c->f[CALES_U], c->f[CALES_V], c->f[CALES_W], c->d_dzfi, dti, dti * c->dli[0], dti * c->dli[1], c->fuse_mean_mask, c->d_gvr_f, c->d_gvr_c, nullptr};
-      F.xwrap = c->step_xskip ? n[0] : 0;
-      if (F.mean_mask) {
-        const size_t need = 3 * (size_t)xblocks_c * NCH;
-        if (c->n_mpart < need) { if (c->d_mpart) hipFree(c->d_mpart); HIPCHK(c, hipMalloc(&c->d_mpart, need * sizeof(real))); c->n_mpart = need; }
-        F.part = c->d_mpart; F.pstride = (int)(xblocks_c * NCH);
-      }
-    }
-    for (int ch = 0; ch < NCH; ++ch) {
-      const long rb = (long)n[1] * kpc * ch, re = rb + rows_c;
-      { ProfScope ps(c, fill ? "fillps_fft_x_fwd" : "fft_x_fwd");
-        F.pofs = (int)(xblocks_c * ch);
-        if (fill && c->xkind) LAUNCH(c, (k_fft_x8<0, 1, 1>), dim3(xblocks_c), dim3(sp->x8_threads), sp->shx8, c->stream, c->g, nh, xiters_c, (const cpx *)c->d_twx, (const cpx *)c->d_twx_post, (const cpx *)c->d_twy_post, pp, 1., S, slab_spec, F, rb, re);
-        else if (fill) LAUNCH(c, (k_fft_x8<0, 0, 1>), dim3(xblocks_c), dim3(sp->x8_threads), sp->shx8, c->stream, c->g, nh, xiters_c, (const cpx *)c->d_twx, (const cpx *)c->d_twx_post, (const cpx *)c->d_twy_post, pp, 1., S, slab_spec, F, rb, re);
-        else if (c->xkind) LAUNCH(c, (k_fft_x8<0, 1>), dim3(xblocks_c), dim3(sp->x8_threads), sp->shx8, c->stream, c->g, nh, xiters_c, (const cpx *)c->d_twx, (const cpx *)c->d_twx_post, (const cpx *)c->d_twy_post, pp, 1., S, slab_spec, FillArgs{}, rb, re);
-        else LAUNCH(c, (k_fft_x8<0, 0>), dim3(xblocks_c), dim3(sp->x8_threads), sp->shx8, c->stream, c->g, nh, xiters_c, (const cpx *)c->d_twx, (const cpx *)c->d_twx_post, (const cpx *)c->d_twy_post, pp, 1., S, slab_spec, FillArgs{}, rb, re); }
-      if (int e = exchange_chunk(0, ch)) return e;
-    }
-    if (fill && F.mean_mask) { pend_mean_mask = F.mean_mask; pend_mean_part = F.part; pend_mean_nblk = (int)(xblocks_c * NCH); }
-    for (int ch = 0; ch < NCH; ++ch) {
-      HIPCHK(c, hipStreamWaitEvent(c->stream, ev_arrived[ch], 0));
-      ProfScope ps(c, "fft_y_fwd");
-      const dim3 gy((ncol_y + CB8 - 1) / CB8, (kpc + ykchunk_c - 1) / ykchunk_c);
-      if (use16y) launch_y16(0, gy, ykchunk_c, kpc * ch, kpc * (ch + 1));
-      else if (c->ykind) LAUNCH(c, (k_fft_y8<0, 1>), gy, dim3(sp->y8_threads), sp->shy8, c->stream, c->g, n2g, ncol_y, ykchunk_c, (const cpx *)c->d_twy, (const cpx *)c->scr_twyd, S, mode_spec, kpc * ch, kpc * (ch + 1));
-      else LAUNCH(c, (k_fft_y8r<0>), gy, dim3(sp->y8_threads), sp->shy8r, c->stream, c->g, n2g, ncol, ykchunk_c, (const cpx *)c->d_twy, S, mode_spec, kpc * ch, kpc * (ch + 1));
-    }
-  } else {
-  if (poisson && c->fuse_fillps_dti != 0. && sp->x8) {
-    ProfScope ps(c, "fillps_fft_x_fwd");
+  // fillps inside the forward x transform; the bulk means it sums: several ranks all-reduce them on the context's stream, and RCCL orders the operations of
+  // one communicator across streams -- issued between the chunk exchanges it would hold the y transforms back, so the pipelined solve reduces them after the z sweep
+  const bool fill = P.poisson && c->fuse_fillps_dti != 0. && use8x;
+  FillArgs F{};
+  if (fill) {
     const real dti = c->fuse_fillps_dti;
-    FillArgs F{c->f[CALES_U], c->f[CALES_V], c->f[CALES_W], c->d_dzfi, dti, dti * c->dli[0], dti * c->dli[1], c->fuse_mean_mask, c->d_gvr_f, c->d_gvr_c, nullptr};
+    F = FillArgs{c->f[CALES_U], c->f[CALES_V], c->f[CALES_W], c->d_dzfi, dti, dti * c->dli[0], dti * c->dli[1], c->fuse_mean_mask, c->d_gvr_f, c->d_gvr_c, nullptr};
     F.xwrap = c->step_xskip ? n[0] : 0;
     if (F.mean_mask) {
-      if (c->n_mpart < 3 * (size_t)xblocks) { if (c->d_mpart) hipFree(c->d_mpart); HIPCHK(c, hipMalloc(&c->d_mpart, 3 * (size_t)xblocks * sizeof(real))); c->n_mpart = 3 * (size_t)xblocks; }
-      F.part = c->d_mpart;
+      const size_t need = 3 * (size_t)xblk_f * NCH;
+      if (c->n_mpart < need) { if (c->d_mpart) hipFree(c->d_mpart); HIPCHK(c, hipMalloc(&c->d_mpart, need * sizeof(real))); c->n_mpart = need; }
+      F.part = c->d_mpart; if (pipe) F.pstride = (int)(xblocks_c * NCH);
     }
-    if (c->xkind) LAUNCH(c, (k_fft_x8<0, 1, 1>), dim3(xblocks), dim3(sp->x8_threads), sp->shx8, c->stream, c->g, nh, xiters,
-                                     (const cpx *)c->d_twx, (const cpx *)c->d_twx_post, (const cpx *)c->d_twy_post, pp, 1., S, slab_spec, F);
-    else LAUNCH(c, (k_fft_x8<0, 0, 1>), dim3(xblocks), dim3(sp->x8_threads), sp->shx8, c->stream, c->g, nh, xiters,
-                            (const cpx *)c->d_twx, (const cpx *)c->d_twx_post, (const cpx *)c->d_twy_post, pp, 1., S, slab_spec, F);
-    if (F.mean_mask) if (int e = op_force_from_partials(c, F.mean_mask, F.part, (int)xblocks)) return e;
-  } else { ProfScope ps(c, "fft_x_fwd");
-    if (use8x && c->xkind) LAUNCH(c, (k_fft_x8<0, 1>), dim3(xblocks), dim3(sp->x8_threads), sp->shx8, c->stream, c->g, nh, xiters,
-                                   (const cpx *)c->d_twx, (const cpx *)c->d_twx_post, (const cpx *)c->d_twy_post, pp, 1., S, slab_spec);
-    else if (use8x) LAUNCH(c, (k_fft_x8<0, 0>), dim3(xblocks), dim3(sp->x8_threads), sp->shx8, c->stream, c->g, nh, xiters,
-                                   (const cpx *)c->d_twx, (const cpx *)c->d_twx_post, (const cpx *)c->d_twy_post, pp, 1., S, slab_spec);
-    else if (c->xkind >= 5) LAUNCH(c, k_dst1<0>, dim3((unsigned)nrows), dim3(256), (size_t)2 * (VS->p1x.N + 1) * sizeof(cpx), c->stream, c->g, VS->p1x, 0, (const cpx *)VS->tw1x, pp, 1., S, slab_spec, c->xkind, 0);
-    else if (c->xkind == 3) LAUNCH(c, (k_fft_x4<0, 0>), dim3((unsigned)((nrows + sp->Rx - 1) / sp->Rx)), dim3(256), sp->shx, c->stream, c->g, sp->px, sp->Rx,
-                       (const cpx *)c->d_twx, (const cpx *)c->d_tw4x, pp, 1., S, slab_spec);
-    else if (c->xkind == 4) LAUNCH(c, (k_fft_x4<0, 1>), dim3((unsigned)((nrows + sp->Rx - 1) / sp->Rx)), dim3(256), sp->shx, c->stream, c->g, sp->px, sp->Rx,
-                       (const cpx *)c->d_twx, (const cpx *)c->d_tw4x, pp, 1., S, slab_spec);
-    else LAUNCH(c, k_fft_x<0>, dim3((unsigned)((nrows + sp->Rx - 1) / sp->Rx)), dim3(256), sp->shx, c->stream, c->g, sp->px, sp->Rx, c->xkind,
-                       (const cpx *)c->d_twx, (const cpx *)c->d_twx_post, (const cpx *)c->d_twy_post, pp, 1., S, slab_spec); }
-  if (dist) { ProfScope ps(c, "alltoall"); if (c->comm.a2a(c->comm.user, 0, a2a_count)) { c->err = "alltoall callback failed"; return 1; } }
-  { ProfScope ps(c, "fft_y_fwd");
-    if (c->ykind >= 5) LAUNCH(c, k_dst1<1>, dim3(ncol, n[2]), dim3(256), (size_t)2 * (VS->p1y.N + 1) * sizeof(cpx), c->stream, c->g, VS->p1y, ncol, (const cpx *)VS->tw1y, pp, 1., S, mode_spec, c->ykind, 0);
-    else if (c->ykind == 3) LAUNCH(c, k_fft_y4<0>, dim3((ncol + sp->CBy4 - 1) / sp->CBy4, n[2]), dim3(256), sp->shy4, c->stream, c->g, sp->py4, sp->CBy4, ncol, (const cpx *)c->d_twy4, (const cpx *)c->d_tw4y, S, mode_spec);
-    else if (c->ykind == 4) LAUNCH(c, k_fft_y4<1>, dim3((ncol + sp->CBy4 - 1) / sp->CBy4, n[2]), dim3(256), sp->shy4, c->stream, c->g, sp->py4, sp->CBy4, ncol, (const cpx *)c->d_twy4, (const cpx *)c->d_tw4y, S, mode_spec);
-    else if (use16y) launch_y16(0, dim3((ncol_y + 7) / 8, ychunks), ykchunk, 0, -1);
-    else if (use8y && c->ykind) LAUNCH(c, (k_fft_y8<0, 1>), dim3((ncol_y + CB8 - 1) / CB8, ychunks), dim3(sp->y8_threads), sp->shy8, c->stream, c->g, n2g, ncol_y, ykchunk, (const cpx *)c->d_twy, (const cpx *)c->scr_twyd, S, mode_spec);
-    else if (use8y) LAUNCH(c, (k_fft_y8r<0>), dim3((ncol + CB8 - 1) / CB8, ychunks), dim3(sp->y8_threads), sp->shy8r, c->stream, c->g, n2g, ncol, ykchunk, (const cpx *)c->d_twy, S, mode_spec);
-    else LAUNCH(c, k_fft_y<0>, dim3((ncol + sp->CBy - 1) / sp->CBy, n[2]), dim3(256), sp->shy, c->stream, c->g, sp->py, sp->CBy, ncol, c->ykind, (const cpx *)c->d_twy, (const cpx *)c->scr_twyd, S, mode_spec); }
   }
-  // pressure equation without a Dirichlet condition in z: the zero-eigenvalue mode (if x and y have one) is singular
-  const int fixnull = (poisson && CBP(c, 0, 3) != 'D' && CBP(c, 1, 3) != 'D' && !c->fl.keep_null_mode) ? 1 : 0;
+  for (int ch = 0; ch < NCH; ++ch) {
+    long rb, re; rows_of(ch, rb, re);
+    { ProfScope ps(c, fill ? "fillps_fft_x_fwd" : "fft_x_fwd");
+      F.pofs = (int)(xblk_f * ch);
+      fft_x<0>(c, P, pp, S, slab_spec, xblk_f, xit_f, fill ? &F : nullptr, rb, re);
+      if (F.mean_mask && !pipe) if (int e = op_force_from_partials(c, F.mean_mask, F.part, (int)xblk_f)) return e; }
+    if (pipe) if (int e = exchange_chunk(0, ch)) return e;
+  }
+  if (dist && !pipe) { ProfScope ps(c, "alltoall"); if (c->comm.a2a(c->comm.user, 0, a2a_count)) { c->err = "alltoall callback failed"; return 1; } }
+  for (int ch = 0; ch < NCH; ++ch) {
+    if (pipe) HIPCHK(c, hipStreamWaitEvent(c->stream, ev_arrived[ch], 0));
+    ProfScope ps(c, "fft_y_fwd");
+    fft_y<0>(c, P, pp, S, mode_spec, ncol, ncol_y, ykc, k0_of(ch), k1_of(ch));
+  }
   // CALES_KEEP_NULL_MODE: the singular column in the reference's sequential order (k_null_column); the rank that holds mode 0 does it
-  const bool refnull = poisson && lscale == (real)1. && CBP(c, 0, 3) != 'D' && CBP(c, 1, 3) != 'D' && c->fl.keep_null_mode && mofs == 0;
+  const bool refnull = P.refnull && mofs == 0;
   if (refnull) {
     if (!c->d_nullw) HIPCHK(c, hipMalloc(&c->d_nullw, (size_t)5 * (c->C.ng[2] + 2) * sizeof(real)));
-    LAUNCH(c, k_null_column, dim3(1), dim3(64), 0, c->stream, c->g, S, nz, periodic_z ? 1 : 0, da, db, dc, c->d_lamx, c->d_lamy, mode_spec, c->d_nullw, 0);
+    LAUNCH(c, k_null_column, dim3(1), dim3(64), 0, c->stream, c->g, S, nz, P.periodic_z ? 1 : 0, da, db, dc, P.lamx, P.lamy, mode_spec, c->d_nullw, 0);
   }
   { ProfScope ps(c, "gaussel_z");
-    dim3 b(64, 4), gr((ncol + 63) / 64, (n2g + 3) / 4);
-    if (c->xkind && !c->ykind)       // real x modes paired into complex columns + periodic y: Hermitian separation of rows ky and N-ky
-      LAUNCH(c, k_gaussel_herm, dim3((unsigned)(((long)4 * ncol * (n2g / 2 + 1) + 255) / 256)), dim3(256), 0, c->stream, c->g, nz, ncol, n2g, mofs, c->C.ng[0] / 2, S, lscale,
-                         da, db, dc, c->d_lamx, c->d_lamy, (real *)mode_spec, c->scr1, fixnull);
-    else if ((periodic_z || fixnull || !poisson || CBP(c, 0, 3) == 'D' || CBP(c, 1, 3) == 'D') &&
-             [&]() {
-               TileMap T{}; T.blocked = dist ? 1 : 0; T.cw = cw; T.n2l = n[1]; T.mofs = mofs; T.nmode = c->xkind ? c->C.ng[0] / 2 : nmodes; T.nyq = nyq ? 1 : 0;
-               T.kstride = (size_t)2 * cw * n[1]; T.segstride = T.kstride * n[2];
-               const int ndbl = dist ? 2 * cw * n[1] : (c->xkind ? 2 * (c->C.ng[0] / 2) : 2 * nmodes), nseg = dist ? c->P : n2g;
-               if (periodic_z)      // the cyclic closure inside the tile (gaussel_periodic, solver.f90:109-150)
-                 return c->xkind ? gaussel_tile<1, 1>(c, nz, ndbl, nseg, lscale, da, db, dc, (real *)mode_spec, fixnull, T)
-                                 : gaussel_tile<2, 1>(c, nz, ndbl, nseg, lscale, da, db, dc, (real *)mode_spec, fixnull, T);
-               return c->xkind ? gaussel_tile<1>(c, nz, ndbl, nseg, lscale, da, db, dc, (real *)mode_spec, fixnull, T)
-                               : gaussel_tile<2>(c, nz, ndbl, nseg, lscale, da, db, dc, (real *)mode_spec, fixnull, T); }()) {}
-    else if (c->xkind && !periodic_z)
-      LAUNCH(c, k_gaussel_ri, dim3((unsigned)(((long)2 * ncol * n2g + 255) / 256)), dim3(256), 0, c->stream, c->g, nz, ncol, n2g, mofs, c->C.ng[0] / 2, S, lscale, da, db, dc,
-                         c->d_lamx, c->d_lamy, (real *)mode_spec, c->scr1, fixnull, 1);
-    else if (periodic_z && c->xkind)      // real x modes (one eigenvalue each) with the periodic-z closure: scalar columns of the in-place spectrum, one rank
-      LAUNCH(c, (k_gaussel<real, 1>), dim3((2 * (c->C.ng[0] / 2) + 63) / 64, (n2g + 3) / 4), b, 0, c->stream, c->g, nz, 2 * (c->C.ng[0] / 2), n2g, 1, 0, 2 * (c->C.ng[0] / 2), S, lscale,
-                         da, db, dc, c->d_lamx, c->d_lamy, pp, c->scr1, c->scr2, fixnull);
-    else if (c->xkind) LAUNCH(c, k_gaussel_split, gr, b, 0, c->stream, c->g, nz, ncol, n2g, mofs, c->C.ng[0] / 2, S, lscale, da, db, dc, c->d_lamx, c->d_lamy,
-                                     (real2 *)mode_spec, (real2 *)c->scr1, fixnull);
-    else if (periodic_z) LAUNCH(c, (k_gaussel<real2, 1>), gr, b, 0, c->stream, c->g, nz, ncol, n2g, 0, mofs, mh, S, lscale, da, db, dc, c->d_lamx, c->d_lamy, (real *)mode_spec, c->scr1, c->scr2, fixnull);
-    else LAUNCH(c, k_gaussel_ri, dim3((unsigned)(((long)2 * ncol * n2g + 255) / 256)), dim3(256), 0, c->stream, c->g, nz, ncol, n2g, mofs, mh, S, lscale, da, db, dc, c->d_lamx, c->d_lamy, (real *)mode_spec, c->scr1, fixnull, 0); }
-  if (nyq && mofs == 0) {      // the packed column of the modes 0 and n1/2 (the tile left it out); same coefficient table as the tile of this nz
+    const dim3 b(64, 4), gr((ncol + 63) / 64, (n2g + 3) / 4);
+    real *ms = (real *)mode_spec;
+    switch (P.zk) {
+    case ZKernel::herm:
+      LAUNCH(c, k_gaussel_herm, dim3((unsigned)(((long)4 * ncol * (n2g / 2 + 1) + 255) / 256)), dim3(256), 0, c->stream, c->g, nz, ncol, n2g, mofs, nh, S, lscale,
+             da, db, dc, P.lamx, P.lamy, ms, c->scr1, P.fixnull);
+      break;
+    case ZKernel::tile: {
+      TileMap T{}; T.blocked = dist ? 1 : 0; T.cw = cw; T.n2l = n[1]; T.mofs = mofs; T.nmode = P.xkind ? nh : nmodes; T.nyq = P.nyq ? 1 : 0;
+      T.kstride = (size_t)2 * cw * n[1]; T.segstride = T.kstride * n[2];
+      const int ndbl = dist ? 2 * cw * n[1] : (P.xkind ? 2 * nh : 2 * nmodes), nseg = dist ? c->P : n2g;
+      // periodic z: the cyclic closure inside the tile (gaussel_periodic, solver.f90:109-150)
+      if (P.periodic_z && P.xkind) gaussel_tile<1, 1>(c, nz, ndbl, nseg, lscale, da, db, dc, P.lamx, P.lamy, ms, P.fixnull, T);
+      else if (P.periodic_z) gaussel_tile<2, 1>(c, nz, ndbl, nseg, lscale, da, db, dc, P.lamx, P.lamy, ms, P.fixnull, T);
+      else if (P.xkind) gaussel_tile<1>(c, nz, ndbl, nseg, lscale, da, db, dc, P.lamx, P.lamy, ms, P.fixnull, T);
+      else gaussel_tile<2>(c, nz, ndbl, nseg, lscale, da, db, dc, P.lamx, P.lamy, ms, P.fixnull, T);
+      break; }
+    case ZKernel::ri:
+      LAUNCH(c, k_gaussel_ri, dim3((unsigned)(((long)2 * ncol * n2g + 255) / 256)), dim3(256), 0, c->stream, c->g, nz, ncol, n2g, mofs, P.xkind ? nh : mh, S, lscale,
+             da, db, dc, P.lamx, P.lamy, ms, c->scr1, P.fixnull, P.xkind ? 1 : 0);
+      break;
+    case ZKernel::periodic_real:      // real x modes (one eigenvalue each) with the periodic-z closure: scalar columns of the in-place spectrum, one rank
+      LAUNCH(c, (k_gaussel<real, 1>), dim3((2 * nh + 63) / 64, (n2g + 3) / 4), b, 0, c->stream, c->g, nz, 2 * nh, n2g, 1, 0, 2 * nh, S, lscale,
+             da, db, dc, P.lamx, P.lamy, pp, c->scr1, c->scr2, P.fixnull);
+      break;
+    case ZKernel::periodic_cpx:
+      LAUNCH(c, (k_gaussel<real2, 1>), gr, b, 0, c->stream, c->g, nz, ncol, n2g, 0, mofs, mh, S, lscale, da, db, dc, P.lamx, P.lamy, ms, c->scr1, c->scr2, P.fixnull);
+      break;
+    } }
+  if (P.nyq && mofs == 0) {      // the packed column of the modes 0 and n1/2, which the tile left out (the path takes the tile: solver_setup)
     ProfScope ps(c, "gaussel_z");
-    if (nz <= 128) launch_gaussel_nyq<2>(c, nz, n2g, nh, lscale, da, db, dc, mode_spec, fixnull, S, c->d_abct);
-    else if (nz <= 256) launch_gaussel_nyq<4>(c, nz, n2g, nh, lscale, da, db, dc, mode_spec, fixnull, S, c->d_abct);
-    else if (nz <= 512) launch_gaussel_nyq<8>(c, nz, n2g, nh, lscale, da, db, dc, mode_spec, fixnull, S, c->d_abct);
-    else launch_gaussel_nyq<16>(c, nz, n2g, nh, lscale, da, db, dc, mode_spec, fixnull, S, c->d_abct);
+    gaussel_nyq(c, P.ykind == 0, nz, n2g, nh, lscale, da, db, dc, P.lamx, P.lamy, mode_spec, P.fixnull, S);
   }
-  if (refnull) LAUNCH(c, k_null_column, dim3(1), dim3(64), 0, c->stream, c->g, S, nz, periodic_z ? 1 : 0, da, db, dc, c->d_lamx, c->d_lamy, mode_spec, c->d_nullw, 1);
-  if (pend_mean_mask) if (int e = op_force_from_partials(c, pend_mean_mask, pend_mean_part, pend_mean_nblk)) return e;
-  if (pipe) {
-    for (int ch = 0; ch < NCH; ++ch) {
-      { ProfScope ps(c, "fft_y_bwd");
-        const dim3 gy((ncol_y + CB8 - 1) / CB8, (kpc + ykchunk_c - 1) / ykchunk_c);
-        if (use16y) launch_y16(1, gy, ykchunk_c, kpc * ch, kpc * (ch + 1));
-        else if (c->ykind) LAUNCH(c, (k_fft_y8<1, 1>), gy, dim3(sp->y8_threads), sp->shy8, c->stream, c->g, n2g, ncol_y, ykchunk_c, (const cpx *)c->d_twy, (const cpx *)c->scr_twyd, S, mode_spec, kpc * ch, kpc * (ch + 1));
-        else LAUNCH(c, (k_fft_y8r<1>), gy, dim3(sp->y8_threads), sp->shy8r, c->stream, c->g, n2g, ncol, ykchunk_c, (const cpx *)c->d_twy, S, mode_spec, kpc * ch, kpc * (ch + 1)); }
-      if (int e = exchange_chunk(1, ch)) return e;
-    }
-    for (int ch = 0; ch < NCH; ++ch) {
-      HIPCHK(c, hipStreamWaitEvent(c->stream, ev_arrived[ch], 0));
-      ProfScope ps(c, "fft_x_bwd");
-      const long rb = (long)n[1] * kpc * ch, re = rb + rows_c;
-      if (c->xkind) LAUNCH(c, (k_fft_x8<1, 1>), dim3(xblocks_c), dim3(sp->x8_threads), sp->shx8, c->stream, c->g, nh, xiters_c, (const cpx *)c->d_twx, (const cpx *)c->d_twx_post, (const cpx *)c->d_twy_post, pp, c->normfft, S, slab_spec, FillArgs{}, rb, re);
-      else LAUNCH(c, (k_fft_x8<1, 0>), dim3(xblocks_c), dim3(sp->x8_threads), sp->shx8, c->stream, c->g, nh, xiters_c, (const cpx *)c->d_twx, (const cpx *)c->d_twx_post, (const cpx *)c->d_twy_post, pp, c->normfft, S, slab_spec, FillArgs{}, rb, re);
-    }
-  } else {
-  { ProfScope ps(c, "fft_y_bwd");
-    if (c->ykind >= 5) LAUNCH(c, k_dst1<1>, dim3(ncol, n[2]), dim3(256), (size_t)2 * (VS->p1y.N + 1) * sizeof(cpx), c->stream, c->g, VS->p1y, ncol, (const cpx *)VS->tw1y, pp, 1., S, mode_spec, c->ykind, 1);
-    else if (c->ykind == 3) LAUNCH(c, k_fft_y4<0>, dim3((ncol + sp->CBy4 - 1) / sp->CBy4, n[2]), dim3(256), sp->shy4, c->stream, c->g, sp->py4, sp->CBy4, ncol, (const cpx *)c->d_twy4, (const cpx *)c->d_tw4y, S, mode_spec);
-    else if (c->ykind == 4) LAUNCH(c, k_fft_y4<1>, dim3((ncol + sp->CBy4 - 1) / sp->CBy4, n[2]), dim3(256), sp->shy4, c->stream, c->g, sp->py4, sp->CBy4, ncol, (const cpx *)c->d_twy4, (const cpx *)c->d_tw4y, S, mode_spec);
-    else if (use16y) launch_y16(1, dim3((ncol_y + 7) / 8, ychunks), ykchunk, 0, -1);
-    else if (use8y && c->ykind) LAUNCH(c, (k_fft_y8<1, 1>), dim3((ncol_y + CB8 - 1) / CB8, ychunks), dim3(sp->y8_threads), sp->shy8, c->stream, c->g, n2g, ncol_y, ykchunk, (const cpx *)c->d_twy, (const cpx *)c->scr_twyd, S, mode_spec);
-    else if (use8y) LAUNCH(c, (k_fft_y8r<1>), dim3((ncol + CB8 - 1) / CB8, ychunks), dim3(sp->y8_threads), sp->shy8r, c->stream, c->g, n2g, ncol, ykchunk, (const cpx *)c->d_twy, S, mode_spec);
-    else LAUNCH(c, k_fft_y<1>, dim3((ncol + sp->CBy - 1) / sp->CBy, n[2]), dim3(256), sp->shy, c->stream, c->g, sp->py, sp->CBy, ncol, c->ykind, (const cpx *)c->d_twy, (const cpx *)c->scr_twyd, S, mode_spec); }
-  if (dist) { ProfScope ps(c, "alltoall"); if (c->comm.a2a(c->comm.user, 1, a2a_count)) { c->err = "alltoall callback failed"; return 1; } }
-  { ProfScope ps(c, "fft_x_bwd");
-    if (use8x && c->xkind) LAUNCH(c, (k_fft_x8<1, 1>), dim3(xblocks_b), dim3(sp->x8_threads), sp->shx8, c->stream, c->g, nh, xiters_b,
-                                   (const cpx *)c->d_twx, (const cpx *)c->d_twx_post, (const cpx *)c->d_twy_post, pp, c->normfft, S, slab_spec);
-    else if (use8x) LAUNCH(c, (k_fft_x8<1, 0>), dim3(xblocks_b), dim3(sp->x8_threads), sp->shx8, c->stream, c->g, nh, xiters_b,
-                                   (const cpx *)c->d_twx, (const cpx *)c->d_twx_post, (const cpx *)c->d_twy_post, pp, c->normfft, S, slab_spec);
-    else if (c->xkind >= 5) LAUNCH(c, k_dst1<2>, dim3((unsigned)nrows), dim3(256), (size_t)2 * (VS->p1x.N + 1) * sizeof(cpx), c->stream, c->g, VS->p1x, 0, (const cpx *)VS->tw1x, pp, c->normfft, S, slab_spec, c->xkind, 1);
-    else if (c->xkind == 3) LAUNCH(c, (k_fft_x4<1, 0>), dim3((unsigned)((nrows + sp->Rx - 1) / sp->Rx)), dim3(256), sp->shx, c->stream, c->g, sp->px, sp->Rx,
-                       (const cpx *)c->d_twx, (const cpx *)c->d_tw4x, pp, c->normfft, S, slab_spec);
-    else if (c->xkind == 4) LAUNCH(c, (k_fft_x4<1, 1>), dim3((unsigned)((nrows + sp->Rx - 1) / sp->Rx)), dim3(256), sp->shx, c->stream, c->g, sp->px, sp->Rx,
-                       (const cpx *)c->d_twx, (const cpx *)c->d_tw4x, pp, c->normfft, S, slab_spec);
-    else LAUNCH(c, k_fft_x<1>, dim3((unsigned)((nrows + sp->Rx - 1) / sp->Rx)), dim3(256), sp->shx, c->stream, c->g, sp->px, sp->Rx, c->xkind,
-                       (const cpx *)c->d_twx, (const cpx *)c->d_twx_post, (const cpx *)c->d_twy_post, pp, c->normfft, S, slab_spec); }
+  if (refnull) LAUNCH(c, k_null_column, dim3(1), dim3(64), 0, c->stream, c->g, S, nz, P.periodic_z ? 1 : 0, da, db, dc, P.lamx, P.lamy, mode_spec, c->d_nullw, 1);
+  if (F.mean_mask && pipe) if (int e = op_force_from_partials(c, F.mean_mask, F.part, (int)(xblocks_c * NCH))) return e;
+  for (int ch = 0; ch < NCH; ++ch) {
+    { ProfScope ps(c, "fft_y_bwd");
+      fft_y<1>(c, P, pp, S, mode_spec, ncol, ncol_y, ykc, k0_of(ch), k1_of(ch)); }
+    if (pipe) if (int e = exchange_chunk(1, ch)) return e;
+  }
+  if (dist && !pipe) { ProfScope ps(c, "alltoall"); if (c->comm.a2a(c->comm.user, 1, a2a_count)) { c->err = "alltoall callback failed"; return 1; } }
+  for (int ch = 0; ch < NCH; ++ch) {
+    if (pipe) HIPCHK(c, hipStreamWaitEvent(c->stream, ev_arrived[ch], 0));
+    long rb, re; rows_of(ch, rb, re);
+    ProfScope ps(c, "fft_x_bwd");
+    fft_x<1>(c, P, pp, S, slab_spec, xblk_b, xit_b, nullptr, rb, re);
   }
   LAUNCHCHK(c);
   return 0;
 }
 
-// the kernels the pressure solve of this context takes (cales_describe_plan): the selections of solve_field above, by name
+// the kernels the pressure solve of this context takes (cales_describe_plan): its path, by name
 std::string solver_path_name(cales_ctx *c) {
-  SolverPlans *sp = find_plans(c);
-  if (!sp) return "unset";
+  if (!c->solver) return "unset";
+  const SolvePath &P = c->solver->pres;
   static const char *kinds[] = {"PP", "NN", "DD", "ND", "DN"};
-  const bool use8x = sp->x8 && c->xkind <= 1, use8y = sp->y8 && c->ykind <= 1;
-  const bool perz = CBP(c, 0, 3) == 'P' && CBP(c, 1, 3) == 'P';
-  const int nz = c->n[2];
-  const bool hasd = CBP(c, 0, 3) == 'D' || CBP(c, 1, 3) == 'D';
-  const bool tile = !(c->xkind && !c->ykind) && (perz || hasd || !c->fl.keep_null_mode) && !(nz < (perz ? 4 : 2) || nz > 1024 || c->fl.gaussel_march);
-  std::string s = std::string("x:") + kinds[c->xkind] + (use8x ? "/radix8" : c->xkind >= 3 ? "/dct4" : "/mixed_radix");
-  s += std::string(",y:") + kinds[c->ykind] + (use8y ? (c->ykind ? "/radix8" : "/radix8_register_ends") : c->ykind >= 3 ? "/dct4" : "/mixed_radix");
-  s += std::string(",z:") + (c->xkind && !c->ykind ? "thomas_hermitian" : tile ? (perz ? "lds_tile_periodic" : "lds_tile") : "thomas_march");
-  if (c->nyq_ok) s += ",modes_0_and_n1/2:one_column";
+  std::string s = std::string("x:") + kinds[P.xkind] + (P.xk == XKernel::fft_x8 ? "/radix8" : P.xk == XKernel::fft_x4 ? "/dct4" : "/mixed_radix");
+  s += std::string(",y:") + kinds[P.ykind] + (radix8_y(P.yk) ? (P.ykind ? "/radix8" : "/radix8_register_ends") : P.yk == YKernel::fft_y4 ? "/dct4" : "/mixed_radix");
+  s += std::string(",z:") + (P.zk == ZKernel::herm ? "thomas_hermitian" : P.zk == ZKernel::tile ? (P.periodic_z ? "lds_tile_periodic" : "lds_tile") : "thomas_march");
+  if (P.nyq) s += ",modes_0_and_n1/2:one_column";
   if (c->fl.keep_null_mode) s += ",null_mode:reference_order";
   return s;
 }
 
 int op_solver(cales_ctx *c) {
-  return solve_field(c, c->f[CALES_PP], c->d_a, c->d_b, c->d_c, c->n[2], 1., CBP(c, 0, 3) == 'P' && CBP(c, 1, 3) == 'P', true);
+  if (!c->solver) { c->err = "solver not initialised"; return 1; }
+  return solve_field(c, c->solver->pres, c->f[CALES_PP], c->d_a, c->d_b, c->d_c, 1.);
 }
 
 // z-only Helmholtz systems have the same matrix for every column (no eigenvalue shift): the pivots z_l and c'_l of the
@@ -2353,11 +2370,12 @@ int op_helmholtz_z(cales_ctx *c, int ivel, real alpha) {
   const int *n = c->n; const int n3 = n[2];
   const bool fused = c->defer_imp_rhs;
   int has[2] = {0, 0};
-  const char *bcz0 = &c->cbcvel[6 * (ivel - 1) + 4];
-  const int q0 = (ivel == 3 && bcz0[1] == 'D') ? 1 : 0;
-  // the in-LDS sweep evaluates the boundary term itself (RhsBz): no pass, no plane
-  const bool tile_path = !(bcz0[0] == 'P' && bcz0[1] == 'P') && !c->fl.helmholtz_z_per_column && n3 - q0 >= 2 && n3 - q0 <= 512 &&
-                         n3 <= 64 * (n3 - q0 <= 128 ? 2 : n3 - q0 <= 256 ? 4 : 8) && !c->fl.gaussel_march;
+  const char *bcz = &c->cbcvel[6 * (ivel - 1) + 4];
+  const int q = (ivel == 3 && bcz[1] == 'D') ? 1 : 0;
+  const bool periodic = bcz[0] == 'P' && bcz[1] == 'P';
+  // the in-LDS tile of the pressure solve on the real field (u, dudtd in, u out: 3 words instead of 5) where its nz + q planes fit; it evaluates the
+  // boundary term itself (RhsBz): no pass, no plane
+  const bool tile_path = !periodic && !c->fl.helmholtz_z_per_column && tile_takes(c, n3 - q, false) && n3 - q <= 512 && n3 <= 64 * (n3 - q <= 128 ? 2 : n3 - q <= 256 ? 4 : 8);
   RhsBz RB[2] = {};
   if (fused && tile_path) rhs_b_velz_args(c, ivel, alpha, RB, has);
   else if (int e = op_rhs_b_velz(c, ivel, alpha, fused ? c->scr2 : nullptr, fused ? has : nullptr)) return e;
@@ -2368,28 +2386,24 @@ int op_helmholtz_z(cales_ctx *c, int ivel, real alpha) {
     if (!c->d_hztab) { const hipError_t e = hipMalloc(&c->d_hztab, (size_t)12 * 3 * 64 * 16 * sizeof(real)); if (e != hipSuccess) c->d_hztab = nullptr; }
     if (c->d_hztab) {
       int sl = -1;
-      for (int q4 = 0; q4 < 4; ++q4) { const auto &h4 = c->hz_tab[ivel - 1][q4]; if (h4.ok && h4.alpha == alpha && h4.nz == n3 - q0) sl = q4; }
+      for (int q4 = 0; q4 < 4; ++q4) { const auto &h4 = c->hz_tab[ivel - 1][q4]; if (h4.ok && h4.alpha == alpha && h4.nz == n3 - q) sl = q4; }
       hz_ready = sl >= 0;
-      if (sl < 0) { sl = c->hz_next[ivel - 1]; c->hz_next[ivel - 1] = (sl + 1) % 4; c->hz_tab[ivel - 1][sl].alpha = alpha; c->hz_tab[ivel - 1][sl].nz = n3 - q0; c->hz_tab[ivel - 1][sl].ok = true; }
+      if (sl < 0) { sl = c->hz_next[ivel - 1]; c->hz_next[ivel - 1] = (sl + 1) % 4; c->hz_tab[ivel - 1][sl].alpha = alpha; c->hz_tab[ivel - 1][sl].nz = n3 - q; c->hz_tab[ivel - 1][sl].ok = true; }
       hz = c->d_hztab + (size_t)(4 * (ivel - 1) + sl) * 3 * 64 * 16;
     }
   }
   if (!hz_ready) LAUNCH(c, k_scale_abc, dim3((n3 + 63) / 64), dim3(64), 0, c->stream, n3, alpha, c->d_av[ivel - 1], c->d_bv[ivel - 1], c->d_cv[ivel - 1], abc, abc + n3, abc + 2 * n3);
-  const char *bcz = &c->cbcvel[6 * (ivel - 1) + 4];
-  const int q = (ivel == 3 && bcz[1] == 'D') ? 1 : 0;
-  const bool periodic = bcz[0] == 'P' && bcz[1] == 'P';
   dim3 b(64, 4), gr((n[0] + 63) / 64, (n[1] + 3) / 4);
   real *fld = c->f[CALES_U + ivel - 1];
   Spec S; S.blocked = 0; S.cw = 0; S.n2l = n[1]; S.n3 = n3;
   if (periodic) LAUNCH(c, (k_gaussel<real, 1>), gr, b, 0, c->stream, c->g, n3 - q, n[0], n[1], 1, 0, n[0], S, 1., abc, abc + n3, abc + 2 * n3, (const real *)nullptr, (const real *)nullptr, fld, c->scr1, c->scr2, 0);
   else if (c->fl.helmholtz_z_per_column) LAUNCH(c, (k_gaussel<real, 0>), gr, b, 0, c->stream, c->g, n3 - q, n[0], n[1], 1, 0, n[0], S, 1., abc, abc + n3, abc + 2 * n3, (const real *)nullptr, (const real *)nullptr, fld, c->scr1, c->scr2, 0);
-  else if (c->P >= 1 && n3 - q >= 2 && n3 - q <= 512 && n3 <= 64 * (n3 - q <= 128 ? 2 : n3 - q <= 256 ? 4 : 8) && !c->fl.gaussel_march && [&]() {
-             // the in-LDS tile of the pressure solve on the real field: u, dudtd in, u out (3 words instead of 5)
-             TileMap T{}; T.nolam = 1; T.nq = n3;
-             if (fused) { T.dud = c->f[CALES_DUDTD + ivel - 1] + 1; T.hf12 = c->hf12; T.force = c->C.is_forced[ivel - 1] ? c->d_force + (ivel - 1) : nullptr;
-                          T.blo = RB[0]; T.bhi = RB[1]; T.has_lo = has[0]; T.has_hi = has[1]; }
-             return gaussel_tile<2>(c, n3 - q, n[0], n[1], 1., abc, abc + n3, abc + 2 * n3, fld + 1, 0, T, hz, hz_ready); }()) {}
-  else {
+  else if (tile_path) {
+    TileMap T{}; T.nolam = 1; T.nq = n3;
+    if (fused) { T.dud = c->f[CALES_DUDTD + ivel - 1] + 1; T.hf12 = c->hf12; T.force = c->C.is_forced[ivel - 1] ? c->d_force + (ivel - 1) : nullptr;
+                 T.blo = RB[0]; T.bhi = RB[1]; T.has_lo = has[0]; T.has_hi = has[1]; }
+    gaussel_tile<2>(c, n3 - q, n[0], n[1], 1., abc, abc + n3, abc + 2 * n3, c->solver->pres.lamx, c->solver->pres.lamy, fld + 1, 0, T, hz, hz_ready);
+  } else {
     real *zz = abc + 3 * n3, *dd = abc + 4 * n3;       // behind the scaled coefficients (cales_create reserves 6 (n3+2) doubles)
     LAUNCH(c, k_thomas_coef, dim3(1), dim3(64), 0, c->stream, n3 - q, abc, abc + n3, abc + 2 * n3, zz, dd);
     if (fused) LAUNCH(c, k_gaussel_cols_rhs, gr, b, 0, c->stream, c->g, n3 - q, n3, abc, zz, dd, fld, c->f[CALES_DUDTD + ivel - 1], c->hf12,
@@ -2408,7 +2422,7 @@ int op_helmholtz_z(cales_ctx *c, int ivel, real alpha) {
 // Built on first use. (As in the reference, the face-centred NN and ND sets are not exact inverses of the discrete operator -- REDFT00 of n
 // points goes with eigenvalues of period n, REDFT10 with half-integer ones; measured on the oracle: residual of (1 + alpha L) x = r of a
 // few per cent -- while PP, DD and DN are exact to round-off. They are provided because the reference provides them.)
-static int velset_build(cales_ctx *c, SolverPlans &sp, int iv, VelSet &V) {
+static int velocity_path(cales_ctx *c, Solver &s, int iv, SolvePath &V) {
   const int n1 = c->C.ng[0], n2g = c->C.ng[1];
   const char *bc = &c->cbcvel[6 * iv];
   auto kind = [&](int d) -> int {
@@ -2438,61 +2452,32 @@ static int velset_build(cales_ctx *c, SolverPlans &sp, int iv, VelSet &V) {
   // fft.f90:99,136,142: normfft = prod norm(1) (n + norm(2) - ix): 1 n (PP), 2 n ('c' pairs, 'f' ND/DN), 2 (n + 1 - 1) ('f' DD), 2 (n - 1) ('f' NN)
   auto nrm = [](int kd, int nn) -> real { return kd == 0 ? (real)nn : kd == 6 ? 2. * (nn - 1) : 2. * nn; };
   V.normfft = 1. / (nrm(V.xkind, n1) * nrm(V.ykind, n2g));
-  auto mk = [&](int N, real **dev) -> int {
-    std::vector<real> t(2 * (size_t)N); const real pi = std::acos(-1.0);
-    for (int q = 0; q < N; ++q) { const real ang = -2. * pi * q / N; t[2 * q] = std::cos(ang); t[2 * q + 1] = std::sin(ang); }
-    HIPCHK(c, hipMalloc(dev, t.size() * sizeof(real)));
-    HIPCHK(c, hipMemcpy(*dev, t.data(), t.size() * sizeof(real), hipMemcpyHostToDevice));
-    return 0;
-  };
   auto next = [](int kd, int nn) { return kd == 5 ? 2 * nn : kd == 6 ? 2 * (nn - 1) : 4 * nn; };      // points of the symmetric extension (k_dst1)
   if (V.xkind >= 5) { const int N = next(V.xkind, n1);
-    if (N < 2 || !make_plan(N, V.p1x) || (size_t)2 * (N + 1) * sizeof(cpx) > 150 * 1024) { c->err = "helmholtz: x line not supported by the face-centred transform kernel"; return 1; } if (mk(N, &V.tw1x)) return 1; }
+    if (N < 2 || !make_plan(N, V.p1x) || (size_t)2 * (N + 1) * sizeof(cpx) > 150 * 1024) { c->err = "helmholtz: x line not supported by the face-centred transform kernel"; return 1; } if (upload_twiddles(c, N, N, &V.tw1x)) return 1; }
   if (V.ykind >= 5) { const int N = next(V.ykind, n2g);
-    if (N < 2 || !make_plan(N, V.p1y) || (size_t)2 * (N + 1) * sizeof(cpx) > 150 * 1024) { c->err = "helmholtz: y line not supported by the face-centred transform kernel"; return 1; } if (mk(N, &V.tw1y)) return 1; }
+    if (N < 2 || !make_plan(N, V.p1y) || (size_t)2 * (N + 1) * sizeof(cpx) > 150 * 1024) { c->err = "helmholtz: y line not supported by the face-centred transform kernel"; return 1; } if (upload_twiddles(c, N, N, &V.tw1y)) return 1; }
   if (V.xkind >= 5 || V.ykind >= 5) { HIPSOFT(c, hipFuncSetAttribute((const void *)k_dst1<0>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024)); HIPSOFT(c, hipFuncSetAttribute((const void *)k_dst1<1>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024)); HIPSOFT(c, hipFuncSetAttribute((const void *)k_dst1<2>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024)); }
   // the DCT-IV / DST-IV kernels (kinds 3, 4) read tables that solver_setup makes only when the pressure needs them
-  const real pi = std::acos(-1.0);
-  if ((V.xkind == 3 || V.xkind == 4) && !c->d_tw4x) {
-    const int nh = n1 / 2; std::vector<real> t(4 * (size_t)nh);
-    for (int q = 0; q < nh; ++q) { const real a1 = -pi * (4. * q + 1.) / (4. * n1), a2 = -pi * q / (real)n1;
-                                   t[2 * q] = std::cos(a1); t[2 * q + 1] = std::sin(a1); t[2 * (nh + q)] = std::cos(a2); t[2 * (nh + q) + 1] = std::sin(a2); }
-    HIPCHK(c, hipMalloc(&c->d_tw4x, t.size() * sizeof(real)));
-    HIPCHK(c, hipMemcpy(c->d_tw4x, t.data(), t.size() * sizeof(real), hipMemcpyHostToDevice));
-  }
-  if ((V.ykind == 3 || V.ykind == 4) && !c->d_tw4y) {
-    if (!make_plan(n2g / 2, sp.py4)) { c->err = "helmholtz: ng(2)/2 must factor into primes <= 127"; return 1; }
-    sp.CBy4 = 4; sp.shy4 = (size_t)2 * sp.CBy4 * 2 * (n2g / 2 + 1) * sizeof(cpx);
-    while (sp.shy4 > 60 * 1024 && sp.CBy4 > 1) { sp.CBy4 /= 2; sp.shy4 = (size_t)2 * sp.CBy4 * 2 * (n2g / 2 + 1) * sizeof(cpx); }
-    if (sp.shy4 > 64 * 1024) { c->err = "helmholtz: y line too long for the LDS-resident DCT-IV"; return 1; }
-    const int nh2 = n2g / 2; std::vector<real> t(4 * (size_t)nh2);
-    for (int q = 0; q < nh2; ++q) { const real a1 = -pi * (4. * q + 1.) / (4. * n2g), a2 = -pi * q / (real)n2g;
-                                    t[2 * q] = std::cos(a1); t[2 * q + 1] = std::sin(a1); t[2 * (nh2 + q)] = std::cos(a2); t[2 * (nh2 + q) + 1] = std::sin(a2); }
-    HIPCHK(c, hipMalloc(&c->d_tw4y, t.size() * sizeof(real)));
-    HIPCHK(c, hipMemcpy(c->d_tw4y, t.data(), t.size() * sizeof(real), hipMemcpyHostToDevice));
-    if (!c->d_twy4) { if (mk(n2g / 2, &c->d_twy4)) return 1; }
-  }
-  V.ready = true;
+  if ((V.xkind == 3 || V.xkind == 4) && !s.tw4x && upload_dct4_weights(c, n1, &s.tw4x)) return 1;
+  if ((V.ykind == 3 || V.ykind == 4) && dct4_y_setup(c, s, "helmholtz")) return 1;
+  const char *bcz = &c->cbcvel[6 * iv + 4];
+  V.nz = c->n[2] - ((iv == 2 && bcz[1] == 'D') ? 1 : 0); V.periodic_z = bcz[0] == 'P' && bcz[1] == 'P'; V.poisson = false;
+  V.cw = c->cw;
+  choose_kernels(c, s, V);
   return 0;
 }
 int op_helmholtz(cales_ctx *c, int ivel, real alpha) {
   if (c->C.impdiff != 1) { c->err = "helmholtz needs impdiff = 1"; return 1; }
-  PlanSlot *slot = find_slot(c);
-  if (!slot) { c->err = "solver not initialised"; return 1; }
-  VelSet &V = slot->vs[ivel - 1];
-  if (!V.ready) if (int e = velset_build(c, slot->sp, ivel - 1, V)) return e;
+  Solver *s = c->solver;
+  if (!s) { c->err = "solver not initialised"; return 1; }
+  SolvePath &V = s->vel[ivel - 1];
+  if (!s->vel_ready[ivel - 1]) { if (int e = velocity_path(c, *s, ivel - 1, V)) return e; s->vel_ready[ivel - 1] = true; }
   ProfScope ps(c, "helmholtz_xyz");
   const int n3 = c->n[2];
   if (int e = op_rhs_b_velxy(c, ivel, alpha)) return e;      // main.f90:424-431: boundary terms of the x and y faces, then z
   if (int e = op_rhs_b_velz(c, ivel, alpha)) return e;
   real *abc = c->d_red + 64 + 16 * (n3 + 2);
   LAUNCH(c, k_scale_abc, dim3((n3 + 63) / 64), dim3(64), 0, c->stream, n3, alpha, c->d_av[ivel - 1], c->d_bv[ivel - 1], c->d_cv[ivel - 1], abc, abc + n3, abc + 2 * n3);
-  const char *bcz = &c->cbcvel[6 * (ivel - 1) + 4];
-  const int q = (ivel == 3 && bcz[1] == 'D') ? 1 : 0;
-  // the solve runs with the component's kinds, eigenvalues and normalisation in place of the pressure's
-  const int xk = c->xkind, yk = c->ykind; real *lx = c->d_lamx, *ly = c->d_lamy; const real nf = c->normfft;
-  c->xkind = V.xkind; c->ykind = V.ykind; c->d_lamx = V.lamx; c->d_lamy = V.lamy; c->normfft = V.normfft; c->cur_velset = &V;
-  const int e = solve_field(c, c->f[CALES_U + ivel - 1], abc, abc + n3, abc + 2 * n3, n3 - q, alpha, bcz[0] == 'P' && bcz[1] == 'P', false);
-  c->xkind = xk; c->ykind = yk; c->d_lamx = lx; c->d_lamy = ly; c->normfft = nf; c->cur_velset = nullptr;
-  return e;
+  return solve_field(c, V, c->f[CALES_U + ivel - 1], abc, abc + n3, abc + 2 * n3, alpha);
 }
