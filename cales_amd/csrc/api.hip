@@ -158,6 +158,7 @@ void cales_destroy(cales_ctx *c) {
   delete c;
 }
 
+static bool fold_correc_possible(const cales_ctx *c);      // (with make_plan below)
 int cales_create(const cales_case *cs, void *stream, cales_ctx **out) {
   if (!cs || !out) { g_create_err = "null argument"; return 1; }
   *out = nullptr;
@@ -221,6 +222,10 @@ int cales_create(const cales_case *cs, void *stream, cales_ctx **out) {
   std::vector<real> hb[11][3];
   hs_initbc(c, hb);
   for (int q = 0; q < 11; ++q) if (upload_bound(c, *bs[q], hb[q])) return fail(6);
+  // walls (sgs.f90:70-83,154-171); those in y are global properties of the case, not of the slab (distances use global indices)
+  for (int d = 1; d <= 3; ++d) for (int s = 0; s <= 1; ++s) c->is_wall[s + 2 * (d - 1)] = (ISB(c, s, d) && CBV(c, s, d, d) == 'D') ? 1. : 0.;
+  for (int s = 0; s <= 1; ++s) c->is_wall[s + 2] = (!(cs->cbcpre[2] == 'P' && cs->cbcpre[3] == 'P') && CBV(c, s, 2, 2) == 'D') ? 1. : 0.;
+  sgs_setup(c);      // the form of cmpt_sgs: which scratch fields it needs, whether the projection can fold into it
   // pressure boundary r.h.s. (main.f90:317, bound.f90:447-499)
   { const int *n = c->n;
     const real dx01[2] = {c->dl[0], c->dl[0]}, dy01[2] = {c->dl[1], c->dl[1]};
@@ -232,8 +237,9 @@ int cales_create(const cales_case *cs, void *stream, cales_ctx **out) {
     if (upload_vec(c, &c->rhsbp[0], rx) || upload_vec(c, &c->rhsbp[1], ry) || upload_vec(c, &c->rhsbp[2], rz)) return fail(7); }
   // fields (haloed); r.h.s. buffers use the same layout so every kernel shares one index
   const int nfields = cs->impdiff ? CALES_NFIELDS : CALES_DUDTD;
-  // several slabs with the dynamic model: companions behind u, v, w (both buffer sets) and two behind pp (common.hpp, vel_comp)
-  c->vel_comp = P > 1 && cs->sgstype == 2;
+  // several slabs where some plan can take StepPlan::fold_rows2 (three fields under 4 GB, four rows per slab, the one-launch ghost-cell kernel):
+  // companions behind u, v, w (both buffer sets) and two behind pp (common.hpp, vel_comp)
+  c->vel_comp = P > 1 && fold_correc_possible(c) && c->n[1] >= 4 && 3 * (c->ntot + 2 * LINE_REALS) * sizeof(real) < (1ull << 32) && !c->fl.unmerged_bc;
   for (int q = 0; q < nfields; ++q) {
     if (q == CALES_PP) continue;
     if (c->vel_comp && q <= CALES_W) { real *two[2]; if (field_alloc_multi(c, 2, two)) return fail(8); c->f[q] = two[0]; }
@@ -250,9 +256,6 @@ int cales_create(const cales_case *cs, void *stream, cales_ctx **out) {
   c->res = c->d_red;
   if (hipHostMalloc((void **)&c->h_red, 64 * sizeof(real)) != hipSuccess) { c->err = "hipHostMalloc failed"; return fail(11); }
   // sgs scratch (sgs.f90:70-83,154-171)
-  for (int d = 1; d <= 3; ++d) for (int s = 0; s <= 1; ++s) c->is_wall[s + 2 * (d - 1)] = (ISB(c, s, d) && CBV(c, s, d, d) == 'D') ? 1. : 0.;
-  // wall flags are global properties of the case, not of the slab (distances use global indices)
-  for (int s = 0; s <= 1; ++s) c->is_wall[s + 2] = (!(cs->cbcpre[2] == 'P' && cs->cbcpre[3] == 'P') && CBV(c, s, 2, 2) == 'D') ? 1. : 0.;
   if (cs->sgstype >= 1) {
     if (field_alloc(c, &c->s0)) return fail(12);
     const int nw = cs->sgstype == 1 ? 3 : 6;
@@ -262,13 +265,14 @@ int cales_create(const cales_case *cs, void *stream, cales_ctx **out) {
     if (field_alloc(c, &c->uc) || field_alloc(c, &c->vc) || field_alloc(c, &c->wc) || field_alloc(c, &c->uf) ||
         field_alloc(c, &c->vf) || field_alloc(c, &c->wf) || field_alloc(c, &c->alph2) || dev_alloc(c, &c->d_p1d, 2 * (size_t)n3 + 2))
       return fail(13);
-    if (dsmag_pairs(c)) {      // |S|Sij as three fields of pairs between K_AC and the fused last pass: the twelve scalar scratch fields of the other forms are not needed
+    if (c->sgs.pair) {      // |S|Sij as three fields of pairs between K_AC and the fused last pass: the twelve scalar scratch fields of the other forms are not needed
       for (int m = 0; m < 3; ++m) { real *b = nullptr; if (dev_alloc(c, &b, 2 * c->ntot + 2 * LINE_REALS)) return fail(13); c->ss2[m] = b + 2 * c->field_ofs; }
     } else
     for (int m = 0; m < 6; ++m) if (field_alloc(c, &c->sij[m]) || field_alloc(c, &c->mij[m])) return fail(13);
   }
   if (solver_setup(c)) return fail(14);
   { hipDeviceProp_t pr; int dev = 0; if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&pr, dev) == hipSuccess) c->ncu = pr.multiProcessorCount; }
+  if (sgs_setup_launches(c)) return fail(14);
   if (hipStreamSynchronize(c->stream) != hipSuccess) { c->err = "sync failed"; return fail(15); }
   if (!c->launch_err.empty()) { c->err = c->launch_err; return fail(16); }      // a set-up kernel (twiddles, tables) or attribute call failed
   *out = c;
@@ -365,7 +369,7 @@ int cales_helmholtz(cales_ctx *c, int ivel, real alpha) { ENTRY(c, op_helmholtz(
 int cales_helmholtz_z(cales_ctx *c, int ivel, real alpha) { if (ivel < 1 || ivel > 3) { c->err = "ivel must be 1..3"; return 1; } ENTRY(c, op_helmholtz_z(c, ivel, alpha)); }
 int cales_correc(cales_ctx *c, real dtrk) { ENTRY(c, op_correc(c, dtrk)); }
 int cales_updatep(cales_ctx *c, real alpha) { ENTRY(c, op_updatep(c, alpha)); }
-int cales_cmpt_sgs(cales_ctx *c) { ENTRY(c, op_cmpt_sgs(c)); }
+int cales_cmpt_sgs(cales_ctx *c) { ENTRY(c, op_cmpt_sgs(c, nullptr)); }
 int cales_chkdt(cales_ctx *c, real *dtmax) { ENTRY(c, op_chkdt(c, dtmax)); }
 int cales_chkdiv(cales_ctx *c, real *divtot, real *divmax) { ENTRY(c, op_chkdiv(c, divtot, divmax)); }
 int cales_out1d_single_point_chan(cales_ctx *c, real *buf) { if (!c || !buf) return 1; ENTRY(c, op_stats_chan(c, buf)); }
@@ -462,34 +466,45 @@ static int finish_pending(cales_ctx *c) {
 }
 // ---- the plan of a step (StepPlan, common.hpp): every decision about WHICH form of an operator a substep takes is made here, from the case, the
 // switches and the state recorded in the plan's in_* fields -- step_body below only reads the result.
+// The conditions of the plan known when the context is created (all but comm.on and the solver's radix-8 x plan): cales_create allocates the companion
+// fields of fold_rows2 from them too (vel_comp). fillps inside the forward x transform: homogeneous pressure BCs (no boundary r.h.s.)
+static bool fuse_fill_possible(const cales_ctx *c) {
+  bool ok = !c->fl.unfused_fillps;
+  for (int d = 0; d < 3; ++d) ok = ok && ((c->C.bcpre[2 * d] == 0. && c->C.bcpre[2 * d + 1] == 0.) || c->C.cbcpre[2 * d] == 'P');
+  return ok;
+}
+// xskip: periodic x, explicit diffusion, no wall model, the fused passes everywhere -- every kernel of the step wraps around instead of reading x ghost
+// columns, which are then left alone until the step returns (common.hpp, step_xskip)
+static bool xskip_possible(const cales_ctx *c) {
+  const Flags &fl = c->fl;
+  bool ok = !fl.xghosts_in_step && CBP(c, 0, 1) == 'P' && CBP(c, 1, 1) == 'P' && c->C.impdiff == 0 && !fl.unfused_rk && !fl.unfused_correc && c->sgs.wraps_x;
+  for (int q = 0; q < 6; ++q) ok = ok && c->C.lwm[q] == 0;
+  return ok;
+}
+// fold_correc: dynamic model with |S|Sij as pair fields (SgsPath::pair: x and y periodic), z periodic or two no-slip walls, xskip: the projection
+// u = u* - dtrk grad(pp) (+ the deferred forcing) and p += pp are folded into the strain-rate pass of cmpt_sgs, which reads the velocity anyway --
+// the correction pass (9 words per cell) disappears (dsmag_fast, k_corr_strain_tile)
+static bool fold_correc_possible(const cales_ctx *c) {
+  bool ok = fuse_fill_possible(c) && xskip_possible(c) && c->sgs.pair && !c->fl.unfolded_correc && c->n[0] % 64 == 0;      // (whole 64-cell tiles in x)
+  const bool perz = CBV(c, 0, 3, 3) == 'P' && CBV(c, 1, 3, 3) == 'P';
+  bool walls = CBP(c, 0, 3) == 'N' && CBP(c, 1, 3) == 'N';
+  for (int iv = 1; iv <= 3; ++iv) for (int sd = 0; sd <= 1; ++sd) walls = walls && CBV(c, sd, 3, iv) == 'D';
+  // several slabs: the pass reaches the companion field of pp with 32-bit offsets (two fields under 4 GB)
+  // (at least two rows per slab: row 2 goes to the companion field BEFORE the exchange, and with one row per slab "row 2" is the stale ghost row n2+1)
+  return ok && (perz || walls) && (c->P == 1 || (c->n[1] >= 2 && 2 * (c->ntot + 2 * LINE_REALS) * sizeof(real) < (1ull << 32)));
+}
 static void make_plan(cales_ctx *c) {
   StepPlan pl;
   pl.valid = true;
   pl.in_visct_zero = c->visct_zero; pl.in_sgs_first = c->sgs_first; pl.in_comm_on = c->comm.on; pl.in_overlap = c->comm_stream != nullptr;
   const Flags &fl = c->fl;
   for (int q = 0; q < 6; ++q) if (c->C.lwm[q] != 0) pl.any_wm = true;      // (of the case: a face owned by another slab counts)
-  // fillps inside the forward x transform: homogeneous pressure BCs (no boundary r.h.s.) and a radix-8 x plan; the transform then also sums the bulk
-  // means of the forced components (their increment is only needed by the correction kernel)
-  pl.fuse_fill = !fl.unfused_fillps && solver_can_fuse_fillps(c);
-  for (int d = 0; d < 3; ++d) pl.fuse_fill = pl.fuse_fill && ((c->C.bcpre[2 * d] == 0. && c->C.bcpre[2 * d + 1] == 0.) || c->C.cbcpre[2 * d] == 'P');
-  // periodic x, explicit diffusion, no wall model, the fused passes everywhere: every kernel of the step wraps around instead of reading x ghost
-  // columns, which are then left alone until the step returns (common.hpp, step_xskip)
-  pl.xskip = !fl.xghosts_in_step && CBP(c, 0, 1) == 'P' && CBP(c, 1, 1) == 'P' && c->C.impdiff == 0 && !fl.unfused_rk && !fl.unfused_correc &&
-             pl.fuse_fill && sgs_wraps_x(c) && !pl.any_wm;
-  // dynamic model, x and y periodic (|S|Sij as pair fields), z periodic or two no-slip walls, explicit diffusion, no wall model: the projection
-  // u = u* - dtrk grad(pp) (+ the deferred forcing) and p += pp are folded into the strain-rate pass of cmpt_sgs, which reads the velocity anyway --
-  // the correction pass (9 words per cell) disappears (dsmag_fast, k_corr_strain_tile)
-  pl.fold_correc = pl.xskip && c->C.sgstype == 2 && c->C.impdiff == 0 && dsmag_pairs(c) && !fl.unfolded_correc && !fl.unfused_correc && c->n[0] % 64 == 0;      // (whole 64-cell tiles in x)
-  { const bool perz = CBV(c, 0, 3, 3) == 'P' && CBV(c, 1, 3, 3) == 'P';
-    bool walls = true;
-    for (int iv = 1; iv <= 3; ++iv) for (int sd = 0; sd <= 1; ++sd) walls = walls && CBV(c, sd, 3, iv) == 'D';
-    walls = walls && CBP(c, 0, 3) == 'N' && CBP(c, 1, 3) == 'N';
-    pl.fold_correc = pl.fold_correc && (perz || walls);
-    // several slabs: the pass reaches the companion field of pp with 32-bit offsets (two fields under 4 GB), exchanges through the slab hooks
-    // (at least two rows per slab: row 2 goes to the companion field BEFORE the exchange, and with one row per slab "row 2" is the stale ghost row n2+1)
-    if (c->P > 1) pl.fold_correc = pl.fold_correc && c->comm.on && c->n[1] >= 2 && 2 * (c->ntot + 2 * LINE_REALS) * sizeof(real) < (1ull << 32);
-    // ... with a second ghost row of the prediction and a third of pp (companion fields) the pass forms the ghost rows of all its outputs itself
-    pl.fold_rows2 = pl.fold_correc && c->P > 1 && c->vel_comp && c->n[1] >= 4 && 3 * (c->ntot + 2 * LINE_REALS) * sizeof(real) < (1ull << 32) && !fl.unmerged_bc; }
+  // (fuse_fill: the transform then also sums the bulk means of the forced components, whose increment only the correction kernel needs)
+  pl.fuse_fill = fuse_fill_possible(c) && solver_can_fuse_fillps(c);
+  pl.xskip = pl.fuse_fill && xskip_possible(c);
+  pl.fold_correc = pl.xskip && fold_correc_possible(c) && (c->P == 1 || c->comm.on);      // (several slabs: through the slab hooks)
+  // ... with a second ghost row of the prediction and a third of pp (the companion fields: vel_comp) the pass forms the ghost rows of all its outputs itself
+  pl.fold_rows2 = pl.fold_correc && c->vel_comp;
   // no subgrid model, explicit or z-implicit diffusion, no wall model, every direction periodic or between walls with homogeneous Neumann pressure
   // (Taylor-Green, channels, cavities without a model): the projection and pressure update of substeps 1 and 2 are applied by the momentum pass of the
   // NEXT substep while it loads its planes (k_momrk<.., CORR = 1>) -- between the two the fields hold the prediction, whose ghost cells receive the
@@ -573,12 +588,13 @@ static int step_body(cales_ctx *c, real dt) {
   const bool pending_in = c->fold_mom_dtrk != 0.;      // the step before left its last projection to this step's first momentum pass
   LAUNCH(c, k_zero6, dim3(1), dim3(64), 0, c->stream, c->d_force, pending_in ? 3 : 0);     // dpdl(:) = 0
   c->in_step = true;
-  struct Reset { cales_ctx *c; bool keep = false; ~Reset() { c->in_step = false; c->step_xskip = false; c->bc_nride = 0; c->fold_dtrk = 0.; c->fold_rows2 = false; if (!keep) { c->fold_mom_dtrk = 0.; c->fold_mom_pdone = false; } c->bc_view_dtrk = 0.; c->defer_force = false; c->defer_imp_rhs = false; c->fuse_fillps_dti = 0.; c->fuse_mean_mask = 0; c->bc_skip_wm = false; c->skip_rhs_store = false; c->defer_halo = false; c->bc_no_halo = false; } } reset{c};      // also on the error returns
+  struct Reset { cales_ctx *c; bool keep = false; ~Reset() { c->in_step = false; c->step_xskip = false; c->bc_nride = 0; if (!keep) { c->fold_mom_dtrk = 0.; c->fold_mom_pdone = false; } c->bc_view_dtrk = 0.; c->defer_force = false; c->defer_imp_rhs = false; c->fuse_fillps_dti = 0.; c->fuse_mean_mask = 0; c->bc_skip_wm = false; c->skip_rhs_store = false; c->defer_halo = false; c->bc_no_halo = false; } } reset{c};      // also on the error returns
   if (c->pend_xrefresh && !pl.xskip) {      // the step before left the x ghost columns stale and this one reads them
     c->pend_xrefresh = false; c->step_xskip = true;
     if (int e = end_of_step_refresh(c)) return e;
   }
   c->step_xskip = pl.xskip;
+  SgsFold fold{0., pl.fold_rows2, pl.defer_force ? pl.force_mask : 0};      // (pl.fold_correc: the projection each substep leaves to cmpt_sgs)
   for (int irk = 1; irk <= 3; ++irk) {
     const real dtrk = (rk[irk - 1][0] + rk[irk - 1][1]) * dt, dtrki = 1. / dtrk;
     real alpha = 0.;
@@ -634,8 +650,9 @@ static int step_body(cales_ctx *c, real dt) {
       if (int e = op_boundp_multi(c, 2, two, 0)) return e;
     } else
     if (int e = op_boundp(c, c->f[CALES_PP], 0)) return e;
-    if (pl.fold_correc) { c->fold_dtrk = dtrk; c->fold_rows2 = pl.fold_rows2; }      // correc, bounduvw, updatep, boundp(p): inside the cmpt_sgs below (dsmag_fast)
-    else if (pl.fold_mom && (irk < 3 || pl.lazy_last)) {
+    if (pl.fold_correc) {      // correc, bounduvw, updatep, boundp(p): inside the cmpt_sgs below (dsmag_fast)
+      fold.dtrk = dtrk;
+    } else if (pl.fold_mom && (irk < 3 || pl.lazy_last)) {
       // the ghost cells of the projected velocity now (through the corrected view), its interior cells and p + pp in the next momentum pass -- the next
       // substep's, or after the third substep the next step's (finish_pending for every other entry of the C-ABI)
       c->fold_mom_fmask = c->defer_force ? pl.force_mask : 0;
@@ -652,7 +669,7 @@ static int step_body(cales_ctx *c, real dt) {
       c->fold_mom_dtrk = dtrk;
     } else if (int e = project_now(c, dtrk, alpha)) return e;
     c->visct_bc_done = false;
-    { const int e = op_cmpt_sgs(c); c->fold_dtrk = 0.; c->fold_rows2 = false; c->defer_force = false; if (e) return e; }
+    { const int e = op_cmpt_sgs(c, pl.fold_correc ? &fold : nullptr); c->defer_force = false; if (e) return e; }
     if (pl.visct_ghosts && !c->visct_bc_done) { if (int e = op_boundp(c, c->f[CALES_VISCT], 1)) return e; }
     c->visct_bc_done = false;
   }

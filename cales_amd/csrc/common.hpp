@@ -140,6 +140,31 @@ struct StepPlan {
   int mean_mask = 0, force_mask = 0;
 };
 
+// Block -> tile map of the plane-marching tile kernels (band_map below), and the launch geometry of a tile pass (grid: 1-D through bm where bm.gx != 0)
+struct BandMap { int gx, gy, gz, sub; };
+struct TileGeom { dim3 block, grid; int kchunk = 0; BandMap bm{0, 0, 0, 0}; };
+
+// The path of cmpt_sgs (k_sgs.hip), decided once by cales_create (sgs_setup; sgs_setup_launches once the CU count is known) and only read after:
+// op_cmpt_sgs launches it, sgs_path_name prints it, cales_create allocates its scratch fields, make_plan folds the projection only into pair fields.
+enum class SgsForm { none, smag_rows, smag_reference, dsmag_tiles, dsmag_reference };
+// the instantiation of each launch site (32 / 64: unsigned / size_t byte offsets; yw: walls or wall-model faces in y; ucf: the last pass forms the
+// cell-centred velocity). Pair fields imply x and y periodic, 32-bit offsets and ucf: one instantiation each.
+enum class StrainKernel { corr_rows2, corr, yw32, yw64, pair, plain32, plain64 };      // k_corr_strain_tile<unsigned, TYC(, EXT = 1)> | k_strain_tile<OFF, TYS, YW(, PAIR)>
+enum class LmfKernel { pair, yw_ucf32, yw_ucf64, yw32, yw64, ucf32, ucf64, plain32, plain64 };      // k_lmf_tile<OFF, YW, UCF(, PAIR)>
+enum class SmagKernel { yw32, yw64, plain32, plain64 };      // k_smag_rows<OFF, YW>
+struct SgsPath {
+  SgsForm form = SgsForm::none;
+  bool pair = false, lazy = false, ucf = false, small = false, yw = false;      // |S|Sij as pair fields (ss2); lazy: |S| straight into visct (homogeneous sgs BCs)
+  bool wraps_x = true;      // reads wrapped interior columns where x is periodic (cales_step may leave the x ghost columns stale)
+  // static kernel arguments (y walls: dsmag those this rank owns, smag_rows those of the case -- global distances, the shear reaches every slab)
+  int zlo = 0, zhi = 0, wmlo = 0, wmhi = 0, wylo = 0, wyhi = 0, wmylo = 0, wmyhi = 0; real flo = 0., fhi = 0.;
+  int perz = 0, perx = 0, skipz = 0, lmf_ty = 0;
+  StrainKernel strain = StrainKernel::plain64; LmfKernel lmf = LmfKernel::plain64; SmagKernel smag = SmagKernel::plain64;
+  TileGeom strain_geo, corr_geo, corr_rows2_geo, lmf_geo, smag_geo;      // (lmf_geo unbanded: the overlap of cmpt_sgs splits it per call)
+};
+// op_cmpt_sgs inside cales_step: the projection folded into the strain-rate pass (StepPlan::fold_correc; rows2: fold_rows2; fmask: deferred forcing)
+struct SgsFold { real dtrk; bool rows2; int fmask; };
+
 struct KernelStat { std::string name; int64_t calls = 0; real ms = 0.; };
 struct Solver;      // k_solver.hip
 
@@ -179,9 +204,10 @@ struct cales_ctx {
   real *d_force;                    // f(3) + dpdl(3) accumulators on device
   int red_blocks;
   // sgs scratch
-  real *ss2[3] = {nullptr, nullptr, nullptr};      // |S|Sij as three pair fields (2 ntot reals each; dsmag_pairs, k_sgs.hip) instead of sij / mij
+  real *ss2[3] = {nullptr, nullptr, nullptr};      // |S|Sij as three pair fields (2 ntot reals each; SgsPath::pair) instead of sij / mij
   real *s0, *wk[6], *sij[6], *mij[6], *uc, *vc, *wc, *uf, *vf, *wf, *alph2, *d_p1d;
   real is_wall[6];
+  SgsPath sgs;      // see SgsPath above
   bool sgs_first;
   // decomposition
   int P = 1, rank = 0; bool per_y = true; int cw = 0;      // cw: complex mode columns per rank (padded)
@@ -225,9 +251,6 @@ struct cales_ctx {
   // interior column instead (a ghost-column update touches two cache lines per row and field for two values: 1.2 of 45 ms per step at 512^3) -- and
   // are brought up to date once, when the step returns
   bool step_xskip = false;
-  // cales_step, dynamic model on one rank with x and y periodic: the velocity correction and the pressure update of the substep are done by the
-  // strain-rate pass of the cmpt_sgs that follows (k_strain_tile<.., CORR = 1>, k_sgs.hip) -- != 0: the dtrk of the pending projection
-  real fold_dtrk = 0.; bool fold_rows2 = false;      // (fold_rows2: with two ghost rows of the prediction, StepPlan)
   // cales_step without subgrid model (explicit diffusion, one rank, every direction periodic or between no-slip walls with Neumann pressure): the
   // projection of substeps 1 and 2 is applied by the momentum pass of the NEXT substep while it loads its planes (k_momrk<.., CORR = 1>); the ghost
   // cells of the prediction receive their final values through a corrected view in the ghost-cell kernels (bc_view_dtrk). != 0: the dtrk of the
@@ -342,15 +365,15 @@ int op_out2d_duct(cales_ctx *c, real *buf);
 bool solver_can_fuse_fillps(cales_ctx *c);
 int solver_mode_columns(cales_ctx *c);      // complex mode columns per rank of the pressure solve
 std::string solver_path_name(cales_ctx *c);      // which transform / tridiagonal kernels the pressure solve of this context takes (cales_describe_plan)
-const char *sgs_path_name(const cales_ctx *c);      // likewise for cmpt_sgs
+const char *sgs_path_name(const cales_ctx *c);      // likewise for cmpt_sgs (SgsPath)
+void sgs_setup(cales_ctx *c);               // SgsPath: form, flags, static kernel arguments and kernels (needs is_wall)
+int sgs_setup_launches(cales_ctx *c);       // ... and the launch geometry of its tile passes (needs ncu)
 int op_force_from_partials(cales_ctx *c, int mask, const real *part, int nblk);
 int op_correc_updatep(cales_ctx *c, real dtrk, real alpha, int upd);
 int op_updatep(cales_ctx *c, real alpha);
-int op_cmpt_sgs(cales_ctx *c);
-bool dsmag_pairs(const cales_ctx *c);
+int op_cmpt_sgs(cales_ctx *c, const SgsFold *fold);      // fold: the projection folded into the strain-rate pass (cales_step), nullptr: not folded
 int op_boundp_wide(cales_ctx *c, int nf, real **p2, int which);      // ghost cells of pair fields (y, z; x periodic and wrapped by the consumers)
 int op_xwrap_zghost(cales_ctx *c, int nf, real **f);      // periodic copy of the x ghost columns on the planes k = 0 and n3+1
-bool sgs_wraps_x(const cales_ctx *c);      // the SGS pass of this case reads wrapped interior columns instead of x ghost columns
 int op_chkdt(cales_ctx *c, real *dtmax);
 int op_chkdiv(cales_ctx *c, real *divtot, real *divmax);
 int solver_setup(cales_ctx *c);
@@ -415,13 +438,17 @@ __device__ inline real wave_sum_lane63(real s) {
 // takes bands of `sub` consecutive y tiles with all their x tiles and k chunks (x fastest, then y inside the band, then k), so that the halo
 // rows and columns two neighbouring tiles both read meet in one XCD's L2 instead of being fetched over the fabric twice. With the plain 3-D
 // grid every y neighbour sits on another XCD. The grid is padded to whole bands; blocks of the padding return at once (false).
-struct BandMap { int gx, gy, gz, sub; };
 static inline BandMap band_map(int gx, int gy, int gz) { BandMap m{gx, gy, gz, 1}; m.sub = gy >= 64 ? 8 : (gy + 7) / 8; if (m.sub < 1) m.sub = 1; return m; }
 // The plain 3-D grid already gives every XCD fixed x-tile columns (y neighbours in one L2) when the number of x tiles divides 8 or is a multiple
 // of it -- the 64-wide tiles of power-of-two grids: there the bands bring nothing (momentum pass 8.0 -> 8.6 ms/step at 512^3, measured) and
 // are not used; the 62-wide tiles (9 per 512 cells: the XCD of a tile then runs along diagonals) and odd sizes take the bands.
 static inline bool band_wanted(int gx) { return !(gx % 8 == 0 || 8 % gx == 0); }
 static inline unsigned band_blocks(const BandMap &m) { return 8u * m.gx * m.sub * m.gz * ((m.gy + 8 * m.sub - 1) / (8 * m.sub)); }
+// a tile launch through the band map where that helps (band_wanted): the grid becomes the padded 1-D grid of the bands
+static inline TileGeom with_bands(TileGeom t) {
+  if (band_wanted(t.grid.x)) { t.bm = band_map(t.grid.x, t.grid.y, t.grid.z); t.grid = dim3(band_blocks(t.bm), 1, 1); }
+  return t;
+}
 __device__ inline bool band_block(const BandMap &m, int &bx, int &by, int &bz) {
   unsigned s = blockIdx.x >> 3; const unsigned xcd = blockIdx.x & 7u;
   bx = s % m.gx; s /= m.gx; const unsigned sb = s % m.sub; s /= m.sub; bz = s % m.gz; s /= m.gz;
@@ -438,14 +465,6 @@ __device__ inline void stencil_block(int &bx, int &by, int &bz) {
 }
 #endif
 
-// tile kernels split k into chunks until at least this many blocks exist (several rounds per CU balance the chip)
-// k extent of the chunks the marching tile kernels split the z range into. CALES_KCHUNK overrides (experiments).
-static inline int tile_kchunk(const cales_ctx *c, long nxy_blocks, int n3) {
-  const int forced = c->fl.kchunk;
-  if (forced > 0) return forced < n3 ? forced : n3;
-  return 0;
-}
-static inline long tile_min_blocks(const cales_ctx *c) { return c->fl.tile_min_blocks; }
 // shortest chunk of a grid with fewer blocks than CUs: every block runs at once, a launch lasts (chunk + 3-plane prologue) planes -- 64^3 Taylor-Green:
 // momentum pass 77 -> 54 us per step with chunks of 4 planes instead of 8 (192 blocks of 7 planes against 48 of 11), the step 0.223 -> 0.200 ms
 constexpr int SMALL_KCH = 4;
@@ -470,6 +489,20 @@ static inline int balanced_kchunk(const cales_ctx *c, long nxy_blocks, int n3, i
     if (best < 0 || cost < best) { best = cost; bk = kch; }
   }
   return bk;
+}
+// Geometry of a marching tile kernel (plain 3-D grid): blocks of 64 x (ty + 2), tiles ty x wx over n2 + rows_more rows, k chunks halved until the grid has
+// tile_min_blocks blocks, on small grids one per CU (SMALL_KCH), then balanced over the rounds (balanced_kchunk); CALES_KCHUNK overrides.
+static inline TileGeom tile_geom(const cales_ctx *c, int ty, int wx, int rows_more = 0, int kmax = 1 << 30) {
+  const int *n = c->n;
+  TileGeom t; t.block = dim3(64, ty + 2, 1); t.grid = dim3((n[0] + wx - 1) / wx, (n[1] + rows_more + ty - 1) / ty, 1);
+  const long nxy = (long)t.grid.x * t.grid.y;
+  int kch = n[2];
+  while (nxy * ((n[2] + kch - 1) / kch) < c->fl.tile_min_blocks && kch > 32) kch = (kch + 1) / 2;
+  while (nxy * ((n[2] + kch - 1) / kch) < 256 && kch > SMALL_KCH) kch = (kch + 1) / 2;
+  kch = balanced_kchunk(c, nxy, n[2], kch, kmax);
+  if (c->fl.kchunk > 0) kch = c->fl.kchunk < n[2] ? c->fl.kchunk : n[2];      // (experiments)
+  t.kchunk = kch; t.grid.z = (n[2] + kch - 1) / kch;
+  return t;
 }
 // some wall-model face of the CASE (on whichever rank) has its sampling height inside the first cell: its interpolation reaches the ghost cell (index_wm = 1 / n,
 // wmodel.f90:120-131; the conditions of host_setup.cpp's index search, from global quantities only -- every rank must answer alike: what hangs on the answer

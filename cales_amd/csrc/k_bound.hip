@@ -278,7 +278,7 @@ __global__ __launch_bounds__(256) void k_unpack_y(Geom g, HaloFields H, const re
   if (has_lo) H.dst[f][i + s12 * k] = lo[q];
   if (has_hi) H.dst[f][i + s1 * (g.n2 + 1) + s12 * k] = hi[q];
 }
-// A field of PAIRS (two values per cell, k_sgs.hip dsmag_pairs) is, for every operation that copies whole rows or planes, a field of twice the width:
+// A field of PAIRS (two values per cell, SgsPath::pair) is, for every operation that copies whole rows or planes, a field of twice the width:
 // 2 (n1 + 2) values per row, pitches doubled. Its x ghost "columns" mean nothing in that view -- the callers skip direction x.
 static Geom wide_geom(const cales_ctx *c) { Geom g = c->g; g.n1 = 2 * c->g.n1 + 2; g.s1 = 2 * c->g.s1; g.s12 = 2 * c->g.s12; return g; }
 // (wide[q] != 0: field q is a pair field; nullptr: none is)
@@ -376,7 +376,7 @@ static void all_pfield(cales_ctx *c, AField &F, real *p, int which) {
   }
 }
 // ------------------------------------------------------------------------------------------ boundp (bound.f90:156-200)
-// pair fields (x and y periodic only: dsmag_pairs): the y rows (wrapped on one rank, exchanged between slabs) and the z ghost planes through the
+// pair fields (x and y periodic only: SgsPath::pair): the y rows (wrapped on one rank, exchanged between slabs) and the z ghost planes through the
 // one-launch kernel in the doubled-width view; direction x is the consumers' business (they wrap around)
 int op_boundp_wide(cales_ctx *c, int nf, real **p2, int which) {
   ProfScope ps(c, "boundp");

@@ -272,16 +272,8 @@ int op_momrk(cales_ctx *c, real f1, real f2, real f12) {
   const bool corr = c->fold_mom_dtrk != 0.;
   A.pp = f[CALES_PP]; A.pn = c->scr1; A.cfi = c->fold_mom_dtrk * c->dli[0]; A.cfj = c->fold_mom_dtrk * c->dli[1]; A.cdt = c->fold_mom_dtrk;
   A.force = c->d_force; A.fmask = c->fold_mom_fmask;
-  dim3 b(64, TYM + 2, 1), gr((n[0] + 63) / 64, (n[1] + TYM - 1) / TYM, 1);
-  int kchunk = n[2];
-  while ((long)gr.x * gr.y * ((n[2] + kchunk - 1) / kchunk) < tile_min_blocks(c) && kchunk > 32) kchunk = (kchunk + 1) / 2;
-  // small grids: fewer blocks than one per CU leave most of the chip idle; shorter chunks (their three-plane prologue weighs more) beat that
-  while ((long)gr.x * gr.y * ((n[2] + kchunk - 1) / kchunk) < 256 && kchunk > SMALL_KCH) kchunk = (kchunk + 1) / 2;
-  kchunk = balanced_kchunk(c, (long)gr.x * gr.y, n[2], kchunk);
-  if (int fk = tile_kchunk(c, (long)gr.x * gr.y, n[2])) kchunk = fk;
-  gr.z = (n[2] + kchunk - 1) / kchunk; A.kchunk = kchunk;
-  A.bm = BandMap{0, 0, 0, 0};
-  if (band_wanted(gr.x)) { A.bm = band_map(gr.x, gr.y, gr.z); gr = dim3(band_blocks(A.bm), 1, 1); }
+  const TileGeom t = with_bands(tile_geom(c, TYM, 64));
+  const dim3 b = t.block, gr = t.grid; A.kchunk = t.kchunk; A.bm = t.bm;
   const bool small = (c->ntot + 16) * sizeof(real) < (1ull << 32) && !c->fl.wide_offsets;      // 32-bit byte offsets
   const int nos = c->C.sgstype == 0 && c->visct_zero;     // visct known to be identically zero (never set by the host since the last zeroing)
 #define MOMRK_L2(IMP_, RD_, WR_)                                                                                      \

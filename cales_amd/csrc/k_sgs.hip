@@ -1155,102 +1155,128 @@ __global__ __launch_bounds__(256) void k_fold_ghost_rows(Geom g, const real *__r
   wd[a] = ((fmask & 4) ? ws[a] + f2 : ws[a]) - cdt * dzci[k] * (pz - P0);
   p[a] = p[a] + P0;
 }
-static bool dsmag_fast_ok(const cales_ctx *c) {
-  for (int q = 0; q < 2; ++q) if (c->is_wall[q] != 0. || c->C.lwm[q] != 0) return false;      // walls or wall model in x: general path
-  // walls / wall model in y (ducts): the fused last pass knows the wall rule along y, the two-pass form does not
-  for (int q = 2; q < 4; ++q) if ((c->is_wall[q] != 0. || c->C.lwm[q] != 0) && c->n[1] < 3) return false;
-  return c->n[2] >= 3 && !c->fl.dsmag_reference_sequence;
-}
-// |S|Sij as three fields of pairs between K_AC and the fused last pass: x and y periodic (the one-launch ghost-cell kernel takes a pair field as a
-// field of twice the width), the cell-centred velocity formed by the last pass, 32-bit byte offsets still enough for a field twice as long
-bool dsmag_pairs(const cales_ctx *c) {
-  if (c->C.sgstype != 2 || !dsmag_fast_ok(c) || c->fl.dsmag_xghosts || c->fl.wide_offsets || c->fl.unmerged_bc) return false;
-  for (int q = 0; q < 4; ++q) if (c->C.cbcpre[q] != 'P') return false;
-  const bool perz = c->C.cbcpre[4] == 'P' && c->C.cbcpre[5] == 'P';
-  if (!perz && !(c->is_wall[4] != 0. && c->is_wall[5] != 0.)) return false;      // z: periodic, or two walls (whose ghost planes the filters never read)
-  return (2 * c->ntot + 64) * sizeof(real) < (1ull << 32);
-}
-static int dsmag_fast(cales_ctx *c) {
-  const int *n = c->n; real **f = c->f; real *visct = f[CALES_VISCT];
-  const bool pair = c->ss2[0] != nullptr;
-  dim3 b(BX, BY, 1), gr = grid3(n[0], n[1], n[2], b);
-  real **ssij = c->sij, **mij = c->mij;
-  const int zlo = c->is_wall[4] != 0., zhi = c->is_wall[5] != 0.;
+// ---- the path of cmpt_sgs (SgsPath, common.hpp). sgs_setup: the form, its flags, static kernel arguments and kernels -- from the case, the switches
+// and is_wall, before cales_create allocates the scratch fields of the form (pair fields or sij / mij)
+void sgs_setup(cales_ctx *c) {
+  SgsPath &P = c->sgs;
+  const int *n = c->n; const Flags &fl = c->fl;
+  if (c->C.sgstype == 0) return;
+  bool xw = false, yw = false;      // walls or wall model in x (the reference sequences only), in y
+  for (int q = 0; q < 2; ++q) xw = xw || c->is_wall[q] != 0. || c->C.lwm[q] != 0;
+  for (int q = 2; q < 4; ++q) yw = yw || c->is_wall[q] != 0. || c->C.lwm[q] != 0;
+  if (c->C.sgstype == 1) P.form = !xw && n[2] >= 3 && n[1] >= 2 && !fl.smag_reference_sequence ? SgsForm::smag_rows : SgsForm::smag_reference;
+  // (ducts: the fused last pass knows the wall rule along y from three rows on)
+  else P.form = !xw && !(yw && n[1] < 3) && n[2] >= 3 && !fl.dsmag_reference_sequence ? SgsForm::dsmag_tiles : SgsForm::dsmag_reference;
+  P.wraps_x = P.form == SgsForm::smag_rows || (P.form == SgsForm::dsmag_tiles && !fl.dsmag_xghosts);
+  if (P.form != SgsForm::smag_rows && P.form != SgsForm::dsmag_tiles) return;
+  const bool smag = P.form == SgsForm::smag_rows;
+  P.zlo = c->is_wall[4] != 0.; P.zhi = c->is_wall[5] != 0.;
   // wall-model faces in z: the strain rates see ghost planes extrapolated from the interior (extrapolate(...,lwm) with the
   // grid factor, sgs.f90:683-748) instead of the stress-carrying ghost cells
-  const int wmlo = ISB(c, 0, 3) && LWM(c, 0, 3) != 0, wmhi = ISB(c, 1, 3) && LWM(c, 1, 3) != 0;
-  const real flo = (1. / c->dzci[0]) * c->dzci[1], fhi = (1. / c->dzci[n[2]]) * c->dzci[n[2] - 1];
-  // y walls of a duct, on the rank that owns them: wall rule of the filters along y; wall-model y faces: extrapolated ghost rows for the strain rates
-  const int wylo = ISB(c, 0, 2) && c->is_wall[2] != 0., wyhi = ISB(c, 1, 2) && c->is_wall[3] != 0.;
-  const int wmylo = ISB(c, 0, 2) && LWM(c, 0, 2) != 0, wmyhi = ISB(c, 1, 2) && LWM(c, 1, 2) != 0;
-  // tiles of 62 x TY columns marching in k; k is also split into chunks so that several rounds of blocks balance the chip
-  auto tiles = [&](int ty, int wx, dim3 &mb, dim3 &mg, int &kchunk, int kmax = 1 << 30, int rows_more = 0) {
-    mb = dim3(64, ty + 2, 1); mg = dim3((n[0] + wx - 1) / wx, (n[1] + rows_more + ty - 1) / ty, 1);
-    kchunk = n[2];
-    while ((long)mg.x * mg.y * ((n[2] + kchunk - 1) / kchunk) < tile_min_blocks(c) && kchunk > 32) kchunk = (kchunk + 1) / 2;
-    // small grids: fewer blocks than one per CU leave most of the chip idle; shorter chunks (their three-plane prologue weighs more) beat that
-    while ((long)mg.x * mg.y * ((n[2] + kchunk - 1) / kchunk) < 256 && kchunk > SMALL_KCH) kchunk = (kchunk + 1) / 2;
-    kchunk = balanced_kchunk(c, (long)mg.x * mg.y, n[2], kchunk, kmax);
-    if (int fk = tile_kchunk(c, (long)mg.x * mg.y, n[2])) kchunk = fk;
-    mg.z = (n[2] + kchunk - 1) / kchunk;
-  };
-  dim3 mb, mg; int kch;
-  const bool small = (c->ntot + 16) * sizeof(real) < (1ull << 32) && !c->fl.wide_offsets;      // 32-bit byte offsets (ldb/stb)
-  // lazy form (homogeneous sgs BCs): |S| goes straight into the eddy-viscosity field and the last pass only makes the n3 plane coefficients
-  bool lazy = true;
-  for (int q = 0; q < 6; ++q) lazy = lazy && c->C.bcsgs[q] == 0.;
+  P.wmlo = ISB(c, 0, 3) && LWM(c, 0, 3) != 0; P.wmhi = ISB(c, 1, 3) && LWM(c, 1, 3) != 0;
+  P.flo = (1. / c->dzci[0]) * c->dzci[1]; P.fhi = (1. / c->dzci[n[2]]) * c->dzci[n[2] - 1];
+  // y walls of a duct: dsmag on the rank that owns them (wall rule of the filters along y); smag_rows all of the case (van Driest distances use global
+  // rows, the shear of both walls reaches every slab). Wall-model y faces: extrapolated ghost rows for the strain rates
+  P.wylo = (smag || ISB(c, 0, 2)) && c->is_wall[2] != 0.; P.wyhi = (smag || ISB(c, 1, 2)) && c->is_wall[3] != 0.;
+  P.wmylo = ISB(c, 0, 2) && LWM(c, 0, 2) != 0; P.wmyhi = ISB(c, 1, 2) && LWM(c, 1, 2) != 0;
+  P.yw = P.wylo || P.wyhi || P.wmylo || P.wmyhi;
+  P.small = (c->ntot + 16) * sizeof(real) < (1ull << 32) && !fl.wide_offsets;      // 32-bit byte offsets (ldb/stb)
+  if (smag) { P.smag = P.yw ? (P.small ? SmagKernel::yw32 : SmagKernel::yw64) : (P.small ? SmagKernel::plain32 : SmagKernel::plain64); return; }
+  P.lazy = true; for (int q = 0; q < 6; ++q) P.lazy = P.lazy && c->C.bcsgs[q] == 0.;
+  P.perz = CBP(c, 0, 3) == 'P' && CBP(c, 1, 3) == 'P';
+  P.perx = CBP(c, 0, 1) == 'P' && CBP(c, 1, 1) == 'P' && !fl.dsmag_xghosts;
+  P.skipz = (P.zlo && P.zhi) ? 4 : 0;
   // the cell-centred velocity is not stored where the last pass can form it itself (k_lmf_tile<.., UCF = 1>): x periodic, z walls or periodic
-  const bool perz = CBP(c, 0, 3) == 'P' && CBP(c, 1, 3) == 'P';
-  const bool ucf = CBP(c, 0, 1) == 'P' && CBP(c, 1, 1) == 'P' && !c->fl.dsmag_xghosts && ((zlo && zhi) || perz);
-  // K_AC: |S|, |S|Sij, cell-centred and test-filtered velocity in one pass over u,v,w (no wall-model faces ->
-  // extrapolate(...,lwm) is a no-op; u,v are extrapolated through the z walls, w on the faces is not, sgs.f90:705-710)
-  const bool fold = c->fold_dtrk != 0. && pair && ucf;      // (cales_step decides; pair fields and the cell-centred velocity formed by the last pass: the instantiation that exists)
-  const bool ext = fold && c->fold_rows2 && c->P > 1;      // ... which also forms the ghost rows of its outputs from two ghost rows of the prediction (StepPlan::fold_rows2)
-  if (c->fold_dtrk != 0. && !fold) { c->err = "dsmag: projection folded into the strain-rate pass without pair fields"; return 1; }
+  P.ucf = P.perx && ((P.zlo && P.zhi) || P.perz);
+  // |S|Sij as three fields of pairs between K_AC and the fused last pass: ucf, and y periodic (the one-launch ghost-cell kernel takes a pair field as a
+  // field of twice the width), 32-bit byte offsets still enough for a field twice as long
+  P.pair = P.ucf && CBP(c, 0, 2) == 'P' && CBP(c, 1, 2) == 'P' && !fl.wide_offsets && !fl.unmerged_bc && (2 * c->ntot + 64) * sizeof(real) < (1ull << 32);
+  P.lmf_ty = P.yw ? TYL : TYLF;
+  P.strain = P.pair ? StrainKernel::pair : P.yw ? (P.small ? StrainKernel::yw32 : StrainKernel::yw64) : (P.small ? StrainKernel::plain32 : StrainKernel::plain64);
+  static const LmfKernel lmf[2][2][2] = {{{LmfKernel::plain64, LmfKernel::plain32}, {LmfKernel::ucf64, LmfKernel::ucf32}},
+                                         {{LmfKernel::yw64, LmfKernel::yw32}, {LmfKernel::yw_ucf64, LmfKernel::yw_ucf32}}};      // [yw][ucf][small]
+  P.lmf = P.pair ? LmfKernel::pair : lmf[P.yw][P.ucf][P.small];
+}
+// sgs_setup_launches: the launch geometry of the tile passes (after cales_create has read the CU count: balanced_kchunk)
+int sgs_setup_launches(cales_ctx *c) {
+  SgsPath &P = c->sgs; const int *n = c->n;
+  if (P.form == SgsForm::smag_rows) {
+    // row-marching form: one wave per row of 62 cells; chunks of k so that every CU holds several blocks' worth of independent waves (the LDS-tile
+    // form of this pass -- two barriers per plane, 2.4 against 2.9 TB/s -- lost its A/B in round 2 and went in round 4)
+    const int rgx = (n[0] + 61) / 62, rgy = (n[1] + SROWS - 1) / SROWS;
+    int kr = n[2];
+    // sixteen waves per CU at a time: enough blocks for eight rounds or more, or the last round's idle CUs show (chunks pay a three-plane prologue)
+    while ((long)rgx * rgy * ((n[2] + kr - 1) / kr) < 8192 && kr > 32) kr = (kr + 1) / 2;
+    while ((long)rgx * rgy * ((n[2] + kr - 1) / kr) < 1024 && kr > 8) kr = (kr + 1) / 2;
+    if (c->fl.kchunk > 0) kr = c->fl.kchunk < n[2] ? c->fl.kchunk : n[2];
+    P.smag_geo.kchunk = kr; P.smag_geo.bm = band_map(rgx, rgy, (n[2] + kr - 1) / kr);
+    P.smag_geo.block = dim3(64, SROWS, 1); P.smag_geo.grid = dim3(band_blocks(P.smag_geo.bm), 1, 1);
+  }
+  if (P.form != SgsForm::dsmag_tiles) return 0;
+  // K_AC: tiles of 64 x TYS, folded 64 x TYC (with two ghost rows of the prediction on several slabs: two rows more); the last pass 62 x lmf_ty
+  P.strain_geo = with_bands(tile_geom(c, TYS, 64));
+  if (P.pair) { P.corr_geo = with_bands(tile_geom(c, TYC, 64)); P.corr_rows2_geo = with_bands(tile_geom(c, TYC, 64, 2)); }
+  TileGeom t = tile_geom(c, P.lmf_ty, 62, 0, LMF_KMAX);
+  if ((size_t)2 * n[2] * t.grid.x * t.grid.y > c->ntot) { c->err = "dsmag: partial-sum scratch too small"; return 1; }
+  while (t.kchunk > LMF_KMAX) { t.kchunk = (t.kchunk + 1) / 2; t.grid.z = (n[2] + t.kchunk - 1) / t.kchunk; }      // the kernel keeps a chunk's block sums in LDS
+  P.lmf_geo = t;
+  return 0;
+}
+static int dsmag_fast(cales_ctx *c, const SgsFold *fold) {
+  const SgsPath &P = c->sgs;
+  const int *n = c->n; real **f = c->f; real *visct = f[CALES_VISCT];
+  dim3 b(BX, BY, 1), gr = grid3(n[0], n[1], n[2], b);
+  real **ssij = c->sij, **mij = c->mij;
+  // K_AC: |S|, |S|Sij, cell-centred and test-filtered velocity in one pass over u,v,w (no wall-model faces -> extrapolate(...,lwm) is a no-op; u,v
+  // are extrapolated through the z walls, w on the faces is not, sgs.f90:705-710); fold (pair fields, make_plan): with the projection folded in, ext:
+  // from two ghost rows of the prediction, forming the ghost rows of its outputs too
+  const bool ext = fold && fold->rows2;
   { ProfScope ps(c, fold ? "correc_strain_filter_uvw" : "strain_filter_uvw");
-    tiles(fold ? TYC : TYS, 64, mb, mg, kch, 1 << 30, ext ? 2 : 0);
+    const TileGeom &t = !fold ? P.strain_geo : ext ? P.corr_rows2_geo : P.corr_geo;
     StrainTileArgs S;
-    S.u[0] = f[CALES_U]; S.u[1] = f[CALES_V]; S.u[2] = f[CALES_W]; S.s0 = lazy ? visct : c->s0;
+    S.u[0] = f[CALES_U]; S.u[1] = f[CALES_V]; S.u[2] = f[CALES_W]; S.s0 = P.lazy ? visct : c->s0;
     for (int m = 0; m < 6; ++m) S.ssij[m] = ssij[m];
     for (int m = 0; m < 3; ++m) S.ss2[m] = reinterpret_cast<real2 *>(c->ss2[m]);
-    S.uc[0] = ucf ? nullptr : c->uc; S.uc[1] = ucf ? nullptr : c->vc; S.uc[2] = ucf ? nullptr : c->wc; S.uf[0] = c->uf; S.uf[1] = c->vf; S.uf[2] = c->wf;
-    S.dzci = c->d_dzci; S.dzfi = c->d_dzfi; S.dxi = c->dli[0]; S.dyi = c->dli[1]; S.kchunk = kch; S.zlo = zlo; S.zhi = zhi; S.wmlo = wmlo; S.wmhi = wmhi; S.flo = flo; S.fhi = fhi;
-    S.wylo = wylo; S.wyhi = wyhi; S.wmylo = wmylo; S.wmyhi = wmyhi; S.twy = nullptr; S.dl2 = c->dl[1];
-    S.bm = BandMap{0, 0, 0, 0}; S.perx = c->step_xskip ? 1 : 0;
-    if (band_wanted(mg.x)) { S.bm = band_map(mg.x, mg.y, mg.z); mg = dim3(band_blocks(S.bm), 1, 1); }
+    S.uc[0] = P.ucf ? nullptr : c->uc; S.uc[1] = P.ucf ? nullptr : c->vc; S.uc[2] = P.ucf ? nullptr : c->wc; S.uf[0] = c->uf; S.uf[1] = c->vf; S.uf[2] = c->wf;
+    S.dzci = c->d_dzci; S.dzfi = c->d_dzfi; S.dxi = c->dli[0]; S.dyi = c->dli[1]; S.kchunk = t.kchunk; S.zlo = P.zlo; S.zhi = P.zhi; S.wmlo = P.wmlo; S.wmhi = P.wmhi; S.flo = P.flo; S.fhi = P.fhi;
+    S.wylo = P.wylo; S.wyhi = P.wyhi; S.wmylo = P.wmylo; S.wmyhi = P.wmyhi; S.twy = nullptr; S.dl2 = c->dl[1];
+    S.bm = t.bm; S.perx = c->step_xskip ? 1 : 0;
     if (fold) {      // the projection of this substep is pending (cales_step): corrected velocity on load, u, v, w to the second buffers, p += pp
       S.pp = f[CALES_PP]; S.p = f[CALES_P]; for (int q = 0; q < 3; ++q) S.un[q] = c->f2[q];
-      S.force = c->d_force; S.fmask = c->defer_force ? (c->C.is_forced[0] ? 1 : 0) | (c->C.is_forced[1] ? 2 : 0) | (c->C.is_forced[2] ? 4 : 0) : 0;
-      S.cdt = c->fold_dtrk; S.cfi = c->fold_dtrk * c->dli[0]; S.cfj = c->fold_dtrk * c->dli[1]; S.zper = perz ? 1 : 0;
+      S.force = c->d_force; S.fmask = fold->fmask;
+      S.cdt = fold->dtrk; S.cfi = fold->dtrk * c->dli[0]; S.cfj = fold->dtrk * c->dli[1]; S.zper = P.perz;
       S.pery = c->P == 1 ? 1 : 0; S.ppd = c->pp_companion_bytes;
       const size_t pl = (size_t)(n[0] + 2) * (n[1] + 2);
       S.bcz[0][0] = c->bcu.z; S.bcz[0][1] = c->bcu.z + pl; S.bcz[1][0] = c->bcv.z; S.bcz[1][1] = c->bcv.z + pl;
       S.vcg = c->vc;
-      if (ext) LAUNCH(c, (k_corr_strain_tile<unsigned, TYC, 1>), mg, mb, 0, c->stream, c->g, S);
-      else LAUNCH(c, (k_corr_strain_tile<unsigned, TYC>), mg, mb, 0, c->stream, c->g, S);
-    } else
-    if (wylo || wyhi || wmylo || wmyhi) { if (small) LAUNCH(c, (k_strain_tile<unsigned, TYS, 1>), mg, mb, 0, c->stream, c->g, S); else LAUNCH(c, (k_strain_tile<size_t, TYS, 1>), mg, mb, 0, c->stream, c->g, S); }
-    else if (pair) LAUNCH(c, (k_strain_tile<unsigned, TYS, 0, 1>), mg, mb, 0, c->stream, c->g, S);
-    else if (small) LAUNCH(c, (k_strain_tile<unsigned, TYS, 0>), mg, mb, 0, c->stream, c->g, S); else LAUNCH(c, (k_strain_tile<size_t, TYS, 0>), mg, mb, 0, c->stream, c->g, S); }
+    }
+    switch (!fold ? P.strain : ext ? StrainKernel::corr_rows2 : StrainKernel::corr) {
+    case StrainKernel::corr_rows2: LAUNCH(c, (k_corr_strain_tile<unsigned, TYC, 1>), t.grid, t.block, 0, c->stream, c->g, S); break;
+    case StrainKernel::corr: LAUNCH(c, (k_corr_strain_tile<unsigned, TYC>), t.grid, t.block, 0, c->stream, c->g, S); break;
+    case StrainKernel::yw32: LAUNCH(c, (k_strain_tile<unsigned, TYS, 1>), t.grid, t.block, 0, c->stream, c->g, S); break;
+    case StrainKernel::yw64: LAUNCH(c, (k_strain_tile<size_t, TYS, 1>), t.grid, t.block, 0, c->stream, c->g, S); break;
+    case StrainKernel::pair: LAUNCH(c, (k_strain_tile<unsigned, TYS, 0, 1>), t.grid, t.block, 0, c->stream, c->g, S); break;
+    case StrainKernel::plain32: LAUNCH(c, (k_strain_tile<unsigned, TYS, 0>), t.grid, t.block, 0, c->stream, c->g, S); break;
+    case StrainKernel::plain64: LAUNCH(c, (k_strain_tile<size_t, TYS, 0>), t.grid, t.block, 0, c->stream, c->g, S); break;
+    } }
   if (fold) {
     // the corrected velocity sits in the second buffers: swap (as the fused momentum pass does), give the normal component its two z faces -- the
     // reference's correc covers w(:,:,0) (correc.f90:60-66) and leaves w(:,:,n3+1) as it was, and bounduvw with is_correc touches neither -- and
-    // fill the ghost cells of u, v, w and p (the pressure rides along) as main.f90:500-504 does after correc / updatep
+    // fill the ghost cells of u, v, w and p (the pressure rides along: pair fields come with the one-launch ghost-cell kernel) as main.f90:500-504
+    // does after correc / updatep
     for (int q = 0; q < 3; ++q) std::swap(c->f[CALES_U + q], c->f2[q]);
-    if (!perz)
-      LAUNCH(c, k_wface_fold, dim3((n[0] + 2 + 63) / 64, (n[1] + 2 + 3) / 4), dim3(64, 4), 0, c->stream, c->g, c->f2[2], c->f[CALES_W], f[CALES_PP], c->fold_dtrk * c->dzci[0]);
-    if (!c->fl.unmerged_bc) { c->bc_nride = 1; c->bc_ride[0] = f[CALES_P]; c->bc_ride_which[0] = 0; }
+    if (!P.perz)
+      LAUNCH(c, k_wface_fold, dim3((n[0] + 2 + 63) / 64, (n[1] + 2 + 3) / 4), dim3(64, 4), 0, c->stream, c->g, c->f2[2], c->f[CALES_W], f[CALES_PP], fold->dtrk * c->dzci[0]);
+    c->bc_nride = 1; c->bc_ride[0] = f[CALES_P]; c->bc_ride_which[0] = 0;
     // several slabs: the ghost rows of u, v, w and p do not travel at all -- k_fold_ghost_rows forms them from the prediction's ghost rows and pp's,
     // the ghost-cell kernel below gives them their x and z ghost cells (round 5: in the same exchange as the scratch fields', fifteen planes; now eleven)
-    const bool local_rows = c->P > 1 && !c->fl.unmerged_bc;
-    if (local_rows && !ext)      // (ext: the strain-rate pass has formed them itself)
+    if (c->P > 1 && !ext)      // (ext: the strain-rate pass has formed them itself)
       LAUNCH(c, k_fold_ghost_rows, dim3((n[0] + 63) / 64, (n[2] + 3) / 4, 2), dim3(64, 4), 0, c->stream, c->g, c->f2[0], c->f2[1], c->f2[2], c->f[CALES_U], c->f[CALES_V],
-             c->f[CALES_W], f[CALES_PP], c->scr2, f[CALES_P], c->d_force, c->defer_force ? (c->C.is_forced[0] ? 1 : 0) | (c->C.is_forced[1] ? 2 : 0) | (c->C.is_forced[2] ? 4 : 0) : 0,
-             c->fold_dtrk * c->dli[0], c->fold_dtrk * c->dli[1], c->fold_dtrk, c->d_dzci, c->step_xskip ? 1 : 0);
+             c->f[CALES_W], f[CALES_PP], c->scr2, f[CALES_P], c->d_force, fold->fmask, fold->dtrk * c->dli[0], fold->dtrk * c->dli[1], fold->dtrk, c->d_dzci, c->step_xskip ? 1 : 0);
     const bool no_halo_before = c->bc_no_halo;
-    c->bc_no_halo = no_halo_before || local_rows;
+    c->bc_no_halo = no_halo_before || c->P > 1;
     const int e = op_bounduvw(c, c->bcu, c->bcv, c->bcw, 1, 1, c->f[CALES_U], c->f[CALES_V], c->f[CALES_W]);
-    const bool rode = !c->fl.unmerged_bc && c->bc_nride == 0; c->bc_nride = 0;
+    const bool rode = c->bc_nride == 0; c->bc_nride = 0;
     int e2 = 0;
     if (!e && !rode) e2 = op_boundp(c, f[CALES_P], 0);
     c->bc_no_halo = no_halo_before;
@@ -1258,80 +1284,78 @@ static int dsmag_fast(cales_ctx *c) {
   }
   // sgs-type ghost cells: only the periodic exchange matters (products of ghosts = ghosts of products; the wall ghosts are
   // replaced by the extrapolation rule inside the filters)
-  // These twelve scratch fields are read by the tile kernels only: with periodic x their ghost columns are not filled (the
+  // These twelve scratch fields are read by the tile kernels only: with periodic x their ghost columns are not filled (perx: the
   // kernels wrap around instead; an x ghost update touches four cache lines per row for two values), and the z ghost planes
-  // of the quantities the wall rule covers are never read.
-  const int perx = (CBP(c, 0, 1) == 'P' && CBP(c, 1, 1) == 'P' && !c->fl.dsmag_xghosts) ? 1 : 0;
-  const int skipz = (zlo && zhi) ? 4 : 0;
+  // of the quantities the wall rule covers are never read (skipz).
   // several ranks with the second stream: the y-halo rows of the twelve scratch fields travel while the interior tiles of the last pass run
   const bool overlap = c->P > 1 && c->comm.halo_s && c->comm_stream && !ext;      // (ext: no row of these fields travels)
-  // (every check that can fail comes BEFORE the deferred exchange is queued: an error return behind halo_flush_deferred would leave the
-  //  exchange in flight on the second stream with nobody joining it)
-  const int lmf_ty = (wylo || wyhi || wmylo || wmyhi) ? TYL : TYLF;      // tile height of the fused last pass (k_lmf_tile<.., YW>)
-  { dim3 tb, tg; int tk; tiles(lmf_ty, 62, tb, tg, tk);
-    if ((size_t)2 * n[2] * tg.x * tg.y > c->ntot) { c->err = "dsmag: partial-sum scratch too small"; return 1; } }
   // several ranks: ONE exchange for the y-halo rows of all these fields (six |S|Sij, three filtered velocities, v_c, and |S| itself in the lazy form
   // inside cales_step) instead of one per ghost-cell call; their ghost-cell kernels run first, the rows that then arrive carry the neighbour's
   // x/z ghost cells
   c->defer_halo = c->P > 1 && !ext;
   const bool no_halo_before = c->bc_no_halo;
   if (ext) c->bc_no_halo = true;      // the ghost rows of every field below were formed by the strain-rate pass: their x and z ghost cells only
-  c->bc_skip = perx | skipz;
-  int e_ = pair ? op_boundp_wide(c, 3, c->ss2, 1) : op_boundp_multi(c, 6, ssij, 1);
-  c->bc_skip = perx;
+  c->bc_skip = P.perx | P.skipz;
+  int e_ = P.pair ? op_boundp_wide(c, 3, c->ss2, 1) : op_boundp_multi(c, 6, ssij, 1);
+  c->bc_skip = P.perx;
   if (!e_) e_ = op_bounduvw(c, c->bcuf, c->bcvf, c->bcwf, 0, 0, c->uf, c->vf, c->wf);
-  c->bc_skip = perx | skipz;
-  if (!e_ && !ucf) { real *cc[3] = {c->uc, c->vc, c->wc}; e_ = op_boundp_multi(c, 3, cc, 1); }
-  if (!e_ && ucf && ext) { real *cc[1] = {c->vc}; e_ = op_boundp_multi(c, 1, cc, 1); }      // (v_c of the two ghost rows came from the strain-rate pass)
-  else if (!e_ && ucf && !(wylo && wyhi)) {      // v_c of the rows 1 and n2 only: their copies in the ghost rows (periodic wrap or the slab neighbours') are what the last pass reads for row 0
+  c->bc_skip = P.perx | P.skipz;
+  if (!e_ && !P.ucf) { real *cc[3] = {c->uc, c->vc, c->wc}; e_ = op_boundp_multi(c, 3, cc, 1); }
+  if (!e_ && P.ucf && ext) { real *cc[1] = {c->vc}; e_ = op_boundp_multi(c, 1, cc, 1); }      // (v_c of the two ghost rows came from the strain-rate pass)
+  else if (!e_ && P.ucf && !(P.wylo && P.wyhi)) {      // v_c of the rows 1 and n2 only: their copies in the ghost rows (periodic wrap or the slab neighbours') are what the last pass reads for row 0
     LAUNCH(c, k_vc_edge_rows, dim3((n[0] + 2 + 63) / 64, (n[2] + 2 + 3) / 4), dim3(64, 4), 0, c->stream, c->g, f[CALES_V], c->vc);
     real *cc[1] = {c->vc}; e_ = op_boundp_multi(c, 1, cc, 1); }
   c->bc_skip = 0;
-  if (!e_ && lazy && c->in_step && c->P > 1) { e_ = op_boundp(c, visct, 1); c->visct_bc_done = !e_; }      // |S| is final (K_AC wrote it): its rows travel along
+  if (!e_ && P.lazy && c->in_step && c->P > 1) { e_ = op_boundp(c, visct, 1); c->visct_bc_done = !e_; }      // |S| is final (K_AC wrote it): its rows travel along
   c->defer_halo = false;
   c->bc_no_halo = no_halo_before;
   if (!e_ && c->P > 1) e_ = halo_flush_deferred(c, overlap);
   if (e_) { c->deferred.clear(); c->deferred_wide.clear(); return e_; }
   LijMijArgs L;
-  L.uc[0] = ucf ? f[CALES_U] : c->uc; L.uc[1] = ucf ? f[CALES_V] : c->vc; L.uc[2] = ucf ? f[CALES_W] : c->wc; L.uf[0] = c->uf; L.uf[1] = c->vf; L.uf[2] = c->wf;
-  L.vcg = c->vc; L.perz = perz ? 1 : 0; L.xwrap = c->step_xskip ? 1 : 0;
+  L.uc[0] = P.ucf ? f[CALES_U] : c->uc; L.uc[1] = P.ucf ? f[CALES_V] : c->vc; L.uc[2] = P.ucf ? f[CALES_W] : c->wc; L.uf[0] = c->uf; L.uf[1] = c->vf; L.uf[2] = c->wf;
+  L.vcg = c->vc; L.perz = P.perz; L.xwrap = c->step_xskip ? 1 : 0;
   for (int m = 0; m < 6; ++m) L.mf[m] = mij[m];
   L.part = c->wk[0]; L.dzci = c->d_dzci; L.dzfi = c->d_dzfi; L.dxi = c->dli[0]; L.dyi = c->dli[1];
-  L.zlo = zlo; L.zhi = zhi; L.wmlo = wmlo; L.wmhi = wmhi; L.flo = flo; L.fhi = fhi; L.perx = perx;
-  L.wylo = wylo; L.wyhi = wyhi; L.wmylo = wmylo; L.wmyhi = wmyhi;
+  L.zlo = P.zlo; L.zhi = P.zhi; L.wmlo = P.wmlo; L.wmhi = P.wmhi; L.flo = P.flo; L.fhi = P.fhi; L.perx = P.perx;
+  L.wylo = P.wylo; L.wyhi = P.wyhi; L.wmylo = P.wmylo; L.wmyhi = P.wmyhi;
   {
     // K_B + K_DF in one pass: filter(|S|Sij) on the fly, strain rate of the filtered velocity, Mij, Lij, contractions, plane partial sums
     ProfScope ps(c, "lij_mij_filter_contract");
-    tiles(lmf_ty, 62, mb, mg, kch, LMF_KMAX);
-    while (kch > LMF_KMAX) { kch = (kch + 1) / 2; mg.z = (n[2] + kch - 1) / kch; }      // the kernel keeps a chunk's block sums in LDS
-    L.kchunk = kch; L.nblk = mg.x * mg.y;
+    const TileGeom &t = P.lmf_geo;
+    L.kchunk = t.kchunk; L.nblk = t.grid.x * t.grid.y;
     LmfArgs B; B.L = L; for (int m = 0; m < 6; ++m) B.ss[m] = ssij[m];
     for (int m = 0; m < 3; ++m) B.ss2[m] = reinterpret_cast<const real2 *>(c->ss2[m]);
-    auto launch = [&](int by0, int nby) {
+    B.gx = t.grid.x;
+    auto launch = [&](int by0, int nby) {      // the y tiles by0 .. by0 + nby - 1
       if (nby <= 0) return;
-      B.by0 = by0; B.gx = mg.x; dim3 gg(mg.x, nby, mg.z);
-      B.bm = BandMap{0, 0, 0, 0};
-      if (band_wanted(mg.x)) { B.bm = band_map(mg.x, nby, mg.z); gg = dim3(band_blocks(B.bm), 1, 1); }
-      const bool yw = wylo || wyhi || wmylo || wmyhi;
-#define LMF_LAUNCH(YWV, UCV) do { if (small) LAUNCH(c, (k_lmf_tile<unsigned, YWV, UCV>), gg, mb, 0, c->stream, c->g, B); else LAUNCH(c, (k_lmf_tile<size_t, YWV, UCV>), gg, mb, 0, c->stream, c->g, B); } while (0)
-      if (pair) { if (ucf) LAUNCH(c, (k_lmf_tile<unsigned, 0, 1, 1>), gg, mb, 0, c->stream, c->g, B); else LAUNCH(c, (k_lmf_tile<unsigned, 0, 0, 1>), gg, mb, 0, c->stream, c->g, B); }
-      else if (yw) { if (ucf) LMF_LAUNCH(1, 1); else LMF_LAUNCH(1, 0); } else { if (ucf) LMF_LAUNCH(0, 1); else LMF_LAUNCH(0, 0); }
-#undef LMF_LAUNCH
+      TileGeom s = t; s.grid.y = nby; s = with_bands(s);
+      B.by0 = by0; B.bm = s.bm;
+      switch (P.lmf) {
+      case LmfKernel::pair: LAUNCH(c, (k_lmf_tile<unsigned, 0, 1, 1>), s.grid, s.block, 0, c->stream, c->g, B); break;
+      case LmfKernel::yw_ucf32: LAUNCH(c, (k_lmf_tile<unsigned, 1, 1>), s.grid, s.block, 0, c->stream, c->g, B); break;
+      case LmfKernel::yw_ucf64: LAUNCH(c, (k_lmf_tile<size_t, 1, 1>), s.grid, s.block, 0, c->stream, c->g, B); break;
+      case LmfKernel::yw32: LAUNCH(c, (k_lmf_tile<unsigned, 1, 0>), s.grid, s.block, 0, c->stream, c->g, B); break;
+      case LmfKernel::yw64: LAUNCH(c, (k_lmf_tile<size_t, 1, 0>), s.grid, s.block, 0, c->stream, c->g, B); break;
+      case LmfKernel::ucf32: LAUNCH(c, (k_lmf_tile<unsigned, 0, 1>), s.grid, s.block, 0, c->stream, c->g, B); break;
+      case LmfKernel::ucf64: LAUNCH(c, (k_lmf_tile<size_t, 0, 1>), s.grid, s.block, 0, c->stream, c->g, B); break;
+      case LmfKernel::plain32: LAUNCH(c, (k_lmf_tile<unsigned, 0, 0>), s.grid, s.block, 0, c->stream, c->g, B); break;
+      case LmfKernel::plain64: LAUNCH(c, (k_lmf_tile<size_t, 0, 0>), s.grid, s.block, 0, c->stream, c->g, B); break;
+      }
     };
     if (overlap) {
       // tiles that read the ghost rows j = 0 or j = n2+1 wait for the rows in flight; the others run beside the exchange
-      int hi0 = (int)mg.y; while (hi0 > 1 && (hi0 - 1) * lmf_ty + lmf_ty + 1 >= n[1] + 1) --hi0;      // first tile (> 0) that reaches row n2+1
+      int hi0 = (int)t.grid.y; while (hi0 > 1 && (hi0 - 1) * P.lmf_ty + P.lmf_ty + 1 >= n[1] + 1) --hi0;      // first tile (> 0) that reaches row n2+1
       launch(1, hi0 - 1);
       if (int e = stream_after(c, c->stream, c->comm_stream)) return e;
-      launch(0, 1); launch(hi0, (int)mg.y - hi0);
-    } else launch(0, (int)mg.y);
+      launch(0, 1); launch(hi0, (int)t.grid.y - hi0);
+    } else launch(0, (int)t.grid.y);
     LAUNCH(c, k_plane_fold, dim3(2 * n[2]), dim3(256), 0, c->stream, n[2], L.nblk, c->wk[0], c->d_p1d);
   }
   if (c->P > 1) { if (int e = allreduce_res(c, (int)(c->d_p1d - c->res), 2 * n[2], 0)) return e; }   // sgs.f90:475
   const real gar = c->dl[0] * c->dl[1] / (c->C.l[0] * c->C.l[1]);
-  if (lazy) {
+  if (P.lazy) {
     if (!c->d_cs) HIPCHK(c, hipMalloc(&c->d_cs, (n[2] + 2) * sizeof(real)));
-    LAUNCH(c, k_dsmag_coef, dim3(1), dim3(256), 0, c->stream, n[2], gar, c->d_p1d, c->d_cs, CBP(c, 0, 3) == 'P' && CBP(c, 1, 3) == 'P' ? 1 : 0);
+    LAUNCH(c, k_dsmag_coef, dim3(1), dim3(256), 0, c->stream, n[2], gar, c->d_p1d, c->d_cs, P.perz);
     c->visct_lazy = true;
   } else LAUNCH(c, k_dsmag_final, gr, b, 0, c->stream, c->g, gar, c->d_p1d, c->s0, visct);
   LAUNCHCHK(c);
@@ -1340,15 +1364,16 @@ static int dsmag_fast(cales_ctx *c) {
 
 static inline dim3 lin_grid(size_t n) { size_t b = (n + 255) / 256; if (b > 4096) b = 4096; return dim3((unsigned)b); }
 
-// Static Smagorinsky for cases whose only walls are in z (channels, with or without wall model): strain rate and van Driest
-// damping in one pass of the tile kernel, u,v,w -> visct (4 words/cell instead of the 20 of copy + extrapolate + strain + smag)
-static bool smag_fast_ok(const cales_ctx *c) {
-  for (int q = 0; q < 2; ++q) if (c->is_wall[q] != 0. || c->C.lwm[q] != 0) return false;      // walls or wall model in x: general path
-  return c->n[2] >= 3 && c->n[1] >= 2 && !c->fl.smag_reference_sequence;
-}
 __global__ void k_smag_del(int n, real dl1, real dl2, const real *__restrict__ dzf, real *__restrict__ del) {
   const int k = blockIdx.x * 64 + threadIdx.x;
   if (k < n) del[k] = pow(dl1 * dl2 * dzf[k], 1. / 3.);       // the filter width depends on k only (sgs.f90:145)
+}
+// c->d_del, made by the first Smagorinsky pass that needs it
+static int smag_del(cales_ctx *c) {
+  if (c->d_del) return 0;
+  HIPCHK(c, hipMalloc(&c->d_del, (c->n[2] + 2) * sizeof(real)));
+  LAUNCH(c, k_smag_del, dim3((c->n[2] + 2 + 63) / 64), dim3(64), 0, c->stream, c->n[2] + 2, c->dl[0], c->dl[1], c->d_dzf, c->d_del);
+  return 0;
 }
 // sqrt(tau_w) of the two y walls as planes twy(side, k, i) for the van Driest damping of cells whose nearest wall is a y wall (sgs.f90:117-143,
 // cases 3 and 4). One slab: straight from the fields. Several slabs: the walls belong to the first and the last slab, every other rank needs
@@ -1374,59 +1399,37 @@ static int wall_shear_y_planes(cales_ctx *c, int wylo, int wyhi, const real **ou
   *out = twy;
   return 0;
 }
+// Static Smagorinsky for cases without walls or wall model in x: strain rate and van Driest damping in one pass of the row-marching kernel,
+// u,v,w -> visct (4 words/cell instead of the 20 of copy + extrapolate + strain + smag)
 static int smag_fast(cales_ctx *c) {
-  const int *n = c->n; real **f = c->f;
-  if (!c->d_del) {
-    HIPCHK(c, hipMalloc(&c->d_del, (n[2] + 2) * sizeof(real)));
-    LAUNCH(c, k_smag_del, dim3((n[2] + 2 + 63) / 64), dim3(64), 0, c->stream, n[2] + 2, c->dl[0], c->dl[1], c->d_dzf, c->d_del);
-  }
+  const SgsPath &P = c->sgs; real **f = c->f;
+  if (int e = smag_del(c)) return e;
   StrainTileArgs S = {};
   S.u[0] = f[CALES_U]; S.u[1] = f[CALES_V]; S.u[2] = f[CALES_W]; S.visct = f[CALES_VISCT];
   S.dzci = c->d_dzci; S.dzfi = c->d_dzfi; S.dxi = c->dli[0]; S.dyi = c->dli[1];
-  S.zlo = c->is_wall[4] != 0.; S.zhi = c->is_wall[5] != 0.;
-  S.wmlo = ISB(c, 0, 3) && LWM(c, 0, 3) != 0; S.wmhi = ISB(c, 1, 3) && LWM(c, 1, 3) != 0;
-  S.flo = (1. / c->dzci[0]) * c->dzci[1]; S.fhi = (1. / c->dzci[n[2]]) * c->dzci[n[2] - 1];
+  S.zlo = P.zlo; S.zhi = P.zhi; S.wmlo = P.wmlo; S.wmhi = P.wmhi; S.flo = P.flo; S.fhi = P.fhi;
   S.zc = c->d_zc; S.del = c->d_del; S.l3 = c->C.l[2]; S.visc = c->visc; S.perx = c->step_xskip ? 1 : 0;
-  // walls in y (ducts): is_wall(2:3) is a property of the case, distances use global rows, and the shear of both y walls reaches every slab
-  S.wylo = c->is_wall[2] != 0.; S.wyhi = c->is_wall[3] != 0.; S.dl2 = c->dl[1];
-  S.wmylo = ISB(c, 0, 2) && LWM(c, 0, 2) != 0; S.wmyhi = ISB(c, 1, 2) && LWM(c, 1, 2) != 0;
+  S.wylo = P.wylo; S.wyhi = P.wyhi; S.dl2 = c->dl[1]; S.wmylo = P.wmylo; S.wmyhi = P.wmyhi;
   S.twy = nullptr;
   if (S.wylo || S.wyhi) { if (int e = wall_shear_y_planes(c, S.wylo, S.wyhi, &S.twy)) return e; }
-  const bool small = (c->ntot + 16) * sizeof(real) < (1ull << 32) && !c->fl.wide_offsets;
-  const bool yw = S.wylo || S.wyhi || S.wmylo || S.wmyhi;
-  {
-    // row-marching form: one wave per row of 62 cells; chunks of k so that every CU holds several blocks' worth of independent waves (the LDS-tile
-    // form of this pass -- two barriers per plane, 2.4 against 2.9 TB/s -- lost its A/B in round 2 and went in round 4)
-    const dim3 rb(64, SROWS, 1);
-    const int rgx = (n[0] + 61) / 62, rgy = (n[1] + SROWS - 1) / SROWS;
-    int kr = n[2];
-    // sixteen waves per CU at a time: enough blocks for eight rounds or more, or the last round's idle CUs show (chunks pay a three-plane prologue)
-    while ((long)rgx * rgy * ((n[2] + kr - 1) / kr) < 8192 && kr > 32) kr = (kr + 1) / 2;
-    while ((long)rgx * rgy * ((n[2] + kr - 1) / kr) < 1024 && kr > 8) kr = (kr + 1) / 2;
-    if (int fk = tile_kchunk(c, (long)rgx * rgy, n[2])) kr = fk;
-    S.kchunk = kr; S.bm = band_map(rgx, rgy, (n[2] + kr - 1) / kr);
-    const dim3 rg(band_blocks(S.bm), 1, 1);
-    if (yw) { if (small) LAUNCH(c, (k_smag_rows<unsigned, 1>), rg, rb, 0, c->stream, c->g, S); else LAUNCH(c, (k_smag_rows<size_t, 1>), rg, rb, 0, c->stream, c->g, S); }
-    else if (small) LAUNCH(c, (k_smag_rows<unsigned, 0>), rg, rb, 0, c->stream, c->g, S); else LAUNCH(c, (k_smag_rows<size_t, 0>), rg, rb, 0, c->stream, c->g, S);
-    LAUNCHCHK(c);
-    return 0;
+  const TileGeom &t = P.smag_geo;
+  S.kchunk = t.kchunk; S.bm = t.bm;
+  switch (P.smag) {
+  case SmagKernel::yw32: LAUNCH(c, (k_smag_rows<unsigned, 1>), t.grid, t.block, 0, c->stream, c->g, S); break;
+  case SmagKernel::yw64: LAUNCH(c, (k_smag_rows<size_t, 1>), t.grid, t.block, 0, c->stream, c->g, S); break;
+  case SmagKernel::plain32: LAUNCH(c, (k_smag_rows<unsigned, 0>), t.grid, t.block, 0, c->stream, c->g, S); break;
+  case SmagKernel::plain64: LAUNCH(c, (k_smag_rows<size_t, 0>), t.grid, t.block, 0, c->stream, c->g, S); break;
   }
+  LAUNCHCHK(c);
+  return 0;
 }
 
-// every kernel the SGS pass of this case launches reads wrapped interior columns where x is periodic (cales_step may leave the x ghost columns stale)
-bool sgs_wraps_x(const cales_ctx *c) {
-  if (c->C.sgstype == 0) return true;
-  if (c->C.sgstype == 1) return smag_fast_ok(c);
-  return dsmag_fast_ok(c) && !c->fl.dsmag_xghosts;
-}
-// the form of cmpt_sgs this context takes (cales_describe_plan): the same predicates op_cmpt_sgs / dsmag_fast / smag_fast branch on
+// the form of cmpt_sgs this context takes (cales_describe_plan): the record op_cmpt_sgs launches
 const char *sgs_path_name(const cales_ctx *c) {
-  if (c->C.sgstype == 0) return "none";
-  if (c->C.sgstype == 1) return smag_fast_ok(c) ? "smag_rows" : "smag_reference_sequence";
-  if (!dsmag_fast_ok(c)) return "dsmag_reference_sequence";
-  return dsmag_pairs(c) ? "dsmag_tiles(pair_fields)" : "dsmag_tiles";
+  static const char *names[] = {"none", "smag_rows", "smag_reference_sequence", "dsmag_tiles", "dsmag_reference_sequence"};      // (SgsForm order)
+  return c->sgs.pair ? "dsmag_tiles(pair_fields)" : names[(int)c->sgs.form];
 }
-int op_cmpt_sgs(cales_ctx *c) {
+int op_cmpt_sgs(cales_ctx *c, const SgsFold *fold) {
   const int *n = c->n; const size_t nt = c->ntot;
   real **f = c->f; real *visct = f[CALES_VISCT];
   if (c->C.sgstype == 0) {           // 'none': visct = 0 once (sgs.f90:62-68)
@@ -1442,8 +1445,8 @@ int op_cmpt_sgs(cales_ctx *c) {
       LAUNCH(c, k_alph2, grid3(n[0] + 2, n[1] + 2, n[2] + 2, dim3(64, 4, 1)), dim3(64, 4, 1), 0, c->stream, c->g, c->is_wall[0], c->is_wall[1],
                          c->is_wall[2], c->is_wall[3], c->is_wall[4], c->is_wall[5], c->alph2);
   }
-  if (c->C.sgstype == 2 && dsmag_fast_ok(c)) return dsmag_fast(c);
-  if (c->C.sgstype == 1 && smag_fast_ok(c)) return smag_fast(c);
+  if (c->sgs.form == SgsForm::dsmag_tiles) return dsmag_fast(c, fold);
+  if (c->sgs.form == SgsForm::smag_rows) return smag_fast(c);
   real **wk = c->wk;
   const int if123[3] = {1, 2, 3};
   if (c->C.sgstype == 1) {
@@ -1463,10 +1466,7 @@ int op_cmpt_sgs(cales_ctx *c) {
     SmagArgs A; A.w0 = c->is_wall[0]; A.w1 = c->is_wall[1]; A.w2 = c->is_wall[2]; A.w3 = c->is_wall[3]; A.w4 = c->is_wall[4]; A.w5 = c->is_wall[5];
     A.dl1 = c->dl[0]; A.dl2 = c->dl[1]; A.l3 = c->C.l[2]; A.dxi = c->dli[0]; A.dyi = c->dli[1]; A.visc = c->visc;
     A.sumw = 0.; for (int q = 0; q < 6; ++q) A.sumw += c->is_wall[q];
-    if (!c->d_del) {
-      HIPCHK(c, hipMalloc(&c->d_del, (n[2] + 2) * sizeof(real)));
-      LAUNCH(c, k_smag_del, dim3((n[2] + 2 + 63) / 64), dim3(64), 0, c->stream, n[2] + 2, c->dl[0], c->dl[1], c->d_dzf, c->d_del);
-    }
+    if (int e = smag_del(c)) return e;
     const real *twy = nullptr;      // several slabs: the shear of the y walls comes from the slabs that own them
     if (c->P > 1 && (c->is_wall[2] != 0. || c->is_wall[3] != 0.)) { if (int e = wall_shear_y_planes(c, c->is_wall[2] != 0., c->is_wall[3] != 0., &twy)) return e; }
     LAUNCH(c, k_smag, gr, b, 0, c->stream, c->g, A, c->d_zc, c->d_dzci, c->d_del, f[CALES_U], f[CALES_V], f[CALES_W], c->s0, visct, twy);
