@@ -226,6 +226,7 @@ int cales_create(const cales_case *cs, void *stream, cales_ctx **out) {
   for (int d = 1; d <= 3; ++d) for (int s = 0; s <= 1; ++s) c->is_wall[s + 2 * (d - 1)] = (ISB(c, s, d) && CBV(c, s, d, d) == 'D') ? 1. : 0.;
   for (int s = 0; s <= 1; ++s) c->is_wall[s + 2] = (!(cs->cbcpre[2] == 'P' && cs->cbcpre[3] == 'P') && CBV(c, s, 2, 2) == 'D') ? 1. : 0.;
   sgs_setup(c);      // the form of cmpt_sgs: which scratch fields it needs, whether the projection can fold into it
+  bc_setup(c);       // the form of every BC set in the ghost-cell operators
   // pressure boundary r.h.s. (main.f90:317, bound.f90:447-499)
   { const int *n = c->n;
     const real dx01[2] = {c->dl[0], c->dl[0]}, dy01[2] = {c->dl[1], c->dl[1]};
@@ -401,16 +402,14 @@ static bool fold_mom_ok(const cales_ctx *c) {
   return ok;
 }
 // correction + pressure update of a substep as passes of their own, and the ghost cells of what they produced (main.f90:498-504)
-static int project_now(cales_ctx *c, real dtrk, real alpha) {
+static int project_now(cales_ctx *c, real dtrk, real alpha, int fmask) {
   const bool fuse_cu = !c->fl.unfused_correc && c->C.impdiff != 1;     // updatep only needs pp: one pass with correc
-  { const int e = fuse_cu ? op_correc_updatep(c, dtrk, alpha, 1) : op_correc(c, dtrk); c->defer_force = false; if (e) return e; }
+  if (int e = fuse_cu ? op_correc_updatep(c, dtrk, alpha, 1, fmask) : op_correc(c, dtrk, fmask)) return e;
   // the pressure is final once the fused correction has run: its ghost cells ride along with those of the velocity (one launch, one slab exchange)
-  if (fuse_cu && !c->fl.unmerged_bc) { c->bc_nride = 1; c->bc_ride[0] = c->f[CALES_P]; c->bc_ride_which[0] = 0; }
-  const int e = op_bounduvw(c, c->bcu, c->bcv, c->bcw, 1, 1, c->f[CALES_U], c->f[CALES_V], c->f[CALES_W]);
-  const bool rode = fuse_cu && !c->fl.unmerged_bc && c->bc_nride == 0; c->bc_nride = 0;
-  if (e) return e;
-  if (!fuse_cu) { if (int e2 = op_updatep(c, alpha)) return e2; }
-  if (!rode) { if (int e2 = op_boundp(c, c->f[CALES_P], 0)) return e2; }
+  BcCall b;
+  if (fuse_cu) b.rider(c->f[CALES_P], 0);
+  if (int e = op_bounduvw(c, c->bcu, c->bcv, c->bcw, 1, 1, c->f[CALES_U], c->f[CALES_V], c->f[CALES_W], b)) return e;
+  if (!fuse_cu) { if (int e = op_updatep(c, alpha)) return e; if (int e = op_boundp(c, c->f[CALES_P], 0)) return e; }
   return 0;
 }
 // the ghost cells of everything a caller may look at, all directions (the corners of the x ghost columns with the z ghost planes included), when the
@@ -418,22 +417,14 @@ static int project_now(cales_ctx *c, real dtrk, real alpha) {
 static int end_of_step_refresh(cales_ctx *c) {
   if (!c->step_xskip) return 0;
   c->step_xskip = false;
-  c->bc_nride = 3; c->bc_ride[0] = c->f[CALES_P]; c->bc_ride[1] = c->f[CALES_PP]; c->bc_ride[2] = c->f[CALES_VISCT];
-  c->bc_ride_which[0] = 0; c->bc_ride_which[1] = 0; c->bc_ride_which[2] = 1;
-  if (c->fl.unmerged_bc) c->bc_nride = 0;
-  c->bc_no_halo = true;      // (only the x ghost columns are stale: the rows the neighbours sent are complete but for their two ends, which the local copies fill)
-  struct NoHalo { cales_ctx *c; ~NoHalo() { c->bc_no_halo = false; } } nohalo{c};
-  const int e = op_bounduvw(c, c->bcu, c->bcv, c->bcw, 0, 1, c->f[CALES_U], c->f[CALES_V], c->f[CALES_W]);
-  const bool rode = !c->fl.unmerged_bc && c->bc_nride == 0; c->bc_nride = 0;
-  if (e) return e;
-  if (!(CBV(c, 0, 3, 3) == 'P' && CBV(c, 1, 3, 3) == 'P')) { if (int e2 = op_xwrap_zghost(c, 3, c->f + CALES_U)) return e2; }      // (periodic z: the z copies of the launch above cover the corners)
-  if (!rode) {
-    real *pq[2] = {c->f[CALES_P], c->f[CALES_PP]};
-    if (int e2 = op_boundp_multi(c, 2, pq, 0)) return e2;
-    if (int e2 = op_boundp(c, c->f[CALES_VISCT], 1)) return e2;
-  }
+  BcCall b; b.rows_current = true;      // (only the x ghost columns are stale)
+  b.rider(c->f[CALES_P], 0); b.rider(c->f[CALES_PP], 0); b.rider(c->f[CALES_VISCT], 1);
+  if (int e = op_bounduvw(c, c->bcu, c->bcv, c->bcw, 0, 1, c->f[CALES_U], c->f[CALES_V], c->f[CALES_W], b)) return e;
+  if (!(CBV(c, 0, 3, 3) == 'P' && CBV(c, 1, 3, 3) == 'P')) { if (int e = op_xwrap_zghost(c, 3, c->f + CALES_U)) return e; }      // (periodic z: the z copies of the launch above cover the corners)
   return 0;
 }
+// the mode of a step in progress ends with the scope, on the error returns too
+struct StepMode { cales_ctx *c; ~StepMode() { c->in_step = false; c->step_xskip = false; } };
 // A projection that cales_step left to its successor (fold_mom, third substep) is completed here -- correction pass, ghost cells, and the refresh of
 // the x ghost columns -- before anything else looks at the fields. Collective over the ranks like every entry of the C-ABI.
 static int finish_pending(cales_ctx *c) {
@@ -443,7 +434,7 @@ static int finish_pending(cales_ctx *c) {
     // only the refresh of the x ghost columns is due (cales_step with step_xskip, common.hpp)
     c->pend_xrefresh = false;
     c->in_step = true; c->step_xskip = true;
-    struct Restore { cales_ctx *c; ~Restore() { c->in_step = false; c->step_xskip = false; c->bc_nride = 0; } } restore{c};
+    StepMode mode{c};
     if (int e = end_of_step_refresh(c)) { c->launch_err = "refreshing the x ghost columns failed (" + c->err + "): the context is unusable"; return e; }
     LAUNCHCHK(c);
     return 0;
@@ -451,15 +442,15 @@ static int finish_pending(cales_ctx *c) {
   c->pend_xrefresh = false;      // (the completion below ends with the refresh)
   const real dtrk = c->fold_mom_dtrk;
   c->fold_mom_dtrk = 0.;
-  c->in_step = true; c->step_xskip = c->pend_xskip; c->defer_force = c->fold_mom_fmask != 0;
-  struct Restore { cales_ctx *c; ~Restore() { c->in_step = false; c->step_xskip = false; c->defer_force = false; c->bc_nride = 0; } } restore{c};
+  c->in_step = true; c->step_xskip = c->pend_xskip;
+  StepMode mode{c};
   if (c->fold_mom_pdone) {      // (z-implicit diffusion: the pressure is up to date, ghost cells included)
     c->fold_mom_pdone = false;
-    int e = op_correc(c, dtrk);
+    int e = op_correc(c, dtrk, c->fold_mom_fmask);
     if (!e) e = op_bounduvw(c, c->bcu, c->bcv, c->bcw, 1, 1, c->f[CALES_U], c->f[CALES_V], c->f[CALES_W]);
     if (e) { c->launch_err = "completing a pending projection failed (" + c->err + "): the context is unusable"; return e; }
   } else
-  if (int e = project_now(c, dtrk, 0.)) { c->launch_err = "completing a pending projection failed (" + c->err + "): the context is unusable"; return e; }
+  if (int e = project_now(c, dtrk, 0., c->fold_mom_fmask)) { c->launch_err = "completing a pending projection failed (" + c->err + "): the context is unusable"; return e; }
   if (int e = end_of_step_refresh(c)) { c->launch_err = "completing a pending projection failed (" + c->err + "): the context is unusable"; return e; }
   LAUNCHCHK(c);
   return 0;
@@ -579,8 +570,8 @@ int cales_step(cales_ctx *c, real dt) {
   if (e) { c->launch_err = "an earlier cales_step failed (" + c->err + "): the fields are in an intermediate state, the context is unusable"; return e; }
   return 0;
 }
-// One time step, src/main.f90:417-508. WHICH form every operator takes is the plan's (make_plan); what is left here is the sequence and the
-// hand-over of the plan's decisions to the operators through the context's per-call fields (reset on every return by `reset`).
+// One time step, src/main.f90:417-508. WHICH form every operator takes is the plan's (make_plan); what is left here is the sequence, and the plan's
+// decisions go to the operators as arguments of each call.
 static int step_body(cales_ctx *c, real dt) {
   static const real rk[3][2] = {{32. / 60., 0.}, {25. / 60., -17. / 60.}, {45. / 60., -25. / 60.}};
   const StepPlan pl = current_plan(c);      // (a copy: the plan of THIS step, whatever the step does to the state it was made from)
@@ -588,59 +579,50 @@ static int step_body(cales_ctx *c, real dt) {
   const bool pending_in = c->fold_mom_dtrk != 0.;      // the step before left its last projection to this step's first momentum pass
   LAUNCH(c, k_zero6, dim3(1), dim3(64), 0, c->stream, c->d_force, pending_in ? 3 : 0);     // dpdl(:) = 0
   c->in_step = true;
-  struct Reset { cales_ctx *c; bool keep = false; ~Reset() { c->in_step = false; c->step_xskip = false; c->bc_nride = 0; if (!keep) { c->fold_mom_dtrk = 0.; c->fold_mom_pdone = false; } c->bc_view_dtrk = 0.; c->defer_force = false; c->defer_imp_rhs = false; c->fuse_fillps_dti = 0.; c->fuse_mean_mask = 0; c->bc_skip_wm = false; c->skip_rhs_store = false; c->defer_halo = false; c->bc_no_halo = false; } } reset{c};      // also on the error returns
+  StepMode mode{c};
+  struct Reset { cales_ctx *c; bool keep = false; ~Reset() { if (!keep) { c->fold_mom_dtrk = 0.; c->fold_mom_pdone = false; } } } reset{c};      // (a pending projection does not survive an error return)
   if (c->pend_xrefresh && !pl.xskip) {      // the step before left the x ghost columns stale and this one reads them
     c->pend_xrefresh = false; c->step_xskip = true;
     if (int e = end_of_step_refresh(c)) return e;
   }
   c->step_xskip = pl.xskip;
-  SgsFold fold{0., pl.fold_rows2, pl.defer_force ? pl.force_mask : 0};      // (pl.fold_correc: the projection each substep leaves to cmpt_sgs)
+  const int fmask = pl.defer_force ? pl.force_mask : 0;      // the components whose bulk-forcing increment the projection adds
+  SgsFold fold{0., pl.fold_rows2, fmask};      // (pl.fold_correc: the projection each substep leaves to cmpt_sgs)
   for (int irk = 1; irk <= 3; ++irk) {
     const real dtrk = (rk[irk - 1][0] + rk[irk - 1][1]) * dt, dtrki = 1. / dtrk;
     real alpha = 0.;
-    c->defer_imp_rhs = pl.defer_imp_rhs;
-    c->defer_force = pl.defer_force;
-    c->fuse_mean_mask = pl.mean_mask;
-    c->skip_rhs_store = irk == 3 && !pl.keep_last_rhs;
     const bool p_ghosts_due = c->fold_mom_dtrk != 0. && !c->fold_mom_pdone;      // the momentum pass below stores p + pp of the interior cells: its ghost cells ride along with those of the prediction
-    { const int e = op_rk(c, irk, dt); c->skip_rhs_store = false; if (e) return e; }
-    if (int e = op_bulk_forcing(c)) return e;
+    { RkOpts o; o.mean_mask = pl.mean_mask; o.rhs_in_sweep = pl.defer_imp_rhs; o.store_rhs = irk < 3 || pl.keep_last_rhs;
+      if (int e = op_rk(c, irk, dt, o)) return e; }
+    if (!pl.defer_force && !pl.defer_imp_rhs) { if (int e = op_bulk_forcing(c)) return e; }
     if (c->C.impdiff == 2) {
       alpha = -.5 * c->visc * dtrk;
-      for (int iv = 1; iv <= 3; ++iv) if (int e = op_helmholtz_z(c, iv, alpha)) return e;
+      const real hf12 = .5 * (rk[irk - 1][0] * dt + rk[irk - 1][1] * dt);      // (rounded as rk rounds the factor of its own implicit part)
+      for (int iv = 1; iv <= 3; ++iv) if (int e = op_helmholtz_z(c, iv, alpha, pl.defer_imp_rhs, hf12)) return e;
     } else if (c->C.impdiff == 1) {
       alpha = -.5 * c->visc * dtrk;
       for (int iv = 1; iv <= 3; ++iv) if (int e = op_helmholtz(c, iv, alpha)) return e;
     }
-    c->defer_imp_rhs = false;
-    if (p_ghosts_due && !c->fl.unmerged_bc) { c->bc_nride = 1; c->bc_ride[0] = c->f[CALES_P]; c->bc_ride_which[0] = 0; }
-    { c->bc_skip_wm = pl.skip_first_wm;
+    { BcCall b; b.skip_wm = pl.skip_first_wm;
+      if (p_ghosts_due) b.rider(c->f[CALES_P], 0);
       // (two ghost rows of the prediction, fold_rows2: the rows 2 / n2-1 travel to the neighbours' companion fields in the same message as the rows 1 / n2)
-      c->defer_halo = pl.fold_rows2;
-      int e = op_bounduvw(c, c->bcu, c->bcv, c->bcw, 1, 0, c->f[CALES_U], c->f[CALES_V], c->f[CALES_W]);
+      HaloBatch rows; if (pl.fold_rows2) b.collect = &rows;
+      if (int e = op_bounduvw(c, c->bcu, c->bcv, c->bcw, 1, 0, c->f[CALES_U], c->f[CALES_V], c->f[CALES_W], b)) return e;
       if (pl.fold_rows2) {
-        if (!e) e = halo_y_rows(c, 3, c->f + CALES_U, 2);
-        c->defer_halo = false;
-        if (!e) e = halo_flush_deferred(c, false); else { c->deferred.clear(); c->deferred_wide.clear(); }
-      }
-      c->bc_skip_wm = false;
-      const bool rode = p_ghosts_due && !c->fl.unmerged_bc && c->bc_nride == 0; c->bc_nride = 0;
-      if (e) return e;
-      if (p_ghosts_due && !rode) { if (int e2 = op_boundp(c, c->f[CALES_P], 0)) return e2; } }
-    if (pl.fuse_fill) c->fuse_fillps_dti = dtrki;
-    else { if (int e = op_fillps(c, dtrki)) return e; if (int e = op_updt_rhs_b(c)) return e; }
-    { const int e = op_solver(c); c->fuse_fillps_dti = 0.; if (e) return e; }
+        if (int e = halo_y_rows(c, 3, c->f + CALES_U, 2, b)) return e;
+        if (int e = halo_flush_deferred(c, rows, false)) return e;
+      } }
+    if (!pl.fuse_fill) { if (int e = op_fillps(c, dtrki)) return e; if (int e = op_updt_rhs_b(c)) return e; }
+    if (int e = op_solver(c, pl.fuse_fill ? FusedFill{dtrki, pl.mean_mask} : FusedFill())) return e;
     if (pl.fold_rows2) {
       // three ghost rows of pp above (n2+1, and n2+2, n2+3 in the ghost rows n2+1 of its two companions), two below (0, and -1 in the first companion's row 0):
-      // ONE exchange, behind the ghost-cell kernel (the rows that travel carry their x and z ghost cells)
-      c->defer_halo = true;
+      // ONE exchange, behind the ghost-cell kernel (whole rows travel: the x and z ghost cells the kernel gave them included)
+      HaloBatch rows; BcCall b; b.collect = &rows;
       real *one[1] = {c->f[CALES_PP]};
-      int e = op_boundp(c, c->f[CALES_PP], 0);
-      if (!e) e = halo_y_rows(c, 1, one, 2);
-      if (!e) e = halo_y_rows(c, 1, one, 3);
-      c->defer_halo = false;
-      if (!e) e = halo_flush_deferred(c, false); else { c->deferred.clear(); c->deferred_wide.clear(); }      // (whole rows travel: the x and z ghost cells the kernel above gave them included)
-      if (e) return e;
+      if (int e = op_boundp(c, c->f[CALES_PP], 0, b)) return e;
+      if (int e = halo_y_rows(c, 1, one, 2, b)) return e;
+      if (int e = halo_y_rows(c, 1, one, 3, b)) return e;
+      if (int e = halo_flush_deferred(c, rows, false)) return e;
     } else
     if (pl.fold_correc && c->P > 1) {
       // the folded projection corrects v in the ghost row n2+1 too and needs pp one row further out: row 2 of every slab goes to row 1 of pp's companion
@@ -655,23 +637,19 @@ static int step_body(cales_ctx *c, real dt) {
     } else if (pl.fold_mom && (irk < 3 || pl.lazy_last)) {
       // the ghost cells of the projected velocity now (through the corrected view), its interior cells and p + pp in the next momentum pass -- the next
       // substep's, or after the third substep the next step's (finish_pending for every other entry of the C-ABI)
-      c->fold_mom_fmask = c->defer_force ? pl.force_mask : 0;
-      c->defer_force = false;
+      c->fold_mom_fmask = fmask;
       if (c->C.impdiff == 2) {      // z-implicit diffusion: the pressure update keeps its own pass (updatep.f90:40-46) -- the z Laplacian of pp has no values in ghost cells
         if (int e = op_updatep(c, alpha)) return e;
         if (int e = op_boundp(c, c->f[CALES_P], 0)) return e;
         c->fold_mom_pdone = true;
       }
-      c->bc_view_dtrk = dtrk;
-      const int e = op_bounduvw(c, c->bcu, c->bcv, c->bcw, 1, 1, c->f[CALES_U], c->f[CALES_V], c->f[CALES_W]);
-      c->bc_view_dtrk = 0.;
-      if (e) return e;
+      BcCall b; b.view_dtrk = dtrk; b.view_fmask = fmask;
+      if (int e = op_bounduvw(c, c->bcu, c->bcv, c->bcw, 1, 1, c->f[CALES_U], c->f[CALES_V], c->f[CALES_W], b)) return e;
       c->fold_mom_dtrk = dtrk;
-    } else if (int e = project_now(c, dtrk, alpha)) return e;
-    c->visct_bc_done = false;
-    { const int e = op_cmpt_sgs(c, pl.fold_correc ? &fold : nullptr); c->defer_force = false; if (e) return e; }
-    if (pl.visct_ghosts && !c->visct_bc_done) { if (int e = op_boundp(c, c->f[CALES_VISCT], 1)) return e; }
-    c->visct_bc_done = false;
+    } else if (int e = project_now(c, dtrk, alpha, fmask)) return e;
+    bool visct_ghosts_done = false;
+    if (int e = op_cmpt_sgs(c, pl.fold_correc ? &fold : nullptr, &visct_ghosts_done)) return e;
+    if (pl.visct_ghosts && !visct_ghosts_done) { if (int e = op_boundp(c, c->f[CALES_VISCT], 1)) return e; }
   }
   if (c->fold_mom_dtrk != 0.) { c->pend_xskip = c->step_xskip; reset.keep = true; }      // the last projection is the next step's (or finish_pending's), the refresh with it
   else if (c->step_xskip && !c->fl.eager_projection) c->pend_xrefresh = true;      // the x ghost columns wait for the first caller that is not the next step (finish_pending)

@@ -165,6 +165,44 @@ struct SgsPath {
 // op_cmpt_sgs inside cales_step: the projection folded into the strain-rate pass (StepPlan::fold_correc; rows2: fold_rows2; fmask: deferred forcing)
 struct SgsFold { real dtrk; bool rows2; int fmask; };
 
+// The form each BC set of the case takes in the ghost-cell operators (k_bound.hip), decided once by cales_create (bc_setup) from the BC types, is_bound
+// and Flags, and only read after. No job tables here: they hold field pointers, which the f / f2 swaps change.
+enum class BcForm { merged, all, by_direction };      // k_bc_merged (x, y periodic) | k_bc_all (any pointwise set) | one k_set_bc launch per direction
+struct BcPath {
+  BcForm vel = BcForm::by_direction, wm = BcForm::by_direction, cell[2] = {BcForm::by_direction, BcForm::by_direction};      // velocity set; tangential set of the wall-model faces; pressure [0] / sgs [1] set
+  // the one thing a call decides: k_bc_all does not serve a Neumann condition on face-centred data. Bit d-1: the normal component has one in direction d
+  // on this rank (never with is_correc, which leaves a non-periodic normal direction alone) -- the velocity set takes `all` in calls that skip every such direction
+  int vel_fcn = 0;
+  bool ride[2] = {false, false};      // cell-centred fields with the pressure / sgs set can join the velocity's launch (BcCall::ride)
+};
+// y-halo rows collected over several ghost-cell calls and exchanged in ONE message by halo_flush_deferred: a local of the caller (sixteen planes are what
+// the staging buffers hold). kind: 0 a field, 1 a pair field, 2 / 3 the second / third rows of a field into its first / second companion
+struct HaloBatch { int n = 0; real *p[16]; unsigned char kind[16]; };
+// What a caller inside cales_step asks of ONE call of a ghost-cell operator; default-constructed: the operator as the C-ABI entry runs it
+struct BcCall {
+  int skip = 0;                  // bit d-1: leave direction d alone (the call's consumers do not read it)
+  // bounduvw leaves the wall-model update and the tangential ghost cells of wall-model faces alone: those of the first bounduvw of a substep are rewritten
+  // by the bounduvw that follows the correction before anything reads them (fillps, the solver and correc do not) -- StepPlan::skip_first_wm
+  bool skip_wm = false;
+  // the ghost rows already hold the neighbours' rows, no slab exchange (end-of-step refresh: only the x ghost columns are stale, the rows the neighbours
+  // sent are complete but for their two ends, which the local copies fill; folded strain-rate pass: it formed the ghost rows itself)
+  bool rows_current = false;
+  HaloBatch *collect = nullptr;  // the y-halo rows are collected here instead of exchanged (the caller flushes: halo_flush_deferred)
+  // corrected view (StepPlan::fold_mom): the fields hold the prediction, sources that are interior cells are read as (u* + f) - dtrk grad(pp); fmask: the
+  // components whose bulk-forcing increment the pending projection adds
+  real view_dtrk = 0.; int view_fmask = 0;
+  // bounduvw: cell-centred riders (which: 0 pressure, 1 sgs set). They join the velocity's launch and slab exchange where BcPath::ride allows and z is
+  // not skipped; otherwise bounduvw gives them their ghost cells itself right after the velocity's (boundp, this call minus the riders)
+  int nride = 0; real *ride[3] = {nullptr, nullptr, nullptr}; int ride_which[3] = {0, 0, 0};
+  void rider(real *p, int which) { ride[nride] = p; ride_which[nride++] = which; }
+};
+// rk inside cales_step. mean_mask: the bulk means of these forced components are summed by the forward x transform of the pressure solve (FusedFill);
+// rhs_in_sweep: z-implicit, u -= hf12*dudtd is applied inside the Helmholtz sweep (StepPlan::defer_imp_rhs); store_rhs = false: third substep, nobody reads
+// the new r.h.s. (MomRkArgs::wr_new)
+struct RkOpts { int mean_mask = 0; bool rhs_in_sweep = false, store_rhs = true; };
+// dtrki != 0: the forward x transform of the pressure solve forms pp = div(u*)/dtrk itself and sums the bulk means of the components in mean_mask
+struct FusedFill { real dtrki = 0.; int mean_mask = 0; };
+
 struct KernelStat { std::string name; int64_t calls = 0; real ms = 0.; };
 struct Solver;      // k_solver.hip
 
@@ -208,6 +246,7 @@ struct cales_ctx {
   real *s0, *wk[6], *sij[6], *mij[6], *uc, *vc, *wc, *uf, *vf, *wf, *alph2, *d_p1d;
   real is_wall[6];
   SgsPath sgs;      // see SgsPath above
+  BcPath bc;        // see BcPath above
   bool sgs_first;
   // decomposition
   int P = 1, rank = 0; bool per_y = true; int cw = 0;      // cw: complex mode columns per rank (padded)
@@ -225,8 +264,9 @@ struct cales_ctx {
   // dynamic model, fast path: the eddy-viscosity field holds |S| and d_cs(0:n3+1) the clipped plane coefficients <LM>/<MM> until somebody
   // other than the fused momentum kernel reads it (materialize_visct); visct = |S| * cs(k) is the same product either way
   bool visct_lazy = false; real *d_cs = nullptr;
+  // The mode of the step in progress, read by the host side of nearly every operator. Everything else a step decides reaches the operators as
+  // arguments (BcCall, RkOpts, FusedFill, SgsFold, ...); what remains below besides these two is state that outlives a call (the pending projection).
   bool in_step = false;             // inside cales_step: the operator order is known, dead ghost work can be dropped
-  bool skip_rhs_store = false;      // cales_step, third substep: see MomRkArgs::wr_new
   real *d_stat2 = nullptr;
   real *d_stat = nullptr;      // partial sums and result of the plane statistics
   bool abct_ready = false, force_zeroed = false;
@@ -235,25 +275,14 @@ struct cales_ctx {
   // component, round robin); a hit saves the scaling and the table kernel of that sweep
   struct HzTab { real alpha = 0.; int nz = 0; bool ok = false; } hz_tab[3][4]; int hz_next[3] = {0, 0, 0}; real *d_hztab = nullptr;
   int ncu = 0;      // compute units of the device (balanced_kchunk)
-  int fuse_mean_mask = 0; real *d_mpart = nullptr; size_t n_mpart = 0;      // bulk means of the forced components are summed by that pass too
-  real fuse_fillps_dti = 0.;   // != 0: the forward x transform of the next pressure solve forms pp = div(u*)/dtrk itself (cales_step)
-  bool defer_force = false;      // explicit step, forced directions periodic, no wall model: u += f is applied by the correction kernel
-  bool defer_imp_rhs = false; real hf12 = 0.;   // z-implicit step: u -= hf12*dudtd and u += f are applied inside the Helmholtz sweep
-  bool bc_no_halo = false;      // ghost-cell operators skip the slab exchange (the ghost rows are up to date)
-  bool visct_bc_done = false;   // cmpt_sgs has already updated the ghost cells of the eddy-viscosity field (dsmag, lazy form: with the scratch fields' exchange)
-  bool defer_halo = false; std::vector<real *> deferred; std::vector<unsigned char> deferred_wide;      // (wide: the field is a pair field, rows twice as long)      // y-halo exchanges collected for halo_flush_deferred (k_bound.hip)
-  // cell-centred fields whose ghost-cell update rides along with the next bounduvw that takes the one-launch path (cales_step: the pressure after the
-  // fused correction + pressure update; p, pp and the eddy viscosity at the end of the step); bounduvw clears the count when it has taken them
-  int bc_nride = 0; real *bc_ride[4] = {nullptr, nullptr, nullptr, nullptr}; int bc_ride_which[4] = {0, 0, 0, 0};
-  int bc_skip = 0;         // bit d-1: boundp/bounduvw leave direction d alone (set around calls whose consumers do not need it)
-  bool bc_skip_wm = false; // op_bounduvw leaves the wall-model update and the tangential ghost cells of wall-model faces alone (cales_step, see step_body)
+  real *d_mpart = nullptr; size_t n_mpart = 0;      // partial sums of the bulk means the forward x transform forms (FusedFill::mean_mask)
   // cales_step with periodic x: the x ghost columns are not maintained between the operators of a step -- every kernel of the step reads the wrapped
   // interior column instead (a ghost-column update touches two cache lines per row and field for two values: 1.2 of 45 ms per step at 512^3) -- and
   // are brought up to date once, when the step returns
   bool step_xskip = false;
   // cales_step without subgrid model (explicit diffusion, one rank, every direction periodic or between no-slip walls with Neumann pressure): the
   // projection of substeps 1 and 2 is applied by the momentum pass of the NEXT substep while it loads its planes (k_momrk<.., CORR = 1>); the ghost
-  // cells of the prediction receive their final values through a corrected view in the ghost-cell kernels (bc_view_dtrk). != 0: the dtrk of the
+  // cells of the prediction receive their final values through a corrected view in the ghost-cell kernels (BcCall::view_dtrk). != 0: the dtrk of the
   // pending projection, with the mask of the components whose bulk-forcing increment it adds
   real fold_mom_dtrk = 0.; int fold_mom_fmask = 0;
   bool fold_mom_pdone = false;      // z-implicit diffusion: the pressure update ran as a pass of its own (its z Laplacian of pp cannot be formed in ghost cells), only the velocity is pending
@@ -264,7 +293,6 @@ struct cales_ctx {
   // cales_step with step_xskip returns with the x ghost columns stale and THIS set: the next cales_step does not read them, every other entry of the C-ABI
   // brings them up to date first (finish_pending; local copies, no exchange: safe on several slabs) -- the refresh is 0.2 ms of strided accesses at 512^3
   bool pend_xrefresh = false;
-  real bc_view_dtrk = 0.;      // op_bounduvw: sources are read as (u* + f) - dtrk grad(pp) wherever they are interior cells
   size_t pp_companion_bytes = 0;      // scr2 sits this many bytes behind CALES_PP in one allocation (api.hip field_alloc_multi)
   // several slabs with the dynamic model: u, v, w (both buffer sets) and pp carry COMPANION fields right behind them in their allocations (the same
   // distance for all: comp_one reals) -- the second ghost rows of the folded strain-rate pass (rows -1 and n2+2 in the companion's ghost rows 0 and
@@ -338,24 +366,25 @@ int    hs_check_case(const cales_case *cs, std::string &msg);
 void   hs_bc_rhs(const char *cbc2, const real *bc, int na, int nb, const real *dlc, const real *dlf, char c_or_f, real *rhs);
 
 // ---- device operators (k_*.hip); all asynchronous on c->stream
-int op_bounduvw(cales_ctx *c, DBound &bu, DBound &bv, DBound &bw, int is_updt_wm, int is_correc, real *u, real *v, real *w);
-int op_boundp(cales_ctx *c, real *p, int which);
-int op_boundp_multi(cales_ctx *c, int nf, real **p, int which);
-int halo_flush_deferred(cales_ctx *c, bool overlapped = true);
-int halo_y_rows(cales_ctx *c, int nf, real **flds, int kind);      // kind 2 / 3: rows 2, n2-1 (3, n2-2) of the neighbours into the ghost rows of the fields' first (second) companions
+void bc_setup(cales_ctx *c);                // BcPath (needs is_bound, cbcvel)
+int op_bounduvw(cales_ctx *c, DBound &bu, DBound &bv, DBound &bw, int is_updt_wm, int is_correc, real *u, real *v, real *w, const BcCall &b = BcCall());
+int op_boundp(cales_ctx *c, real *p, int which, const BcCall &b = BcCall());
+int op_boundp_multi(cales_ctx *c, int nf, real **p, int which, const BcCall &b = BcCall());
+int halo_flush_deferred(cales_ctx *c, HaloBatch &rows, bool overlapped = true);
+int halo_y_rows(cales_ctx *c, int nf, real **flds, int kind, const BcCall &b = BcCall());      // kind 2 / 3: rows 2, n2-1 (3, n2-2) of the neighbours into the ghost rows of the fields' first (second) companions
 int op_mom(cales_ctx *c);
-int op_rk(cales_ctx *c, int irk, real dt);
-int op_rk_par(cales_ctx *c, real rkpar1, real rkpar2, real dt);
-int op_momrk(cales_ctx *c, real f1, real f2, real f12);
+int op_rk(cales_ctx *c, int irk, real dt, const RkOpts &o = RkOpts());
+int op_rk_par(cales_ctx *c, real rkpar1, real rkpar2, real dt, const RkOpts &o = RkOpts());
+int op_momrk(cales_ctx *c, real f1, real f2, real f12, const RkOpts &o = RkOpts());
 int op_bulk_forcing(cales_ctx *c);
 int op_bulk_mean_dev(cales_ctx *c, const real *p, int c_or_f, real *d_out);   // result to device scalar
 int op_fillps(cales_ctx *c, real dtrki);
 int op_updt_rhs_b(cales_ctx *c);
-int op_solver(cales_ctx *c);
-int op_helmholtz_z(cales_ctx *c, int ivel, real alpha);
+int op_solver(cales_ctx *c, const FusedFill &fill = FusedFill());
+int op_helmholtz_z(cales_ctx *c, int ivel, real alpha, bool fused_rhs = false, real hf12 = 0.);      // fused_rhs: the sweep forms (u - hf12*dudtd) + f + rhs_b while loading
 extern "C" void cales_comm_release_native(cales_ctx *c);
 int op_helmholtz(cales_ctx *c, int ivel, real alpha);
-int op_correc(cales_ctx *c, real dtrk);
+int op_correc(cales_ctx *c, real dtrk, int fmask = 0);      // fmask: see op_correc_updatep
 int materialize_visct(cales_ctx *c);
 int op_stats_chan(cales_ctx *c, real *buf);
 int op_stats_chan_budget(cales_ctx *c, real *budget, real *leak);
@@ -369,10 +398,12 @@ const char *sgs_path_name(const cales_ctx *c);      // likewise for cmpt_sgs (Sg
 void sgs_setup(cales_ctx *c);               // SgsPath: form, flags, static kernel arguments and kernels (needs is_wall)
 int sgs_setup_launches(cales_ctx *c);       // ... and the launch geometry of its tile passes (needs ncu)
 int op_force_from_partials(cales_ctx *c, int mask, const real *part, int nblk);
-int op_correc_updatep(cales_ctx *c, real dtrk, real alpha, int upd);
+int op_correc_updatep(cales_ctx *c, real dtrk, real alpha, int upd, int fmask = 0);      // fmask: the components whose deferred bulk-forcing increment the pass adds (StepPlan::defer_force)
 int op_updatep(cales_ctx *c, real alpha);
-int op_cmpt_sgs(cales_ctx *c, const SgsFold *fold);      // fold: the projection folded into the strain-rate pass (cales_step), nullptr: not folded
-int op_boundp_wide(cales_ctx *c, int nf, real **p2, int which);      // ghost cells of pair fields (y, z; x periodic and wrapped by the consumers)
+// fold: the projection folded into the strain-rate pass (cales_step), nullptr: not folded; visct_ghosts_done (cales_step): set where the pass has updated the
+// ghost cells of the eddy viscosity itself (dsmag, lazy form on several slabs: with the scratch fields' exchange)
+int op_cmpt_sgs(cales_ctx *c, const SgsFold *fold, bool *visct_ghosts_done = nullptr);
+int op_boundp_wide(cales_ctx *c, int nf, real **p2, int which, const BcCall &b = BcCall());      // ghost cells of pair fields (y, z; x periodic and wrapped by the consumers)
 int op_xwrap_zghost(cales_ctx *c, int nf, real **f);      // periodic copy of the x ghost columns on the planes k = 0 and n3+1
 int op_chkdt(cales_ctx *c, real *dtmax);
 int op_chkdiv(cales_ctx *c, real *divtot, real *divmax);
@@ -515,5 +546,5 @@ static inline bool wm_samples_ghost(const cales_ctx *c) {
   }
   return false;
 }
-static inline int bc_skipped(const cales_ctx *c) { return c->bc_skip | (c->step_xskip ? 1 : 0); }
+static inline int bc_skipped(const cales_ctx *c, const BcCall &b) { return b.skip | (c->step_xskip ? 1 : 0); }
 static inline dim3 grid3(int nx, int ny, int nz, dim3 b) { return dim3((nx + b.x - 1) / b.x, (ny + b.y - 1) / b.y, (nz + b.z - 1) / b.z); }

@@ -20,10 +20,10 @@ __device__ inline real view_rd(const Geom &g, const CorrView &V, int comp, const
   const real cf = comp == 1 ? V.cfi : comp == 2 ? V.cfj : V.dt * V.dzci[k];
   return ((V.fmask >> (comp - 1) & 1) ? v + V.force[comp - 1] : v) - cf * (pb - pc);
 }
-static CorrView corr_view(const cales_ctx *c) {
+static CorrView corr_view(const cales_ctx *c, const BcCall &b) {
   CorrView V{};
-  V.pp = c->f[CALES_PP]; V.dzci = c->d_dzci; V.force = c->d_force; V.cfi = c->bc_view_dtrk * c->dli[0]; V.cfj = c->bc_view_dtrk * c->dli[1]; V.dt = c->bc_view_dtrk;
-  V.fmask = c->fold_mom_fmask; V.perx = c->step_xskip ? 1 : 0;
+  V.pp = c->f[CALES_PP]; V.dzci = c->d_dzci; V.force = c->d_force; V.cfi = b.view_dtrk * c->dli[0]; V.cfj = b.view_dtrk * c->dli[1]; V.dt = b.view_dtrk;
+  V.fmask = b.view_fmask; V.perx = c->step_xskip ? 1 : 0;
   return V;
 }
 struct BcJob {
@@ -229,9 +229,9 @@ static int launch_all(cales_ctx *c, AJobs &J) {
   return 0;
 }
 // one direction of one field: the types of its two ends as the reference's loops over idir / ibound would apply them on this rank
-static void a_dir(cales_ctx *c, ADir &D, int idir, char c0, char c1, int centered, const real *bc0, const real *bc1, real dr0, real dr1) {
+static void a_dir(cales_ctx *c, const BcCall &b, ADir &D, int idir, char c0, char c1, int centered, const real *bc0, const real *bc1, real dr0, real dr1) {
   D.t0 = D.t1 = 0; D.cen = (char)centered; D.dr0 = dr0; D.dr1 = dr1; D.bc0 = bc0; D.bc1 = bc1;
-  if ((bc_skipped(c) >> (idir - 1) & 1) && !(idir == 3 && c0 == 'P' && c1 == 'P')) return;      // (a periodic z is copied even where z is "skipped": the skip is for wall planes nobody reads)
+  if ((bc_skipped(c, b) >> (idir - 1) & 1) && !(idir == 3 && c0 == 'P' && c1 == 'P')) return;      // (a periodic z is copied even where z is "skipped": the skip is for wall planes nobody reads)
   if (c0 == 'P' && c1 == 'P') {
     if (idir == 2 && c->P > 1) return;                // rows exchanged between the slabs (halo_y_comm, before the launch)
     D.t0 = D.t1 = 'P'; return;                        // (x and z are never decomposed: a local copy)
@@ -239,16 +239,29 @@ static void a_dir(cales_ctx *c, ADir &D, int idir, char c0, char c1, int centere
   if (ISB(c, 0, idir)) D.t0 = c0;
   if (ISB(c, 1, idir)) D.t1 = c1;
 }
-static bool a_served(const AJobs &J) {      // no Neumann condition on face-centred data
-  for (int q = 0; q < J.nf; ++q) for (int d = 0; d < 3; ++d) { const ADir &D = J.f[q].d[d]; if (!D.cen && (D.t0 == 'N' || D.t1 == 'N')) return false; }
-  return true;
-}
 // x periodic, y periodic on one rank or exchanged between slabs, z pointwise
 static bool merged_ok(const cales_ctx *c, const char *cbx, const char *cby) {
   if (c->fl.unmerged_bc) return false;
   if (!(cbx[0] == 'P' && cbx[1] == 'P')) return false;
   if (!(cby[0] == 'P' && cby[1] == 'P')) return false;
   return true;
+}
+// BcPath: the form of every BC set of the case (cales_create)
+void bc_setup(cales_ctx *c) {
+  BcPath &B = c->bc;
+  const BcForm other = c->fl.unmerged_bc ? BcForm::by_direction : BcForm::all;
+  for (int w = 0; w < 2; ++w) { const char *cb = w ? c->C.cbcsgs : c->C.cbcpre; B.cell[w] = merged_ok(c, cb, cb + 2) ? BcForm::merged : other; }
+  bool merged = B.cell[0] == BcForm::merged;       // velocity and pressure are periodic together (sanity.f90:163-175)
+  for (int ivel = 1; ivel <= 3 && merged; ++ivel) {
+    for (int d = 1; d <= 2; ++d) merged = merged && CBV(c, 0, d, ivel) == 'P' && CBV(c, 1, d, ivel) == 'P';
+    if (ivel == 3 && (CBV(c, 0, 3, 3) == 'N' || CBV(c, 1, 3, 3) == 'N')) merged = false;      // face-centred Neumann reads the plane it rewrites
+  }
+  B.vel = merged ? BcForm::merged : other;
+  B.wm = other;      // (tangential components only: cell-centred along the wall normal, always served)
+  B.vel_fcn = 0;
+  for (int d = 1; d <= 3; ++d) for (int sd = 0; sd <= 1; ++sd) if (ISB(c, sd, d) && CBV(c, sd, d, d) == 'N') B.vel_fcn |= 1 << (d - 1);
+  // the periodic kernel takes riders whose own set is periodic in x and y, the all-directions kernel any cell-centred set
+  for (int w = 0; w < 2; ++w) B.ride[w] = merged ? B.cell[w] == BcForm::merged : B.vel == BcForm::all;
 }
 
 // y-slab neighbours (bound.f90:619-696 for idir = 2): pack the first/last interior rows of nf fields into the
@@ -282,7 +295,7 @@ __global__ __launch_bounds__(256) void k_unpack_y(Geom g, HaloFields H, const re
 // 2 (n1 + 2) values per row, pitches doubled. Its x ghost "columns" mean nothing in that view -- the callers skip direction x.
 static Geom wide_geom(const cales_ctx *c) { Geom g = c->g; g.n1 = 2 * c->g.n1 + 2; g.s1 = 2 * c->g.s1; g.s12 = 2 * c->g.s12; return g; }
 // (wide[q] != 0: field q is a pair field; nullptr: none is)
-static int halo_y_on(cales_ctx *c, int nf, real **flds, hipStream_t st, bool overlapped, const unsigned char *wide = nullptr) {
+static int halo_y_on(cales_ctx *c, const BcCall &b, int nf, real **flds, hipStream_t st, bool overlapped, const unsigned char *wide = nullptr) {
   const Geom &G = c->g;
   HaloFields H; H.nf = nf; int planes = 0, anyw = 0;
   // (wide[q]: 0 a field, 1 a pair field, 2 / 3 the second / third rows of a field into its first / second companion)
@@ -291,63 +304,69 @@ static int halo_y_on(cales_ctx *c, int nf, real **flds, hipStream_t st, bool ove
     H.p[q] = flds[q]; H.wide[q] = kind == 1; H.off[q] = planes; planes += 1 + H.wide[q]; anyw |= H.wide[q]; H.vcomp[q] = 0;
     H.rofs[q] = kind >= 2 ? (unsigned char)(kind - 1) : 0; H.dst[q] = kind >= 2 ? flds[q] + (size_t)(kind - 1) * c->comp_one : flds[q];
   }
-  if (c->bc_view_dtrk != 0.) {      // op_bounduvw through the corrected view: the velocity rows that leave are those of the projected velocity
-    H.V = corr_view(c);
+  if (b.view_dtrk != 0.) {      // op_bounduvw through the corrected view: the velocity rows that leave are those of the projected velocity
+    H.V = corr_view(c, b);
     for (int q = 0; q < nf; ++q) for (int iv = 0; iv < 3; ++iv) if (flds[q] == c->f[CALES_U + iv] && !H.rofs[q]) H.vcomp[q] = (unsigned char)(iv + 1);
   }
   const int64_t cnt = (int64_t)G.s1 * (c->n[2] + 2) * planes;
   if (4 * cnt > c->comm.nbuf) { c->err = "halo staging buffer too small"; return 1; }
-  dim3 b(64, 4, 1), gr(((G.s1 << anyw) + 63) / 64, (c->n[2] + 2 + 3) / 4, nf);
-  LAUNCH(c, k_pack_y, gr, b, 0, st, G, H, c->comm.A, c->comm.A + cnt);
+  dim3 blk(64, 4, 1), gr(((G.s1 << anyw) + 63) / 64, (c->n[2] + 2 + 3) / 4, nf);
+  LAUNCH(c, k_pack_y, gr, blk, 0, st, G, H, c->comm.A, c->comm.A + cnt);
   { ProfScope ps(c, "halo_exchange", st);
     const int rc = overlapped ? c->comm.halo_s(c->comm.user, 0, cnt, 0, cnt, cnt, (void *)st) : c->comm.halo(c->comm.user, 0, cnt, 0, cnt, cnt);
     if (rc) { c->err = "halo callback failed"; return 1; } }
   const int has_lo = (c->per_y || c->rank > 0) ? 1 : 0, has_hi = (c->per_y || c->rank < c->P - 1) ? 1 : 0;
-  LAUNCH(c, k_unpack_y, gr, b, 0, st, G, H, c->comm.B, c->comm.B + cnt, has_lo, has_hi);
+  LAUNCH(c, k_unpack_y, gr, blk, 0, st, G, H, c->comm.B, c->comm.B + cnt, has_lo, has_hi);
   LAUNCHCHK(c);
   return 0;
 }
-int halo_y_rows(cales_ctx *c, int nf, real **flds, int kind) {
+// the rows of nf fields of one kind: into the caller's batch (BcCall::collect, exchanged later by halo_flush_deferred) or exchanged now
+static int halo_y_kind(cales_ctx *c, const BcCall &b, int nf, real **flds, int kind) {
+  if (b.collect) {
+    HaloBatch &R = *b.collect;
+    if (R.n + nf > 16) { c->err = "halo batch full"; return 1; }
+    for (int q = 0; q < nf; ++q) { R.p[R.n] = flds[q]; R.kind[R.n++] = (unsigned char)kind; }
+    return 0;
+  }
+  unsigned char w[16]; for (int q = 0; q < nf && q < 16; ++q) w[q] = (unsigned char)kind;
+  return halo_y_on(c, b, nf, flds, c->stream, false, w);
+}
+int halo_y_rows(cales_ctx *c, int nf, real **flds, int kind, const BcCall &b) {
   if (!c->comm.on) { c->err = "nranks > 1 but no communication hooks registered (cales_set_comm)"; return 1; }
   if (!c->comp_one || kind < 2 || kind > 3) { c->err = "halo_y_rows: no companion fields"; return 1; }
-  if (c->defer_halo) { for (int q = 0; q < nf; ++q) { c->deferred.push_back(flds[q]); c->deferred_wide.push_back((unsigned char)kind); } return 0; }
-  unsigned char w[16]; for (int q = 0; q < nf && q < 16; ++q) w[q] = (unsigned char)kind;
-  return halo_y_on(c, nf, flds, c->stream, false, w);
+  return halo_y_kind(c, b, nf, flds, kind);
 }
-static int halo_y_comm(cales_ctx *c, int nf, real **flds, bool wide = false) {
+static int halo_y_comm(cales_ctx *c, const BcCall &b, int nf, real **flds, bool wide = false) {
   if (!c->comm.on) { c->err = "nranks > 1 but no communication hooks registered (cales_set_comm)"; return 1; }
-  if (c->bc_no_halo) return 0;      // the ghost rows already hold the neighbours' rows (end-of-step refresh of the x ghost columns, cales_step)
-  if (c->defer_halo) { for (int q = 0; q < nf; ++q) { c->deferred.push_back(flds[q]); c->deferred_wide.push_back(wide ? 1 : 0); } return 0; }      // exchanged later (halo_flush_deferred)
-  unsigned char w[16]; for (int q = 0; q < nf && q < 16; ++q) w[q] = wide ? 1 : 0;
-  return halo_y_on(c, nf, flds, c->stream, false, w);
+  if (b.rows_current) return 0;
+  return halo_y_kind(c, b, nf, flds, wide ? 1 : 0);
 }
-// The y-halo rows of the fields collected while c->defer_halo was set travel on the second stream, after everything queued on the
+// The y-halo rows of the fields collected in `rows` (BcCall::collect) travel on the second stream, after everything queued on the
 // context's stream so far (their ghost-cell kernels included: what those wrote into the ghost rows is overwritten by the rows
 // that arrive, whose own x/z ghost cells the neighbour has already set -- the same values the in-order sequence produces).
 // The caller makes the context's stream wait (stream_after) before the first kernel that reads those ghost rows.
 // overlapped = false: the same batching in order on the context's stream -- one exchange for up to twelve fields instead of one per call.
-int halo_flush_deferred(cales_ctx *c, bool overlapped) {
-  if (c->deferred.empty()) return 0;
+int halo_flush_deferred(cales_ctx *c, HaloBatch &rows, bool overlapped) {
+  if (!rows.n) return 0;
   if (overlapped) { if (int e = stream_after(c, c->comm_stream, c->stream)) return e; }
-  for (size_t q0 = 0; q0 < c->deferred.size();) {      // as many fields per exchange as the staging buffers hold: sixteen planes, a pair field takes two
+  for (int q0 = 0; q0 < rows.n;) {      // as many fields per exchange as the staging buffers hold: sixteen planes, a pair field takes two
     int nf = 0, planes = 0;
-    while (q0 + nf < c->deferred.size() && nf < 16 && planes + 1 + (c->deferred_wide[q0 + nf] == 1) <= 16) { planes += 1 + (c->deferred_wide[q0 + nf] == 1); ++nf; }
-    if (int e = halo_y_on(c, nf, c->deferred.data() + q0, overlapped ? c->comm_stream : c->stream, overlapped, c->deferred_wide.data() + q0)) { c->deferred.clear(); c->deferred_wide.clear(); return e; }
+    while (q0 + nf < rows.n && planes + 1 + (rows.kind[q0 + nf] == 1) <= 16) { planes += 1 + (rows.kind[q0 + nf] == 1); ++nf; }
+    if (int e = halo_y_on(c, BcCall(), nf, rows.p + q0, overlapped ? c->comm_stream : c->stream, overlapped, rows.kind + q0)) return e;
     q0 += nf;
   }
-  c->deferred_wide.clear();
-  c->deferred.clear();
+  rows.n = 0;
   return 0;
 }
 // halo exchange in the non-pencil directions: y across slabs (or a periodic copy on one rank), z always local
-static int halo_self(cales_ctx *c, int nf, real **flds) {
-  if (c->P > 1) { if (int e = halo_y_comm(c, nf, flds)) return e; }
+static int halo_self(cales_ctx *c, const BcCall &b, int nf, real **flds) {
+  if (c->P > 1) { if (int e = halo_y_comm(c, b, nf, flds)) return e; }
   for (int idir = (c->P > 1 ? 3 : 2); idir <= 3; ++idir) {
     const bool periodic = idir == 2 ? c->per_y : !ISB(c, 0, 3);
     if (!periodic) continue;             // not periodic: neighbours are MPI_PROC_NULL
     BcJobs J; J.njobs = 0; J.idir = idir;
-    const bool view = c->bc_view_dtrk != 0.;      // op_bounduvw through the corrected view: the periodic copies are those of the projected velocity
-    if (view) J.V = corr_view(c);
+    const bool view = b.view_dtrk != 0.;      // op_bounduvw through the corrected view: the periodic copies are those of the projected velocity
+    if (view) J.V = corr_view(c, b);
     for (int q = 0; q < nf; ++q) {
       if (J.njobs == 6) { if (int e = launch_jobs(c, J)) return e; J.njobs = 0; }
       add_job(J, flds[q], 'P', 0, 1, nullptr, 0.);
@@ -367,25 +386,25 @@ static void merged_pfield(cales_ctx *c, MField &F, real *p, int which) {
   F.bc0 = plane(bc, 3, 0, c->n); F.bc1 = plane(bc, 3, 1, c->n); F.dr0 = c->dzc[0]; F.dr1 = c->dzc[c->n[2]];
 }
 // a cell-centred field with the pressure (which = 0) or the sgs (1) BC set as one entry of the all-directions kernel
-static void all_pfield(cales_ctx *c, AField &F, real *p, int which) {
+static void all_pfield(cales_ctx *c, const BcCall &b, AField &F, real *p, int which) {
   const char *cbc = which == 0 ? c->C.cbcpre : c->C.cbcsgs; const DBound &bc = which == 0 ? c->bcp : c->bcs;
   F.p = p; F.vcomp = 0;
   for (int idir = 1; idir <= 3; ++idir) {
     const real dr0 = idir < 3 ? c->dl[idir - 1] : c->dzc[0], dr1 = idir < 3 ? c->dl[idir - 1] : c->dzc[c->n[2]];
-    a_dir(c, F.d[idir - 1], idir, cbc[2 * (idir - 1)], cbc[2 * (idir - 1) + 1], 1, plane(bc, idir, 0, c->n), plane(bc, idir, 1, c->n), dr0, dr1);
+    a_dir(c, b, F.d[idir - 1], idir, cbc[2 * (idir - 1)], cbc[2 * (idir - 1) + 1], 1, plane(bc, idir, 0, c->n), plane(bc, idir, 1, c->n), dr0, dr1);
   }
 }
 // ------------------------------------------------------------------------------------------ boundp (bound.f90:156-200)
 // pair fields (x and y periodic only: SgsPath::pair): the y rows (wrapped on one rank, exchanged between slabs) and the z ghost planes through the
 // one-launch kernel in the doubled-width view; direction x is the consumers' business (they wrap around)
-int op_boundp_wide(cales_ctx *c, int nf, real **p2, int which) {
+int op_boundp_wide(cales_ctx *c, int nf, real **p2, int which, const BcCall &b) {
   ProfScope ps(c, "boundp");
   const char *cbc = which == 0 ? c->C.cbcpre : c->C.cbcsgs;
-  if (!merged_ok(c, cbc, cbc + 2) || nf > 8 || !(bc_skipped(c) & 1)) { c->err = "pair fields need periodic x and y and a caller that skips direction x"; return 1; }
-  if (c->P > 1) { if (int e = halo_y_comm(c, nf, p2, true)) return e; }
+  if (c->bc.cell[which] != BcForm::merged || nf > 8 || !(bc_skipped(c, b) & 1)) { c->err = "pair fields need periodic x and y and a caller that skips direction x"; return 1; }
+  if (c->P > 1) { if (int e = halo_y_comm(c, b, nf, p2, true)) return e; }
   const bool per_z = cbc[4] == 'P' && cbc[5] == 'P';
   const Geom G = wide_geom(c);
-  MJobs J; J.nf = nf; J.do_x = 0; J.wrap_y = c->P == 1; J.do_z = per_z || !(bc_skipped(c) & 4);
+  MJobs J; J.nf = nf; J.do_x = 0; J.wrap_y = c->P == 1; J.do_z = per_z || !(bc_skipped(c, b) & 4);
   if (!J.wrap_y && !J.do_z) return 0;
   for (int q = 0; q < nf; ++q) {
     merged_pfield(c, J.f[q], p2[q], which);
@@ -396,29 +415,30 @@ int op_boundp_wide(cales_ctx *c, int nf, real **p2, int which) {
   return launch_merged(c, J, &G);
 }
 // nf <= 8 fields with the same BC set in one halo exchange and as few launches as the job table allows
-int op_boundp_multi(cales_ctx *c, int nf, real **p, int which) {
+int op_boundp_multi(cales_ctx *c, int nf, real **p, int which, const BcCall &b) {
   ProfScope ps(c, "boundp");
   const char *cbc = which == 0 ? c->C.cbcpre : c->C.cbcsgs; const DBound &bc = which == 0 ? c->bcp : c->bcs;
-  if (merged_ok(c, cbc, cbc + 2) && nf <= 8) {      // x, y periodic: all three directions in one launch (k_bc_merged)
-    if (c->P > 1) { if (int e = halo_y_comm(c, nf, p)) return e; }
+  const BcForm form = c->bc.cell[which];
+  if (form == BcForm::merged && nf <= 8) {      // x, y periodic: all three directions in one launch (k_bc_merged)
+    if (c->P > 1) { if (int e = halo_y_comm(c, b, nf, p)) return e; }
     const bool per_z = cbc[4] == 'P' && cbc[5] == 'P';
-    MJobs J; J.nf = nf; J.do_x = !(bc_skipped(c) & 1); J.wrap_y = c->P == 1; J.do_z = per_z || !(bc_skipped(c) & 4);
+    MJobs J; J.nf = nf; J.do_x = !(bc_skipped(c, b) & 1); J.wrap_y = c->P == 1; J.do_z = per_z || !(bc_skipped(c, b) & 4);
     for (int q = 0; q < nf; ++q) merged_pfield(c, J.f[q], p[q], which);
     return launch_merged(c, J);
   }
-  if (!c->fl.unmerged_bc) {      // every other set of a cell-centred field: all directions in one launch (k_bc_all), six fields at a time
-    if (c->P > 1) { if (int e = halo_y_comm(c, nf, p)) return e; }
+  if (form != BcForm::by_direction) {      // every other set of a cell-centred field: all directions in one launch (k_bc_all), six fields at a time
+    if (c->P > 1) { if (int e = halo_y_comm(c, b, nf, p)) return e; }
     for (int q0 = 0; q0 < nf; q0 += 6) {
       AJobs J; J.nf = std::min(6, nf - q0); J.V = CorrView{};
-      for (int q = 0; q < J.nf; ++q) all_pfield(c, J.f[q], p[q0 + q], which);
+      for (int q = 0; q < J.nf; ++q) all_pfield(c, b, J.f[q], p[q0 + q], which);
       if (int e = launch_all(c, J)) return e;
     }
     return 0;
   }
-  if (int e = halo_self(c, nf, p)) return e;
+  if (int e = halo_self(c, b, nf, p)) return e;
   for (int idir = 1; idir <= 3; ++idir) {
     if (!ISB(c, 0, idir) && !ISB(c, 1, idir)) continue;
-    if (bc_skipped(c) >> (idir - 1) & 1) continue;
+    if (bc_skipped(c, b) >> (idir - 1) & 1) continue;
     BcJobs J; J.njobs = 0; J.idir = idir;
     const real dr0 = idir < 3 ? c->dl[idir - 1] : c->dzc[0], dr1 = idir < 3 ? c->dl[idir - 1] : c->dzc[c->n[2]];
     const char c0 = cbc[0 + 2 * (idir - 1)], c1 = cbc[1 + 2 * (idir - 1)];
@@ -434,7 +454,7 @@ int op_boundp_multi(cales_ctx *c, int nf, real **p, int which) {
   }
   return 0;
 }
-int op_boundp(cales_ctx *c, real *p, int which) { real *fl[1] = {p}; return op_boundp_multi(c, 1, fl, which); }
+int op_boundp(cales_ctx *c, real *p, int which, const BcCall &b) { real *fl[1] = {p}; return op_boundp_multi(c, 1, fl, which, b); }
 
 // ------------------------------------------------------------------------------------------ wall model (wmodel.f90:65-335)
 __device__ inline real vel_relative(real v1, real v2, real coef, real mag) {
@@ -579,57 +599,33 @@ static int updt_wallmodelbc(cales_ctx *c, DBound &bu, DBound &bv, DBound &bw, co
 }
 
 // ------------------------------------------------------------------------------------------ bounduvw (bound.f90:18-154)
-int op_bounduvw(cales_ctx *c, DBound &bu, DBound &bv, DBound &bw, int is_updt_wm, int is_correc, real *u, real *v, real *w) {
+// rode: the riders of the call (BcCall::ride) went with the velocity's launch
+static int bounduvw_launches(cales_ctx *c, DBound &bu, DBound &bv, DBound &bw, int is_updt_wm, int is_correc, real *u, real *v, real *w, const BcCall &b, bool &rode) {
   ProfScope ps(c, "bounduvw");
   const int *n = c->n;
   real *fl[3] = {u, v, w};
   DBound *bnd[3] = {&bu, &bv, &bw};
   // corrected view (cales_step, fold_mom): the fields hold the prediction, the ghost cells receive the values of the projected velocity
-  const bool view = c->bc_view_dtrk != 0.;
-  const CorrView V = view ? corr_view(c) : CorrView{};
-  bool merged = merged_ok(c, c->C.cbcpre, c->C.cbcpre + 2);       // velocity and pressure are periodic together (sanity.f90:163-175)
-  for (int ivel = 1; ivel <= 3 && merged; ++ivel) {
-    for (int d = 1; d <= 2; ++d) merged = merged && CBV(c, 0, d, ivel) == 'P' && CBV(c, 1, d, ivel) == 'P';
-    if (ivel == 3 && (CBV(c, 0, 3, 3) == 'N' || CBV(c, 1, 3, 3) == 'N')) merged = false;      // face-centred Neumann reads the plane it rewrites
+  const bool view = b.view_dtrk != 0.;
+  const CorrView V = view ? corr_view(c, b) : CorrView{};
+  const int skipped = bc_skipped(c, b);
+  // the form of the velocity set (BcPath): k_bc_all only while no direction of this call holds a Neumann condition on the normal component
+  BcForm form = c->bc.vel;
+  if (form == BcForm::all && !is_correc && (c->bc.vel_fcn & ~skipped)) form = BcForm::by_direction;
+  // riders: cell-centred fields join the velocity's launch -- and its slab exchange
+  int nr = 0;
+  if (b.nride > 0 && form != BcForm::by_direction && !(skipped & 4)) {
+    nr = b.nride;
+    for (int q = 0; q < b.nride; ++q) if (!c->bc.ride[b.ride_which[q]]) nr = 0;
   }
-  // the all-directions kernel for the sets the periodic one does not serve: types of every (component, direction, end) as the loops below would apply them
-  AJobs JA; JA.nf = 0; JA.V = V; bool allv = false; int nra = 0; real *alla[6] = {fl[0], fl[1], fl[2], nullptr, nullptr, nullptr};
-  if (!merged && !c->fl.unmerged_bc) {
-    JA.nf = 3;
-    for (int ivel = 1; ivel <= 3; ++ivel) {
-      AField &F = JA.f[ivel - 1]; F.p = fl[ivel - 1]; F.vcomp = view ? (char)ivel : 0;
-      for (int idir = 1; idir <= 3; ++idir) {
-        const bool periodic = CBV(c, 0, idir, idir) == 'P' && CBV(c, 1, idir, idir) == 'P', normal = ivel == idir;
-        const real dr0 = idir < 3 ? c->dl[idir - 1] : (normal ? c->dzf[0] : c->dzc[0]), dr1 = idir < 3 ? c->dl[idir - 1] : (normal ? c->dzf[n[2]] : c->dzc[n[2]]);
-        char c0 = CBV(c, 0, idir, ivel), c1 = CBV(c, 1, idir, ivel);
-        if (normal && is_correc && !periodic) c0 = c1 = 0;      // the corrected normal velocity keeps its wall value (bound.f90:60-75)
-        a_dir(c, F.d[idir - 1], idir, c0, c1, normal ? 0 : 1, plane(*bnd[ivel - 1], idir, 0, n), plane(*bnd[ivel - 1], idir, 1, n), dr0, dr1);
-        if (!c0 && !c1) F.d[idir - 1].t0 = F.d[idir - 1].t1 = 0;
-        if (!normal) { if (LWM(c, 0, idir) != 0) F.d[idir - 1].t0 = 0; if (LWM(c, 1, idir) != 0) F.d[idir - 1].t1 = 0; }      // set below from the wall-model stress
-      }
-    }
-    allv = a_served(JA);
-    if (allv && c->bc_nride > 0 && c->bc_nride <= 3 && !(bc_skipped(c) & 4)) {      // riders (cales_step): cell-centred fields join this launch -- and this slab exchange
-      nra = c->bc_nride;
-      for (int q = 0; q < nra; ++q) { all_pfield(c, JA.f[3 + q], c->bc_ride[q], c->bc_ride_which[q]); alla[3 + q] = c->bc_ride[q]; }
-      JA.nf = 3 + nra;
-    }
-  }
-  if (merged) {
-    // riders (cales_step): cell-centred fields whose BC sets take the one-launch kernel too join this launch -- and this slab exchange
-    int nr = 0;
-    if (c->bc_nride > 0 && !(bc_skipped(c) & 4)) {
-      bool ok = true;
-      for (int q = 0; q < c->bc_nride; ++q) { const char *cb = c->bc_ride_which[q] == 0 ? c->C.cbcpre : c->C.cbcsgs; ok = ok && merged_ok(c, cb, cb + 2); }
-      if (ok) nr = c->bc_nride;
-    }
-    real *all[8] = {fl[0], fl[1], fl[2]};
-    for (int q = 0; q < nr; ++q) all[3 + q] = c->bc_ride[q];
-    if (c->P > 1) { if (int e = halo_y_comm(c, 3 + nr, all)) return e; }
+  rode = nr > 0;
+  real *all[6] = {fl[0], fl[1], fl[2], nullptr, nullptr, nullptr};
+  for (int q = 0; q < nr; ++q) all[3 + q] = b.ride[q];
+  if (form == BcForm::merged) {
+    if (c->P > 1) { if (int e = halo_y_comm(c, b, 3 + nr, all)) return e; }
     const bool per_z = CBV(c, 0, 3, 3) == 'P' && CBV(c, 1, 3, 3) == 'P';
-    MJobs J; J.nf = 3 + nr; J.do_x = !(bc_skipped(c) & 1); J.wrap_y = c->P == 1; J.do_z = per_z || !(bc_skipped(c) & 4);
-    for (int q = 0; q < nr; ++q) merged_pfield(c, J.f[3 + q], c->bc_ride[q], c->bc_ride_which[q]);
-    if (nr) c->bc_nride = 0;      // taken
+    MJobs J; J.nf = 3 + nr; J.do_x = !(skipped & 1); J.wrap_y = c->P == 1; J.do_z = per_z || !(skipped & 4);
+    for (int q = 0; q < nr; ++q) merged_pfield(c, J.f[3 + q], b.ride[q], b.ride_which[q]);
     J.V = V;
     for (int ivel = 1; ivel <= 3; ++ivel) {
       MField &F = J.f[ivel - 1]; F.p = fl[ivel - 1]; F.vcomp = view ? (char)ivel : 0;
@@ -643,16 +639,30 @@ int op_bounduvw(cales_ctx *c, DBound &bu, DBound &bv, DBound &bw, int is_updt_wm
       if (!normal) { if (LWM(c, 0, 3) != 0) F.t0 = 0; if (LWM(c, 1, 3) != 0) F.t1 = 0; }      // set below from the wall-model stress
     }
     if (int e = launch_merged(c, J)) return e;
-  } else if (allv) {
-    // every other pointwise set: the three directions of the three components (and of the riders) in ONE launch (k_bc_all)
-    if (c->P > 1) { if (int e = halo_y_comm(c, 3 + nra, alla)) return e; }
-    if (nra) c->bc_nride = 0;      // taken
+  } else if (form == BcForm::all) {
+    // every other pointwise set: the three directions of the three components (and of the riders) in ONE launch (k_bc_all), types of every (component,
+    // direction, end) as the loops of the per-direction form would apply them
+    AJobs JA; JA.nf = 3 + nr; JA.V = V;
+    for (int ivel = 1; ivel <= 3; ++ivel) {
+      AField &F = JA.f[ivel - 1]; F.p = fl[ivel - 1]; F.vcomp = view ? (char)ivel : 0;
+      for (int idir = 1; idir <= 3; ++idir) {
+        const bool periodic = CBV(c, 0, idir, idir) == 'P' && CBV(c, 1, idir, idir) == 'P', normal = ivel == idir;
+        const real dr0 = idir < 3 ? c->dl[idir - 1] : (normal ? c->dzf[0] : c->dzc[0]), dr1 = idir < 3 ? c->dl[idir - 1] : (normal ? c->dzf[n[2]] : c->dzc[n[2]]);
+        char c0 = CBV(c, 0, idir, ivel), c1 = CBV(c, 1, idir, ivel);
+        if (normal && is_correc && !periodic) c0 = c1 = 0;      // the corrected normal velocity keeps its wall value (bound.f90:60-75)
+        a_dir(c, b, F.d[idir - 1], idir, c0, c1, normal ? 0 : 1, plane(*bnd[ivel - 1], idir, 0, n), plane(*bnd[ivel - 1], idir, 1, n), dr0, dr1);
+        if (!c0 && !c1) F.d[idir - 1].t0 = F.d[idir - 1].t1 = 0;
+        if (!normal) { if (LWM(c, 0, idir) != 0) F.d[idir - 1].t0 = 0; if (LWM(c, 1, idir) != 0) F.d[idir - 1].t1 = 0; }      // set below from the wall-model stress
+      }
+    }
+    for (int q = 0; q < nr; ++q) all_pfield(c, b, JA.f[3 + q], b.ride[q], b.ride_which[q]);
+    if (c->P > 1) { if (int e = halo_y_comm(c, b, 3 + nr, all)) return e; }
     if (int e = launch_all(c, JA)) return e;
   } else {
-  if (int e = halo_self(c, 3, fl)) return e;
+  if (int e = halo_self(c, b, 3, fl)) return e;
   for (int idir = 1; idir <= 3; ++idir) {
     if (!ISB(c, 0, idir) && !ISB(c, 1, idir)) continue;
-    if (bc_skipped(c) >> (idir - 1) & 1) continue;
+    if (skipped >> (idir - 1) & 1) continue;
     BcJobs J; J.njobs = 0; J.idir = idir;
     const bool periodic = CBV(c, 0, idir, idir) == 'P' && CBV(c, 1, idir, idir) == 'P';
     const bool impose_norm = (!is_correc) || periodic;
@@ -681,11 +691,9 @@ int op_bounduvw(cales_ctx *c, DBound &bu, DBound &bv, DBound &bw, int is_updt_wm
     if (int e = launch_jobs(c, J)) return e;
   }
   }
-  // cales_step, first bounduvw of a substep (bc_skip_wm): the wall-model planes and the tangential ghost cells they set are rewritten by the bounduvw that
-  // follows the correction before anything reads them (fillps, the solver and correc do not) -- see step_body
-  if (c->bc_skip_wm) return 0;
+  if (b.skip_wm) return 0;
   if (is_updt_wm) if (int e = updt_wallmodelbc(c, bu, bv, bw, u, v, w)) return e;
-  if (!c->fl.unmerged_bc) {      // tangential Neumann BCs carrying the wall-model stress (bound.f90:125-148): every wall-model face in one launch
+  if (c->bc.wm == BcForm::all) {      // tangential Neumann BCs carrying the wall-model stress (bound.f90:125-148): every wall-model face in one launch
     AJobs JW; JW.nf = 3; JW.V = V; bool any = false;
     for (int ivel = 1; ivel <= 3; ++ivel) {
       AField &F = JW.f[ivel - 1]; F.p = fl[ivel - 1]; F.vcomp = view ? (char)ivel : 0;
@@ -697,8 +705,7 @@ int op_bounduvw(cales_ctx *c, DBound &bu, DBound &bv, DBound &bw, int is_updt_wm
         if (ISB(c, 1, idir) && LWM(c, 1, idir) != 0) { D.t1 = CBV(c, 1, idir, ivel); any = true; }
       }
     }
-    if (!any) return 0;
-    if (a_served(JW)) return launch_all(c, JW);
+    return any ? launch_all(c, JW) : 0;
   }
   for (int idir = 1; idir <= 3; ++idir) {   // ... or one launch per direction
     BcJobs J; J.njobs = 0; J.idir = idir;
@@ -709,6 +716,19 @@ int op_bounduvw(cales_ctx *c, DBound &bu, DBound &bv, DBound &bw, int is_updt_wm
         add_job(J, fl[ivel - 1], CBV(c, ib, idir, ivel), ib, 1, plane(*bnd[ivel - 1], idir, ib, n), ib ? drt1 : drt0);
     }
     if (int e = launch_jobs(c, J)) return e;
+  }
+  return 0;
+}
+int op_bounduvw(cales_ctx *c, DBound &bu, DBound &bv, DBound &bw, int is_updt_wm, int is_correc, real *u, real *v, real *w, const BcCall &b) {
+  bool rode = false;
+  if (int e = bounduvw_launches(c, bu, bv, bw, is_updt_wm, is_correc, u, v, w, b, rode)) return e;
+  if (!b.nride || rode) return 0;
+  // the riders could not join (BcPath::ride, a skipped z, CALES_UNMERGED_BC): their ghost cells now, consecutive riders of one BC set together
+  BcCall alone = b; alone.nride = 0;
+  for (int q0 = 0, q1; q0 < b.nride; q0 = q1) {
+    real *p[3];
+    for (q1 = q0; q1 < b.nride && b.ride_which[q1] == b.ride_which[q0]; ++q1) p[q1 - q0] = b.ride[q1];
+    if (int e = op_boundp_multi(c, q1 - q0, p, b.ride_which[q0], alone)) return e;
   }
   return 0;
 }

@@ -255,7 +255,7 @@ __global__ __launch_bounds__(256) void k_copy_ghosts(Geom g, GhostCopy G) {     
   G.dst[f][c] = G.src[f][c];
 }
 // mom_xyz_ad + update of rk (rk.f90:74-94); leaves the new velocities in c->f[CALES_U..W] (pointers swapped with c->f2)
-int op_momrk(cales_ctx *c, real f1, real f2, real f12) {
+int op_momrk(cales_ctx *c, real f1, real f2, real f12, const RkOpts &o) {
   ProfScope ps(c, "mom_rk_fused");
   const int *n = c->n; real **f = c->f;
   MomRkArgs A;
@@ -265,7 +265,7 @@ int op_momrk(cales_ctx *c, real f1, real f2, real f12) {
   A.du = f[CALES_DUDT]; A.dv = f[CALES_DVDT]; A.dw = f[CALES_DWDT]; A.dud = f[CALES_DUDTD]; A.dvd = f[CALES_DVDTD]; A.dwd = f[CALES_DWDTD];
   A.cs = c->visct_lazy ? c->d_cs : nullptr;
   A.dzci = c->d_dzci; A.dzfi = c->d_dzfi; A.dxi = c->dli[0]; A.dyi = c->dli[1]; A.visc = c->visc;
-  A.rd_old = f2 != 0.; A.wr_new = !c->skip_rhs_store;
+  A.rd_old = f2 != 0.; A.wr_new = o.store_rhs;
   A.perx = c->step_xskip ? 1 : 0;      // (operator-level calls read the ghost columns the caller provided, as the reference does)
   A.f1 = f1; A.f2 = f2; A.f12 = f12; A.bfx = c->C.bforce[0]; A.bfy = c->C.bforce[1]; A.bfz = c->C.bforce[2];
   // the projection of the substep before is still pending (cales_step, fold_mom): this pass applies it while loading

@@ -1115,8 +1115,6 @@ __global__ __launch_bounds__(256) void k_plane_fold(int n3, int nblk, const real
 }
 
 int allreduce_res(cales_ctx *c, int slot, int count, int op);
-int op_boundp(cales_ctx *c, real *p, int which);
-int op_boundp_multi(cales_ctx *c, int nf, real **p, int which);
 // v_c = (v(j) + v(j-1))/2 of the rows j = 1 and j = n2 (all i, k, ghost columns and planes included): the two rows whose copies the ghost-cell update /
 // the slab exchange puts into the ghost rows 0 and n2+1 of `vc` -- k_lmf_tile<.., UCF = 1> reads row 0 from there
 __global__ __launch_bounds__(256) void k_vc_edge_rows(Geom g, const real *__restrict__ v, real *__restrict__ vc) {
@@ -1222,7 +1220,7 @@ int sgs_setup_launches(cales_ctx *c) {
   P.lmf_geo = t;
   return 0;
 }
-static int dsmag_fast(cales_ctx *c, const SgsFold *fold) {
+static int dsmag_fast(cales_ctx *c, const SgsFold *fold, bool *visct_ghosts_done) {
   const SgsPath &P = c->sgs;
   const int *n = c->n; real **f = c->f; real *visct = f[CALES_VISCT];
   dim3 b(BX, BY, 1), gr = grid3(n[0], n[1], n[2], b);
@@ -1267,20 +1265,13 @@ static int dsmag_fast(cales_ctx *c, const SgsFold *fold) {
     for (int q = 0; q < 3; ++q) std::swap(c->f[CALES_U + q], c->f2[q]);
     if (!P.perz)
       LAUNCH(c, k_wface_fold, dim3((n[0] + 2 + 63) / 64, (n[1] + 2 + 3) / 4), dim3(64, 4), 0, c->stream, c->g, c->f2[2], c->f[CALES_W], f[CALES_PP], fold->dtrk * c->dzci[0]);
-    c->bc_nride = 1; c->bc_ride[0] = f[CALES_P]; c->bc_ride_which[0] = 0;
     // several slabs: the ghost rows of u, v, w and p do not travel at all -- k_fold_ghost_rows forms them from the prediction's ghost rows and pp's,
     // the ghost-cell kernel below gives them their x and z ghost cells (round 5: in the same exchange as the scratch fields', fifteen planes; now eleven)
     if (c->P > 1 && !ext)      // (ext: the strain-rate pass has formed them itself)
       LAUNCH(c, k_fold_ghost_rows, dim3((n[0] + 63) / 64, (n[2] + 3) / 4, 2), dim3(64, 4), 0, c->stream, c->g, c->f2[0], c->f2[1], c->f2[2], c->f[CALES_U], c->f[CALES_V],
              c->f[CALES_W], f[CALES_PP], c->scr2, f[CALES_P], c->d_force, fold->fmask, fold->dtrk * c->dli[0], fold->dtrk * c->dli[1], fold->dtrk, c->d_dzci, c->step_xskip ? 1 : 0);
-    const bool no_halo_before = c->bc_no_halo;
-    c->bc_no_halo = no_halo_before || c->P > 1;
-    const int e = op_bounduvw(c, c->bcu, c->bcv, c->bcw, 1, 1, c->f[CALES_U], c->f[CALES_V], c->f[CALES_W]);
-    const bool rode = c->bc_nride == 0; c->bc_nride = 0;
-    int e2 = 0;
-    if (!e && !rode) e2 = op_boundp(c, f[CALES_P], 0);
-    c->bc_no_halo = no_halo_before;
-    if (e || e2) { c->deferred.clear(); c->deferred_wide.clear(); return e ? e : e2; }
+    BcCall bc; bc.rows_current = c->P > 1; bc.rider(f[CALES_P], 0);
+    if (int e = op_bounduvw(c, c->bcu, c->bcv, c->bcw, 1, 1, c->f[CALES_U], c->f[CALES_V], c->f[CALES_W], bc)) return e;
   }
   // sgs-type ghost cells: only the periodic exchange matters (products of ghosts = ghosts of products; the wall ghosts are
   // replaced by the extrapolation rule inside the filters)
@@ -1292,25 +1283,23 @@ static int dsmag_fast(cales_ctx *c, const SgsFold *fold) {
   // several ranks: ONE exchange for the y-halo rows of all these fields (six |S|Sij, three filtered velocities, v_c, and |S| itself in the lazy form
   // inside cales_step) instead of one per ghost-cell call; their ghost-cell kernels run first, the rows that then arrive carry the neighbour's
   // x/z ghost cells
-  c->defer_halo = c->P > 1 && !ext;
-  const bool no_halo_before = c->bc_no_halo;
-  if (ext) c->bc_no_halo = true;      // the ghost rows of every field below were formed by the strain-rate pass: their x and z ghost cells only
-  c->bc_skip = P.perx | P.skipz;
-  int e_ = P.pair ? op_boundp_wide(c, 3, c->ss2, 1) : op_boundp_multi(c, 6, ssij, 1);
-  c->bc_skip = P.perx;
-  if (!e_) e_ = op_bounduvw(c, c->bcuf, c->bcvf, c->bcwf, 0, 0, c->uf, c->vf, c->wf);
-  c->bc_skip = P.perx | P.skipz;
-  if (!e_ && !P.ucf) { real *cc[3] = {c->uc, c->vc, c->wc}; e_ = op_boundp_multi(c, 3, cc, 1); }
-  if (!e_ && P.ucf && ext) { real *cc[1] = {c->vc}; e_ = op_boundp_multi(c, 1, cc, 1); }      // (v_c of the two ghost rows came from the strain-rate pass)
-  else if (!e_ && P.ucf && !(P.wylo && P.wyhi)) {      // v_c of the rows 1 and n2 only: their copies in the ghost rows (periodic wrap or the slab neighbours') are what the last pass reads for row 0
+  HaloBatch rows;
+  BcCall bc; bc.skip = P.perx | P.skipz;
+  if (ext) bc.rows_current = true;      // the ghost rows of every field below were formed by the strain-rate pass: their x and z ghost cells only
+  else if (c->P > 1) bc.collect = &rows;
+  BcCall bz = bc; bz.skip = P.perx;      // (the filtered velocity: its z ghost planes are read)
+  if (int e = P.pair ? op_boundp_wide(c, 3, c->ss2, 1, bc) : op_boundp_multi(c, 6, ssij, 1, bc)) return e;
+  if (int e = op_bounduvw(c, c->bcuf, c->bcvf, c->bcwf, 0, 0, c->uf, c->vf, c->wf, bz)) return e;
+  if (!P.ucf) { real *cc[3] = {c->uc, c->vc, c->wc}; if (int e = op_boundp_multi(c, 3, cc, 1, bc)) return e; }
+  else if (ext) { if (int e = op_boundp(c, c->vc, 1, bc)) return e; }      // (v_c of the two ghost rows came from the strain-rate pass)
+  else if (!(P.wylo && P.wyhi)) {      // v_c of the rows 1 and n2 only: their copies in the ghost rows (periodic wrap or the slab neighbours') are what the last pass reads for row 0
     LAUNCH(c, k_vc_edge_rows, dim3((n[0] + 2 + 63) / 64, (n[2] + 2 + 3) / 4), dim3(64, 4), 0, c->stream, c->g, f[CALES_V], c->vc);
-    real *cc[1] = {c->vc}; e_ = op_boundp_multi(c, 1, cc, 1); }
-  c->bc_skip = 0;
-  if (!e_ && P.lazy && c->in_step && c->P > 1) { e_ = op_boundp(c, visct, 1); c->visct_bc_done = !e_; }      // |S| is final (K_AC wrote it): its rows travel along
-  c->defer_halo = false;
-  c->bc_no_halo = no_halo_before;
-  if (!e_ && c->P > 1) e_ = halo_flush_deferred(c, overlap);
-  if (e_) { c->deferred.clear(); c->deferred_wide.clear(); return e_; }
+    if (int e = op_boundp(c, c->vc, 1, bc)) return e; }
+  if (P.lazy && visct_ghosts_done && c->P > 1) {      // inside cales_step |S| is final (K_AC wrote it): its rows travel along
+    BcCall bv = bc; bv.skip = 0;
+    if (int e = op_boundp(c, visct, 1, bv)) return e;
+    *visct_ghosts_done = true; }
+  if (int e = halo_flush_deferred(c, rows, overlap)) return e;
   LijMijArgs L;
   L.uc[0] = P.ucf ? f[CALES_U] : c->uc; L.uc[1] = P.ucf ? f[CALES_V] : c->vc; L.uc[2] = P.ucf ? f[CALES_W] : c->wc; L.uf[0] = c->uf; L.uf[1] = c->vf; L.uf[2] = c->wf;
   L.vcg = c->vc; L.perz = P.perz; L.xwrap = c->step_xskip ? 1 : 0;
@@ -1429,7 +1418,7 @@ const char *sgs_path_name(const cales_ctx *c) {
   static const char *names[] = {"none", "smag_rows", "smag_reference_sequence", "dsmag_tiles", "dsmag_reference_sequence"};      // (SgsForm order)
   return c->sgs.pair ? "dsmag_tiles(pair_fields)" : names[(int)c->sgs.form];
 }
-int op_cmpt_sgs(cales_ctx *c, const SgsFold *fold) {
+int op_cmpt_sgs(cales_ctx *c, const SgsFold *fold, bool *visct_ghosts_done) {
   const int *n = c->n; const size_t nt = c->ntot;
   real **f = c->f; real *visct = f[CALES_VISCT];
   if (c->C.sgstype == 0) {           // 'none': visct = 0 once (sgs.f90:62-68)
@@ -1445,7 +1434,7 @@ int op_cmpt_sgs(cales_ctx *c, const SgsFold *fold) {
       LAUNCH(c, k_alph2, grid3(n[0] + 2, n[1] + 2, n[2] + 2, dim3(64, 4, 1)), dim3(64, 4, 1), 0, c->stream, c->g, c->is_wall[0], c->is_wall[1],
                          c->is_wall[2], c->is_wall[3], c->is_wall[4], c->is_wall[5], c->alph2);
   }
-  if (c->sgs.form == SgsForm::dsmag_tiles) return dsmag_fast(c, fold);
+  if (c->sgs.form == SgsForm::dsmag_tiles) return dsmag_fast(c, fold, visct_ghosts_done);
   if (c->sgs.form == SgsForm::smag_rows) return smag_fast(c);
   real **wk = c->wk;
   const int if123[3] = {1, 2, 3};

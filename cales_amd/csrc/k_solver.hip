@@ -2134,7 +2134,7 @@ static void fft_y(cales_ctx *c, const SolvePath &P, real *pp, const Spec &S, rea
 
 // FFT x, FFT y, tridiagonal z, and back, in place on `pp` along path P; (da,db,dc,lscale) = (a,b,c,1) for the pressure Poisson equation,
 // (alpha a, alpha b + 1, alpha c, alpha) for the Helmholtz equation of a velocity component (main.f90:435-445)
-static int solve_field(cales_ctx *c, const SolvePath &P, real *pp, const real *da, const real *db, const real *dc, real lscale) {
+static int solve_field(cales_ctx *c, const SolvePath &P, real *pp, const real *da, const real *db, const real *dc, real lscale, const FusedFill &ff = FusedFill()) {
   const int *n = c->n;
   const int mh = n[0] / 2 + 1, n2g = c->C.ng[1], nh = c->C.ng[0] / 2, nz = P.nz;
   const long nrows = (long)n[1] * n[2];
@@ -2208,11 +2208,11 @@ static int solve_field(cales_ctx *c, const SolvePath &P, real *pp, const real *d
     return mark(c->comm_stream, ev_arrived[ch]); };
   // fillps inside the forward x transform; the bulk means it sums: several ranks all-reduce them on the context's stream, and RCCL orders the operations of
   // one communicator across streams -- issued between the chunk exchanges it would hold the y transforms back, so the pipelined solve reduces them after the z sweep
-  const bool fill = P.poisson && c->fuse_fillps_dti != 0. && use8x;
+  const bool fill = P.poisson && ff.dtrki != 0. && use8x;
   FillArgs F{};
   if (fill) {
-    const real dti = c->fuse_fillps_dti;
-    F = FillArgs{c->f[CALES_U], c->f[CALES_V], c->f[CALES_W], c->d_dzfi, dti, dti * c->dli[0], dti * c->dli[1], c->fuse_mean_mask, c->d_gvr_f, c->d_gvr_c, nullptr};
+    const real dti = ff.dtrki;
+    F = FillArgs{c->f[CALES_U], c->f[CALES_V], c->f[CALES_W], c->d_dzfi, dti, dti * c->dli[0], dti * c->dli[1], ff.mean_mask, c->d_gvr_f, c->d_gvr_c, nullptr};
     F.xwrap = c->step_xskip ? n[0] : 0;
     if (F.mean_mask) {
       const size_t need = 3 * (size_t)xblk_f * NCH;
@@ -2305,9 +2305,9 @@ std::string solver_path_name(cales_ctx *c) {
   return s;
 }
 
-int op_solver(cales_ctx *c) {
+int op_solver(cales_ctx *c, const FusedFill &fill) {
   if (!c->solver) { c->err = "solver not initialised"; return 1; }
-  return solve_field(c, c->solver->pres, c->f[CALES_PP], c->d_a, c->d_b, c->d_c, 1.);
+  return solve_field(c, c->solver->pres, c->f[CALES_PP], c->d_a, c->d_b, c->d_c, 1., fill);
 }
 
 // z-only Helmholtz systems have the same matrix for every column (no eigenvalue shift): the pivots z_l and c'_l of the
@@ -2364,11 +2364,10 @@ __global__ void k_scale_abc(int n, real alpha, const real *a, const real *b, con
 int op_rhs_b_velz(cales_ctx *c, int ivel, real alpha, real *planes = nullptr, int *has = nullptr);
 void rhs_b_velz_args(cales_ctx *c, int ivel, real alpha, RhsBz *R, int *has);
 int op_rhs_b_velxy(cales_ctx *c, int ivel, real alpha);
-int op_helmholtz_z(cales_ctx *c, int ivel, real alpha) {
+int op_helmholtz_z(cales_ctx *c, int ivel, real alpha, bool fused, real hf12) {
   if (c->C.impdiff != 2) { c->err = "helmholtz_z needs impdiff = 2"; return 1; }
   ProfScope ps(c, "helmholtz_z");
   const int *n = c->n; const int n3 = n[2];
-  const bool fused = c->defer_imp_rhs;
   int has[2] = {0, 0};
   const char *bcz = &c->cbcvel[6 * (ivel - 1) + 4];
   const int q = (ivel == 3 && bcz[1] == 'D') ? 1 : 0;
@@ -2400,13 +2399,13 @@ int op_helmholtz_z(cales_ctx *c, int ivel, real alpha) {
   else if (c->fl.helmholtz_z_per_column) LAUNCH(c, (k_gaussel<real, 0>), gr, b, 0, c->stream, c->g, n3 - q, n[0], n[1], 1, 0, n[0], S, 1., abc, abc + n3, abc + 2 * n3, (const real *)nullptr, (const real *)nullptr, fld, c->scr1, c->scr2, 0);
   else if (tile_path) {
     TileMap T{}; T.nolam = 1; T.nq = n3;
-    if (fused) { T.dud = c->f[CALES_DUDTD + ivel - 1] + 1; T.hf12 = c->hf12; T.force = c->C.is_forced[ivel - 1] ? c->d_force + (ivel - 1) : nullptr;
+    if (fused) { T.dud = c->f[CALES_DUDTD + ivel - 1] + 1; T.hf12 = hf12; T.force = c->C.is_forced[ivel - 1] ? c->d_force + (ivel - 1) : nullptr;
                  T.blo = RB[0]; T.bhi = RB[1]; T.has_lo = has[0]; T.has_hi = has[1]; }
     gaussel_tile<2>(c, n3 - q, n[0], n[1], 1., abc, abc + n3, abc + 2 * n3, c->solver->pres.lamx, c->solver->pres.lamy, fld + 1, 0, T, hz, hz_ready);
   } else {
     real *zz = abc + 3 * n3, *dd = abc + 4 * n3;       // behind the scaled coefficients (cales_create reserves 6 (n3+2) doubles)
     LAUNCH(c, k_thomas_coef, dim3(1), dim3(64), 0, c->stream, n3 - q, abc, abc + n3, abc + 2 * n3, zz, dd);
-    if (fused) LAUNCH(c, k_gaussel_cols_rhs, gr, b, 0, c->stream, c->g, n3 - q, n3, abc, zz, dd, fld, c->f[CALES_DUDTD + ivel - 1], c->hf12,
+    if (fused) LAUNCH(c, k_gaussel_cols_rhs, gr, b, 0, c->stream, c->g, n3 - q, n3, abc, zz, dd, fld, c->f[CALES_DUDTD + ivel - 1], hf12,
                                   c->C.is_forced[ivel - 1] ? c->d_force + (ivel - 1) : (const real *)nullptr, c->scr2, has[0], has[1]);
     else LAUNCH(c, k_gaussel_cols, gr, b, 0, c->stream, c->g, n3 - q, abc, zz, dd, fld);
   }

@@ -259,18 +259,18 @@ int op_force_from_partials(cales_ctx *c, int mask, const real *part, int nblk) {
 
 __global__ void k_zero_force(real *force) { if (threadIdx.x < 3) force[threadIdx.x] = 0.; }
 
-int op_rk(cales_ctx *c, int irk, real dt) {
+int op_rk(cales_ctx *c, int irk, real dt, const RkOpts &o) {
   static const real rk[3][2] = {{32. / 60., 0.}, {25. / 60., -17. / 60.}, {45. / 60., -25. / 60.}};   // param.f90:27-29
-  return op_rk_par(c, rk[irk - 1][0], rk[irk - 1][1], dt);
+  return op_rk_par(c, rk[irk - 1][0], rk[irk - 1][1], dt, o);
 }
 // rk(rkpar, ..., dt, ...) of rk.f90:17 with the caller's coefficients
-int op_rk_par(cales_ctx *c, real rkpar1, real rkpar2, real dt) {
+int op_rk_par(cales_ctx *c, real rkpar1, real rkpar2, real dt, const RkOpts &o) {
   const real f1 = rkpar1 * dt, f2 = rkpar2 * dt, f12 = f1 + f2;
   real **f = c->f;
   dim3 b(BX, BY, 1), gr = grid3(c->n[0], c->n[1], c->n[2], b);
   const bool unfused = c->fl.unfused_rk;
   if (!unfused && c->n[2] >= 2) {
-    if (int e = op_momrk(c, f1, f2, f12)) return e;
+    if (int e = op_momrk(c, f1, f2, f12, o)) return e;
   } else {
     if (int e = op_mom(c)) return e;
     ProfScope ps(c, "rk_update");
@@ -286,9 +286,8 @@ int op_rk_par(cales_ctx *c, real rkpar1, real rkpar2, real dt) {
   for (int q = 0; q < 3; ++q) std::swap(f[CALES_DUDT + q], f[CALES_DUDTO + q]);     // swap, rk.f90:98-100
   if (!(c->C.is_forced[0] && c->C.is_forced[1] && c->C.is_forced[2]) && !c->force_zeroed) {      // unforced components stay zero for good
     LAUNCH(c, k_zero_force, dim3(1), dim3(64), 0, c->stream, c->d_force); c->force_zeroed = true; }
-  for (int q = 0; q < 3; ++q) if (c->C.is_forced[q] && !(c->fuse_mean_mask >> q & 1)) if (int e = forcing_component(c, q)) return e;
-  c->hf12 = .5 * f12;
-  if (c->C.impdiff && !c->defer_imp_rhs) {
+  for (int q = 0; q < 3; ++q) if (c->C.is_forced[q] && !(o.mean_mask >> q & 1)) if (int e = forcing_component(c, q)) return e;
+  if (c->C.impdiff && !o.rhs_in_sweep) {
     ProfScope ps(c, "rk_imp_rhs");
     LAUNCH(c, k_rk_imp_rhs, gr, b, 0, c->stream, c->g, .5 * f12, f[CALES_U], f[CALES_V], f[CALES_W], f[CALES_DUDTD], f[CALES_DVDTD], f[CALES_DWDTD]);
   }
@@ -307,7 +306,7 @@ __global__ __launch_bounds__(BX *BY) void k_bulk_forcing(Geom g, real *__restric
   if (fz) w[c] += force[2];
 }
 int op_bulk_forcing(cales_ctx *c) {
-  if (!(c->C.is_forced[0] || c->C.is_forced[1] || c->C.is_forced[2]) || c->defer_imp_rhs || c->defer_force) return 0;
+  if (!(c->C.is_forced[0] || c->C.is_forced[1] || c->C.is_forced[2])) return 0;
   ProfScope ps(c, "bulk_forcing");
   dim3 b(BX, BY, 1), gr = grid3(c->n[0], c->n[1], c->n[2], b);
   LAUNCH(c, k_bulk_forcing, gr, b, 0, c->stream, c->g, c->f[CALES_U], c->f[CALES_V], c->f[CALES_W], c->d_force,
@@ -350,7 +349,7 @@ __global__ __launch_bounds__(BX *BY) void k_correc(Geom g, real fi, real fj, rea
 // Line-aligned form of the same loops, optionally fused with updatep (updatep.f90:30-47; UPD = 1 explicit, 2 z-implicit):
 // a wave covers the 64 cells i = 1 + 64 bx + lane of one row (whole 128-B lines), p(i+1) comes from the next lane, pp is
 // read once for both operators. The ghost columns i = 0 and i = n1+1 of the reference's ranges are left to k_correc_edge.
-// fmask != 0 (cales_step, see defer_force): the bulk-forcing increment of this substep (mom.f90:311-335, interior cells) is
+// fmask != 0 (cales_step, StepPlan::defer_force): the bulk-forcing increment of this substep (mom.f90:311-335, interior cells) is
 // added here instead of in a pass of its own -- (u + f) - dt dp/dx, the same two roundings in the same order.
 // (A k-marching variant with the pressure planes in registers measured slower: the kernel is a pure stream.)
 template <int UPD>
@@ -390,14 +389,13 @@ __global__ __launch_bounds__(256) void k_correc_edge(Geom g, real fi, real fj, r
   if (k <= g.n3) w[c] = w[c] - dt * dzci[k] * (pp[c + g.s12] - pc);
 }
 // upd = 0: correc only; 1: correc + updatep in one pass (cales_step)
-int op_correc_updatep(cales_ctx *c, real dt, real alpha, int upd) {
+int op_correc_updatep(cales_ctx *c, real dt, real alpha, int upd, int fmask) {
   ProfScope ps(c, upd ? "correc_updatep" : "correc");
   const int *n = c->n;
   dim3 b(BX, BY, 1), gr((n[0] + BX - 1) / BX, (n[1] + 2 + BY - 1) / BY, n[2] + 2);
   real *f_[4] = {c->f[CALES_U], c->f[CALES_V], c->f[CALES_W], c->f[CALES_P]};
   const real fi = dt * c->dli[0], fj = dt * c->dli[1];
   const int mode = !upd ? 0 : (c->C.impdiff == 2 ? 2 : 1);
-  const int fmask = c->defer_force ? (c->C.is_forced[0] ? 1 : 0) | (c->C.is_forced[1] ? 2 : 0) | (c->C.is_forced[2] ? 4 : 0) : 0;
   const int perx = c->step_xskip ? 1 : 0;      // (operator-level calls read the ghost column of pp the caller provided)
   if (mode == 0) LAUNCH(c, k_correc_cell<0>, gr, b, 0, c->stream, c->g, fi, fj, dt, alpha, c->d_dzci, c->d_dzfi, c->f[CALES_PP], f_[0], f_[1], f_[2], f_[3], c->d_force, fmask, perx);
   else if (mode == 1) LAUNCH(c, k_correc_cell<1>, gr, b, 0, c->stream, c->g, fi, fj, dt, alpha, c->d_dzci, c->d_dzfi, c->f[CALES_PP], f_[0], f_[1], f_[2], f_[3], c->d_force, fmask, perx);
@@ -410,8 +408,8 @@ int op_correc_updatep(cales_ctx *c, real dt, real alpha, int upd) {
   LAUNCHCHK(c);
   return 0;
 }
-int op_correc(cales_ctx *c, real dt) {
-  if (!c->fl.unfused_correc) return op_correc_updatep(c, dt, 0., 0);
+int op_correc(cales_ctx *c, real dt, int fmask) {
+  if (!c->fl.unfused_correc) return op_correc_updatep(c, dt, 0., 0, fmask);
   ProfScope ps(c, "correc");
   dim3 b(BX, BY, 1), gr = grid3(c->n[0] + 2, c->n[1] + 2, c->n[2] + 2, b);
   LAUNCH(c, k_correc, gr, b, 0, c->stream, c->g, dt * c->dli[0], dt * c->dli[1], dt, c->d_dzci, c->f[CALES_PP], c->f[CALES_U],
