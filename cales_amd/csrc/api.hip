@@ -457,7 +457,8 @@ static int finish_pending(cales_ctx *c) {
 }
 // ---- the plan of a step (StepPlan, common.hpp): every decision about WHICH form of an operator a substep takes is made here, from the case, the
 // switches and the state recorded in the plan's in_* fields -- step_body below only reads the result.
-// The conditions of the plan known when the context is created (all but comm.on and the solver's radix-8 x plan): cales_create allocates the companion
+// The conditions of the plan known when the context is created (all but comm.on and the solver's radix-8 x plan -- ng(1)/2 a power of two or 3, 5, 9 times
+// one, solver_setup; a row of whole 64-cell tiles that misses it, 448 cells say, gets companions it never uses): cales_create allocates the companion
 // fields of fold_rows2 from them too (vel_comp). fillps inside the forward x transform: homogeneous pressure BCs (no boundary r.h.s.)
 static bool fuse_fill_possible(const cales_ctx *c) {
   bool ok = !c->fl.unfused_fillps;

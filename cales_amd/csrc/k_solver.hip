@@ -9,6 +9,7 @@
 //   z pass : Thomas algorithm, one thread per complex mode (re,im share the pivots), coalesced over x.
 //   then y and x inverse passes, scaled by normfft.
 // Transforms are radix-4/2/3/5 Stockham stages in LDS (ping-pong buffers), twiddles from a table.
+// (Lines of 2^p, and of 3, 5, 9 times 2^p from 48 points on, take the radix-8 register transforms below instead: fft_line8.)
 // Spectral layout differs from FFTW's half-complex order; eigenvalues are laid out to match, so the
 // solution p = solver(rhs) is the same discrete function (checked against the oracle).
 #include "common.hpp"
@@ -142,10 +143,72 @@ __device__ inline void fft8_regs(cpx *v) {   // natural order in -> natural orde
 // LDS index skew: one extra slot every 8 complex, so the stride-8 scatter of the first stage (and the transposed
 // loads/stores of the callers) spread over the banks
 __device__ inline int lpad(int i) { return i + (i >> 3); }
+// Lines of N = r 2^p, r = 3, 5, 9 (ODD = 1 of fft_line8): the odd factor goes FIRST, as one radix-3 or radix-5 stage or two radix-3 stages in the same
+// single buffer, and the radix-8 / 4 / 2 body follows with Ns starting at r instead of 1 -- a Stockham stage sorts for any order of the radices. The line
+// keeps its T = N/8 threads (what the callers' rows, aligned pairs and Nyquist slot hang on), so the N/R butterflies of an odd stage are dealt round-robin:
+// thread t takes j = t + b T < N/R, i.e. 8/R of them on average -- three slots for radix 3 (two of three threads use all three), two for radix 5 (three of
+// five use both). One stage of uneven load against a line held by another number of threads and a second copy of every caller.
+template <int R, int INV>
+__device__ inline void fft_odd_regs(cpx *v) {   // natural order in and out, R = 3 or 5 (the butterflies of fft_stage)
+  if (R == 3) {
+    const real s3 = INV ? 0.86602540378443864676 : -0.86602540378443864676;
+    const cpx s = cadd(v[1], v[2]), d = csub(v[1], v[2]);
+    const cpx m = {(real)(v[0].x - 0.5 * s.x), (real)(v[0].y - 0.5 * s.y)}, rot = {-s3 * d.y, s3 * d.x};   // i*s3*d
+    v[0] = cadd(v[0], s); v[1] = cadd(m, rot); v[2] = csub(m, rot);
+  } else {
+    const real c1 = 0.30901699437494742410, c2 = -0.80901699437494742410;
+    const real s1 = INV ? 0.95105651629515357212 : -0.95105651629515357212, s2 = INV ? 0.58778525229247312917 : -0.58778525229247312917;
+    const cpx a = cadd(v[1], v[4]), b = csub(v[1], v[4]), c = cadd(v[2], v[3]), d = csub(v[2], v[3]);
+    const cpx m1 = {v[0].x + c1 * a.x + c2 * c.x, v[0].y + c1 * a.y + c2 * c.y}, m2 = {v[0].x + c2 * a.x + c1 * c.x, v[0].y + c2 * a.y + c1 * c.y};
+    const cpx r1 = {-(s1 * b.y + s2 * d.y), s1 * b.x + s2 * d.x}, r2 = {-(s2 * b.y - s1 * d.y), s2 * b.x - s1 * d.x};
+    v[0] = cadd(v[0], cadd(a, c)); v[1] = cadd(m1, r1); v[4] = csub(m1, r1); v[2] = cadd(m2, r2); v[3] = csub(m2, r2);
+  }
+}
+// one odd stage (radix R, NS = 1 first, 3 for the second radix-3 stage of r = 9); all threads of the block call it, the line is in buf before and after
+template <int R, int NS, int INV>
+__device__ inline void fft_odd_stage(int N, cpx *buf, int t, const cpx *__restrict__ tw) {
+  constexpr int NB = (8 + R - 1) / R;
+  const int T = N >> 3, M = N / R, tstep = N / (NS * R);
+  cpx v[NB][R];
+#pragma unroll
+  for (int b = 0; b < NB; ++b) {
+    const int j = t + b * T;
+    if (j < M) {
+#pragma unroll
+      for (int q = 0; q < R; ++q) v[b][q] = buf[lpad(j + q * M)];
+      if (NS > 1) {
+        const int k = j % NS;
+#pragma unroll
+        for (int q = 1; q < R; ++q) v[b][q] = tw_mul<INV>(v[b][q], tw[k * q * tstep]);
+      }
+      fft_odd_regs<R, INV>(v[b]);
+    }
+  }
+  __syncthreads();
+#pragma unroll
+  for (int b = 0; b < NB; ++b) {
+    const int j = t + b * T;
+    if (j < M) {
+      const int k = j % NS, j0 = (j - k) * R + k;
+#pragma unroll
+      for (int q = 0; q < R; ++q) buf[lpad(j0 + q * NS)] = v[b][q];
+    }
+  }
+  __syncthreads();
+}
 template <int INV>
+__device__ inline int fft_odd_stages(int N, cpx *buf, int t, const cpx *__restrict__ tw) {      // returns r = the Ns the power-of-two body starts from
+  int r = N >> 3; while (!(r & 1)) r >>= 1;
+  if (r == 5) { fft_odd_stage<5, 1, INV>(N, buf, t, tw); return 5; }
+  fft_odd_stage<3, 1, INV>(N, buf, t, tw);
+  if (r == 9) fft_odd_stage<3, 3, INV>(N, buf, t, tw);
+  return r;
+}
+template <int INV, int ODD = 0>
 __device__ inline void fft_line8(int N, cpx *buf, int t, const cpx *__restrict__ tw) {
   const int T = N >> 3;
   int Ns = 1;
+  if constexpr (ODD) Ns = fft_odd_stages<INV>(N, buf, t, tw);
   while (Ns * 8 <= N) {                         // radix-8 stages, one butterfly per thread
     const int M = N >> 3, tstep = N / (Ns * 8), k = t % Ns, j0 = (t - k) * 8 + k;
     cpx v[8];
@@ -263,7 +326,9 @@ __device__ inline int dct_src(int e, int n) { return e < n / 2 ? 2 * e : 2 * (n 
 // mean_mask != 0: the pass also sums comp*grid_vol_ratio(k) of the forced velocity components it reads anyway (bulk_mean,
 // utils.f90:35-44), one partial per block and component -> the separate reduction pass over u disappears.
 struct FillArgs { const real *u, *v, *w, *dzfi; real dti, dtidxi, dtidyi; int mean_mask; const real *gvr_f, *gvr_c; real *part; int pstride = 0, pofs = 0; int xwrap = 0; };      // xwrap = n1 with periodic x: u(0) is read as u(n1) (the ghost column may be stale inside cales_step), 0 otherwise      // pstride: partial sums per component over all launches of a chunked pass (0: gridDim.x)
-template <int INV, int KIND, int FILL = 0>
+// ODD = 1: nh = r 2^p with r = 3, 5, 9 (fft_line8<.., 1>) -- the same rows, prefetch, post / pre step, fillps and packed slot; T = nh/8 is then not a
+// power of two and the block (a whole number of rows, at most 256 threads) not a whole number of waves, which only the sum of the bulk means has to know.
+template <int INV, int KIND, int FILL = 0, int ODD = 0>
 // (the Neumann forward pass with fillps held 256 VGPRs + 13 AGPRs, i.e. ONE wave per SIMD; two blocks per CU cap it at 256 in all: 18 spilled
 //  registers, 10.3 -> 7.3 ms at 1024^3)
 __global__ __launch_bounds__(256, (KIND == 1 && FILL == 1) ? 2 : 1) void k_fft_x8(Geom g, int nh, int iters, const cpx *__restrict__ twg, const cpx *__restrict__ twpg,
@@ -355,7 +420,7 @@ __global__ __launch_bounds__(256, (KIND == 1 && FILL == 1) ? 2 : 1) void k_fft_x
     }
     real *rowp = p + g.ix(0, j, k);
     if (!INV) {
-      fft_line8<0>(nh, A, t, tw);
+      fft_line8<0, ODD>(nh, A, t, tw);
       if (live) {
         for (int kk = t; kk <= nh / 2; kk += T) {
           const cpx zk = A[lpad(kk)], zm = cconj(A[lpad((nh - kk) % nh)]);
@@ -391,7 +456,7 @@ __global__ __launch_bounds__(256, (KIND == 1 && FILL == 1) ? 2 : 1) void k_fft_x
         if (kk != 0 && 2 * kk != nh) A[lpad(nh - kk)] = zb;
       }
       __syncthreads();
-      fft_line8<1>(nh, A, t, tw);
+      fft_line8<1, ODD>(nh, A, t, tw);
       if (live) {
 #pragma unroll
         for (int e = 0; e < NE; ++e) {
@@ -411,6 +476,17 @@ __global__ __launch_bounds__(256, (KIND == 1 && FILL == 1) ? 2 : 1) void k_fft_x
     for (int q = 0; q < 3; ++q) {
       if (!(F.mean_mask >> q & 1)) continue;
       real v = macc[q];
+      if constexpr (ODD) {      // the last wave is not full: every thread's sum through LDS, then the first (full) wave
+        red[threadIdx.x] = v;
+        __syncthreads();
+        if (threadIdx.x < 64) {
+          v = 0.; for (unsigned i = threadIdx.x; i < blockDim.x; i += 64) v += red[i];
+          for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+          if (threadIdx.x == 0) F.part[(size_t)q * (F.pstride ? F.pstride : gridDim.x) + F.pofs + blockIdx.x] = v;
+        }
+        __syncthreads();
+        continue;
+      }
       for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
       if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
       __syncthreads();
@@ -516,7 +592,8 @@ __global__ __launch_bounds__(256) void k_fft_y4(Geom g, FftPlan P, int CB, int n
 
 // y pass for N = n2 = 2^p: CB = blockDim.x / (N/8) adjacent complex columns; persistent over `kchunk` planes with
 // register prefetch of the next plane; twiddles in LDS.
-template <int INV, int KIND>
+// ODD = 1: N = r 2^p with r = 3, 5, 9 (fft_line8<.., 1>), both kinds; the host keeps CB a multiple of eight columns (four for the longest lines).
+template <int INV, int KIND, int ODD = 0>
 __global__ __launch_bounds__(512) void k_fft_y8(Geom g, int N, int ncols, int kchunk, const cpx *__restrict__ twg,
                                                  const cpx *__restrict__ twd, Spec S, real2 *__restrict__ pc, int k0 = 0, int k1 = -1) {      // planes k0+1..k1 (k1 < 0: all)
   extern __shared__ __align__(16) unsigned char smem[];
@@ -531,6 +608,13 @@ __global__ __launch_bounds__(512) void k_fft_y8(Geom g, int N, int ncols, int kc
   for (int q = threadIdx.x; q < N; q += blockDim.x) tw[q] = twg[q];
   const int NE = 8;                                                          // CB*N / blockDim.x
   cpx nxt[NE];
+  // element e of a thread: q = threadIdx.x + e blockDim.x -> column q % CB, row q / CB. blockDim.x = CB T, so that is column threadIdx.x % CB and row
+  // threadIdx.x / CB + e T: ONE division where CB is no power of two (ODD), and addresses a constant stride apart
+  const int ecol = threadIdx.x % CB, erow = threadIdx.x / CB;
+  auto elem = [&](int e, int &col, int &j) {
+    if constexpr (ODD) { col = ecol; j = erow + e * T; }
+    else { const int q = threadIdx.x + e * blockDim.x; col = q % CB; j = q / CB; }
+  };
   // (every global access unconditional -- columns beyond the last one repeat it: their lanes transform a copy of the last column and store ITS values to
   //  ITS places once more. A branch around a load or a store makes every wait of the plane loop an s_waitcnt vmcnt(0): the wait for the prefetched
   //  plane then also waits for the write acknowledgements of the plane just stored; tools/memseq.py shows counted waits where it showed `w0`.
@@ -538,7 +622,7 @@ __global__ __launch_bounds__(512) void k_fft_y8(Geom g, int N, int ncols, int kc
   auto fetch = [&](int k) {
 #pragma unroll
     for (int e = 0; e < NE; ++e) {
-      const int q = threadIdx.x + e * blockDim.x, col = q % CB, j = q / CB;
+      int col, j; elem(e, col, j);
       const real2 v = pc[S.at_mode(g, min(m0 + col, ncols - 1), j + 1, k)]; nxt[e] = cpx{v.x, v.y};
     }
   };
@@ -549,7 +633,7 @@ __global__ __launch_bounds__(512) void k_fft_y8(Geom g, int N, int ncols, int kc
   for (int k = kbeg; k <= kend; ++k) {
 #pragma unroll
     for (int e = 0; e < NE; ++e) {
-      const int q = threadIdx.x + e * blockDim.x, col = q % CB, j = q / CB;
+      int col, j; elem(e, col, j);
       base[(size_t)col * ld + lpad((kind && !INV) ? makhoul(j) : j)] = nxt[e];
     }
     __syncthreads();
@@ -558,19 +642,19 @@ __global__ __launch_bounds__(512) void k_fft_y8(Geom g, int N, int ncols, int kc
       cpx tmp[NE];
 #pragma unroll
       for (int e = 0; e < NE; ++e) {
-        const int q = threadIdx.x + e * blockDim.x, col = q % CB, kk = q / CB;
+        int col, kk; elem(e, col, kk);
         const cpx ck = base[(size_t)col * ld + lpad(kk)], cm = kk == 0 ? cpx{0., 0.} : base[(size_t)col * ld + lpad(N - kk)];
         tmp[e] = cmul(cconj(twd[kk]), cpx{ck.x + cm.y, ck.y - cm.x});
       }
       __syncthreads();
 #pragma unroll
-      for (int e = 0; e < NE; ++e) { const int q = threadIdx.x + e * blockDim.x, col = q % CB, kk = q / CB; base[(size_t)col * ld + lpad(kk)] = tmp[e]; }
+      for (int e = 0; e < NE; ++e) { int col, kk; elem(e, col, kk); base[(size_t)col * ld + lpad(kk)] = tmp[e]; }
       __syncthreads();
     }
-    fft_line8<INV>(N, base + (size_t)(threadIdx.x / T) * ld, threadIdx.x % T, tw);
+    fft_line8<INV, ODD>(N, base + (size_t)(threadIdx.x / T) * ld, threadIdx.x % T, tw);
 #pragma unroll
     for (int e = 0; e < NE; ++e) {
-      const int q = threadIdx.x + e * blockDim.x, c2 = q % CB, j = q / CB;
+      int c2, j; elem(e, c2, j);
       {
         const cpx *Zc = base + (size_t)c2 * ld;
         cpx v;
@@ -1847,6 +1931,7 @@ struct SolvePath {
   bool nyq = false;              // the modes 0 and n1/2 share mode column 0 (Spec::nyq): k_gaussel_nyq solves it after the tile
   int cw = 0;                    // complex mode columns per rank
   int xrows = 1, ycols = 1;      // rows per block of k_fft_x8, columns per block of the radix-8 y kernels
+  int xodd = 0, yodd = 0;        // fft_x8 / fft_y8 on a line of r 2^p points: r = 3, 5, 9 (the ODD = 1 instantiations); 0: a power of two
   real *lamx = nullptr, *lamy = nullptr; real normfft = 1.;      // eigenvalues per stored spectral index; scale of the inverse transforms
   FftPlan p1x, p1y; real *tw1x = nullptr, *tw1y = nullptr;      // k_dst1 (face-centred kinds)
 };
@@ -1854,6 +1939,7 @@ struct SolvePath {
 struct Solver {
   FftPlan px, py, py4; int Rx, CBy, CBy4 = 0; size_t shx, shy, shy4 = 0;
   bool x8, y8, y16 = false; int x8_threads, y8_threads; size_t shx8, shy8, shy8r, shy16 = 0;
+  int xodd = 0, yodd = 0;        // the odd factor of an x / y line the radix-8 kernels take (SolvePath::xodd, yodd)
   real *twx = nullptr, *twx_post = nullptr, *twy = nullptr, *twy_post = nullptr, *twyd = nullptr;      // twiddle tables; twy_post, twyd: DCT weights of x, of y
   real *tw4x = nullptr, *tw4y = nullptr, *twy4 = nullptr;         // DCT-IV weights of x and y, twiddles of the N/2-point y lines
   SolvePath pres, vel[3]; bool vel_ready[3] = {false, false, false};
@@ -1899,6 +1985,8 @@ static void choose_kernels(cales_ctx *c, const Solver &s, SolvePath &P) {
   const bool use8x = s.x8 && P.xkind <= 1, use8y = s.y8 && P.ykind <= 1;
   P.xk = use8x ? XKernel::fft_x8 : P.xkind >= 5 ? XKernel::dst1 : P.xkind >= 3 ? XKernel::fft_x4 : XKernel::fft_x;
   P.yk = P.ykind >= 5 ? YKernel::dst1 : P.ykind >= 3 ? YKernel::fft_y4 : !use8y ? YKernel::fft_y : s.y16 ? YKernel::fft_y16 : P.ykind ? YKernel::fft_y8 : YKernel::fft_y8r;
+  P.xodd = use8x ? s.xodd : 0; P.yodd = use8y ? s.yodd : 0;
+  if (P.yodd) P.yk = YKernel::fft_y8;      // the staged kernel knows both kinds at these lengths
   P.xrows = use8x ? s.x8_threads / (nh / 8) : 1;
   P.ycols = P.yk == YKernel::fft_y16 ? 8 : use8y ? s.y8_threads / (n2g / 8) : 1;
   const bool hasd = CBP(c, 0, 3) == 'D' || CBP(c, 1, 3) == 'D';
@@ -1932,15 +2020,30 @@ int solver_setup(cales_ctx *c) {
   if (s.shx > 64 * 1024 || s.shy > 64 * 1024) { c->err = "solver: line too long for the LDS-resident transform"; return 1; }
   // power-of-two lines take the radix-8 register kernels
   auto pow2 = [](int v) { return v >= 16 && (v & (v - 1)) == 0; };
-  s.x8 = pow2(n1 / 2) && n1 / 2 <= 1024 && P.xkind <= 1; s.y8 = pow2(n2g) && n2g <= 1024;
+  // ... and so do lines of 3, 5, 9 times 2^p, p >= 3, from 48 points on (CALES_FFT_NO_ODD_RADIX: those stay with the Stockham kernels)
+  auto odd_of = [&](int v) { int r = v, p = 0; while (r % 2 == 0) { r /= 2; ++p; } return (!c->fl.fft_no_odd_radix && (r == 3 || r == 5 || r == 9) && p >= 3 && v >= 48 && v <= 1024) ? r : 0; };
+  s.xodd = P.xkind <= 1 ? odd_of(n1 / 2) : 0; s.yodd = P.ykind <= 1 ? odd_of(n2g) : 0;
+  s.x8 = ((pow2(n1 / 2) && n1 / 2 <= 1024) || s.xodd) && P.xkind <= 1; s.y8 = (pow2(n2g) && n2g <= 1024) || s.yodd;
   if (s.x8) { const int T = (n1 / 2) / 8; s.x8_threads = T >= 256 ? T : (256 / T) * T;
-              s.shx8 = ((size_t)(s.x8_threads / T) * (n1 / 2 + n1 / 16 + 2) + (n1 + 1) + (P.xkind ? n1 / 2 + 1 : 0)) * sizeof(cpx); }
+              s.shx8 = ((size_t)(s.x8_threads / T) * (n1 / 2 + n1 / 16 + 2) + (n1 + 1) + (P.xkind ? n1 / 2 + 1 : 0)) * sizeof(cpx);
+              if (s.xodd && s.shx8 > 64 * 1024) {      // 768-point Neumann rows
+#define X8_ATTR(...) HIPSOFT(c, hipFuncSetAttribute((const void *)k_fft_x8<__VA_ARGS__>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)s.shx8))
+                X8_ATTR(0, 0, 0, 1); X8_ATTR(1, 0, 0, 1); X8_ATTR(0, 0, 1, 1); X8_ATTR(0, 1, 0, 1); X8_ATTR(1, 1, 0, 1); X8_ATTR(0, 1, 1, 1);
+#undef X8_ATTR
+              } }
   if (s.y8) { const int T = n2g / 8; int CB = std::max(1, std::min(std::max(8, 256 / T), 512 / T));
+              if (s.yodd) CB = CB >= 8 ? CB / 8 * 8 : 4;      // whole 128-B row segments; the longest lines (576, 640, 768 points) half ones, like 1024
               while (CB > 1 && ((size_t)CB * (n2g + n2g / 8 + 1) + n2g) * sizeof(cpx) > 150 * 1024) CB /= 2;
               s.y8_threads = CB * T; s.shy8 = ((size_t)CB * (n2g + n2g / 8 + 1) + n2g) * sizeof(cpx);
               s.shy8r = ((size_t)CB * ((((n2g + n2g / 8) + 15) & ~15) + 4) + n2g) * sizeof(cpx);      // k_fft_y8r: line pitch = 4 (mod 16) slots
               if (s.shy8r > 64 * 1024) { HIPSOFT(c, hipFuncSetAttribute((const void *)k_fft_y8r<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)s.shy8r));
                                          HIPSOFT(c, hipFuncSetAttribute((const void *)k_fft_y8r<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)s.shy8r)); }
+              if (s.yodd && s.shy8 > 64 * 1024) {      // 768-point lines: 4 columns need 66 KB
+                HIPSOFT(c, hipFuncSetAttribute((const void *)k_fft_y8<0, 0, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)s.shy8));
+                HIPSOFT(c, hipFuncSetAttribute((const void *)k_fft_y8<1, 0, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)s.shy8));
+                HIPSOFT(c, hipFuncSetAttribute((const void *)k_fft_y8<0, 1, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)s.shy8));
+                HIPSOFT(c, hipFuncSetAttribute((const void *)k_fft_y8<1, 1, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)s.shy8));
+              } else
               if (s.shy8 > 64 * 1024) {      // n2 = 1024: 4 columns (64-B row segments) need 90 KB of LDS
                 HIPSOFT(c, hipFuncSetAttribute((const void *)k_fft_y8<0, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)s.shy8));
                 HIPSOFT(c, hipFuncSetAttribute((const void *)k_fft_y8<1, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)s.shy8)); } }
@@ -1962,6 +2065,8 @@ int solver_setup(cales_ctx *c) {
   if (P.ykind >= 3) { if (dct4_y_setup(c, s, "solver")) return 1; s.y8 = false; }
   if (P.ykind == 2) s.y8 = false;      // the sign changes of the Dirichlet-Dirichlet transform live in the generic y kernel only
   if (c->fl.fft_generic) s.x8 = s.y8 = false;
+  if (!s.x8) s.xodd = 0;
+  if (!s.y8) s.yodd = 0;
   if (!s.y8) s.y16 = false;
   // eigenvalues (initsolver.f90:66-98); x: modes 0..n1/2 (half-complex symmetry), y: modes 0..n2-1
   std::vector<real> lx(n1 + 2, 0.), ly(n2g);
@@ -2083,8 +2188,10 @@ __global__ void k_null_column(Geom g, Spec S, int nz, int periodic, const real *
 // F (forward only): the pass forms pp = div(u*)/dtrk itself (fillps). y: the planes k0+1..k1 (k1 < 0: all), the radix-8 kernels `kchunk` planes per block.
 // The other kernels take the whole field in a geometry of their own.
 template <int INV, int KIND, int FILL>
-static void launch_x8(cales_ctx *c, const Solver &s, unsigned blocks, int iters, real *pp, real scale, const Spec &S, real2 *spec, const FillArgs &F, long rb, long re) {
-  LAUNCH(c, (k_fft_x8<INV, KIND, FILL>), dim3(blocks), dim3(s.x8_threads), s.shx8, c->stream, c->g, c->C.ng[0] / 2, iters, (const cpx *)s.twx, (const cpx *)s.twx_post,
+static void launch_x8(cales_ctx *c, const Solver &s, bool odd, unsigned blocks, int iters, real *pp, real scale, const Spec &S, real2 *spec, const FillArgs &F, long rb, long re) {
+  if (odd) LAUNCH(c, (k_fft_x8<INV, KIND, FILL, 1>), dim3(blocks), dim3(s.x8_threads), s.shx8, c->stream, c->g, c->C.ng[0] / 2, iters, (const cpx *)s.twx, (const cpx *)s.twx_post,
+         (const cpx *)s.twy_post, pp, scale, S, spec, F, rb, re);
+  else LAUNCH(c, (k_fft_x8<INV, KIND, FILL>), dim3(blocks), dim3(s.x8_threads), s.shx8, c->stream, c->g, c->C.ng[0] / 2, iters, (const cpx *)s.twx, (const cpx *)s.twx_post,
          (const cpx *)s.twy_post, pp, scale, S, spec, F, rb, re);
 }
 template <int INV>
@@ -2094,8 +2201,8 @@ static void fft_x(cales_ctx *c, const SolvePath &P, real *pp, const Spec &S, rea
   const long nrows = (long)c->n[1] * c->n[2];
   const dim3 gx((unsigned)((nrows + s.Rx - 1) / s.Rx));
   if (P.xk == XKernel::fft_x8) {
-    if constexpr (INV == 0) if (F) { if (P.xkind) launch_x8<0, 1, 1>(c, s, blocks, iters, pp, scale, S, spec, *F, rb, re); else launch_x8<0, 0, 1>(c, s, blocks, iters, pp, scale, S, spec, *F, rb, re); return; }
-    if (P.xkind) launch_x8<INV, 1, 0>(c, s, blocks, iters, pp, scale, S, spec, FillArgs{}, rb, re); else launch_x8<INV, 0, 0>(c, s, blocks, iters, pp, scale, S, spec, FillArgs{}, rb, re);
+    if constexpr (INV == 0) if (F) { if (P.xkind) launch_x8<0, 1, 1>(c, s, P.xodd != 0, blocks, iters, pp, scale, S, spec, *F, rb, re); else launch_x8<0, 0, 1>(c, s, P.xodd != 0, blocks, iters, pp, scale, S, spec, *F, rb, re); return; }
+    if (P.xkind) launch_x8<INV, 1, 0>(c, s, P.xodd != 0, blocks, iters, pp, scale, S, spec, FillArgs{}, rb, re); else launch_x8<INV, 0, 0>(c, s, P.xodd != 0, blocks, iters, pp, scale, S, spec, FillArgs{}, rb, re);
   } else if (P.xk == XKernel::dst1)
     LAUNCH(c, k_dst1<2 * INV>, dim3((unsigned)nrows), dim3(256), (size_t)2 * (P.p1x.N + 1) * sizeof(cpx), c->stream, c->g, P.p1x, 0, (const cpx *)P.tw1x, pp, scale, S, spec, P.xkind, INV);
   else if (P.xk == XKernel::fft_x4 && P.xkind == 3) LAUNCH(c, (k_fft_x4<INV, 0>), gx, dim3(256), s.shx, c->stream, c->g, s.px, s.Rx, (const cpx *)s.twx, (const cpx *)s.tw4x, pp, scale, S, spec);
@@ -2124,6 +2231,9 @@ static void fft_y(cales_ctx *c, const SolvePath &P, real *pp, const Spec &S, rea
     if (P.ykind) fft_y16<INV, 1>(c, s, gy, ncol_y, kchunk, S, spec, k0, k1); else fft_y16<INV, 0>(c, s, gy, ncol_y, kchunk, S, spec, k0, k1);
     break;
   case YKernel::fft_y8:
+    if (P.yodd && P.ykind) LAUNCH(c, (k_fft_y8<INV, 1, 1>), gy, dim3(s.y8_threads), s.shy8, c->stream, c->g, n2g, ncol_y, kchunk, (const cpx *)s.twy, (const cpx *)s.twyd, S, spec, k0, k1);
+    else if (P.yodd) LAUNCH(c, (k_fft_y8<INV, 0, 1>), gy, dim3(s.y8_threads), s.shy8, c->stream, c->g, n2g, ncol_y, kchunk, (const cpx *)s.twy, (const cpx *)s.twyd, S, spec, k0, k1);
+    else
     LAUNCH(c, (k_fft_y8<INV, 1>), gy, dim3(s.y8_threads), s.shy8, c->stream, c->g, n2g, ncol_y, kchunk, (const cpx *)s.twy, (const cpx *)s.twyd, S, spec, k0, k1); break;
   case YKernel::fft_y8r:
     LAUNCH(c, (k_fft_y8r<INV>), dim3((ncol + P.ycols - 1) / P.ycols, gy.y), dim3(s.y8_threads), s.shy8r, c->stream, c->g, n2g, ncol, kchunk, (const cpx *)s.twy, S, spec, k0, k1); break;
@@ -2298,7 +2408,8 @@ std::string solver_path_name(cales_ctx *c) {
   const SolvePath &P = c->solver->pres;
   static const char *kinds[] = {"PP", "NN", "DD", "ND", "DN"};
   std::string s = std::string("x:") + kinds[P.xkind] + (P.xk == XKernel::fft_x8 ? "/radix8" : P.xk == XKernel::fft_x4 ? "/dct4" : "/mixed_radix");
-  s += std::string(",y:") + kinds[P.ykind] + (radix8_y(P.yk) ? (P.ykind ? "/radix8" : "/radix8_register_ends") : P.yk == YKernel::fft_y4 ? "/dct4" : "/mixed_radix");
+  if (P.xodd) s += "x" + std::to_string(P.xodd);
+  s += std::string(",y:") + kinds[P.ykind] + (radix8_y(P.yk) ? (P.yodd ? "/radix8x" + std::to_string(P.yodd) : P.ykind ? "/radix8" : "/radix8_register_ends") : P.yk == YKernel::fft_y4 ? "/dct4" : "/mixed_radix");
   s += std::string(",z:") + (P.zk == ZKernel::herm ? "thomas_hermitian" : P.zk == ZKernel::tile ? (P.periodic_z ? "lds_tile_periodic" : "lds_tile") : "thomas_march");
   if (P.nyq) s += ",modes_0_and_n1/2:one_column";
   if (c->fl.keep_null_mode) s += ",null_mode:reference_order";
