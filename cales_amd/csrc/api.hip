@@ -11,7 +11,7 @@ void launch_failed(cales_ctx *c, const char *what, hipError_t e) {
 }
 // every operator entry: refuse a failed context, run, and report a launch that failed on the way
 static int finish_pending(cales_ctx *c);
-// ... and first of all completes a projection that cales_step left to its successor (common.hpp, pend_xskip)
+// ... and first of all completes a projection that cales_step left to its successor (common.hpp, cales_ctx::pend)
 #define ENTER(c) do { LAUNCHCHK(c); if (const int pe_ = finish_pending(c)) return pe_; } while (0)
 #define ENTRY(c, expr) do { ENTER(c); const int e_ = (expr); if (e_) return e_; LAUNCHCHK(c); return 0; } while (0)
 
@@ -214,8 +214,7 @@ int cales_create(const cales_case *cs, void *stream, cales_ctx **out) {
     return fail(5);
   // which faces are physical boundaries of this slab (initmpi.f90:201-204 for x-pencils; y is the decomposed direction)
   c->is_bound[0] = c->is_bound[1] = 1;
-  { const bool per_y = cs->cbcpre[2] == 'P' && cs->cbcpre[3] == 'P';
-    c->is_bound[2] = (!per_y && r == 0) ? 1 : 0; c->is_bound[3] = (!per_y && r == P - 1) ? 1 : 0;
+  { c->is_bound[2] = (!c->per_y && r == 0) ? 1 : 0; c->is_bound[3] = (!c->per_y && r == P - 1) ? 1 : 0;
     const bool per_z = cs->cbcpre[4] == 'P' && cs->cbcpre[5] == 'P';
     c->is_bound[4] = c->is_bound[5] = per_z ? 0 : 1; }
   // boundary-condition tables (bound.f90:726-867)
@@ -224,7 +223,7 @@ int cales_create(const cales_case *cs, void *stream, cales_ctx **out) {
   for (int q = 0; q < 11; ++q) if (upload_bound(c, *bs[q], hb[q])) return fail(6);
   // walls (sgs.f90:70-83,154-171); those in y are global properties of the case, not of the slab (distances use global indices)
   for (int d = 1; d <= 3; ++d) for (int s = 0; s <= 1; ++s) c->is_wall[s + 2 * (d - 1)] = (ISB(c, s, d) && CBV(c, s, d, d) == 'D') ? 1. : 0.;
-  for (int s = 0; s <= 1; ++s) c->is_wall[s + 2] = (!(cs->cbcpre[2] == 'P' && cs->cbcpre[3] == 'P') && CBV(c, s, 2, 2) == 'D') ? 1. : 0.;
+  for (int s = 0; s <= 1; ++s) c->is_wall[s + 2] = (!c->per_y && CBV(c, s, 2, 2) == 'D') ? 1. : 0.;
   sgs_setup(c);      // the form of cmpt_sgs: which scratch fields it needs, whether the projection can fold into it
   bc_setup(c);       // the form of every BC set in the ghost-cell operators
   // pressure boundary r.h.s. (main.f90:317, bound.f90:447-499)
@@ -274,6 +273,7 @@ int cales_create(const cales_case *cs, void *stream, cales_ctx **out) {
   if (solver_setup(c)) return fail(14);
   { hipDeviceProp_t pr; int dev = 0; if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&pr, dev) == hipSuccess) c->ncu = pr.multiProcessorCount; }
   if (sgs_setup_launches(c)) return fail(14);
+  mom_setup(c);
   if (hipStreamSynchronize(c->stream) != hipSuccess) { c->err = "sync failed"; return fail(15); }
   if (!c->launch_err.empty()) { c->err = c->launch_err; return fail(16); }      // a set-up kernel (twiddles, tables) or attribute call failed
   *out = c;
@@ -390,8 +390,7 @@ __global__ __launch_bounds__(256) void k_row2_to_companion(Geom g, const real *_
 // the projection of a substep may be left to the next momentum pass (step_body): static conditions of the case and the switches
 static bool fold_mom_ok(const cales_ctx *c) {
   bool ok = !c->fl.unfolded_mom && c->C.sgstype == 0 && c->visct_zero && !c->sgs_first && (c->C.impdiff == 0 || c->C.impdiff == 2) && (c->P == 1 || c->comm.on) && c->n[2] >= 3 &&
-            !c->fl.unfused_rk && !c->fl.unfused_correc;
-  for (int q = 0; q < 6; ++q) ok = ok && c->C.lwm[q] == 0;
+            !c->fl.unfused_rk && !c->fl.unfused_correc && !any_wm(c);
   for (int d = 1; d <= 3 && ok; ++d) {
     bool per = CBP(c, 0, d) == 'P' && CBP(c, 1, d) == 'P', walls = CBP(c, 0, d) == 'N' && CBP(c, 1, d) == 'N' && c->C.bcpre[2 * (d - 1)] == 0. && c->C.bcpre[2 * (d - 1) + 1] == 0.;
     // (walls: the normal component is prescribed -- with the homogeneous Neumann pressure its face values do not change in the projection --, the tangential
@@ -401,9 +400,10 @@ static bool fold_mom_ok(const cales_ctx *c) {
   }
   return ok;
 }
+static bool fuse_cu_possible(const cales_ctx *c) { return !c->fl.unfused_correc && c->C.impdiff != 1; }     // updatep only needs pp: one pass with correc
 // correction + pressure update of a substep as passes of their own, and the ghost cells of what they produced (main.f90:498-504)
 static int project_now(cales_ctx *c, real dtrk, real alpha, int fmask) {
-  const bool fuse_cu = !c->fl.unfused_correc && c->C.impdiff != 1;     // updatep only needs pp: one pass with correc
+  const bool fuse_cu = fuse_cu_possible(c);
   if (int e = fuse_cu ? op_correc_updatep(c, dtrk, alpha, 1, fmask) : op_correc(c, dtrk, fmask)) return e;
   // the pressure is final once the fused correction has run: its ghost cells ride along with those of the velocity (one launch, one slab exchange)
   BcCall b;
@@ -428,30 +428,18 @@ struct StepMode { cales_ctx *c; ~StepMode() { c->in_step = false; c->step_xskip 
 // A projection that cales_step left to its successor (fold_mom, third substep) is completed here -- correction pass, ghost cells, and the refresh of
 // the x ghost columns -- before anything else looks at the fields. Collective over the ranks like every entry of the C-ABI.
 static int finish_pending(cales_ctx *c) {
-  if (c->in_step) return 0;
-  if (c->fold_mom_dtrk == 0.) {
-    if (!c->pend_xrefresh) return 0;
-    // only the refresh of the x ghost columns is due (cales_step with step_xskip, common.hpp)
-    c->pend_xrefresh = false;
-    c->in_step = true; c->step_xskip = true;
-    StepMode mode{c};
-    if (int e = end_of_step_refresh(c)) { c->launch_err = "refreshing the x ghost columns failed (" + c->err + "): the context is unusable"; return e; }
-    LAUNCHCHK(c);
-    return 0;
-  }
-  c->pend_xrefresh = false;      // (the completion below ends with the refresh)
-  const real dtrk = c->fold_mom_dtrk;
-  c->fold_mom_dtrk = 0.;
-  c->in_step = true; c->step_xskip = c->pend_xskip;
+  if (c->in_step || (c->pend.dtrk == 0. && !c->pend_xrefresh)) return 0;
+  const PendingProjection pj = c->pend; const bool due = pj.dtrk != 0.;      // (not due: only the refresh of the x ghost columns is, cales_step with step_xskip)
+  c->pend = PendingProjection(); c->pend_xrefresh = false;
+  c->in_step = true; c->step_xskip = due ? pj.xskip : true;
   StepMode mode{c};
-  if (c->fold_mom_pdone) {      // (z-implicit diffusion: the pressure is up to date, ghost cells included)
-    c->fold_mom_pdone = false;
-    int e = op_correc(c, dtrk, c->fold_mom_fmask);
+  int e = 0;
+  if (due && pj.p_done) {      // (z-implicit diffusion: the pressure is up to date, ghost cells included)
+    e = op_correc(c, pj.dtrk, pj.fmask);
     if (!e) e = op_bounduvw(c, c->bcu, c->bcv, c->bcw, 1, 1, c->f[CALES_U], c->f[CALES_V], c->f[CALES_W]);
-    if (e) { c->launch_err = "completing a pending projection failed (" + c->err + "): the context is unusable"; return e; }
-  } else
-  if (int e = project_now(c, dtrk, 0., c->fold_mom_fmask)) { c->launch_err = "completing a pending projection failed (" + c->err + "): the context is unusable"; return e; }
-  if (int e = end_of_step_refresh(c)) { c->launch_err = "completing a pending projection failed (" + c->err + "): the context is unusable"; return e; }
+  } else if (due) e = project_now(c, pj.dtrk, 0., pj.fmask);
+  if (!e) e = end_of_step_refresh(c);      // (the completion ends with the refresh)
+  if (e) { c->launch_err = std::string(due ? "completing a pending projection" : "refreshing the x ghost columns") + " failed (" + c->err + "): the context is unusable"; return e; }
   LAUNCHCHK(c);
   return 0;
 }
@@ -466,12 +454,11 @@ static bool fuse_fill_possible(const cales_ctx *c) {
   return ok;
 }
 // xskip: periodic x, explicit diffusion, no wall model, the fused passes everywhere -- every kernel of the step wraps around instead of reading x ghost
-// columns, which are then left alone until the step returns (common.hpp, step_xskip)
+// columns, which are then left alone until the step returns (common.hpp, step_xskip). (The switches here and in fold_mom_ok, not MomPath::fused: cales_create
+// asks through fold_correc_possible before mom_setup has run)
 static bool xskip_possible(const cales_ctx *c) {
   const Flags &fl = c->fl;
-  bool ok = !fl.xghosts_in_step && CBP(c, 0, 1) == 'P' && CBP(c, 1, 1) == 'P' && c->C.impdiff == 0 && !fl.unfused_rk && !fl.unfused_correc && c->sgs.wraps_x;
-  for (int q = 0; q < 6; ++q) ok = ok && c->C.lwm[q] == 0;
-  return ok;
+  return !fl.xghosts_in_step && CBP(c, 0, 1) == 'P' && CBP(c, 1, 1) == 'P' && c->C.impdiff == 0 && !fl.unfused_rk && !fl.unfused_correc && c->sgs.wraps_x && !any_wm(c);
 }
 // fold_correc: dynamic model with |S|Sij as pair fields (SgsPath::pair: x and y periodic), z periodic or two no-slip walls, xskip: the projection
 // u = u* - dtrk grad(pp) (+ the deferred forcing) and p += pp are folded into the strain-rate pass of cmpt_sgs, which reads the velocity anyway --
@@ -490,7 +477,7 @@ static void make_plan(cales_ctx *c) {
   pl.valid = true;
   pl.in_visct_zero = c->visct_zero; pl.in_sgs_first = c->sgs_first; pl.in_comm_on = c->comm.on; pl.in_overlap = c->comm_stream != nullptr;
   const Flags &fl = c->fl;
-  for (int q = 0; q < 6; ++q) if (c->C.lwm[q] != 0) pl.any_wm = true;      // (of the case: a face owned by another slab counts)
+  pl.any_wm = any_wm(c);
   // (fuse_fill: the transform then also sums the bulk means of the forced components, whose increment only the correction kernel needs)
   pl.fuse_fill = fuse_fill_possible(c) && solver_can_fuse_fillps(c);
   pl.xskip = pl.fuse_fill && xskip_possible(c);
@@ -522,7 +509,7 @@ static void make_plan(cales_ctx *c) {
   // explicit step, forced directions periodic: the velocity between the forcing and the correction is only differenced along the forced direction
   // (fillps) -- the increment is added by the correction kernel, one pass less. With a wall model only where its first update is skipped (above):
   // k_wallmodel would otherwise sample the velocity without the increment
-  pl.fuse_cu = !fl.unfused_correc && c->C.impdiff != 1;     // updatep only needs pp: one pass with correc
+  pl.fuse_cu = fuse_cu_possible(c);
   { bool ok = c->C.impdiff == 0 && pl.fuse_cu && !fl.unfused_forcing && (!pl.any_wm || pl.skip_first_wm);
     for (int d = 0; d < 3; ++d) if (c->C.is_forced[d]) ok = ok && c->cbcvel[6 * d + 2 * d] == 'P' && c->cbcvel[6 * d + 2 * d + 1] == 'P';
     pl.force_mask = (c->C.is_forced[0] ? 1 : 0) | (c->C.is_forced[1] ? 2 : 0) | (c->C.is_forced[2] ? 4 : 0);
@@ -552,7 +539,7 @@ int cales_describe_plan(cales_ctx *c, char *buf, int buflen) {
   if (pl.any_wm) s += std::string(";first_wall_model_update=") + (pl.skip_first_wm ? "skipped" : "kept");
   s += std::string(";ghost_cells=") + (c->fl.unmerged_bc ? "by_direction" : "one_launch");
   s += std::string(";visct_ghost_cells=") + (pl.visct_ghosts ? "updated" : "zero_field");
-  s += std::string(";momentum=") + (c->fl.unfused_rk ? "mom+rk_update" : "fused_mom_rk");
+  s += std::string(";momentum=") + (c->mom.fused ? "fused_mom_rk" : "mom+rk_update");
   s += std::string(";sgs=") + sgs_path_name(c);
   s += std::string(";solver=") + solver_path_name(c);
   if (c->P > 1) s += ";mode_columns_per_rank=" + std::to_string(solver_mode_columns(c));      // of the pressure solve (padded to whole 128-B lines where that costs 6 % or less: solver_setup)
@@ -576,12 +563,14 @@ int cales_step(cales_ctx *c, real dt) {
 static int step_body(cales_ctx *c, real dt) {
   static const real rk[3][2] = {{32. / 60., 0.}, {25. / 60., -17. / 60.}, {45. / 60., -25. / 60.}};
   const StepPlan pl = current_plan(c);      // (a copy: the plan of THIS step, whatever the step does to the state it was made from)
-  if (c->fold_mom_dtrk != 0. && !pl.fold_mom) { if (int e = finish_pending(c)) return e; }      // (the conditions changed between two steps: a field was set by hand)
-  const bool pending_in = c->fold_mom_dtrk != 0.;      // the step before left its last projection to this step's first momentum pass
-  LAUNCH(c, k_zero6, dim3(1), dim3(64), 0, c->stream, c->d_force, pending_in ? 3 : 0);     // dpdl(:) = 0
+  if (c->pend.dtrk != 0. && !pl.fold_mom) { if (int e = finish_pending(c)) return e; }      // (the conditions changed between two steps: a field was set by hand)
+  // The pending projection is this step's from here on: the one the step before left to this step's first momentum pass, then that of every substep that
+  // folds. It goes back to the context in one place, at the end of a step that succeeded -- an error return leaves none behind
+  PendingProjection pend = c->pend;
+  c->pend = PendingProjection();
+  LAUNCH(c, k_zero6, dim3(1), dim3(64), 0, c->stream, c->d_force, pend.dtrk != 0. ? 3 : 0);     // dpdl(:) = 0
   c->in_step = true;
   StepMode mode{c};
-  struct Reset { cales_ctx *c; bool keep = false; ~Reset() { if (!keep) { c->fold_mom_dtrk = 0.; c->fold_mom_pdone = false; } } } reset{c};      // (a pending projection does not survive an error return)
   if (c->pend_xrefresh && !pl.xskip) {      // the step before left the x ghost columns stale and this one reads them
     c->pend_xrefresh = false; c->step_xskip = true;
     if (int e = end_of_step_refresh(c)) return e;
@@ -592,9 +581,10 @@ static int step_body(cales_ctx *c, real dt) {
   for (int irk = 1; irk <= 3; ++irk) {
     const real dtrk = (rk[irk - 1][0] + rk[irk - 1][1]) * dt, dtrki = 1. / dtrk;
     real alpha = 0.;
-    const bool p_ghosts_due = c->fold_mom_dtrk != 0. && !c->fold_mom_pdone;      // the momentum pass below stores p + pp of the interior cells: its ghost cells ride along with those of the prediction
-    { RkOpts o; o.mean_mask = pl.mean_mask; o.rhs_in_sweep = pl.defer_imp_rhs; o.store_rhs = irk < 3 || pl.keep_last_rhs;
-      if (int e = op_rk(c, irk, dt, o)) return e; }
+    const bool p_ghosts_due = pend.dtrk != 0. && !pend.p_done;      // the momentum pass below stores p + pp of the interior cells: its ghost cells ride along with those of the prediction
+    { RkOpts o; o.mean_mask = pl.mean_mask; o.rhs_in_sweep = pl.defer_imp_rhs; o.store_rhs = irk < 3 || pl.keep_last_rhs; o.pending = pend.dtrk != 0. ? &pend : nullptr;
+      if (int e = op_rk(c, irk, dt, o)) return e;
+      pend = PendingProjection(); }
     if (!pl.defer_force && !pl.defer_imp_rhs) { if (int e = op_bulk_forcing(c)) return e; }
     if (c->C.impdiff == 2) {
       alpha = -.5 * c->visc * dtrk;
@@ -638,21 +628,20 @@ static int step_body(cales_ctx *c, real dt) {
     } else if (pl.fold_mom && (irk < 3 || pl.lazy_last)) {
       // the ghost cells of the projected velocity now (through the corrected view), its interior cells and p + pp in the next momentum pass -- the next
       // substep's, or after the third substep the next step's (finish_pending for every other entry of the C-ABI)
-      c->fold_mom_fmask = fmask;
+      pend.dtrk = dtrk; pend.fmask = fmask; pend.xskip = pl.xskip;
       if (c->C.impdiff == 2) {      // z-implicit diffusion: the pressure update keeps its own pass (updatep.f90:40-46) -- the z Laplacian of pp has no values in ghost cells
         if (int e = op_updatep(c, alpha)) return e;
         if (int e = op_boundp(c, c->f[CALES_P], 0)) return e;
-        c->fold_mom_pdone = true;
+        pend.p_done = true;
       }
-      BcCall b; b.view_dtrk = dtrk; b.view_fmask = fmask;
+      BcCall b; b.view_dtrk = pend.dtrk; b.view_fmask = pend.fmask;
       if (int e = op_bounduvw(c, c->bcu, c->bcv, c->bcw, 1, 1, c->f[CALES_U], c->f[CALES_V], c->f[CALES_W], b)) return e;
-      c->fold_mom_dtrk = dtrk;
     } else if (int e = project_now(c, dtrk, alpha, fmask)) return e;
     bool visct_ghosts_done = false;
     if (int e = op_cmpt_sgs(c, pl.fold_correc ? &fold : nullptr, &visct_ghosts_done)) return e;
     if (pl.visct_ghosts && !visct_ghosts_done) { if (int e = op_boundp(c, c->f[CALES_VISCT], 1)) return e; }
   }
-  if (c->fold_mom_dtrk != 0.) { c->pend_xskip = c->step_xskip; reset.keep = true; }      // the last projection is the next step's (or finish_pending's), the refresh with it
+  if (pend.dtrk != 0.) c->pend = pend;      // (lazy_last) the last projection is the next step's (or finish_pending's), the refresh with it
   else if (c->step_xskip && !c->fl.eager_projection) c->pend_xrefresh = true;      // the x ghost columns wait for the first caller that is not the next step (finish_pending)
   else if (int e = end_of_step_refresh(c)) return e;
   c->h_red[40] = dt;

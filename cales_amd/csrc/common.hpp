@@ -166,6 +166,22 @@ struct SgsPath {
 // op_cmpt_sgs inside cales_step: the projection folded into the strain-rate pass (StepPlan::fold_correc; rows2: fold_rows2; fmask: deferred forcing)
 struct SgsFold { real dtrk; bool rows2; int fmask; };
 
+// What the momentum + RK pass is (k_momrk.hip, op_rk_par), decided once by cales_create (mom_setup, once the CU count is known) and only read after. No field
+// pointers here either: MomRkArgs is filled per call, and so is what a call decides (NOS from visct_zero, RD / WR from the substep, CORR from RkOpts::pending)
+struct MomPath {
+  bool fused = true;      // k_momrk; false (CALES_UNFUSED_RK): k_mom + k_rk_update
+  int imp = 0;            // the IMP form of the kernels (impdiff)
+  bool small = false;     // 32-bit byte offsets (ldb/stb)
+  TileGeom geo;           // tiles of 64 x TYM
+  // some face of the case has a wall model: the ghost layers of u, v, w travel to the second buffers with every operator-level call, inside cales_step
+  // only where something reads them before the next bounduvw rewrites them (a wall model that samples the ghost cell itself; CALES_UNMERGED_BC)
+  bool wm = false, wm_ghosts_in_step = false;
+};
+// A projection u = (u* + f) - dtrk grad(pp), p += pp that cales_step has left to the next momentum pass (StepPlan::fold_mom); due when dtrk != 0. fmask: the
+// components whose bulk-forcing increment it adds. p_done: z-implicit diffusion, the pressure update ran as a pass of its own (its z Laplacian of pp cannot
+// be formed in ghost cells), only the velocity is pending. xskip: the step that left it left the x ghost columns alone (step_xskip)
+struct PendingProjection { real dtrk = 0.; int fmask = 0; bool p_done = false, xskip = false; };
+
 // The form each BC set of the case takes in the ghost-cell operators (k_bound.hip), decided once by cales_create (bc_setup) from the BC types, is_bound
 // and Flags, and only read after. No job tables here: they hold field pointers, which the f / f2 swaps change.
 enum class BcForm { merged, all, by_direction };      // k_bc_merged (x, y periodic) | k_bc_all (any pointwise set) | one k_set_bc launch per direction
@@ -199,8 +215,8 @@ struct BcCall {
 };
 // rk inside cales_step. mean_mask: the bulk means of these forced components are summed by the forward x transform of the pressure solve (FusedFill);
 // rhs_in_sweep: z-implicit, u -= hf12*dudtd is applied inside the Helmholtz sweep (StepPlan::defer_imp_rhs); store_rhs = false: third substep, nobody reads
-// the new r.h.s. (MomRkArgs::wr_new)
-struct RkOpts { int mean_mask = 0; bool rhs_in_sweep = false, store_rhs = true; };
+// the new r.h.s. (MomRkArgs::wr_new); pending: the projection of the substep before, which the fused pass applies while it loads (k_momrk<.., CORR>)
+struct RkOpts { int mean_mask = 0; bool rhs_in_sweep = false, store_rhs = true; const PendingProjection *pending = nullptr; };
 // dtrki != 0: the forward x transform of the pressure solve forms pp = div(u*)/dtrk itself and sums the bulk means of the components in mean_mask
 struct FusedFill { real dtrki = 0.; int mean_mask = 0; };
 
@@ -248,6 +264,7 @@ struct cales_ctx {
   real is_wall[6];
   SgsPath sgs;      // see SgsPath above
   BcPath bc;        // see BcPath above
+  MomPath mom;      // see MomPath above
   bool sgs_first;
   // decomposition
   int P = 1, rank = 0; bool per_y = true; int cw = 0;      // cw: complex mode columns per rank (padded)
@@ -266,7 +283,7 @@ struct cales_ctx {
   // other than the fused momentum kernel reads it (materialize_visct); visct = |S| * cs(k) is the same product either way
   bool visct_lazy = false; real *d_cs = nullptr;
   // The mode of the step in progress, read by the host side of nearly every operator. Everything else a step decides reaches the operators as
-  // arguments (BcCall, RkOpts, FusedFill, SgsFold, ...); what remains below besides these two is state that outlives a call (the pending projection).
+  // arguments (BcCall, RkOpts, FusedFill, SgsFold, ...)
   bool in_step = false;             // inside cales_step: the operator order is known, dead ghost work can be dropped
   real *d_stat2 = nullptr;
   real *d_stat = nullptr;      // partial sums and result of the plane statistics
@@ -281,18 +298,11 @@ struct cales_ctx {
   // interior column instead (a ghost-column update touches two cache lines per row and field for two values: 1.2 of 45 ms per step at 512^3) -- and
   // are brought up to date once, when the step returns
   bool step_xskip = false;
-  // cales_step without subgrid model (explicit diffusion, one rank, every direction periodic or between no-slip walls with Neumann pressure): the
-  // projection of substeps 1 and 2 is applied by the momentum pass of the NEXT substep while it loads its planes (k_momrk<.., CORR = 1>); the ghost
-  // cells of the prediction receive their final values through a corrected view in the ghost-cell kernels (BcCall::view_dtrk). != 0: the dtrk of the
-  // pending projection, with the mask of the components whose bulk-forcing increment it adds
-  real fold_mom_dtrk = 0.; int fold_mom_fmask = 0;
-  bool fold_mom_pdone = false;      // z-implicit diffusion: the pressure update ran as a pass of its own (its z Laplacian of pp cannot be formed in ghost cells), only the velocity is pending
-  // The third substep's projection stays pending ACROSS the return of cales_step (fold_mom_dtrk != 0 outside a step): the next step's first momentum
-  // pass applies it, or -- finish_pending in api.hip -- the first other entry of the C-ABI that reads or writes a field (every one of them calls it,
-  // cales_sync included: a caller never sees the prediction). pend_xskip: the x ghost columns were left alone by that step.
-  bool pend_xskip = false;
-  // cales_step with step_xskip returns with the x ghost columns stale and THIS set: the next cales_step does not read them, every other entry of the C-ABI
-  // brings them up to date first (finish_pending; local copies, no exchange: safe on several slabs) -- the refresh is 0.2 ms of strided accesses at 512^3
+  // What outlives a call of cales_step, written by step_body as it returns and taken off by the next step or by finish_pending (api.hip), which every other
+  // entry of the C-ABI that reads or writes a field calls first (cales_sync included: a caller never sees the prediction). pend: the third substep's
+  // projection (StepPlan::lazy_last) -- the next step's first momentum pass applies it. pend_xrefresh: only the x ghost columns are due (a step with
+  // step_xskip; local copies, no exchange: safe on several slabs) -- the next cales_step does not read them, the refresh is 0.2 ms of strided accesses at 512^3
+  PendingProjection pend;
   bool pend_xrefresh = false;
   size_t pp_companion_bytes = 0;      // scr2 sits this many bytes behind CALES_PP in one allocation (api.hip field_alloc_multi)
   // several slabs with the dynamic model: u, v, w (both buffer sets) and pp carry COMPANION fields right behind them in their allocations (the same
@@ -377,6 +387,7 @@ int op_mom(cales_ctx *c);
 int op_rk(cales_ctx *c, int irk, real dt, const RkOpts &o = RkOpts());
 int op_rk_par(cales_ctx *c, real rkpar1, real rkpar2, real dt, const RkOpts &o = RkOpts());
 int op_momrk(cales_ctx *c, real f1, real f2, real f12, const RkOpts &o = RkOpts());
+void mom_setup(cales_ctx *c);               // MomPath (needs ncu)
 int op_bulk_forcing(cales_ctx *c);
 int op_bulk_mean_dev(cales_ctx *c, const real *p, int c_or_f, real *d_out);   // result to device scalar
 int op_fillps(cales_ctx *c, real dtrki);
@@ -536,6 +547,7 @@ static inline TileGeom tile_geom(const cales_ctx *c, int ty, int wx, int rows_mo
   t.kchunk = kch; t.grid.z = (n[2] + kch - 1) / kch;
   return t;
 }
+static inline bool any_wm(const cales_ctx *c) { for (int q = 0; q < 6; ++q) if (c->C.lwm[q] != 0) return true; return false; }      // some face of the CASE has a wall model (a face owned by another slab counts)
 // some wall-model face of the CASE (on whichever rank) has its sampling height inside the first cell: its interpolation reaches the ghost cell (index_wm = 1 / n,
 // wmodel.f90:120-131; the conditions of host_setup.cpp's index search, from global quantities only -- every rank must answer alike: what hangs on the answer
 // moves an all-reduce from one place of the substep to another)

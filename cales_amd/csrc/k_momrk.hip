@@ -254,9 +254,37 @@ __global__ __launch_bounds__(256) void k_copy_ghosts(Geom g, GhostCopy G) {     
   const size_t c = idir == 1 ? g.ix(m, a, b) : idir == 2 ? g.ix(a, m, b) : g.ix(a, b, m);
   G.dst[f][c] = G.src[f][c];
 }
-// mom_xyz_ad + update of rk (rk.f90:74-94); leaves the new velocities in c->f[CALES_U..W] (pointers swapped with c->f2)
+// ---- which k_momrk a call launches. The 64 instantiations: IMP x offset type x NOS x RD x WR without a pending projection (48), and with one
+// the two forms that exist -- explicit with the pressure update inside (IMP = 0, CORR = 1), z-implicit with the velocity only (IMP = 2, CORR = 2), both
+// without subgrid model -- x offset type x RD x WR (16). corr is 0 or the CORR of those two (op_momrk refuses a pending projection on any other form)
+typedef void (*MomRkKernel)(Geom, MomRkArgs);
+template <typename OFF, int RD, int WR> static MomRkKernel momrk_form(int imp, bool nos, int corr) {
+  if (corr) return corr == 2 ? k_momrk<2, OFF, 1, RD, WR, 2> : k_momrk<0, OFF, 1, RD, WR, 1>;
+  if (imp == 2) return nos ? k_momrk<2, OFF, 1, RD, WR> : k_momrk<2, OFF, 0, RD, WR>;
+  if (imp == 1) return nos ? k_momrk<1, OFF, 1, RD, WR> : k_momrk<1, OFF, 0, RD, WR>;
+  return nos ? k_momrk<0, OFF, 1, RD, WR> : k_momrk<0, OFF, 0, RD, WR>;
+}
+template <int RD, int WR> static MomRkKernel momrk_offsets(bool small, int imp, bool nos, int corr) {
+  return small ? momrk_form<unsigned, RD, WR>(imp, nos, corr) : momrk_form<size_t, RD, WR>(imp, nos, corr);
+}
+// (read the old r.h.s., store the new one): (0,1) first substep, (1,1) second, (1,0) third inside cales_step; (0,0) a first substep whose r.h.s. nobody keeps
+static MomRkKernel momrk_kernel(const MomPath &M, bool nos, bool rd, bool wr, int corr) {
+  return rd ? (wr ? momrk_offsets<1, 1>(M.small, M.imp, nos, corr) : momrk_offsets<1, 0>(M.small, M.imp, nos, corr))
+            : (wr ? momrk_offsets<0, 1>(M.small, M.imp, nos, corr) : momrk_offsets<0, 0>(M.small, M.imp, nos, corr));
+}
+void mom_setup(cales_ctx *c) {
+  MomPath &M = c->mom;
+  M.fused = !c->fl.unfused_rk; M.imp = c->C.impdiff;
+  M.small = (c->ntot + 16) * sizeof(real) < (1ull << 32) && !c->fl.wide_offsets;
+  M.geo = with_bands(tile_geom(c, TYM, 64));
+  M.wm = any_wm(c); M.wm_ghosts_in_step = wm_samples_ghost(c) || c->fl.unmerged_bc;
+}
+// mom_xyz_ad + update of rk (rk.f90:74-94): what is fixed comes from MomPath, what the call decides from its arguments -- o.pending is the projection to apply
+// while loading (cales_step, fold_mom; the caller owns it). Leaves the new velocities in c->f[CALES_U..W] (pointers swapped with c->f2) and, with a pending
+// projection that includes the pressure update, p + pp of the interior cells in c->f[CALES_P] (swapped with c->scr1; the caller renews its ghost cells)
 int op_momrk(cales_ctx *c, real f1, real f2, real f12, const RkOpts &o) {
   ProfScope ps(c, "mom_rk_fused");
+  const MomPath &M = c->mom; const PendingProjection *pj = o.pending;
   const int *n = c->n; real **f = c->f;
   MomRkArgs A;
   A.u = f[CALES_U]; A.v = f[CALES_V]; A.w = f[CALES_W]; A.s = f[CALES_VISCT]; A.p = f[CALES_P];
@@ -268,53 +296,29 @@ int op_momrk(cales_ctx *c, real f1, real f2, real f12, const RkOpts &o) {
   A.rd_old = f2 != 0.; A.wr_new = o.store_rhs;
   A.perx = c->step_xskip ? 1 : 0;      // (operator-level calls read the ghost columns the caller provided, as the reference does)
   A.f1 = f1; A.f2 = f2; A.f12 = f12; A.bfx = c->C.bforce[0]; A.bfy = c->C.bforce[1]; A.bfz = c->C.bforce[2];
-  // the projection of the substep before is still pending (cales_step, fold_mom): this pass applies it while loading
-  const bool corr = c->fold_mom_dtrk != 0.;
-  A.pp = f[CALES_PP]; A.pn = c->scr1; A.cfi = c->fold_mom_dtrk * c->dli[0]; A.cfj = c->fold_mom_dtrk * c->dli[1]; A.cdt = c->fold_mom_dtrk;
-  A.force = c->d_force; A.fmask = c->fold_mom_fmask;
-  const TileGeom t = with_bands(tile_geom(c, TYM, 64));
-  const dim3 b = t.block, gr = t.grid; A.kchunk = t.kchunk; A.bm = t.bm;
-  const bool small = (c->ntot + 16) * sizeof(real) < (1ull << 32) && !c->fl.wide_offsets;      // 32-bit byte offsets
-  const int nos = c->C.sgstype == 0 && c->visct_zero;     // visct known to be identically zero (never set by the host since the last zeroing)
-#define MOMRK_L2(IMP_, RD_, WR_)                                                                                      \
-  do {                                                                                                                 \
-    if (small) { if (nos) LAUNCH(c, (k_momrk<IMP_, unsigned, 1, RD_, WR_>), gr, b, 0, c->stream, c->g, A);              \
-                 else LAUNCH(c, (k_momrk<IMP_, unsigned, 0, RD_, WR_>), gr, b, 0, c->stream, c->g, A); }                \
-    else { if (nos) LAUNCH(c, (k_momrk<IMP_, size_t, 1, RD_, WR_>), gr, b, 0, c->stream, c->g, A);                      \
-           else LAUNCH(c, (k_momrk<IMP_, size_t, 0, RD_, WR_>), gr, b, 0, c->stream, c->g, A); }                        \
-  } while (0)
-  // (read the old r.h.s., store the new one): (0,1) first substep, (1,1) second, (1,0) third inside cales_step; (0,0) a first substep whose r.h.s. nobody keeps
-#define MOMRK_LAUNCH(IMP_)                                                                                             \
-  do {                                                                                                                 \
-    if (A.rd_old && A.wr_new) MOMRK_L2(IMP_, 1, 1); else if (A.rd_old) MOMRK_L2(IMP_, 1, 0);                            \
-    else if (A.wr_new) MOMRK_L2(IMP_, 0, 1); else MOMRK_L2(IMP_, 0, 0);                                                 \
-  } while (0)
-  const bool pdone = corr && c->fold_mom_pdone;      // the pressure was updated by a pass of its own (z-implicit diffusion): velocity only (CORR = 2)
-  if (corr) {
-    if (!(nos && ((c->C.impdiff == 0 && !pdone) || (c->C.impdiff == 2 && pdone)))) { c->err = "momrk: a pending projection needs the no-subgrid-model form, explicit or z-implicit"; return 1; }
+  const real cdt = pj ? pj->dtrk : 0.;
+  A.pp = f[CALES_PP]; A.pn = c->scr1; A.cfi = cdt * c->dli[0]; A.cfj = cdt * c->dli[1]; A.cdt = cdt;
+  A.force = c->d_force; A.fmask = pj ? pj->fmask : 0;
+  A.kchunk = M.geo.kchunk; A.bm = M.geo.bm;
+  const bool nos = c->C.sgstype == 0 && c->visct_zero;     // visct known to be identically zero (never set by the host since the last zeroing)
+  const bool pdone = pj && pj->p_done;      // the pressure was updated by a pass of its own (z-implicit diffusion): velocity only (CORR = 2)
+  if (pj) {
+    if (!(nos && ((M.imp == 0 && !pdone) || (M.imp == 2 && pdone)))) { c->err = "momrk: a pending projection needs the no-subgrid-model form, explicit or z-implicit"; return 1; }
     // periodic rows read without ghost columns: lane 63 of the last tile takes pp(i+1) from its right-halo lane, which has a cell of its own only while the
     // wrapped column n1+1 is not lane 63 itself -- rows shorter than a tile or whole tiles. step_xskip implies the radix-8 x plan (ng(1)/2 a power of two
     // or 3, 5, 9 times one: solver_can_fuse_fillps), hence an even n1, so nothing reaches this today; the kernel's assumption is enforced here rather than left to that coincidence
     if (A.perx && n[0] % 64 == 63) { c->err = "momrk: the folded projection with wrapped x columns needs n1 % 64 != 63"; return 1; }
-#define MOMRK_CORR(IMP_, CORR_, RD_, WR_) do { if (small) LAUNCH(c, (k_momrk<IMP_, unsigned, 1, RD_, WR_, CORR_>), gr, b, 0, c->stream, c->g, A); else LAUNCH(c, (k_momrk<IMP_, size_t, 1, RD_, WR_, CORR_>), gr, b, 0, c->stream, c->g, A); } while (0)
-#define MOMRK_CORR4(IMP_, CORR_) do { if (A.rd_old && A.wr_new) MOMRK_CORR(IMP_, CORR_, 1, 1); else if (A.rd_old) MOMRK_CORR(IMP_, CORR_, 1, 0); else if (A.wr_new) MOMRK_CORR(IMP_, CORR_, 0, 1); else MOMRK_CORR(IMP_, CORR_, 0, 0); } while (0)
-    if (pdone) MOMRK_CORR4(2, 2); else MOMRK_CORR4(0, 1);
-#undef MOMRK_CORR4
-#undef MOMRK_CORR
-  } else
-  if (c->C.impdiff == 2) MOMRK_LAUNCH(2); else if (c->C.impdiff == 1) MOMRK_LAUNCH(1); else MOMRK_LAUNCH(0);
-#undef MOMRK_LAUNCH
-#undef MOMRK_L2
+  }
+  const MomRkKernel k_momrk_form = momrk_kernel(M, nos, A.rd_old, A.wr_new, !pj ? 0 : pdone ? 2 : 1);
+  LAUNCH(c, k_momrk_form, M.geo.grid, M.geo.block, 0, c->stream, c->g, A);
   LAUNCHCHK(c);
-  bool wm = false; for (int q = 0; q < 6; ++q) wm = wm || c->C.lwm[q] != 0;
-  // (inside cales_step the only reader of those ghost layers before the next bounduvw rewrites them is a wall model that samples the ghost cell itself)
-  if (wm && (!c->in_step || wm_samples_ghost(c) || c->fl.unmerged_bc)) {
+  if (M.wm && (!c->in_step || M.wm_ghosts_in_step)) {
     GhostCopy G; for (int q = 0; q < 3; ++q) { G.src[q] = c->f[CALES_U + q]; G.dst[q] = c->f2[q]; }
     const int na = std::max(n[0], n[1]), nb = std::max(n[1], n[2]);
     LAUNCH(c, k_copy_ghosts, dim3((na + 2 + 63) / 64, (nb + 2 + 3) / 4, 18), dim3(64, 4, 1), 0, c->stream, c->g, G);
     LAUNCHCHK(c);
   }
   for (int q = 0; q < 3; ++q) std::swap(c->f[CALES_U + q], c->f2[q]);
-  if (corr) { if (!pdone) std::swap(c->f[CALES_P], c->scr1); c->fold_mom_dtrk = 0.; c->fold_mom_pdone = false; }      // the updated pressure (interior cells; the caller renews its ghost cells)
+  if (pj && !pdone) std::swap(c->f[CALES_P], c->scr1);
   return 0;
 }

@@ -107,16 +107,10 @@ int op_mom(cales_ctx *c) {
   if (int e = materialize_visct(c)) return e;
   ProfScope ps(c, "mom_xyz_ad");
   dim3 b(BX, BY, 1), gr = grid3(c->n[0], c->n[1], c->n[2], b);
-  real **f = c->f;
-  if (c->C.impdiff == 2)
-    LAUNCH(c, k_mom<2>, gr, b, 0, c->stream, c->g, f[CALES_U], f[CALES_V], f[CALES_W], f[CALES_VISCT], c->d_dzci, c->d_dzfi,
-                       c->dli[0], c->dli[1], c->visc, f[CALES_DUDT], f[CALES_DVDT], f[CALES_DWDT], f[CALES_DUDTD], f[CALES_DVDTD], f[CALES_DWDTD]);
-  else if (c->C.impdiff == 1)
-    LAUNCH(c, k_mom<1>, gr, b, 0, c->stream, c->g, f[CALES_U], f[CALES_V], f[CALES_W], f[CALES_VISCT], c->d_dzci, c->d_dzfi,
-                       c->dli[0], c->dli[1], c->visc, f[CALES_DUDT], f[CALES_DVDT], f[CALES_DWDT], f[CALES_DUDTD], f[CALES_DVDTD], f[CALES_DWDTD]);
-  else
-    LAUNCH(c, k_mom<0>, gr, b, 0, c->stream, c->g, f[CALES_U], f[CALES_V], f[CALES_W], f[CALES_VISCT], c->d_dzci, c->d_dzfi,
-                       c->dli[0], c->dli[1], c->visc, f[CALES_DUDT], f[CALES_DVDT], f[CALES_DWDT], (real *)nullptr, (real *)nullptr, (real *)nullptr);
+  real **f = c->f; const int imp = c->C.impdiff;      // (the dudtd fields exist with implicit diffusion only)
+  const auto k_mom_imp = imp == 2 ? k_mom<2> : imp == 1 ? k_mom<1> : k_mom<0>;
+  LAUNCH(c, k_mom_imp, gr, b, 0, c->stream, c->g, f[CALES_U], f[CALES_V], f[CALES_W], f[CALES_VISCT], c->d_dzci, c->d_dzfi, c->dli[0], c->dli[1], c->visc,
+                    f[CALES_DUDT], f[CALES_DVDT], f[CALES_DWDT], imp ? f[CALES_DUDTD] : nullptr, imp ? f[CALES_DVDTD] : nullptr, imp ? f[CALES_DWDTD] : nullptr);
   LAUNCHCHK(c);
   return 0;
 }
@@ -268,20 +262,18 @@ int op_rk_par(cales_ctx *c, real rkpar1, real rkpar2, real dt, const RkOpts &o) 
   const real f1 = rkpar1 * dt, f2 = rkpar2 * dt, f12 = f1 + f2;
   real **f = c->f;
   dim3 b(BX, BY, 1), gr = grid3(c->n[0], c->n[1], c->n[2], b);
-  const bool unfused = c->fl.unfused_rk;
-  if (!unfused && c->n[2] >= 2) {
+  if (c->mom.fused) {
     if (int e = op_momrk(c, f1, f2, f12, o)) return e;
   } else {
+    // (unreachable today: a projection is left pending only where the fused pass follows, fold_mom_ok in api.hip)
+    if (o.pending) { c->err = "rk: a pending projection needs the fused momentum pass"; return 1; }
     if (int e = op_mom(c)) return e;
     ProfScope ps(c, "rk_update");
-    if (c->C.impdiff)
-      LAUNCH(c, k_rk_update<1>, gr, b, 0, c->stream, c->g, f1, f2, f12, c->dli[0], c->dli[1], c->C.bforce[0], c->C.bforce[1], c->C.bforce[2],
-                         c->d_dzci, f[CALES_P], f[CALES_U], f[CALES_V], f[CALES_W], f[CALES_DUDT], f[CALES_DVDT], f[CALES_DWDT],
-                         f[CALES_DUDTO], f[CALES_DVDTO], f[CALES_DWDTO], f[CALES_DUDTD], f[CALES_DVDTD], f[CALES_DWDTD]);
-    else
-      LAUNCH(c, k_rk_update<0>, gr, b, 0, c->stream, c->g, f1, f2, f12, c->dli[0], c->dli[1], c->C.bforce[0], c->C.bforce[1], c->C.bforce[2],
-                         c->d_dzci, f[CALES_P], f[CALES_U], f[CALES_V], f[CALES_W], f[CALES_DUDT], f[CALES_DVDT], f[CALES_DWDT],
-                         f[CALES_DUDTO], f[CALES_DVDTO], f[CALES_DWDTO], (real *)nullptr, (real *)nullptr, (real *)nullptr);
+    const bool imp = c->C.impdiff != 0;
+    const auto k_rk_update_imp = imp ? k_rk_update<1> : k_rk_update<0>;
+    LAUNCH(c, k_rk_update_imp, gr, b, 0, c->stream, c->g, f1, f2, f12, c->dli[0], c->dli[1], c->C.bforce[0], c->C.bforce[1], c->C.bforce[2],
+                       c->d_dzci, f[CALES_P], f[CALES_U], f[CALES_V], f[CALES_W], f[CALES_DUDT], f[CALES_DVDT], f[CALES_DWDT],
+                       f[CALES_DUDTO], f[CALES_DVDTO], f[CALES_DWDTO], imp ? f[CALES_DUDTD] : nullptr, imp ? f[CALES_DVDTD] : nullptr, imp ? f[CALES_DWDTD] : nullptr);
   }
   for (int q = 0; q < 3; ++q) std::swap(f[CALES_DUDT + q], f[CALES_DUDTO + q]);     // swap, rk.f90:98-100
   if (!(c->C.is_forced[0] && c->C.is_forced[1] && c->C.is_forced[2]) && !c->force_zeroed) {      // unforced components stay zero for good
@@ -397,9 +389,8 @@ int op_correc_updatep(cales_ctx *c, real dt, real alpha, int upd, int fmask) {
   const real fi = dt * c->dli[0], fj = dt * c->dli[1];
   const int mode = !upd ? 0 : (c->C.impdiff == 2 ? 2 : 1);
   const int perx = c->step_xskip ? 1 : 0;      // (operator-level calls read the ghost column of pp the caller provided)
-  if (mode == 0) LAUNCH(c, k_correc_cell<0>, gr, b, 0, c->stream, c->g, fi, fj, dt, alpha, c->d_dzci, c->d_dzfi, c->f[CALES_PP], f_[0], f_[1], f_[2], f_[3], c->d_force, fmask, perx);
-  else if (mode == 1) LAUNCH(c, k_correc_cell<1>, gr, b, 0, c->stream, c->g, fi, fj, dt, alpha, c->d_dzci, c->d_dzfi, c->f[CALES_PP], f_[0], f_[1], f_[2], f_[3], c->d_force, fmask, perx);
-  else LAUNCH(c, k_correc_cell<2>, gr, b, 0, c->stream, c->g, fi, fj, dt, alpha, c->d_dzci, c->d_dzfi, c->f[CALES_PP], f_[0], f_[1], f_[2], f_[3], c->d_force, fmask, perx);
+  const auto k_correc_cell_mode = mode == 0 ? k_correc_cell<0> : mode == 1 ? k_correc_cell<1> : k_correc_cell<2>;
+  LAUNCH(c, k_correc_cell_mode, gr, b, 0, c->stream, c->g, fi, fj, dt, alpha, c->d_dzci, c->d_dzfi, c->f[CALES_PP], f_[0], f_[1], f_[2], f_[3], c->d_force, fmask, perx);
   // periodic x: the ghost columns are overwritten by the periodic copy of the bounduvw that always follows (main.f90:500) -- inside
   // cales_step their correction is dead work
   if (!(c->in_step && c->cbcvel[0] == 'P' && c->cbcvel[1] == 'P'))
@@ -434,9 +425,8 @@ __global__ __launch_bounds__(BX *BY) void k_updatep(Geom g, real alpha, real dxi
 int op_updatep(cales_ctx *c, real alpha) {
   ProfScope ps(c, "updatep");
   dim3 b(BX, BY, 1), gr = grid3(c->n[0], c->n[1], c->n[2], b);
-  if (c->C.impdiff == 2) LAUNCH(c, k_updatep<2>, gr, b, 0, c->stream, c->g, alpha, c->dli[0], c->dli[1], c->d_dzci, c->d_dzfi, c->f[CALES_PP], c->f[CALES_P]);
-  else if (c->C.impdiff == 1) LAUNCH(c, k_updatep<1>, gr, b, 0, c->stream, c->g, alpha, c->dli[0], c->dli[1], c->d_dzci, c->d_dzfi, c->f[CALES_PP], c->f[CALES_P]);
-  else LAUNCH(c, k_updatep<0>, gr, b, 0, c->stream, c->g, alpha, c->dli[0], c->dli[1], c->d_dzci, c->d_dzfi, c->f[CALES_PP], c->f[CALES_P]);
+  const auto k_updatep_imp = c->C.impdiff == 2 ? k_updatep<2> : c->C.impdiff == 1 ? k_updatep<1> : k_updatep<0>;
+  LAUNCH(c, k_updatep_imp, gr, b, 0, c->stream, c->g, alpha, c->dli[0], c->dli[1], c->d_dzci, c->d_dzfi, c->f[CALES_PP], c->f[CALES_P]);
   LAUNCHCHK(c);
   return 0;
 }
@@ -793,15 +783,9 @@ int op_chkdt(cales_ctx *c, real *dtmax) {
   if (int e = materialize_visct(c)) return e;
   const int nbx = 8, np = nbx * c->n[2];
   real **f = c->f;
-  if (c->C.impdiff == 2)
-    LAUNCH(c, k_chkdt_partial<2>, dim3(nbx, c->n[2]), dim3(64, 4), 0, c->stream, c->g, 1. / c->dl[0], 1. / c->dl[1], c->visc, c->d_dzci,
-                       c->d_dzfi, f[CALES_VISCT], f[CALES_U], f[CALES_V], f[CALES_W], c->d_red + 64, c->d_red + 64 + np);
-  else if (c->C.impdiff == 1)
-    LAUNCH(c, k_chkdt_partial<1>, dim3(nbx, c->n[2]), dim3(64, 4), 0, c->stream, c->g, 1. / c->dl[0], 1. / c->dl[1], c->visc, c->d_dzci,
-                       c->d_dzfi, f[CALES_VISCT], f[CALES_U], f[CALES_V], f[CALES_W], c->d_red + 64, c->d_red + 64 + np);
-  else
-    LAUNCH(c, k_chkdt_partial<0>, dim3(nbx, c->n[2]), dim3(64, 4), 0, c->stream, c->g, 1. / c->dl[0], 1. / c->dl[1], c->visc, c->d_dzci,
-                       c->d_dzfi, f[CALES_VISCT], f[CALES_U], f[CALES_V], f[CALES_W], c->d_red + 64, c->d_red + 64 + np);
+  const auto k_chkdt_partial_imp = c->C.impdiff == 2 ? k_chkdt_partial<2> : c->C.impdiff == 1 ? k_chkdt_partial<1> : k_chkdt_partial<0>;
+  LAUNCH(c, k_chkdt_partial_imp, dim3(nbx, c->n[2]), dim3(64, 4), 0, c->stream, c->g, 1. / c->dl[0], 1. / c->dl[1], c->visc, c->d_dzci,
+                     c->d_dzfi, f[CALES_VISCT], f[CALES_U], f[CALES_V], f[CALES_W], c->d_red + 64, c->d_red + 64 + np);
   LAUNCH(c, k_fold, dim3(1), dim3(256), 0, c->stream, c->d_red + 64, np, 1, c->res, 0);
   LAUNCH(c, k_fold, dim3(1), dim3(256), 0, c->stream, c->d_red + 64 + np, np, 1, c->res, 1);
   if (int e = allreduce_res(c, 0, 2, 1)) return e;

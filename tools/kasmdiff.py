@@ -1,0 +1,49 @@
+#!/usr/bin/env python3
+"""Device code of two trees, kernel by kernel:  tools/kasmdiff.py OTHER_CSRC_DIR unit [unit ...]   (units: k_momrk k_stencil ...)
+Compiles every unit of this tree's cales_amd/csrc and of OTHER_CSRC_DIR (cales_amd/csrc INSIDE a full checkout of the commit to compare with, e.g. a
+git worktree: common.hpp includes ../../include/cales.h) to gfx950 assembly, FP64 and
+-DCALES_SINGLE, and compares per kernel symbol: the same set of symbols, the same instructions between a symbol's label and its .Lfunc_end (comments
+dropped, the function index of local labels removed: a refactor of the host side may change the ORDER in which the kernels are emitted) and the same
+.amdhsa_ resource lines. Exit status 1 when anything differs. No GPU needed."""
+import os, re, subprocess, sys, tempfile
+
+HERE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "cales_amd", "csrc")
+FLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950", "--cuda-device-only", "-S"]
+SP = ["-DCALES_SINGLE", "-Wno-c++11-narrowing", "-Wno-implicit-const-int-float-conversion"]
+
+
+def kernels(path):
+    """{symbol: (instruction lines, .amdhsa_ lines)}"""
+    body, res, cur, hsa = {}, {}, None, None
+    for line in open(path):
+        t = re.sub(r"\.LBB\d+_", ".LBB_", line.split(";")[0]).strip()
+        m = re.match(r"(_Z\w+):$", t)
+        if t.startswith(".amdhsa_kernel"): hsa = t.split()[1]; res[hsa] = []      # (the descriptor sits between the label and .Lfunc_end)
+        elif t.startswith(".end_amdhsa_kernel"): hsa = None
+        elif hsa is not None: res[hsa].append(t)
+        elif m and cur is None: cur = m.group(1); body[cur] = []
+        elif cur is not None and t.startswith(".Lfunc_end"): cur = None
+        elif cur is not None and t: body[cur].append(t)
+    return {k: (body[k], res.get(k)) for k in body if k in res}      # (kernels only: device functions have no descriptor)
+
+
+def main():
+    other, units, bad = sys.argv[1], sys.argv[2:], 0
+    with tempfile.TemporaryDirectory() as tmp:
+        for unit in units:
+            for prec, extra in (("fp64", []), ("fp32", SP)):
+                ks = []
+                for tag, src in (("a", HERE), ("b", other)):
+                    out = os.path.join(tmp, f"{unit}.{prec}.{tag}.s")
+                    r = subprocess.run(["/opt/rocm/bin/hipcc", "-w"] + FLAGS + extra + [unit + ".hip", "-o", out], cwd=src, capture_output=True, text=True)
+                    if r.returncode: sys.exit(f"compiling {unit}.hip in {src} ({prec}) failed:\n{r.stderr}")
+                    ks.append(kernels(out))
+                diff = sorted(set(ks[0]) ^ set(ks[1])) + sorted(k for k in set(ks[0]) & set(ks[1]) if ks[0][k] != ks[1][k])
+                print(f"{unit} {prec}: {len(ks[0])} / {len(ks[1])} kernels, {len(diff)} differ")
+                for k in diff: print("   ", subprocess.run(["c++filt", k], capture_output=True, text=True).stdout.strip())
+                bad += len(diff)
+    sys.exit(1 if bad else 0)
+
+
+if __name__ == "__main__":
+    main()
