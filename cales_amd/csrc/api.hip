@@ -148,7 +148,7 @@ void cales_destroy(cales_ctx *c) {
   DBound *bs[11] = {&c->bcu, &c->bcv, &c->bcw, &c->bcp, &c->bcs, &c->bcuf, &c->bcvf, &c->bcwf, &c->bcu_mag, &c->bcv_mag, &c->bcw_mag};
   for (auto *b : bs) free_bound(*b);
   for (int d = 0; d < 3; ++d) hipFree(c->rhsbp[d]);
-  field_free(c, c->scr1); hipFree(c->d_red); hipFree(c->d_force); if (c->d_mpart) hipFree(c->d_mpart); if (c->d_abct) hipFree(c->d_abct); if (c->d_hztab) hipFree(c->d_hztab); if (c->d_cs) hipFree(c->d_cs); if (c->d_nullw) hipFree(c->d_nullw); if (c->d_stat) hipFree(c->d_stat); if (c->d_stat2) hipFree(c->d_stat2); hipHostFree(c->h_red);
+  field_free(c, c->scr1); hipFree(c->d_red); hipFree(c->d_force); if (c->d_mpart) hipFree(c->d_mpart); if (c->d_cs) hipFree(c->d_cs); if (c->d_stat) hipFree(c->d_stat); if (c->d_stat2) hipFree(c->d_stat2); hipHostFree(c->h_red);
   field_free(c, c->s0); field_free(c, c->uc); field_free(c, c->vc); field_free(c, c->wc); field_free(c, c->uf); field_free(c, c->vf); field_free(c, c->wf); field_free(c, c->alph2); if (!c->p1d_in_comm) hipFree(c->d_p1d);
   for (int m = 0; m < 6; ++m) { field_free(c, c->wk[m]); field_free(c, c->sij[m]); field_free(c, c->mij[m]); }
   for (int m = 0; m < 3; ++m) if (c->ss2[m]) hipFree(c->ss2[m] - 2 * c->field_ofs);
@@ -174,8 +174,8 @@ int cales_create(const cales_case *cs, void *stream, cales_ctx **out) {
   c->d_dzc = c->d_dzf = c->d_zc = c->d_zf = c->d_dzci = c->d_dzfi = c->d_gvr_c = c->d_gvr_f = nullptr;
   DBound *bs[11] = {&c->bcu, &c->bcv, &c->bcw, &c->bcp, &c->bcs, &c->bcuf, &c->bcvf, &c->bcwf, &c->bcu_mag, &c->bcv_mag, &c->bcw_mag};
   for (auto *b : bs) b->x = b->y = b->z = nullptr;
-  for (int d = 0; d < 3; ++d) { c->rhsbp[d] = nullptr; c->d_av[d] = c->d_bv[d] = c->d_cv[d] = nullptr; }
-  c->rhsbz_vel = c->d_a = c->d_b = c->d_c = nullptr;
+  for (int d = 0; d < 3; ++d) c->rhsbp[d] = nullptr;
+  c->rhsbz_vel = nullptr;
   c->scr1 = c->scr2 = c->d_red = c->h_red = c->d_force = nullptr;
   c->s0 = c->uc = c->vc = c->wc = c->uf = c->vf = c->wf = c->alph2 = c->d_p1d = nullptr;
   for (int m = 0; m < 6; ++m) c->wk[m] = c->sij[m] = c->mij[m] = nullptr;
@@ -252,7 +252,7 @@ int cales_create(const cales_case *cs, void *stream, cales_ctx **out) {
     else if (field_alloc(c, &c->f2[q])) return fail(9);
   }
   c->red_blocks = 8;
-  if (dev_alloc(c, &c->d_red, 64 + 16 * (size_t)(n3 + 2) + 6 * (size_t)(n3 + 2)) || dev_alloc(c, &c->d_force, 8)) return fail(10);
+  if (dev_alloc(c, &c->d_red, 64 + 16 * (size_t)(n3 + 2)) || dev_alloc(c, &c->d_force, 8)) return fail(10);
   c->res = c->d_red;
   if (hipHostMalloc((void **)&c->h_red, 64 * sizeof(real)) != hipSuccess) { c->err = "hipHostMalloc failed"; return fail(11); }
   // sgs scratch (sgs.f90:70-83,154-171)

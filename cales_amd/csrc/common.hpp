@@ -250,9 +250,8 @@ struct cales_ctx {
   real *rhsbp[3];        // (na,nb,0:1)
   real *rhsbz_vel;       // scratch (n1,n2,0:1) for z-implicit Helmholtz r.h.s.
   // solver
-  Solver *solver = nullptr;  // k_solver.hip: plans, tables and the path of every solved field (solver_setup / solver_teardown)
-  real *d_a, *d_b, *d_c;     // tridiagonal (n3)
-  real *d_av[3], *d_bv[3], *d_cv[3];
+  // k_solver.hip: plans, tables and the path of every solved field; the z solves' coefficients, chunked tables and scratch (solver_setup / solver_teardown)
+  Solver *solver = nullptr;
   real *scr1, *scr2;         // solver scratch (haloed size)
   // reductions
   real *d_red; real *h_red;       // partial sums / results (pinned host)
@@ -287,11 +286,7 @@ struct cales_ctx {
   bool in_step = false;             // inside cales_step: the operator order is known, dead ghost work can be dropped
   real *d_stat2 = nullptr;
   real *d_stat = nullptr;      // partial sums and result of the plane statistics
-  bool abct_ready = false, force_zeroed = false;
-  real *d_abct = nullptr;      // tridiagonal coefficients in the chunked order of k_gaussel_tile
-  // z-only Helmholtz sweeps: the chunked tables of (ivel, alpha) pairs already seen -- three alphas per step, the same every step while dt stays (four slots per
-  // component, round robin); a hit saves the scaling and the table kernel of that sweep
-  struct HzTab { real alpha = 0.; int nz = 0; bool ok = false; } hz_tab[3][4]; int hz_next[3] = {0, 0, 0}; real *d_hztab = nullptr;
+  bool force_zeroed = false;
   int ncu = 0;      // compute units of the device (balanced_kchunk)
   real *d_mpart = nullptr; size_t n_mpart = 0;      // partial sums of the bulk means the forward x transform forms (FusedFill::mean_mask)
   // cales_step with periodic x: the x ghost columns are not maintained between the operators of a step -- every kernel of the step reads the wrapped
@@ -310,7 +305,6 @@ struct cales_ctx {
   // n2+1; pp a second companion for row n2+3), exchanged from the rows 2 / n2-1 (3) of the neighbours (k_bound.hip, halo kinds 2 and 3)
   bool vel_comp = false; size_t comp_one = 0; real *scr3 = nullptr;
   int field_ofs = 0;       // doubles between a field's allocation and its element (0,0,0)
-  real *d_nullw = nullptr; // work space of k_null_column (CALES_KEEP_NULL_MODE)
 };
 
 #define CBV(c, side, dir, vel) ((c)->cbcvel[(side) + 2 * ((dir) - 1) + 6 * ((vel) - 1)])

@@ -1539,19 +1539,6 @@ __global__ __launch_bounds__(256) void k_gaussel_nyq(Geom g, int nz, int N, int 
     } else { p[S.at_mode(g, 0, ky + 1, k + 1)] = make_real2(ar, ai); p[S.at_mode(g, 0, kp + 1, k + 1)] = make_real2(br, bi); }
   }
 }
-template <int M>
-static void launch_gaussel_nyq(cales_ctx *c, bool herm, int nz, int N, int nh, real lscale, const real *da, const real *db, const real *dc, const real *lamx, const real *lamy, real2 *p, int fixnull, const Spec &S, const real *tab) {
-  constexpr int lds = 4 * (64 * (M + 1) + GT_PAD) * 8;
-  if (herm) LAUNCH(c, (k_gaussel_nyq<M, 1>), dim3(N / 2 + 1), dim3(256), lds, c->stream, c->g, nz, N, nh, lscale, tab, lamx, lamy, p, fixnull, S, da, db, dc);
-  else LAUNCH(c, (k_gaussel_nyq<M, 0>), dim3(N / 2), dim3(256), lds, c->stream, c->g, nz, N, nh, lscale, tab, lamx, lamy, p, fixnull, S, da, db, dc);
-}
-// the packed column of the modes 0 and n1/2 (periodic y: Hermitian pairing of the rows); reads the coefficient table the tile of this nz built
-static void gaussel_nyq(cales_ctx *c, bool herm, int nz, int N, int nh, real lscale, const real *da, const real *db, const real *dc, const real *lamx, const real *lamy, real2 *p, int fixnull, const Spec &S) {
-  if (nz <= 128) launch_gaussel_nyq<2>(c, herm, nz, N, nh, lscale, da, db, dc, lamx, lamy, p, fixnull, S, c->d_abct);
-  else if (nz <= 256) launch_gaussel_nyq<4>(c, herm, nz, N, nh, lscale, da, db, dc, lamx, lamy, p, fixnull, S, c->d_abct);
-  else if (nz <= 512) launch_gaussel_nyq<8>(c, herm, nz, N, nh, lscale, da, db, dc, lamx, lamy, p, fixnull, S, c->d_abct);
-  else launch_gaussel_nyq<16>(c, herm, nz, N, nh, lscale, da, db, dc, lamx, lamy, p, fixnull, S, c->d_abct);
-}
 // The same tile PERSISTENT over `tpb` neighbouring tiles of a segment, for nz = 1024 planes in chunks of sixteen (the 1024^3 cavity): the
 // classic form holds one block of 1024 threads and 140 KB of LDS per CU, so the load of a tile, its solve and its store run one after the other (5.6 ms
 // at 1024^3, 0.38 of the HBM peak). Here a block has 512 threads -- at two waves per SIMD the 256 registers a thread may use hold the NEXT tile (sixteen
@@ -1759,58 +1746,6 @@ __global__ __launch_bounds__(512, 2) void k_gaussel_tile_p(Geom g, int nz, int n
   if (tile0 < tend) one_tile(tile0);
   for (int tile = tile0 + 1; tile < tend; ++tile) one_tile(tile);
 }
-template <int M, int NV, int PER = 0>
-static void launch_gaussel_tile(cales_ctx *c, int nz, int ndbl, int nrow, real lscale, const real *da, const real *db, const real *dc, const real *lamx,
-                               const real *lamy, real *p, int fixnull, const TileMap &T, real *tab_of_caller, bool tab_ready) {
-  constexpr int W = gt_width(M, NV), lds = W * (64 * (M + 1) + GT_PAD) * 8 + (GT_TL && M == 16 ? 2 * 64 * M * 8 : 0);
-  static bool once = false;
-  if (!once) {
-    HIPSOFT(c, hipFuncSetAttribute((const void *)k_gaussel_tile<M, NV, PER>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    if constexpr (NV == 2 && PER == 0) HIPSOFT(c, hipFuncSetAttribute((const void *)k_gaussel_tile<M, NV, PER, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    once = true;
-  }
-  // (a failed allocation fails the context: launch_failed is sticky, op_solver's LAUNCHCHK returns it -- the z solve is never skipped silently)
-  if (!c->d_abct) { const hipError_t e = hipMalloc(&c->d_abct, 2 * 3 * 64 * 16 * sizeof(real)); if (e != hipSuccess) { c->d_abct = nullptr; launch_failed(c, "hipMalloc(tridiagonal coefficient table)", e); return; } }
-  // the pressure operands never change: their table is built once (Helmholtz operands are rescaled every substep -> second table)
-  const bool pressure = da == c->d_a;
-  real *tab = tab_of_caller ? tab_of_caller : c->d_abct + (pressure ? 0 : 3 * 64 * 16);
-  // (periodic z: the table holds the n-1 rows of the system proper; identity rows from row n on)
-  if (tab_of_caller ? !tab_ready : (!pressure || !c->abct_ready)) LAUNCH(c, k_abc_chunked, dim3((64 * M + 255) / 256), dim3(256), 0, c->stream, PER ? nz - 1 : nz, M, da, db, dc, tab);
-  if (pressure && !tab_of_caller) c->abct_ready = true;
-  if constexpr (NV == 2 && PER == 0) {
-    if (T.dud) { LAUNCH(c, (k_gaussel_tile<M, NV, PER, 1>), dim3((ndbl + W - 1) / W, nrow), dim3(64 * W / NV), lds, c->stream, c->g, nz, ndbl, lscale, tab, lamx, lamy, p, fixnull, T, da, db, dc); return; }
-  }
-  if (T.dud) { launch_failed(c, "k_gaussel_tile: the Helmholtz form exists for pairs of real columns and non-periodic z only", hipErrorInvalidValue); return; }
-  LAUNCH(c, (k_gaussel_tile<M, NV, PER>), dim3((ndbl + W - 1) / W, nrow), dim3(64 * W / NV), lds, c->stream, c->g, nz, ndbl, lscale, tab,
-                     lamx, lamy, p, fixnull, T, da, db, dc);
-}
-// the persistent form (k_gaussel_tile_p): pressure operands only (their table is built once), tiles per block so that ~2048 blocks or more remain
-template <int NV>
-static void launch_gaussel_tile_p(cales_ctx *c, int nz, int ndbl, int nrow, real lscale, const real *da, const real *db, const real *dc, const real *lamx, const real *lamy, real *p, int fixnull, const TileMap &T) {
-  constexpr int M = 16, W = gt_width(M, NV), lds = W * (64 * (M + 1) + GT_PAD) * 8 + (GT_TL ? 2 * 64 * M * 8 : 0);
-  static bool once = false;
-  if (!once) { HIPSOFT(c, hipFuncSetAttribute((const void *)k_gaussel_tile_p<NV>, hipFuncAttributeMaxDynamicSharedMemorySize, lds)); once = true; }
-  if (!c->d_abct) { const hipError_t e = hipMalloc(&c->d_abct, 2 * 3 * 64 * 16 * sizeof(real)); if (e != hipSuccess) { c->d_abct = nullptr; launch_failed(c, "hipMalloc(tridiagonal coefficient table)", e); return; } }
-  const bool pressure = da == c->d_a;
-  real *tab = c->d_abct + (pressure ? 0 : 3 * 64 * 16);
-  if (!pressure || !c->abct_ready) LAUNCH(c, k_abc_chunked, dim3((64 * M + 255) / 256), dim3(256), 0, c->stream, nz, M, da, db, dc, tab);
-  if (pressure) c->abct_ready = true;
-  const int ntile = ndbl / W;
-  int tpb = 1; while (tpb * 2 <= ntile && tpb < 32 && (long)nrow * ((ntile + 2 * tpb - 1) / (2 * tpb)) >= 2048) tpb *= 2;
-  LAUNCH(c, (k_gaussel_tile_p<NV>), dim3((ntile + tpb - 1) / tpb, nrow), dim3(512), lds, c->stream, c->g, nz, ndbl, lscale, tab, lamx, lamy, p, fixnull, T, tpb, da, db, dc);
-}
-// whether the LDS tile solves nz planes (periodic: the cyclic closure inside the tile); the callers decide with it before they call gaussel_tile
-static bool tile_takes(const cales_ctx *c, int nz, bool periodic) { return nz >= (periodic ? 4 : 2) && nz <= 1024 && !c->fl.gaussel_march; }
-// one rank: ndbl doubles of each of the nrow rows; several ranks (T.blocked): nrow = peers, ndbl = 2 cw n2l doubles per plane of a peer block
-template <int NV, int PER = 0>
-static void gaussel_tile(cales_ctx *c, int nz, int ndbl, int nrow, real lscale, const real *da, const real *db, const real *dc, const real *lamx, const real *lamy,
-                         real *p, int fixnull, const TileMap &T, real *tab = nullptr, bool tab_ready = false) {
-  if (nz <= 128) launch_gaussel_tile<2, NV, PER>(c, nz, ndbl, nrow, lscale, da, db, dc, lamx, lamy, p, fixnull, T, tab, tab_ready);
-  else if (nz <= 256) launch_gaussel_tile<4, NV, PER>(c, nz, ndbl, nrow, lscale, da, db, dc, lamx, lamy, p, fixnull, T, tab, tab_ready);
-  else if (nz <= 512) launch_gaussel_tile<8, NV, PER>(c, nz, ndbl, nrow, lscale, da, db, dc, lamx, lamy, p, fixnull, T, tab, tab_ready);
-  else if (!PER && NV == 1 && nz == 1024 && ndbl % 16 == 0 && !T.dud && !T.nolam && !tab) launch_gaussel_tile_p<1>(c, nz, ndbl, nrow, lscale, da, db, dc, lamx, lamy, p, fixnull, T);
-  else launch_gaussel_tile<16, NV, PER>(c, nz, ndbl, nrow, lscale, da, db, dc, lamx, lamy, p, fixnull, T, tab, tab_ready);
-}
 
 // Non-periodic x (real modes r = 2m, 2m+1 paired into one complex column) with PERIODIC y: the y transform of the pair gives
 // Z_ky = A_ky + i B_ky, A and B the (Hermitian) spectra of the two real columns, which have DIFFERENT x eigenvalues. Rows ky and
@@ -1920,14 +1855,24 @@ __global__ __launch_bounds__(256) void k_gaussel(Geom g, int nz, int ncol, int n
 // it, solver_path_name prints it (cales_describe_plan).
 enum class XKernel { fft_x8, fft_x4, dst1, fft_x };                             // radix-8 | DCT-IV | face-centred | mixed radix
 enum class YKernel { fft_y16, fft_y8, fft_y8r, fft_y4, dst1, fft_y };          // radix-8 (16 | 8 per thread | register ends) | DCT-IV | face-centred | mixed radix
-enum class ZKernel { herm, tile, ri, periodic_real, periodic_cpx };            // k_gaussel_herm | gaussel_tile | k_gaussel_ri | k_gaussel<real, 1> | k_gaussel<real2, 1>
+enum class ZKernel { herm, tile, ri, periodic_real, periodic_cpx };            // k_gaussel_herm | launch_tile | k_gaussel_ri | k_gaussel<real, 1> | k_gaussel<real2, 1>
 static bool radix8_y(YKernel k) { return k == YKernel::fft_y16 || k == YKernel::fft_y8 || k == YKernel::fft_y8r; }
+// planes per lane of the LDS tile that solves nz planes: asked by the tile, the packed column of the modes 0 and n1/2 (it reads the tile's table) and the z-only sweeps
+constexpr int tile_m(int nz) { return nz <= 128 ? 2 : nz <= 256 ? 4 : nz <= 512 ? 8 : 16; }
+// whether the LDS tile solves nz planes (periodic: the cyclic closure inside the tile)
+static bool tile_takes(const cales_ctx *c, int nz, bool periodic) { return nz >= (periodic ? 4 : 2) && nz <= 1024 && !c->fl.gaussel_march; }
+// The tile a z solve takes: k_gaussel_tile<M, NV, PER, DUD>, or k_gaussel_tile_p<1> (persistent: 1024 planes of real x modes in whole 16-column tiles), over ndbl
+// doubles of each of nrow rows (several ranks, TileMap::blocked: nrow peers, ndbl = 2 cw n2l doubles per plane of a peer block), and the chunked table it reads
+constexpr int TILE_TAB = 3 * 64 * 16;      // reals of a table (k_abc_chunked), any M
+struct ZTile { int M = 0, NV = 0, PER = 0, DUD = 0, ndbl = 0, nrow = 0; bool persistent = false; real *tab = nullptr; };
 struct SolvePath {
   int xkind = 0, ykind = 0;      // 0 PP, 1 NN, 2 DD, 3 ND, 4 DN (cell-centred); 5..7 the face-centred kinds of a velocity component (velocity_path)
   XKernel xk = XKernel::fft_x; YKernel yk = YKernel::fft_y; ZKernel zk = ZKernel::ri;
   int nz = 0; bool periodic_z = false, poisson = false;
+  ZTile zt;                      // ZKernel::tile: its instantiation and table (tile_setup)
   int fixnull = 0;               // pressure without a Dirichlet condition in z: the zero-eigenvalue mode (if x and y have one) is singular
   bool refnull = false;          // CALES_KEEP_NULL_MODE: that column in the reference's sequential order (k_null_column)
+  bool null_switch = false;      // ... the switch as given (solver_path_name prints it whether or not the problem is singular)
   bool nyq = false;              // the modes 0 and n1/2 share mode column 0 (Spec::nyq): k_gaussel_nyq solves it after the tile
   int cw = 0;                    // complex mode columns per rank
   int xrows = 1, ycols = 1;      // rows per block of k_fft_x8, columns per block of the radix-8 y kernels
@@ -1935,7 +1880,14 @@ struct SolvePath {
   real *lamx = nullptr, *lamy = nullptr; real normfft = 1.;      // eigenvalues per stored spectral index; scale of the inverse transforms
   FftPlan p1x, p1y; real *tw1x = nullptr, *tw1y = nullptr;      // k_dst1 (face-centred kinds)
 };
-// the solver state a context owns (cales_ctx::solver): line plans and launch geometry of the transforms, their tables, the paths
+// A z-only Helmholtz sweep of the z-implicit step (op_helmholtz_z), one per velocity component: nz = n3 - q unknowns (q = 1: w under a Dirichlet top) and their form
+enum class HzForm { thomas_periodic, thomas_per_column, tile, cols };      // k_gaussel<real, 1> | k_gaussel<real, 0> (CALES_HELMHOLTZ_Z_PER_COLUMN) | the LDS tile on the real field | k_thomas_coef + k_gaussel_cols(_rhs): shared pivots
+struct HzPath {
+  HzForm form = HzForm::cols; int nz = 0, q = 0; ZTile zt; TileMap T{};      // tile: M, NV = 2, PER = 0 and the static part of its map, nolam, nq = n3 (DUD and the table are the call's: fused or not, the slot)
+  // the chunked tables of the alphas this component has seen -- three per step, the same every step while dt stays (four slots, round robin, in Solver::tab_hz)
+  real alpha[4] = {0., 0., 0., 0.}; bool ok[4] = {false, false, false, false}; int next = 0;
+};
+// the solver state a context owns (cales_ctx::solver): line plans and launch geometry of the transforms, their tables, the paths, the memory of the z solves
 struct Solver {
   FftPlan px, py, py4; int Rx, CBy, CBy4 = 0; size_t shx, shy, shy4 = 0;
   bool x8, y8, y16 = false; int x8_threads, y8_threads; size_t shx8, shy8, shy8r, shy16 = 0;
@@ -1943,7 +1895,54 @@ struct Solver {
   real *twx = nullptr, *twx_post = nullptr, *twy = nullptr, *twy_post = nullptr, *twyd = nullptr;      // twiddle tables; twy_post, twyd: DCT weights of x, of y
   real *tw4x = nullptr, *tw4y = nullptr, *twy4 = nullptr;         // DCT-IV weights of x and y, twiddles of the N/2-point y lines
   SolvePath pres, vel[3]; bool vel_ready[3] = {false, false, false};
+  HzPath hz[3];                  // impdiff = 2
+  real *d_a = nullptr, *d_b, *d_c, *d_av[3] = {nullptr, nullptr, nullptr}, *d_bv[3], *d_cv[3];      // tridiagonal (a | b | c, n3 each) of the pressure; of the velocity components, unscaled (impdiff)
+  real *d_scaled = nullptr;      // 5 n3 reals, see scaled_abc (impdiff)
+  // chunked tables: the pressure's, built once by solver_setup (its operands never change); the 3-D implicit Helmholtz solves', rebuilt by every solve (its alpha
+  // rescales the operands; impdiff = 1); 3 x 4 of the z-only sweeps (HzPath::alpha)
+  real *tab_pres = nullptr, *tab_imp3d = nullptr, *tab_hz = nullptr;
+  real *d_nullw = nullptr;       // work space of k_null_column (CALES_KEEP_NULL_MODE)
 };
+// a, b, c of a Helmholtz solve scaled with its alpha (k_scale_abc, main.f90:435-437) and the pivots zz, dd of the shared-pivot columns (k_thomas_coef)
+struct ScaledAbc { real *a, *b, *c, *zz, *dd; };
+static ScaledAbc scaled_abc(const cales_ctx *c) { real *p = c->solver->d_scaled; const int n3 = c->n[2]; return {p, p + n3, p + 2 * n3, p + 3 * n3, p + 4 * n3}; }
+// ---- the LDS tiles of the z solves: every instantiation named once (tile_kernel, launch_nyq), launched from one place each
+typedef void (*TileKernel)(Geom, int, int, real, const real *, const real *, const real *, real *, int, TileMap, const real *, const real *, const real *);
+static TileKernel tile_kernel(const ZTile &Z) {
+#define TILE(M, NV, PER, DUD) case 1000 * M + 100 * NV + 10 * PER + DUD: return k_gaussel_tile<M, NV, PER, DUD>
+  switch (1000 * Z.M + 100 * Z.NV + 10 * Z.PER + Z.DUD) {
+  TILE(2, 1, 0, 0); TILE(4, 1, 0, 0); TILE(8, 1, 0, 0); TILE(16, 1, 0, 0);      // real x modes, one eigenvalue per column
+  TILE(2, 2, 0, 0); TILE(4, 2, 0, 0); TILE(8, 2, 0, 0); TILE(16, 2, 0, 0);      // complex modes / pairs of real columns
+  TILE(2, 1, 1, 0); TILE(4, 1, 1, 0); TILE(8, 1, 1, 0); TILE(16, 1, 1, 0);      // periodic z
+  TILE(2, 2, 1, 0); TILE(4, 2, 1, 0); TILE(8, 2, 1, 0); TILE(16, 2, 1, 0);
+  TILE(2, 2, 0, 1); TILE(4, 2, 0, 1); TILE(8, 2, 0, 1);                         // the z-only sweeps forming their r.h.s. while loading: 512 unknowns at most
+  default: return nullptr;
+  }
+#undef TILE
+}
+static int tile_lds(int M) { return 16 * (64 * (M + 1) + GT_PAD) * 8 + (GT_TL && M == 16 ? 2 * 64 * M * 8 : 0); }
+// set-up: the kernel of Z may use its LDS (a kernel that does not exist fails here) -- per context, which may sit on another device than the one before it
+static void tile_attr(cales_ctx *c, const ZTile &Z) { HIPSOFT(c, hipFuncSetAttribute(Z.persistent ? (const void *)k_gaussel_tile_p<1> : (const void *)tile_kernel(Z), hipFuncAttributeMaxDynamicSharedMemorySize, tile_lds(Z.M))); }
+// a, b, c in the chunked order of an M-plane tile (periodic z: nsys = nz - 1, the rows of the system proper; identity rows behind them)
+static void tile_table(cales_ctx *c, int M, int nsys, const real *da, const real *db, const real *dc, real *tab) { LAUNCH(c, k_abc_chunked, dim3((64 * M + 255) / 256), dim3(256), 0, c->stream, nsys, M, da, db, dc, tab); }
+// the coefficients come from Z.tab; ra, rb_, rc, the raw ones, are read by the periodic instantiations only (their closure)
+static void launch_tile(cales_ctx *c, const ZTile &Z, int nz, real lscale, const real *ra, const real *rb_, const real *rc, const real *lamx, const real *lamy, real *p, int fixnull, const TileMap &T) {
+  if (Z.persistent) {      // tiles per block so that ~2048 blocks or more remain
+    const int ntile = Z.ndbl / 16; int tpb = 1; while (tpb * 2 <= ntile && tpb < 32 && (long)Z.nrow * ((ntile + 2 * tpb - 1) / (2 * tpb)) >= 2048) tpb *= 2;
+    LAUNCH(c, (k_gaussel_tile_p<1>), dim3((ntile + tpb - 1) / tpb, Z.nrow), dim3(512), tile_lds(16), c->stream, c->g, nz, Z.ndbl, lscale, Z.tab, lamx, lamy, p, fixnull, T, tpb, ra, rb_, rc);
+    return;
+  }
+  const TileKernel k_gaussel_tile_form = tile_kernel(Z);
+  LAUNCH(c, k_gaussel_tile_form, dim3((Z.ndbl + 15) / 16, Z.nrow), dim3(64 * 16 / Z.NV), tile_lds(Z.M), c->stream, c->g, nz, Z.ndbl, lscale, Z.tab, lamx, lamy, p, fixnull, T, ra, rb_, rc);
+}
+// the packed column of the modes 0 and n1/2 (periodic y: Hermitian pairing of the rows), after the tile of the same path and from the same table
+typedef void (*NyqKernel)(Geom, int, int, int, real, const real *, const real *, const real *, real2 *, int, Spec, const real *, const real *, const real *);
+static void launch_nyq(cales_ctx *c, const ZTile &Z, bool herm, int nz, int N, int nh, real lscale, const real *lamx, const real *lamy, real2 *p, int fixnull, const Spec &S) {
+  static const NyqKernel forms[4][2] = {{k_gaussel_nyq<2, 0>, k_gaussel_nyq<2, 1>}, {k_gaussel_nyq<4, 0>, k_gaussel_nyq<4, 1>}, {k_gaussel_nyq<8, 0>, k_gaussel_nyq<8, 1>}, {k_gaussel_nyq<16, 0>, k_gaussel_nyq<16, 1>}};
+  const NyqKernel k_gaussel_nyq_form = forms[Z.M == 2 ? 0 : Z.M == 4 ? 1 : Z.M == 8 ? 2 : 3][herm ? 1 : 0];
+  LAUNCH(c, k_gaussel_nyq_form, dim3(herm ? N / 2 + 1 : N / 2), dim3(256), 4 * (64 * (Z.M + 1) + GT_PAD) * 8, c->stream, c->g, nz, N, nh, lscale, Z.tab, lamx, lamy, p, fixnull, S,
+         (const real *)nullptr, (const real *)nullptr, (const real *)nullptr);
+}
 
 bool solver_can_fuse_fillps(cales_ctx *c) { return c->solver && c->solver->x8; }
 int solver_mode_columns(cales_ctx *c) { return c->solver ? c->solver->pres.cw : c->cw; }
@@ -1991,11 +1990,19 @@ static void choose_kernels(cales_ctx *c, const Solver &s, SolvePath &P) {
   P.ycols = P.yk == YKernel::fft_y16 ? 8 : use8y ? s.y8_threads / (n2g / 8) : 1;
   const bool hasd = CBP(c, 0, 3) == 'D' || CBP(c, 1, 3) == 'D';
   P.fixnull = (P.poisson && !hasd && !c->fl.keep_null_mode) ? 1 : 0;
-  P.refnull = P.poisson && !hasd && c->fl.keep_null_mode;
+  P.refnull = P.poisson && !hasd && c->fl.keep_null_mode; P.null_switch = c->fl.keep_null_mode;
   if (P.xkind && !P.ykind) P.zk = ZKernel::herm;      // real x modes paired into complex columns + periodic y: Hermitian separation of rows ky and N-ky
   else if ((P.periodic_z || P.fixnull || !P.poisson || hasd) && tile_takes(c, P.nz, P.periodic_z)) P.zk = ZKernel::tile;
   else if (P.xkind) P.zk = P.periodic_z ? ZKernel::periodic_real : ZKernel::ri;
   else P.zk = P.periodic_z ? ZKernel::periodic_cpx : ZKernel::ri;
+}
+// ... and its tile, for a path whose kernels, nyq and cw are set: the instantiation, its extent, its LDS attribute, the table it reads
+static void tile_setup(cales_ctx *c, SolvePath &P, real *tab) {
+  if (P.zk != ZKernel::tile) return;
+  ZTile &Z = P.zt; Z.M = tile_m(P.nz); Z.NV = P.xkind ? 1 : 2; Z.PER = P.periodic_z ? 1 : 0; Z.tab = tab;
+  Z.ndbl = c->P > 1 ? 2 * P.cw * c->n[1] : P.xkind ? 2 * (c->C.ng[0] / 2) : 2 * (P.nyq ? c->n[0] / 2 : c->n[0] / 2 + 1); Z.nrow = c->P > 1 ? c->P : c->C.ng[1];
+  Z.persistent = !Z.PER && Z.NV == 1 && P.nz == 1024 && Z.ndbl % 16 == 0;      // full tiles of full chunks only (k_gaussel_tile_p)
+  tile_attr(c, Z);
 }
 
 int solver_setup(cales_ctx *c) {
@@ -2094,12 +2101,15 @@ int solver_setup(cales_ctx *c) {
   HIPCHK(c, hipMemcpy(P.lamx, lx.data(), (n1 + 2) * sizeof(real), hipMemcpyHostToDevice));
   HIPCHK(c, hipMemcpy(P.lamy, ly.data(), n2g * sizeof(real), hipMemcpyHostToDevice));
   // tridiagonal (initsolver.f90:127-169), pressure: cell-centred
-  std::vector<real> a(n3), b(n3), cc(n3);
-  hs_tridmatrix(&c->C.cbcpre[4], n3, c->dzci.data(), c->dzfi.data(), 'c', a.data(), b.data(), cc.data());
-  HIPCHK(c, hipMalloc(&c->d_a, n3 * sizeof(real))); HIPCHK(c, hipMalloc(&c->d_b, n3 * sizeof(real))); HIPCHK(c, hipMalloc(&c->d_c, n3 * sizeof(real)));
-  HIPCHK(c, hipMemcpy(c->d_a, a.data(), n3 * sizeof(real), hipMemcpyHostToDevice));
-  HIPCHK(c, hipMemcpy(c->d_b, b.data(), n3 * sizeof(real), hipMemcpyHostToDevice));
-  HIPCHK(c, hipMemcpy(c->d_c, cc.data(), n3 * sizeof(real), hipMemcpyHostToDevice));
+  std::vector<real> abc(3 * (size_t)n3);      // a | b | c
+  hs_tridmatrix(&c->C.cbcpre[4], n3, c->dzci.data(), c->dzfi.data(), 'c', abc.data(), abc.data() + n3, abc.data() + 2 * n3);
+  HIPCHK(c, hipMalloc(&s.d_a, abc.size() * sizeof(real))); s.d_b = s.d_a + n3; s.d_c = s.d_a + 2 * n3;
+  HIPCHK(c, hipMemcpy(s.d_a, abc.data(), abc.size() * sizeof(real), hipMemcpyHostToDevice));
+  if (P.zk == ZKernel::tile) {      // the pressure's tile and its table, built here once
+    HIPCHK(c, hipMalloc(&s.tab_pres, TILE_TAB * sizeof(real))); tile_setup(c, P, s.tab_pres);
+    tile_table(c, P.zt.M, P.zt.PER ? n3 - 1 : n3, s.d_a, s.d_b, s.d_c, s.tab_pres);
+  }
+  if (P.refnull) HIPCHK(c, hipMalloc(&s.d_nullw, (size_t)5 * (n3 + 2) * sizeof(real)));
   P.normfft = 1. / ((P.xkind ? 2. : 1.) * (real)n1 * (P.ykind ? 2. : 1.) * (real)n2g);   // fft.f90:99,136,142; find_fft norm = [1,0] (PP) / [2,0] (NN)
   if (upload_twiddles(c, n1 / 2, n1 / 2, &s.twx)) return 1;
   if (upload_twiddles(c, n1, n1 / 2 + 1, &s.twx_post)) return 1;
@@ -2107,25 +2117,35 @@ int solver_setup(cales_ctx *c) {
   if (upload_twiddles(c, 4 * n1, n1 / 2 + 1, &s.twy_post)) return 1;      // DCT weights e^{-i pi k/(2 n1)}, k = 0..n1/2 (x)
   if (upload_twiddles(c, 4 * n2g, n2g, &s.twyd)) return 1;               // e^{-i pi k/(2 n2)}, k = 0..n2-1 (y)
   if (P.xkind >= 3 && upload_dct4_weights(c, n1, &s.tw4x)) return 1;    // DCT-IV weights (k_fft_x4)
-  if (c->C.impdiff)
-    for (int iv = 0; iv < 3; ++iv) {
-      hs_tridmatrix(&c->cbcvel[6 * iv + 4], n3, c->dzci.data(), c->dzfi.data(), iv == 2 ? 'f' : 'c', a.data(), b.data(), cc.data());
-      HIPCHK(c, hipMalloc(&c->d_av[iv], 3 * n3 * sizeof(real)));   // a | b | c (unscaled); scaled copies follow
-      c->d_bv[iv] = c->d_av[iv] + n3; c->d_cv[iv] = c->d_av[iv] + 2 * n3;
-      HIPCHK(c, hipMemcpy(c->d_av[iv], a.data(), n3 * sizeof(real), hipMemcpyHostToDevice));
-      HIPCHK(c, hipMemcpy(c->d_bv[iv], b.data(), n3 * sizeof(real), hipMemcpyHostToDevice));
-      HIPCHK(c, hipMemcpy(c->d_cv[iv], cc.data(), n3 * sizeof(real), hipMemcpyHostToDevice));
-    }
+  if (!c->C.impdiff) return 0;
+  for (int iv = 0; iv < 3; ++iv) {
+    hs_tridmatrix(&c->cbcvel[6 * iv + 4], n3, c->dzci.data(), c->dzfi.data(), iv == 2 ? 'f' : 'c', abc.data(), abc.data() + n3, abc.data() + 2 * n3);
+    HIPCHK(c, hipMalloc(&s.d_av[iv], abc.size() * sizeof(real))); s.d_bv[iv] = s.d_av[iv] + n3; s.d_cv[iv] = s.d_av[iv] + 2 * n3;
+    HIPCHK(c, hipMemcpy(s.d_av[iv], abc.data(), abc.size() * sizeof(real), hipMemcpyHostToDevice));
+  }
+  HIPCHK(c, hipMalloc(&s.d_scaled, (size_t)5 * n3 * sizeof(real))); HIPCHK(c, hipMemset(s.d_scaled, 0, (size_t)5 * n3 * sizeof(real)));
+  if (c->C.impdiff == 1) HIPCHK(c, hipMalloc(&s.tab_imp3d, TILE_TAB * sizeof(real)));      // (the paths themselves on their first solve: velocity_path)
+  if (c->C.impdiff != 2) return 0;
+  // the z-only sweeps: the in-LDS tile of the pressure solve on the real field (u, dudtd in, u out: 3 words instead of 5) where its nz + q planes fit
+  for (int iv = 0; iv < 3; ++iv) {
+    HzPath &H = s.hz[iv]; const char *bcz = &c->cbcvel[6 * iv + 4];
+    H.q = (iv == 2 && bcz[1] == 'D') ? 1 : 0; H.nz = n3 - H.q;
+    H.form = (bcz[0] == 'P' && bcz[1] == 'P') ? HzForm::thomas_periodic : c->fl.helmholtz_z_per_column ? HzForm::thomas_per_column
+           : (tile_takes(c, H.nz, false) && H.nz <= 512 && n3 <= 64 * tile_m(H.nz)) ? HzForm::tile : HzForm::cols;
+    if (H.form != HzForm::tile) continue;
+    H.T.nolam = 1; H.T.nq = n3; H.zt.M = tile_m(H.nz); H.zt.NV = 2; H.zt.ndbl = n[0]; H.zt.nrow = n[1];
+    for (int dud = 0; dud <= 1; ++dud) { H.zt.DUD = dud; tile_attr(c, H.zt); }      // as the operator runs it | inside cales_step, forming its r.h.s.
+    if (!s.tab_hz) HIPCHK(c, hipMalloc(&s.tab_hz, (size_t)12 * TILE_TAB * sizeof(real)));
+  }
   return 0;
 }
 void solver_teardown(cales_ctx *c) {
   if (Solver *s = c->solver) {
     for (const SolvePath *P : {&s->pres, &s->vel[0], &s->vel[1], &s->vel[2]}) { hipFree(P->lamx); hipFree(P->lamy); hipFree(P->tw1x); hipFree(P->tw1y); }
     for (real *t : {s->twx, s->twx_post, s->twy, s->twy_post, s->twyd, s->tw4x, s->tw4y, s->twy4}) hipFree(t);
+    for (real *t : {s->d_a, s->d_av[0], s->d_av[1], s->d_av[2], s->d_scaled, s->tab_pres, s->tab_imp3d, s->tab_hz, s->d_nullw}) hipFree(t);
     delete s; c->solver = nullptr;
   }
-  hipFree(c->d_a); hipFree(c->d_b); hipFree(c->d_c);
-  for (int iv = 0; iv < 3; ++iv) hipFree(c->d_av[iv]);
 }
 
 // CALES_KEEP_NULL_MODE: the zero-eigenvalue column of a singular pressure problem (no Dirichlet condition in z) solved in the REFERENCE's own
@@ -2346,10 +2366,7 @@ static int solve_field(cales_ctx *c, const SolvePath &P, real *pp, const real *d
   }
   // CALES_KEEP_NULL_MODE: the singular column in the reference's sequential order (k_null_column); the rank that holds mode 0 does it
   const bool refnull = P.refnull && mofs == 0;
-  if (refnull) {
-    if (!c->d_nullw) HIPCHK(c, hipMalloc(&c->d_nullw, (size_t)5 * (c->C.ng[2] + 2) * sizeof(real)));
-    LAUNCH(c, k_null_column, dim3(1), dim3(64), 0, c->stream, c->g, S, nz, P.periodic_z ? 1 : 0, da, db, dc, P.lamx, P.lamy, mode_spec, c->d_nullw, 0);
-  }
+  if (refnull) LAUNCH(c, k_null_column, dim3(1), dim3(64), 0, c->stream, c->g, S, nz, P.periodic_z ? 1 : 0, da, db, dc, P.lamx, P.lamy, mode_spec, c->solver->d_nullw, 0);
   { ProfScope ps(c, "gaussel_z");
     const dim3 b(64, 4), gr((ncol + 63) / 64, (n2g + 3) / 4);
     real *ms = (real *)mode_spec;
@@ -2361,12 +2378,9 @@ static int solve_field(cales_ctx *c, const SolvePath &P, real *pp, const real *d
     case ZKernel::tile: {
       TileMap T{}; T.blocked = dist ? 1 : 0; T.cw = cw; T.n2l = n[1]; T.mofs = mofs; T.nmode = P.xkind ? nh : nmodes; T.nyq = P.nyq ? 1 : 0;
       T.kstride = (size_t)2 * cw * n[1]; T.segstride = T.kstride * n[2];
-      const int ndbl = dist ? 2 * cw * n[1] : (P.xkind ? 2 * nh : 2 * nmodes), nseg = dist ? c->P : n2g;
-      // periodic z: the cyclic closure inside the tile (gaussel_periodic, solver.f90:109-150)
-      if (P.periodic_z && P.xkind) gaussel_tile<1, 1>(c, nz, ndbl, nseg, lscale, da, db, dc, P.lamx, P.lamy, ms, P.fixnull, T);
-      else if (P.periodic_z) gaussel_tile<2, 1>(c, nz, ndbl, nseg, lscale, da, db, dc, P.lamx, P.lamy, ms, P.fixnull, T);
-      else if (P.xkind) gaussel_tile<1>(c, nz, ndbl, nseg, lscale, da, db, dc, P.lamx, P.lamy, ms, P.fixnull, T);
-      else gaussel_tile<2>(c, nz, ndbl, nseg, lscale, da, db, dc, P.lamx, P.lamy, ms, P.fixnull, T);
+      // the pressure's operands never change, its table is solver_setup's; a Helmholtz solve rescales its operands with the call's alpha: the table anew
+      if (!P.poisson) tile_table(c, P.zt.M, P.zt.PER ? nz - 1 : nz, da, db, dc, P.zt.tab);
+      launch_tile(c, P.zt, nz, lscale, da, db, dc, P.lamx, P.lamy, ms, P.fixnull, T);
       break; }
     case ZKernel::ri:
       LAUNCH(c, k_gaussel_ri, dim3((unsigned)(((long)2 * ncol * n2g + 255) / 256)), dim3(256), 0, c->stream, c->g, nz, ncol, n2g, mofs, P.xkind ? nh : mh, S, lscale,
@@ -2382,9 +2396,9 @@ static int solve_field(cales_ctx *c, const SolvePath &P, real *pp, const real *d
     } }
   if (P.nyq && mofs == 0) {      // the packed column of the modes 0 and n1/2, which the tile left out (the path takes the tile: solver_setup)
     ProfScope ps(c, "gaussel_z");
-    gaussel_nyq(c, P.ykind == 0, nz, n2g, nh, lscale, da, db, dc, P.lamx, P.lamy, mode_spec, P.fixnull, S);
+    launch_nyq(c, P.zt, P.ykind == 0, nz, n2g, nh, lscale, P.lamx, P.lamy, mode_spec, P.fixnull, S);
   }
-  if (refnull) LAUNCH(c, k_null_column, dim3(1), dim3(64), 0, c->stream, c->g, S, nz, P.periodic_z ? 1 : 0, da, db, dc, P.lamx, P.lamy, mode_spec, c->d_nullw, 1);
+  if (refnull) LAUNCH(c, k_null_column, dim3(1), dim3(64), 0, c->stream, c->g, S, nz, P.periodic_z ? 1 : 0, da, db, dc, P.lamx, P.lamy, mode_spec, c->solver->d_nullw, 1);
   if (F.mean_mask && pipe) if (int e = op_force_from_partials(c, F.mean_mask, F.part, (int)(xblocks_c * NCH))) return e;
   for (int ch = 0; ch < NCH; ++ch) {
     { ProfScope ps(c, "fft_y_bwd");
@@ -2410,15 +2424,15 @@ std::string solver_path_name(cales_ctx *c) {
   std::string s = std::string("x:") + kinds[P.xkind] + (P.xk == XKernel::fft_x8 ? "/radix8" : P.xk == XKernel::fft_x4 ? "/dct4" : "/mixed_radix");
   if (P.xodd) s += "x" + std::to_string(P.xodd);
   s += std::string(",y:") + kinds[P.ykind] + (radix8_y(P.yk) ? (P.yodd ? "/radix8x" + std::to_string(P.yodd) : P.ykind ? "/radix8" : "/radix8_register_ends") : P.yk == YKernel::fft_y4 ? "/dct4" : "/mixed_radix");
-  s += std::string(",z:") + (P.zk == ZKernel::herm ? "thomas_hermitian" : P.zk == ZKernel::tile ? (P.periodic_z ? "lds_tile_periodic" : "lds_tile") : "thomas_march");
+  s += std::string(",z:") + (P.zk == ZKernel::herm ? "thomas_hermitian" : P.zk == ZKernel::tile ? (P.zt.PER ? "lds_tile_periodic" : "lds_tile") : "thomas_march");
   if (P.nyq) s += ",modes_0_and_n1/2:one_column";
-  if (c->fl.keep_null_mode) s += ",null_mode:reference_order";
+  if (P.null_switch) s += ",null_mode:reference_order";
   return s;
 }
 
 int op_solver(cales_ctx *c, const FusedFill &fill) {
   if (!c->solver) { c->err = "solver not initialised"; return 1; }
-  return solve_field(c, c->solver->pres, c->f[CALES_PP], c->d_a, c->d_b, c->d_c, 1., fill);
+  return solve_field(c, c->solver->pres, c->f[CALES_PP], c->solver->d_a, c->solver->d_b, c->solver->d_c, 1., fill);
 }
 
 // z-only Helmholtz systems have the same matrix for every column (no eigenvalue shift): the pivots z_l and c'_l of the
@@ -2478,47 +2492,36 @@ int op_rhs_b_velxy(cales_ctx *c, int ivel, real alpha);
 int op_helmholtz_z(cales_ctx *c, int ivel, real alpha, bool fused, real hf12) {
   if (c->C.impdiff != 2) { c->err = "helmholtz_z needs impdiff = 2"; return 1; }
   ProfScope ps(c, "helmholtz_z");
-  const int *n = c->n; const int n3 = n[2];
-  int has[2] = {0, 0};
-  const char *bcz = &c->cbcvel[6 * (ivel - 1) + 4];
-  const int q = (ivel == 3 && bcz[1] == 'D') ? 1 : 0;
-  const bool periodic = bcz[0] == 'P' && bcz[1] == 'P';
-  // the in-LDS tile of the pressure solve on the real field (u, dudtd in, u out: 3 words instead of 5) where its nz + q planes fit; it evaluates the
-  // boundary term itself (RhsBz): no pass, no plane
-  const bool tile_path = !periodic && !c->fl.helmholtz_z_per_column && tile_takes(c, n3 - q, false) && n3 - q <= 512 && n3 <= 64 * (n3 - q <= 128 ? 2 : n3 - q <= 256 ? 4 : 8);
-  RhsBz RB[2] = {};
-  if (fused && tile_path) rhs_b_velz_args(c, ivel, alpha, RB, has);
+  Solver &s = *c->solver; HzPath &H = s.hz[ivel - 1];
+  const int *n = c->n; const int n3 = n[2], nz = H.nz; const bool tile = H.form == HzForm::tile;
+  // the boundary terms: the tile evaluates them itself while it loads (RhsBz: no pass, no plane); the other forms read planes (fused) or find them in the field
+  int has[2] = {0, 0}; RhsBz RB[2] = {};
+  if (fused && tile) rhs_b_velz_args(c, ivel, alpha, RB, has);
   else if (int e = op_rhs_b_velz(c, ivel, alpha, fused ? c->scr2 : nullptr, fused ? has : nullptr)) return e;
-  real *abc = c->d_red + 64 + 16 * (n3 + 2);     // scaled coefficients live behind the reduction partials
-  // the table of this (component, alpha) from an earlier sweep (in-LDS form only: the others read the scaled coefficients themselves)
-  real *hz = nullptr; bool hz_ready = false;
-  if (tile_path) {
-    if (!c->d_hztab) { const hipError_t e = hipMalloc(&c->d_hztab, (size_t)12 * 3 * 64 * 16 * sizeof(real)); if (e != hipSuccess) c->d_hztab = nullptr; }
-    if (c->d_hztab) {
-      int sl = -1;
-      for (int q4 = 0; q4 < 4; ++q4) { const auto &h4 = c->hz_tab[ivel - 1][q4]; if (h4.ok && h4.alpha == alpha && h4.nz == n3 - q) sl = q4; }
-      hz_ready = sl >= 0;
-      if (sl < 0) { sl = c->hz_next[ivel - 1]; c->hz_next[ivel - 1] = (sl + 1) % 4; c->hz_tab[ivel - 1][sl].alpha = alpha; c->hz_tab[ivel - 1][sl].nz = n3 - q; c->hz_tab[ivel - 1][sl].ok = true; }
-      hz = c->d_hztab + (size_t)(4 * (ivel - 1) + sl) * 3 * 64 * 16;
-    }
-  }
-  if (!hz_ready) LAUNCH(c, k_scale_abc, dim3((n3 + 63) / 64), dim3(64), 0, c->stream, n3, alpha, c->d_av[ivel - 1], c->d_bv[ivel - 1], c->d_cv[ivel - 1], abc, abc + n3, abc + 2 * n3);
-  dim3 b(64, 4), gr((n[0] + 63) / 64, (n[1] + 3) / 4);
+  // the tile's table of this alpha from an earlier sweep; the other forms read the scaled coefficients themselves
+  int slot = -1; if (tile) for (int q4 = 0; q4 < 4; ++q4) if (H.ok[q4] && H.alpha[q4] == alpha) slot = q4;
+  const bool hit = slot >= 0; if (tile && !hit) { slot = H.next; H.next = (slot + 1) % 4; H.alpha[slot] = alpha; H.ok[slot] = true; }
+  const ScaledAbc A = scaled_abc(c);
+  if (!hit) LAUNCH(c, k_scale_abc, dim3((n3 + 63) / 64), dim3(64), 0, c->stream, n3, alpha, s.d_av[ivel - 1], s.d_bv[ivel - 1], s.d_cv[ivel - 1], A.a, A.b, A.c);
+  const dim3 b(64, 4), gr((n[0] + 63) / 64, (n[1] + 3) / 4);
   real *fld = c->f[CALES_U + ivel - 1];
+  const real *dud = c->f[CALES_DUDTD + ivel - 1], *force = c->C.is_forced[ivel - 1] ? c->d_force + (ivel - 1) : nullptr;
   Spec S; S.blocked = 0; S.cw = 0; S.n2l = n[1]; S.n3 = n3;
-  if (periodic) LAUNCH(c, (k_gaussel<real, 1>), gr, b, 0, c->stream, c->g, n3 - q, n[0], n[1], 1, 0, n[0], S, 1., abc, abc + n3, abc + 2 * n3, (const real *)nullptr, (const real *)nullptr, fld, c->scr1, c->scr2, 0);
-  else if (c->fl.helmholtz_z_per_column) LAUNCH(c, (k_gaussel<real, 0>), gr, b, 0, c->stream, c->g, n3 - q, n[0], n[1], 1, 0, n[0], S, 1., abc, abc + n3, abc + 2 * n3, (const real *)nullptr, (const real *)nullptr, fld, c->scr1, c->scr2, 0);
-  else if (tile_path) {
-    TileMap T{}; T.nolam = 1; T.nq = n3;
-    if (fused) { T.dud = c->f[CALES_DUDTD + ivel - 1] + 1; T.hf12 = hf12; T.force = c->C.is_forced[ivel - 1] ? c->d_force + (ivel - 1) : nullptr;
-                 T.blo = RB[0]; T.bhi = RB[1]; T.has_lo = has[0]; T.has_hi = has[1]; }
-    gaussel_tile<2>(c, n3 - q, n[0], n[1], 1., abc, abc + n3, abc + 2 * n3, c->solver->pres.lamx, c->solver->pres.lamy, fld + 1, 0, T, hz, hz_ready);
-  } else {
-    real *zz = abc + 3 * n3, *dd = abc + 4 * n3;       // behind the scaled coefficients (cales_create reserves 6 (n3+2) doubles)
-    LAUNCH(c, k_thomas_coef, dim3(1), dim3(64), 0, c->stream, n3 - q, abc, abc + n3, abc + 2 * n3, zz, dd);
-    if (fused) LAUNCH(c, k_gaussel_cols_rhs, gr, b, 0, c->stream, c->g, n3 - q, n3, abc, zz, dd, fld, c->f[CALES_DUDTD + ivel - 1], hf12,
-                                  c->C.is_forced[ivel - 1] ? c->d_force + (ivel - 1) : (const real *)nullptr, c->scr2, has[0], has[1]);
-    else LAUNCH(c, k_gaussel_cols, gr, b, 0, c->stream, c->g, n3 - q, abc, zz, dd, fld);
+  switch (H.form) {
+  case HzForm::thomas_periodic: LAUNCH(c, (k_gaussel<real, 1>), gr, b, 0, c->stream, c->g, nz, n[0], n[1], 1, 0, n[0], S, 1., A.a, A.b, A.c, (const real *)nullptr, (const real *)nullptr, fld, c->scr1, c->scr2, 0); break;
+  case HzForm::thomas_per_column: LAUNCH(c, (k_gaussel<real, 0>), gr, b, 0, c->stream, c->g, nz, n[0], n[1], 1, 0, n[0], S, 1., A.a, A.b, A.c, (const real *)nullptr, (const real *)nullptr, fld, c->scr1, c->scr2, 0); break;
+  case HzForm::tile: {
+    ZTile Z = H.zt; Z.DUD = fused ? 1 : 0; Z.tab = s.tab_hz + (size_t)(4 * (ivel - 1) + slot) * TILE_TAB; TileMap T = H.T;
+    if (fused) { T.dud = dud + 1; T.hf12 = hf12; T.force = force; T.blo = RB[0]; T.bhi = RB[1]; T.has_lo = has[0]; T.has_hi = has[1]; }
+    if (!hit) tile_table(c, Z.M, nz, A.a, A.b, A.c, Z.tab);
+    // On a hit A holds whatever sweep scaled last, another component's coefficients as a rule: the launch reads the cached table alone -- the raw
+    // coefficients are the periodic instantiations' (launch_tile), and this one is not periodic: none are passed
+    launch_tile(c, Z, nz, 1., nullptr, nullptr, nullptr, s.pres.lamx, s.pres.lamy, fld + 1, 0, T);
+    break; }
+  case HzForm::cols:
+    LAUNCH(c, k_thomas_coef, dim3(1), dim3(64), 0, c->stream, nz, A.a, A.b, A.c, A.zz, A.dd);
+    if (fused) LAUNCH(c, k_gaussel_cols_rhs, gr, b, 0, c->stream, c->g, nz, n3, A.a, A.zz, A.dd, fld, dud, hf12, force, c->scr2, has[0], has[1]);
+    else LAUNCH(c, k_gaussel_cols, gr, b, 0, c->stream, c->g, nz, A.a, A.zz, A.dd, fld);
   }
   LAUNCHCHK(c);
   return 0;
@@ -2575,6 +2578,7 @@ static int velocity_path(cales_ctx *c, Solver &s, int iv, SolvePath &V) {
   V.nz = c->n[2] - ((iv == 2 && bcz[1] == 'D') ? 1 : 0); V.periodic_z = bcz[0] == 'P' && bcz[1] == 'P'; V.poisson = false;
   V.cw = c->cw;
   choose_kernels(c, s, V);
+  tile_setup(c, V, s.tab_imp3d);
   return 0;
 }
 int op_helmholtz(cales_ctx *c, int ivel, real alpha) {
@@ -2587,7 +2591,7 @@ int op_helmholtz(cales_ctx *c, int ivel, real alpha) {
   const int n3 = c->n[2];
   if (int e = op_rhs_b_velxy(c, ivel, alpha)) return e;      // main.f90:424-431: boundary terms of the x and y faces, then z
   if (int e = op_rhs_b_velz(c, ivel, alpha)) return e;
-  real *abc = c->d_red + 64 + 16 * (n3 + 2);
-  LAUNCH(c, k_scale_abc, dim3((n3 + 63) / 64), dim3(64), 0, c->stream, n3, alpha, c->d_av[ivel - 1], c->d_bv[ivel - 1], c->d_cv[ivel - 1], abc, abc + n3, abc + 2 * n3);
-  return solve_field(c, V, c->f[CALES_U + ivel - 1], abc, abc + n3, abc + 2 * n3, alpha);
+  const ScaledAbc A = scaled_abc(c);
+  LAUNCH(c, k_scale_abc, dim3((n3 + 63) / 64), dim3(64), 0, c->stream, n3, alpha, s->d_av[ivel - 1], s->d_bv[ivel - 1], s->d_cv[ivel - 1], A.a, A.b, A.c);
+  return solve_field(c, V, c->f[CALES_U + ivel - 1], A.a, A.b, A.c, alpha);
 }

@@ -151,7 +151,14 @@ def test_time_steps(name, ng, nsteps):
     h.close()
 
 
-@pytest.mark.parametrize("name,ng", [("halfchan_imp1d", (16, 16, 16)), ("duct_smag_wm_imp1d", (16, 12, 12)), ("duct_smag_wm_imp1d", (64, 16, 20))])
+# halfchan_imp1d (w has a Dirichlet top: n3 - 1 unknowns) at the n3 where the planes-per-lane rule of the in-LDS tile and its "do n3 planes fit" test switch:
+# 128: 2 planes per lane for u, v and w; 129: 4 for u, v -- w's 128 unknowns take 2, whose tile cannot hold 129 planes: the shared-pivot column kernels;
+# 130: 4 for all three; 257: 8 for u, v, the column kernels for w
+HZ_GRIDS = [(16, 8, 128), (16, 8, 129), (16, 8, 130), (16, 8, 257)]
+
+
+@pytest.mark.parametrize("name,ng", [("halfchan_imp1d", (16, 16, 16)), ("duct_smag_wm_imp1d", (16, 12, 12)), ("duct_smag_wm_imp1d", (64, 16, 20))] +
+                                    [("halfchan_imp1d", ng) for ng in HZ_GRIDS])
 def test_z_implicit_steps_with_a_changing_time_step(name, ng):
     """The z-only Helmholtz sweeps keep the coefficient tables of the (component, alpha) pairs they have seen (four per component; three alphas per step while
     dt stays): seven steps with five different time steps -- hits, misses and evictions -- against the oracle, which scales a, b, c anew for every sweep
@@ -173,6 +180,36 @@ def test_z_implicit_steps_with_a_changing_time_step(name, ng):
     for a, b, nm in ((gu, u, "u"), (gv, v, "v"), (gw, w, "w")):
         assert relerr(a, b) < 1e-9, nm
     assert relerr(gvis, visct) < 1e-7
+    h.close()
+
+
+@pytest.mark.parametrize("alpha", [-1e-5, -1e-2])
+@pytest.mark.parametrize("ivel", [1, 2, 3])
+@pytest.mark.parametrize("ng", HZ_GRIDS)
+def test_helmholtz_z_forms_against_the_oracle(ng, ivel, alpha):
+    """cales_helmholtz_z in every form the z-only sweeps take (the in-LDS tile with 2, 4, 8 planes per lane; the shared-pivot column kernel where w's n3 planes
+    do not fit its tile) against the oracle's updt_rhs_b_velz + solver_gaussel_z on the unknown planes, 1e-12 of the field maximum (the bar of the golden
+    stage test of this operator; on the CPU the oracle and a LAPACK banded solve of these systems differ by 4.2e-15 at most). Then the table cache of the
+    sweeps: the same alpha again (a hit), five other alphas (four slots per component: an eviction) and the first once more -- bit-identical each time."""
+    g, case = load_golden("halfchan_imp1d"); case.ng[:] = ng
+    o = Oracle(case, nthreads=8); h = _hot(case)
+    k = "uvw"[ivel - 1]
+    nz = ng[2] - (1 if ivel == 3 and case.cbcvel[1, 2, 2] == "D" else 0)
+    rng = np.random.RandomState(100 * ivel + ng[2])
+    q0 = o.zeros(); q0[1:-1, 1:-1, 1:-1] = rng.rand(*ng) - 0.5
+    ref = q0.copy(order="F"); o.updt_rhs_b_velz(ivel, alpha, ref); o.solver_gaussel_z(ivel, alpha, ref)
+
+    def sweep(al):
+        h.set(k, q0); h.helmholtz_z(ivel, al)
+        return h.get(k)
+    first = sweep(alpha)
+    err = relerr(first[1:-1, 1:-1, 1:nz + 1], ref[1:-1, 1:-1, 1:nz + 1])
+    print(ng, ivel, alpha, "relerr", err)
+    assert err < 1e-12, (ng, ivel, alpha, err)
+    assert np.array_equal(sweep(alpha), first), "table hit"
+    for m in (2., 3., 5., 7., 11.):
+        sweep(m * alpha)
+    assert np.array_equal(sweep(alpha), first), "after an eviction"
     h.close()
 
 
