@@ -22,6 +22,13 @@ np_real = np.float32 if SINGLE else np.float64
 LIB_PATH = os.environ.get("CALES_LIB", os.path.join(_HERE, "libcales_hip_sp.so" if SINGLE else "libcales_hip.so"))   # CALES_LIB: tuning builds only
 
 SGS = {"none": 0, "smag": 1, "dsmag": 2}
+SGS_DSMAG_FILTER2D = 3      # CALES_SGS_DSMAG_FILTER2D of include/cales.h: 'dsmag' of a -D_FILTER_2D build of the reference
+
+
+def filter2d_env() -> bool:
+    """CALES_FILTER_2D, the run-time form of the reference's -D_FILTER_2D: set to anything but the empty string or 0."""
+    return os.environ.get("CALES_FILTER_2D", "0") not in ("", "0")
+
 FIELDS = dict(u=0, v=1, w=2, p=3, pp=4, visct=5, dudt=6, dvdt=7, dwdt=8, dudto=9, dvdto=10, dwdto=11,
               dudtd=12, dvdtd=13, dwdtd=14)
 
@@ -67,6 +74,9 @@ def make_case(case, nranks: int = 1, rank: int = 0) -> CalesCase:
     if case.sgstype not in SGS:
         raise ValueError("ERROR: unknown SGS model" if case.sgstype != "amd" else "ERROR: AMD model not yet implemented")
     p.sgstype = SGS[case.sgstype]
+    f2d = getattr(case, "filter2d", None)
+    if case.sgstype == "dsmag" and (filter2d_env() if f2d is None else f2d):      # (the reference ignores the flag for 'none' and 'smag')
+        p.sgstype = SGS_DSMAG_FILTER2D
     p.lwm[:] = [int(x) for x in case.lwm.ravel(order="F")]
     p.hwm = float(case.hwm)
     p.impdiff = int(case.impdiff)

@@ -168,6 +168,8 @@ int cales_create(const cales_case *cs, void *stream, cales_ctx **out) {
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) { g_create_err = "no HIP device: the CaLES hot path has no CPU fallback"; return 3; }
   cales_ctx *c = new cales_ctx();
   c->C = *cs;
+  // 'dsmag' of a -D_FILTER_2D build: normalised once -- the model is 'dsmag' everywhere, the plane filter is a property of its path (SgsPath)
+  if (cs->sgstype == CALES_SGS_DSMAG_FILTER2D) { c->C.sgstype = CALES_SGS_DSMAG; c->sgs.filter2d = true; }
   c->fl.read_env();      // the CALES_* switches are fixed for the life of the context
   // zero all device pointers
   for (auto &p : c->f) p = nullptr;
@@ -256,14 +258,14 @@ int cales_create(const cales_case *cs, void *stream, cales_ctx **out) {
   c->res = c->d_red;
   if (hipHostMalloc((void **)&c->h_red, 64 * sizeof(real)) != hipSuccess) { c->err = "hipHostMalloc failed"; return fail(11); }
   // sgs scratch (sgs.f90:70-83,154-171)
-  if (cs->sgstype >= 1) {
+  if (c->C.sgstype >= 1) {
     if (field_alloc(c, &c->s0)) return fail(12);
-    const int nw = cs->sgstype == 1 ? 3 : 6;
+    const int nw = c->C.sgstype == 1 ? 3 : 6;
     for (int m = 0; m < nw; ++m) if (field_alloc(c, &c->wk[m])) return fail(12);
   }
-  if (cs->sgstype == 2) {
+  if (c->C.sgstype == 2) {
     if (field_alloc(c, &c->uc) || field_alloc(c, &c->vc) || field_alloc(c, &c->wc) || field_alloc(c, &c->uf) ||
-        field_alloc(c, &c->vf) || field_alloc(c, &c->wf) || field_alloc(c, &c->alph2) || dev_alloc(c, &c->d_p1d, 2 * (size_t)n3 + 2))
+        field_alloc(c, &c->vf) || field_alloc(c, &c->wf) || (!c->sgs.filter2d && field_alloc(c, &c->alph2)) || dev_alloc(c, &c->d_p1d, 2 * (size_t)n3 + 2))
       return fail(13);
     if (c->sgs.pair) {      // |S|Sij as three fields of pairs between K_AC and the fused last pass: the twelve scalar scratch fields of the other forms are not needed
       for (int m = 0; m < 3; ++m) { real *b = nullptr; if (dev_alloc(c, &b, 2 * c->ntot + 2 * LINE_REALS)) return fail(13); c->ss2[m] = b + 2 * c->field_ofs; }

@@ -283,7 +283,7 @@ int hs_check_case(const cales_case *cs, std::string &msg) {
       if (cs->lwm[5] != 0 && !per_z) ok = ok && h > cs->l[2] - zc[n3] && h < cs->l[2] - zc[1];
       if (!ok) { msg = "invalid wall model height (sanity.f90:224-231)"; return 1; }
     } }
-  if (cs->sgstype < 0 || cs->sgstype > 2) { msg = "unknown SGS model"; return 1; }
+  if (cs->sgstype < 0 || cs->sgstype > CALES_SGS_DSMAG_FILTER2D) { msg = "unknown SGS model"; return 1; }
   // (sanity.f90:98-111 refuses static Smagorinsky with more than two subdomains between two opposite walls because every rank measures the
   // wall distance with its local indices and knows only its own walls' shear. Here distances use global rows and the shear planes of the
   // two y walls are handed to every slab, k_sgs.hip wall_shear_y_planes: any number of y slabs gives the one-rank result.)

@@ -196,6 +196,26 @@ __global__ __launch_bounds__(BX *BY) void k_filter3d(Geom g, const real *__restr
            1. * (Q(-1, -1, -1) + Q(1, -1, -1) + Q(-1, 1, -1) + Q(1, 1, -1) + Q(-1, -1, 1) + Q(1, -1, 1) + Q(-1, 1, 1) + Q(1, 1, 1))) / 64.;
 #undef Q
 }
+// filter2d (sgs.f90:839-847, the -D_FILTER_2D build): 9-point top-hat in the x-y plane, weights 4/2/1 over 16, the reference's expression order
+__global__ __launch_bounds__(BX *BY) void k_filter2d(Geom g, const real *__restrict__ p, real *__restrict__ pf) {
+  int bx_, by_, bz_; stencil_block(bx_, by_, bz_);
+  const int i = bx_ * BX + threadIdx.x + 1, j = by_ * BY + threadIdx.y + 1, k = bz_ + 1;
+  if (i > g.n1 || j > g.n2) return;
+  const size_t c = g.ix(i, j, k);
+  const long sj = g.s1;
+#define Q(di, dj) p[c + (di) + (dj)*sj]
+  pf[c] = (4. * (Q(0, 0)) + 2. * (Q(-1, 0) + Q(0, -1) + Q(1, 0) + Q(0, 1)) + 1. * (Q(-1, -1) + Q(1, -1) + Q(-1, 1) + Q(1, 1))) / 16.;
+#undef Q
+}
+// k_mij with one filter ratio for all cells (alph2 = 2.52 of the -D_FILTER_2D build, sgs.f90:817-821): no field to read
+__global__ __launch_bounds__(BX *BY) void k_mij_a2(Geom g, P6 mij, real a, const real *__restrict__ s0, CP6 sij) {
+  const int i = blockIdx.x * BX + threadIdx.x + 1, j = blockIdx.y * BY + threadIdx.y + 1, k = blockIdx.z + 1;   // sgs.f90:262-272
+  if (i > g.n1 || j > g.n2) return;
+  const size_t c = g.ix(i, j, k);
+  const real s = s0[c];
+#pragma unroll
+  for (int m = 0; m < 6; ++m) mij.p[m][c] = 2. * (mij.p[m][c] - a * s * sij.p[m][c]);
+}
 __global__ __launch_bounds__(BX *BY) void k_mij(Geom g, P6 mij, const real *__restrict__ alph2, const real *__restrict__ s0, CP6 sij) {
   const int i = blockIdx.x * BX + threadIdx.x + 1, j = blockIdx.y * BY + threadIdx.y + 1, k = blockIdx.z + 1;   // sgs.f90:262-272
   if (i > g.n1 || j > g.n2) return;
@@ -560,6 +580,157 @@ __global__ __launch_bounds__(64 * (LMF_TY(YW) + 2)) void k_lmf_tile(Geom g, LmfA
   }
 }
 
+// The last pass under the reference's -D_FILTER_2D (SgsPath::filter2d), for the channel class: x periodic, nothing at the y faces, z between two walls or
+// periodic -- k_lmf_tile<OFF, 0, 1> with everything the plane filter makes unnecessary taken out, as a kernel of its own so that k_lmf_tile stays as it is.
+// Every test filter is (1,2,1)^2/16 of plane k alone (filter2d, sgs.f90:839-847): no z combination and no wall rule for any quantity, so no LO / HI forms of a
+// plane, no rolling x/y-combined planes of |S|Sij (twelve registers: the rows of plane k only, loaded one plane ahead and folded behind the barrier), one
+// plane of the cell-centred velocity instead of three, alph2 = 2.52 in every cell (sgs.f90:817-821). With nothing extrapolated the identity of FUC, F(u_c) =
+// (u_f(i) + u_f(i-1))/2, holds in every plane for all three components: w_f(0) = F(w(0)) next to a wall (both zero) and across a periodic end (both the
+// copy). What stays is the ring of three planes of the filtered velocity for its strain rate, with the ghost planes of wall-model z faces extrapolated
+// (extrapolate(...,lwm) after bounduvw, sgs.f90:256-260), the plane sums and the rules of k_lmf_tile: unconditional global accesses in the plane loop,
+// counted waits, block sums collected in LDS.
+template <typename OFF>
+__global__ __launch_bounds__(64 * (TYLF + 2)) void k_lmf_plane_tile(Geom g, LmfArgs B) {
+  const LijMijArgs &A = B.L;
+  constexpr int TL = TYLF;
+  __shared__ real sh[2][6][TL + 2][64];      // the six products u_c u_c combined along x, double-buffered (one barrier per plane)
+  __shared__ real ring[4][3][TL + 2][64];
+  __shared__ real psum[2][2][TL][16];
+  __shared__ real bsum[2][LMF_KMAX];
+  const int tx = threadIdx.x, ty = threadIdx.y;
+  int bx = blockIdx.x, by = blockIdx.y, bz = blockIdx.z;
+  if (B.bm.gx && !band_block(B.bm, bx, by, bz)) return;
+  by += B.by0;
+  const int i = bx * 62 + tx, j = by * TL + ty;
+  const int kbeg = bz * A.kchunk + 1, kend = min(kbeg + A.kchunk - 1, g.n3);
+  const bool outok = tx >= 1 && tx <= 62 && ty >= 1 && ty <= TL && i <= g.n1 && j <= g.n2;
+  const int iw = A.perx ? (i == 0 ? g.n1 : (i == g.n1 + 1 ? 1 : i)) : i;
+  const int ic = min(iw, g.n1 + 1), jc = min(j, g.n2 + 1);      // clamped: lanes / rows beyond the field read its last ghost column / row
+  const OFF c0 = (OFF)g.ix(ic, jc, 0) * RSZ, sk = (OFF)g.s12 * RSZ, sj = (OFF)g.s1 * RSZ;      // byte offsets
+  const int jo = max(by * TL + 1, min(min(j, by * TL + TL), g.n2));      // the row whose |S|Sij this thread combines with the two beside it (k_lmf_tile)
+  const OFF c0s = (OFF)g.ix(ic, jo, 0) * RSZ;
+  // cell-centred velocity from u, v, w (k_lmf_tile, UCF): v(j) and v(j-1) of this row, or -- ghost row 0 -- the stored v_c of that row with weight 1
+  const real *pva = jc == 0 ? A.vcg : A.uc[1];
+  const OFF ovb = jc > 0 ? sj : 0;
+  const real cva = jc == 0 ? 1. : .5, cvb = jc == 0 ? 0. : .5;
+  const OFF c0m = (OFF)g.ix((A.xwrap && ic == 1) ? g.n1 : max(ic - 1, 0), jc, 0) * RSZ;      // u(i-1): the wrapped column left of the first cell of a row
+  real wprev = ldb(A.uc[2], c0 + (OFF)(kbeg - 1) * sk);      // w of the plane below (plane 0: the wall's value or the periodic copy)
+  auto ucload = [&](int kk, real *o) {      // cell-centred velocity of plane kk (wprev = w of plane kk - 1 on entry, of plane kk on exit)
+    const OFF a = c0 + (OFF)kk * sk;
+    o[0] = .5 * (ldb(A.uc[0], a) + ldb(A.uc[0], c0m + (OFF)kk * sk));
+    o[1] = cva * ldb(pva, a) + cvb * ldb(A.uc[1], a - ovb);
+    const real wn = ldb(A.uc[2], a); o[2] = .5 * (wn + wprev); wprev = wn;
+  };
+  real sc[3], sp[3], sn[3], fn[3];
+  ucload(kbeg, sc); ucload(kbeg + 1, sp);
+#pragma unroll
+  for (int q = 0; q < 3; ++q) {
+    ring[(kbeg - 1) & 3][q][ty][tx] = ldb(A.uf[q], c0 + (OFF)(kbeg - 1) * sk);
+    ring[kbeg & 3][q][ty][tx] = ldb(A.uf[q], c0 + (OFF)kbeg * sk);
+    fn[q] = ldb(A.uf[q], c0 + (OFF)(kbeg + 1) * sk);
+    if (A.wmlo && kbeg == 1 && q < 2) ring[0][q][ty][tx] = (1. + A.flo) * ring[1][q][ty][tx] - A.flo * fn[q];
+  }
+  // |S|Sij of one plane: three rows in, combined along y and x (lanes beside by DPP)
+  auto ssload = [&](int kk, real (*raw)[3]) {
+#pragma unroll
+    for (int q = 0; q < 6; ++q) {
+      const OFF o = c0s + (OFF)kk * sk;
+      raw[q][0] = ldb(B.ss[q], o - sj); raw[q][1] = ldb(B.ss[q], o); raw[q][2] = ldb(B.ss[q], o + sj);
+    }
+  };
+  real rw[6][3];
+  ssload(kbeg, rw);
+  const int blk = by * B.gx + bx;
+  auto fold = [&](int k, int b) {      // block sums of plane k by ONE whole wave, fixed order (k_lmf_tile)
+    const real *p0 = &psum[b][0][0][0], *p1 = &psum[b][1][0][0];
+    static_assert(TL * 16 >= 128 && TL * 16 <= 192, "two or three partials per lane");
+    constexpr int NP3 = TL * 16 - 128;      // partials beyond the first 128
+    const int t3 = min(tx, NP3 > 0 ? NP3 - 1 : 0) + 128; const real w3 = (NP3 > 0 && tx < NP3) ? 1. : 0.;
+    const real a = wave_sum_lane63(NP3 > 0 ? p0[tx] + p0[tx + 64] + w3 * p0[t3] : p0[tx] + p0[tx + 64]),
+               bs = wave_sum_lane63(NP3 > 0 ? p1[tx] + p1[tx + 64] + w3 * p1[t3] : p1[tx] + p1[tx + 64]);
+    if (tx == 63) { bsum[0][k - kbeg] = a; bsum[1][k - kbeg] = bs; }
+  };
+  real zcm = ldc(A.dzci, kbeg - 1), zcc = ldc(A.dzci, kbeg), zfc = ldc(A.dzfi, kbeg);
+  auto plane = [&](const int k, auto hi_c) {
+    constexpr bool HI = decltype(hi_c)::value;      // the plane below a wall-model top face: its ghost plane is extrapolated into the ring
+    const int km = (k - 1) & 3, kc = k & 3, kp = (k + 1) & 3, buf = k & 1;
+    const OFF idx = c0 + (OFF)min(k + 2, g.n3 + 1) * sk;      // plane k+2 (clamped behind the last ghost plane: loaded again, never used)
+    const real zcn = ldc(A.dzci, k + 1), zfn = ldc(A.dzfi, k + 1);
+#pragma unroll
+    for (int q = 0; q < 3; ++q)
+      ring[kp][q][ty][tx] = (HI && A.wmhi && q < 2) ? (1. + A.fhi) * ring[kc][q][ty][tx] - A.fhi * ring[km][q][ty][tx] : fn[q];
+    ucload(min(k + 2, g.n3 + 1), sn);
+#pragma unroll
+    for (int q = 0; q < 3; ++q) fn[q] = ldb(A.uf[q], idx);
+    const real pr[6] = {sc[0] * sc[0], sc[1] * sc[1], sc[2] * sc[2], sc[0] * sc[1], sc[0] * sc[2], sc[1] * sc[2]};      // sgs.f90:283-295
+    real r[6];
+#pragma unroll
+    for (int q = 0; q < 6; ++q) { r[q] = lane_prev(pr[q]) + 2. * pr[q] + lane_next(pr[q]); sh[buf][q][ty][tx] = r[q]; }
+    __syncthreads();
+    if (k > kbeg && ty == 0) fold(k - 1, buf ^ 1);
+    real xc[6];      // filter(|S|Sij) * 16 of plane k: its 18 loads were issued at the end of the previous plane
+#pragma unroll
+    for (int q = 0; q < 6; ++q) { const real Y = rw[q][0] + 2. * rw[q][1] + rw[q][2]; xc[q] = lane_prev(Y) + 2. * Y + lane_next(Y); }
+    real lm = 0., mm = 0.;
+    if (outok) {
+      real L[6];
+#pragma unroll
+      for (int q = 0; q < 6; ++q) L[q] = (sh[buf][q][ty - 1][tx] + 2. * r[q] + sh[buf][q][ty + 1][tx]) / 16.;
+      const real F0 = .5 * (ring[kc][0][ty][tx] + ring[kc][0][ty][tx - 1]), F1 = .5 * (ring[kc][1][ty][tx] + ring[kc][1][ty - 1][tx]),
+                   F2 = .5 * (ring[kc][2][ty][tx] + ring[km][2][ty][tx]);
+      const real l0 = L[0] - F0 * F0, l1 = L[1] - F1 * F1, l2 = L[2] - F2 * F2, l3 = L[3] - F0 * F1, l4 = L[4] - F0 * F2, l5 = L[5] - F1 * F2;
+      // strain rate of the test-filtered velocity (sgs.f90:571-630), the differences telescoped as in k_lmf_tile
+#define RU(dk, dj, di) ring[dk][0][ty + (dj)][tx + (di)]
+#define RV(dk, dj, di) ring[dk][1][ty + (dj)][tx + (di)]
+#define RW(dk, dj, di) ring[dk][2][ty + (dj)][tx + (di)]
+      const real dxi = A.dxi, dyi = A.dyi, zc = zcc, zm = zcm;
+      real sij[6];
+      { const real u_ccc = RU(kc, 0, 0), u_mcc = RU(kc, 0, -1), v_ccc = RV(kc, 0, 0), v_cmc = RV(kc, -1, 0), w_ccc = RW(kc, 0, 0), w_ccm = RW(km, 0, 0);
+        sij[0] = (u_ccc - u_mcc) * dxi; sij[1] = (v_ccc - v_cmc) * dyi; sij[2] = (w_ccc - w_ccm) * zfc;
+        const real du = (RU(kc, 1, 0) - RU(kc, -1, 0)) + (RU(kc, 1, -1) - RU(kc, -1, -1));
+        const real dv = (RV(kc, 0, 1) - RV(kc, 0, -1)) + (RV(kc, -1, 1) - RV(kc, -1, -1));
+        sij[3] = .125 * (du * dyi + dv * dxi);
+        const real up = (RU(kp, 0, 0) - u_ccc) + (RU(kp, 0, -1) - u_mcc), um = (u_ccc - RU(km, 0, 0)) + (u_mcc - RU(km, 0, -1));
+        const real dw = (RW(kc, 0, 1) - RW(kc, 0, -1)) + (RW(km, 0, 1) - RW(km, 0, -1));
+        sij[4] = .125 * (up * zc + um * zm + dw * dxi);
+        const real vp = (RV(kp, 0, 0) - v_ccc) + (RV(kp, -1, 0) - v_cmc), vm = (v_ccc - RV(km, 0, 0)) + (v_cmc - RV(km, -1, 0));
+        const real dw2 = (RW(kc, 1, 0) - RW(kc, -1, 0)) + (RW(km, 1, 0) - RW(km, -1, 0));
+        sij[5] = .125 * (vp * zc + vm * zm + dw2 * dyi); }
+#undef RU
+#undef RV
+#undef RW
+      const real s0 = sqrt(2. * (sij[0] * sij[0] + sij[1] * sij[1] + sij[2] * sij[2] + 2. * (sij[3] * sij[3] + sij[4] * sij[4] + sij[5] * sij[5])));
+      const real a2s0 = 2.52 * s0;      // alph2 of the -D_FILTER_2D build (sgs.f90:817-821)
+      real m[6];
+#pragma unroll
+      for (int q = 0; q < 6; ++q) m[q] = 2. * (xc[q] * (1. / 16.) - a2s0 * sij[q]);      // Mij, sgs.f90:261-272
+      lm = m[0] * l0 + m[1] * l1 + m[2] * l2 + (m[3] * l3 + m[4] * l4 + m[5] * l5) * 2.;       // sgs.f90:344-349
+      mm = m[0] * m[0] + m[1] * m[1] + m[2] * m[2] + (m[3] * m[3] + m[4] * m[4] + m[5] * m[5]) * 2.;       // sgs.f90:350-355
+    }
+    ssload(min(k + 1, g.n3 + 1), rw);
+    lm += dpp_f64<0x111>(lm); lm += dpp_f64<0x112>(lm); mm += dpp_f64<0x111>(mm); mm += dpp_f64<0x112>(mm);      // row_shr 1, 2: lanes 3, 7, 11, ... hold four lanes' sum
+    if ((tx & 3) == 3 && ty >= 1 && ty <= TL) { psum[buf][0][ty - 1][tx >> 2] = lm; psum[buf][1][ty - 1][tx >> 2] = mm; }
+#pragma unroll
+    for (int q = 0; q < 3; ++q) { sc[q] = sp[q]; sp[q] = sn[q]; }
+    zcm = zcc; zcc = zcn; zfc = zfn;
+  };
+  {
+    const std::true_type T; const std::false_type F_;
+    int k = kbeg;
+    const int klast = (A.zhi && kend == g.n3) ? kend - 1 : kend;
+    for (; k <= klast; ++k) plane(k, F_);
+    if (k <= kend) plane(k, T);
+  }
+  __syncthreads();
+  if (ty == 0 && kend >= kbeg) fold(kend, kend & 1);
+  __syncthreads();
+  // the chunk's block sums leave in one go
+  for (int q = ty * 64 + tx; q < 2 * (kend - kbeg + 1); q += 64 * (TL + 2)) {
+    const int w = q & 1, kk = q >> 1;
+    A.part[(size_t)(w * g.n3 + kbeg + kk - 1) * A.nblk + blk] = bsum[w][kk];
+  }
+}
+
 // K_A + K_C in one pass over u,v,w: strain rate (sgs.f90:571-630) stored as |S| and |S|Sij, cell-centred velocity (sgs.f90:860-869) and the
 // test-filtered velocity (sgs.f90:632-679 with the wall rule), all from an LDS ring of three raw planes.
 #ifndef TYS
@@ -617,8 +788,13 @@ __global__ __launch_bounds__(256) void k_wall_shear_y(Geom g, const real *__rest
     twy[(size_t)(g.n3 + 2 + k) * g.s1 + i] = sqrt(0.5 * visc * (sqrt(t1 * t1 + t2 * t2) * dyi));
   }
 }
-template <typename OFF, int TY, int YW, int PAIR = 0>      // YW = 1: walls or wall-model faces in y (ducts); the channel instantiations carry none of that logic
+// F2D = 1 (the reference's -D_FILTER_2D): the filtered velocity is the in-plane (1,2,1)^2/16 of plane k of the raw u, v, w (filter2d, sgs.f90:244-246,839-847):
+// no z combination, no wall rule; the strain rate and the wall-model ghost planes of the ring are what they were
+// (PAIR and F2D: the values 1 and 2 of one template parameter, as in k_lmf_tile.)
+template <typename OFF, int TY, int YW, int SSF = 0>      // YW = 1: walls or wall-model faces in y (ducts); the channel instantiations carry none of that logic
 __global__ __launch_bounds__(64 * (TY + 2)) void k_strain_tile(Geom g, StrainTileArgs A) {
+  constexpr int PAIR = SSF == 1, F2D = SSF == 2;
+  static_assert(!F2D || (!YW && !PAIR), "the plane filter is built for the channel class");
   // (one barrier per plane with four ring slots and double-buffered sums, as in k_lij_mij_tile, measured 13 % slower here)
   __shared__ real ring[3][3][TY + 2][66];      // rows: x-halo cell, 64 own cells, x-halo cell
   __shared__ real shs[3][TY + 2][64];
@@ -681,9 +857,9 @@ __global__ __launch_bounds__(64 * (TY + 2)) void k_strain_tile(Geom g, StrainTil
         const real vp = (hi && q < 2) ? 2. * qc - qm : qp;
         return vm + 2. * qc + vp;
       };
-      const real G = zcomb(tx + 1);
+      const real G = F2D ? ring[kc][q][ty][tx + 1] : zcomb(tx + 1);
       real pv = lane_prev(G), nx = lane_next(G);
-      if (edge) { const real Gh = zcomb(hx); if (tx == 0) pv = Gh; else nx = Gh; }
+      if (edge) { const real Gh = F2D ? ring[kc][q][ty][hx] : zcomb(hx); if (tx == 0) pv = Gh; else nx = Gh; }
       r[q] = pv + 2. * G + nx;
       shs[q][ty][tx] = r[q];
     }
@@ -733,7 +909,7 @@ __global__ __launch_bounds__(64 * (TY + 2)) void k_strain_tile(Geom g, StrainTil
       for (int q = 0; q < 3; ++q) {
         const real dn = shs[q][ty - 1][tx], up = shs[q][ty + 1][tx];
         const real a = (ylo && q != 1) ? 2. * r[q] - up : dn, b = (yhi && q != 1) ? 2. * r[q] - dn : up;
-        stb(A.uf[q], idx, (a + 2. * r[q] + b) / 64.);
+        stb(A.uf[q], idx, (a + 2. * r[q] + b) / (F2D ? 16. : 64.));
       }
     }
     const int t = km; km = kc; kc = kp; kp = t;
@@ -1164,7 +1340,14 @@ void sgs_setup(cales_ctx *c) {
   for (int q = 2; q < 4; ++q) yw = yw || c->is_wall[q] != 0. || c->C.lwm[q] != 0;
   if (c->C.sgstype == 1) P.form = !xw && n[2] >= 3 && n[1] >= 2 && !fl.smag_reference_sequence ? SgsForm::smag_rows : SgsForm::smag_reference;
   // (ducts: the fused last pass knows the wall rule along y from three rows on)
-  else P.form = !xw && !(yw && n[1] < 3) && n[2] >= 3 && !fl.dsmag_reference_sequence ? SgsForm::dsmag_tiles : SgsForm::dsmag_reference;
+  else if (!P.filter2d) P.form = !xw && !(yw && n[1] < 3) && n[2] >= 3 && !fl.dsmag_reference_sequence ? SgsForm::dsmag_tiles : SgsForm::dsmag_reference;
+  else {
+    // the plane filter (-D_FILTER_2D): tiles for the channel class -- x periodic (the kernels wrap around), nothing at the y faces, z between two walls (no-slip
+    // or wall-modelled) or periodic: where the last pass forms the cell-centred velocity itself (ucf below); every other case takes the sequence
+    const bool perx = CBP(c, 0, 1) == 'P' && CBP(c, 1, 1) == 'P' && !fl.dsmag_xghosts, perz = CBP(c, 0, 3) == 'P' && CBP(c, 1, 3) == 'P';
+    const bool zwalls = c->is_wall[4] != 0. && c->is_wall[5] != 0.;
+    P.form = perx && !xw && !yw && (zwalls || perz) && n[2] >= 3 && !fl.dsmag_reference_sequence ? SgsForm::dsmag_tiles : SgsForm::dsmag_reference;
+  }
   P.wraps_x = P.form == SgsForm::smag_rows || (P.form == SgsForm::dsmag_tiles && !fl.dsmag_xghosts);
   if (P.form != SgsForm::smag_rows && P.form != SgsForm::dsmag_tiles) return;
   const bool smag = P.form == SgsForm::smag_rows;
@@ -1188,12 +1371,13 @@ void sgs_setup(cales_ctx *c) {
   P.ucf = P.perx && ((P.zlo && P.zhi) || P.perz);
   // |S|Sij as three fields of pairs between K_AC and the fused last pass: ucf, and y periodic (the one-launch ghost-cell kernel takes a pair field as a
   // field of twice the width), 32-bit byte offsets still enough for a field twice as long
-  P.pair = P.ucf && CBP(c, 0, 2) == 'P' && CBP(c, 1, 2) == 'P' && !fl.wide_offsets && !fl.unmerged_bc && (2 * c->ntot + 64) * sizeof(real) < (1ull << 32);
+  P.pair = !P.filter2d && P.ucf && CBP(c, 0, 2) == 'P' && CBP(c, 1, 2) == 'P' && !fl.wide_offsets && !fl.unmerged_bc && (2 * c->ntot + 64) * sizeof(real) < (1ull << 32);
   P.lmf_ty = P.yw ? TYL : TYLF;
   P.strain = P.pair ? StrainKernel::pair : P.yw ? (P.small ? StrainKernel::yw32 : StrainKernel::yw64) : (P.small ? StrainKernel::plain32 : StrainKernel::plain64);
   static const LmfKernel lmf[2][2][2] = {{{LmfKernel::plain64, LmfKernel::plain32}, {LmfKernel::ucf64, LmfKernel::ucf32}},
                                          {{LmfKernel::yw64, LmfKernel::yw32}, {LmfKernel::yw_ucf64, LmfKernel::yw_ucf32}}};      // [yw][ucf][small]
   P.lmf = P.pair ? LmfKernel::pair : lmf[P.yw][P.ucf][P.small];
+  if (P.filter2d) { P.strain = P.small ? StrainKernel::f2d32 : StrainKernel::f2d64; P.lmf = P.small ? LmfKernel::f2d32 : LmfKernel::f2d64; }      // (ucf, no yw: the form's condition)
 }
 // sgs_setup_launches: the launch geometry of the tile passes (after cales_create has read the CU count: balanced_kchunk)
 int sgs_setup_launches(cales_ctx *c) {
@@ -1256,6 +1440,8 @@ static int dsmag_fast(cales_ctx *c, const SgsFold *fold, bool *visct_ghosts_done
     case StrainKernel::pair: LAUNCH(c, (k_strain_tile<unsigned, TYS, 0, 1>), t.grid, t.block, 0, c->stream, c->g, S); break;
     case StrainKernel::plain32: LAUNCH(c, (k_strain_tile<unsigned, TYS, 0>), t.grid, t.block, 0, c->stream, c->g, S); break;
     case StrainKernel::plain64: LAUNCH(c, (k_strain_tile<size_t, TYS, 0>), t.grid, t.block, 0, c->stream, c->g, S); break;
+    case StrainKernel::f2d32: LAUNCH(c, (k_strain_tile<unsigned, TYS, 0, 2>), t.grid, t.block, 0, c->stream, c->g, S); break;
+    case StrainKernel::f2d64: LAUNCH(c, (k_strain_tile<size_t, TYS, 0, 2>), t.grid, t.block, 0, c->stream, c->g, S); break;
     } }
   if (fold) {
     // the corrected velocity sits in the second buffers: swap (as the fused momentum pass does), give the normal component its two z faces -- the
@@ -1329,6 +1515,8 @@ static int dsmag_fast(cales_ctx *c, const SgsFold *fold, bool *visct_ghosts_done
       case LmfKernel::ucf64: LAUNCH(c, (k_lmf_tile<size_t, 0, 1>), s.grid, s.block, 0, c->stream, c->g, B); break;
       case LmfKernel::plain32: LAUNCH(c, (k_lmf_tile<unsigned, 0, 0>), s.grid, s.block, 0, c->stream, c->g, B); break;
       case LmfKernel::plain64: LAUNCH(c, (k_lmf_tile<size_t, 0, 0>), s.grid, s.block, 0, c->stream, c->g, B); break;
+      case LmfKernel::f2d32: LAUNCH(c, (k_lmf_plane_tile<unsigned>), s.grid, s.block, 0, c->stream, c->g, B); break;
+      case LmfKernel::f2d64: LAUNCH(c, (k_lmf_plane_tile<size_t>), s.grid, s.block, 0, c->stream, c->g, B); break;
       }
     };
     if (overlap) {
@@ -1416,6 +1604,7 @@ static int smag_fast(cales_ctx *c) {
 // the form of cmpt_sgs this context takes (cales_describe_plan): the record op_cmpt_sgs launches
 const char *sgs_path_name(const cales_ctx *c) {
   static const char *names[] = {"none", "smag_rows", "smag_reference_sequence", "dsmag_tiles", "dsmag_reference_sequence"};      // (SgsForm order)
+  if (c->sgs.filter2d) return c->sgs.form == SgsForm::dsmag_tiles ? "dsmag_tiles(filter2d)" : "dsmag_reference_sequence(filter2d)";
   return c->sgs.pair ? "dsmag_tiles(pair_fields)" : names[(int)c->sgs.form];
 }
 int op_cmpt_sgs(cales_ctx *c, const SgsFold *fold, bool *visct_ghosts_done) {
@@ -1430,7 +1619,7 @@ int op_cmpt_sgs(cales_ctx *c, const SgsFold *fold, bool *visct_ghosts_done) {
   dim3 b(BX, BY, 1), gr = grid3(n[0], n[1], n[2], b);
   if (c->sgs_first) {
     c->sgs_first = false;
-    if (c->C.sgstype == 2)
+    if (c->C.sgstype == 2 && !c->sgs.filter2d)      // (the plane filter: 2.52 everywhere, sgs.f90:817-821 -- no field)
       LAUNCH(c, k_alph2, grid3(n[0] + 2, n[1] + 2, n[2] + 2, dim3(64, 4, 1)), dim3(64, 4, 1), 0, c->stream, c->g, c->is_wall[0], c->is_wall[1],
                          c->is_wall[2], c->is_wall[3], c->is_wall[4], c->is_wall[5], c->alph2);
   }
@@ -1474,30 +1663,39 @@ int op_cmpt_sgs(cales_ctx *c, const SgsFold *fold, bool *visct_ghosts_done) {
   for (int m = 0; m < 6; ++m) { csij.p[m] = sij[m]; pwk.p[m] = wk[m]; pmij.p[m] = mij[m]; cmij.p[m] = mij[m]; }
   LAUNCH(c, k_s0sij, lin_grid(nt), dim3(256), 0, c->stream, nt, c->s0, csij, pwk);
   const int if0[6] = {0, 0, 0, 0, 0, 0};
-  if (int e = extrapolate(c, 6, wk, if0, 1)) return e;
-  for (int m = 0; m < 6; ++m) LAUNCH(c, k_filter3d, gr, b, 0, c->stream, c->g, wk[m], mij[m]);
-  LAUNCH(c, k_copy3, lin_grid(nt), dim3(256), 0, c->stream, nt, f[CALES_U], f[CALES_V], f[CALES_W], wk[0], wk[1], wk[2]);
-  if (int e = extrapolate(c, 3, wk, if123, 1)) return e;
-  LAUNCH(c, k_filter3d, gr, b, 0, c->stream, c->g, wk[0], c->uf);
-  LAUNCH(c, k_filter3d, gr, b, 0, c->stream, c->g, wk[1], c->vf);
-  LAUNCH(c, k_filter3d, gr, b, 0, c->stream, c->g, wk[2], c->wf);
+  // the reference's -D_FILTER_2D (sgs.f90:211-247,296-327): filter2d instead of filter3d, WITHOUT the extrapolate(...,cbc) calls in front of the filters, the
+  // first filtered velocity from u, v, w themselves, and one filter ratio; everything else of the sequence is shared
+  const bool f2d = c->sgs.filter2d;
+  auto filter = [&](const real *p, real *pf) {
+    if (f2d) LAUNCH(c, k_filter2d, gr, b, 0, c->stream, c->g, p, pf); else LAUNCH(c, k_filter3d, gr, b, 0, c->stream, c->g, p, pf);
+  };
+  if (!f2d) { if (int e = extrapolate(c, 6, wk, if0, 1)) return e; }
+  for (int m = 0; m < 6; ++m) filter(wk[m], mij[m]);
+  if (!f2d) {
+    LAUNCH(c, k_copy3, lin_grid(nt), dim3(256), 0, c->stream, nt, f[CALES_U], f[CALES_V], f[CALES_W], wk[0], wk[1], wk[2]);
+    if (int e = extrapolate(c, 3, wk, if123, 1)) return e;
+  }
+  filter(f2d ? f[CALES_U] : wk[0], c->uf);
+  filter(f2d ? f[CALES_V] : wk[1], c->vf);
+  filter(f2d ? f[CALES_W] : wk[2], c->wf);
   if (int e = op_bounduvw(c, c->bcuf, c->bcvf, c->bcwf, 0, 0, c->uf, c->vf, c->wf)) return e;
   real *ff[3] = {c->uf, c->vf, c->wf};
   if (int e = extrapolate(c, 3, ff, if123, 0)) return e;
   if (int e = strain_rate(c, c->uf, c->vf, c->wf, c->s0, sij)) return e;
-  LAUNCH(c, k_mij, gr, b, 0, c->stream, c->g, pmij, c->alph2, c->s0, csij);
+  if (f2d) LAUNCH(c, k_mij_a2, gr, b, 0, c->stream, c->g, pmij, (real)2.52, c->s0, csij);
+  else LAUNCH(c, k_mij, gr, b, 0, c->stream, c->g, pmij, c->alph2, c->s0, csij);
   LAUNCH(c, k_interp, gr, b, 0, c->stream, c->g, f[CALES_U], f[CALES_V], f[CALES_W], c->uc, c->vc, c->wc);
   if (int e = op_boundp(c, c->uc, 1)) return e;
   if (int e = op_boundp(c, c->vc, 1)) return e;
   if (int e = op_boundp(c, c->wc, 1)) return e;
   LAUNCH(c, k_uiuj, lin_grid(nt), dim3(256), 0, c->stream, nt, c->uc, c->vc, c->wc, pwk);
-  if (int e = extrapolate(c, 6, wk, if0, 1)) return e;
-  for (int m = 0; m < 6; ++m) LAUNCH(c, k_filter3d, gr, b, 0, c->stream, c->g, wk[m], lij[m]);
+  if (!f2d) { if (int e = extrapolate(c, 6, wk, if0, 1)) return e; }
+  for (int m = 0; m < 6; ++m) filter(wk[m], lij[m]);
   real *cc[3] = {c->uc, c->vc, c->wc};
-  if (int e = extrapolate(c, 3, cc, if0, 1)) return e;
-  LAUNCH(c, k_filter3d, gr, b, 0, c->stream, c->g, c->uc, c->uf);
-  LAUNCH(c, k_filter3d, gr, b, 0, c->stream, c->g, c->vc, c->vf);
-  LAUNCH(c, k_filter3d, gr, b, 0, c->stream, c->g, c->wc, c->wf);
+  if (!f2d) { if (int e = extrapolate(c, 3, cc, if0, 1)) return e; }
+  filter(c->uc, c->uf);
+  filter(c->vc, c->vf);
+  filter(c->wc, c->wf);
   CP6 clij; for (int m = 0; m < 6; ++m) clij.p[m] = lij[m];
   LAUNCH(c, k_contract, gr, b, 0, c->stream, c->g, cmij, clij, c->uf, c->vf, c->wf, wk[0], wk[1]);
   LAUNCH(c, k_plane_sum, dim3(n[2], 2), dim3(256), 0, c->stream, c->g, wk[0], wk[1], c->d_p1d);

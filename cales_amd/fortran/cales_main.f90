@@ -15,6 +15,8 @@
 !
 ! usage: cales [impdiff]      (impdiff = 0 explicit [default], 1 implicit in x,y,z, 2 z-implicit: the reference's build switches
 !                              _IMPDIFF/_IMPDIFF_1D are run-time here); reads ./input.nml
+! environment: CALES_FILTER_2D (set to anything but 0) = the reference's build switch _FILTER_2D: sgstype = 'dsmag' test-filters in the x-y planes
+!              only and uses alph2 = 2.52 everywhere (src/sgs.f90:236-247,316-327,817-821); no effect on 'none' and 'smag'
 program cales
   use, intrinsic :: iso_c_binding
   use, intrinsic :: iso_fortran_env, only: int64
@@ -56,6 +58,8 @@ program cales
   integer :: myid,nranks,n2l,jlo          ! rank, number of ranks, rows of the slab, global row of local row 1 minus 1
   logical :: is_done,kill,is_chan,is_duct
   character(len=512) :: iomsg,arg
+  character(len=16) :: f2d
+  integer :: f2dlen,f2dstat
   character(len=100) :: filename
   character(len=7) :: fldnum
   character(len=4) :: chkptnum
@@ -119,7 +123,10 @@ program cales
   select case(trim(sgstype))
   case('none');  cs%sgstype = 0
   case('smag');  cs%sgstype = 1
-  case('dsmag'); cs%sgstype = 2
+  case('dsmag')
+    cs%sgstype = 2
+    call get_environment_variable('CALES_FILTER_2D',f2d,f2dlen,f2dstat)           ! the run-time form of -D_FILTER_2D
+    if(f2dstat <= 0 .and. f2dlen > 0 .and. trim(f2d) /= '0') cs%sgstype = 3       ! CALES_SGS_DSMAG_FILTER2D (include/cales.h)
   case('amd')                                                                  ! src/sgs.f90:381-382
     if(myid == 0) print*, 'ERROR: AMD model not yet implemented'
     call die

@@ -13,7 +13,7 @@ from __future__ import annotations
 
 import dataclasses
 import re
-from typing import Any, Dict, List, Tuple
+from typing import Any, Dict, List, Optional, Tuple
 
 import numpy as np
 
@@ -160,6 +160,9 @@ class Case:
     hwm: float
     # build-time switches of the reference (configs/flags.mk.example:105-151) are run-time here
     impdiff: int = 0          # 0 explicit, 1 _IMPDIFF, 2 _IMPDIFF + _IMPDIFF_1D
+    # _FILTER_2D: 'dsmag' test-filters in the x-y planes only (sgs.f90:236-247,316-327,817-821); no effect on 'none' and 'smag'.
+    # None: taken from the environment variable CALES_FILTER_2D when the case goes to the library (capi.make_case)
+    filter2d: Optional[bool] = None
 
     @property
     def dl(self) -> np.ndarray:

@@ -39,11 +39,15 @@ typedef struct cales_case {
   char    cbcvel[18], cbcpre[6], cbcsgs[6];
   cales_real  bcvel[18], bcpre[6], bcsgs[6];
   cales_real  bforce[3]; int32_t is_forced[3]; cales_real velf[3];
-  int32_t sgstype;        /* 0 'none', 1 'smag', 2 'dsmag'  (src/sgs.f90:61-153) */
+  int32_t sgstype;        /* 0 'none', 1 'smag', 2 'dsmag', 3 'dsmag' of a -D_FILTER_2D build (src/sgs.f90:61-153; enum cales_sgstype below) */
   int32_t lwm[6]; cales_real hwm;
   int32_t impdiff;        /* 0 explicit; 2 = _IMPDIFF + _IMPDIFF_1D (z-implicit); 1 = _IMPDIFF (3-D implicit; periodic or no-slip wall pairs in x and y) */
   int32_t nranks, rank;   /* y-slab decomposition: rank owns rows rank*ng2/nranks+1 ... */
 } cales_case;
+
+/* cales_case.sgstype. CALES_SGS_DSMAG_FILTER2D is the reference's 'dsmag' built with -D_FILTER_2D: the test filter of the dynamic model acts in the
+ * x-y planes only (filter2d, src/sgs.f90:824-848) and alph2 = 2.52 everywhere (sgs.f90:817-821). The flag changes nothing for 'none' and 'smag'. */
+enum cales_sgstype { CALES_SGS_NONE = 0, CALES_SGS_SMAG = 1, CALES_SGS_DSMAG = 2, CALES_SGS_DSMAG_FILTER2D = 3 };
 
 typedef struct cales_ctx cales_ctx;
 

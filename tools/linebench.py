@@ -4,11 +4,13 @@
   python tools/linebench.py les/_manuscript_turbulent_channel:own turbulent_channel.nml:768x384x256:sgs=dsmag duct_wall_model_512.nml:640x320x320:impdiff=2
 
 An entry is CASE:GRID[:key=value,...]. CASE ending in .nml is a file of cales_amd/cases, anything else a key of tests/golden/examples.json (the
-namelists of the examples the reference ships, kept as data); GRID is n1xn2xn3 or `own`; keys: sgs (none | smag | dsmag), impdiff (0 | 1 | 2).
+namelists of the examples the reference ships, kept as data); GRID is n1xn2xn3 or `own`; keys: sgs (none | smag | dsmag), impdiff (0 | 1 | 2),
+filter (2d | 3d: the test filter of the dynamic model, Case.filter2d -- the reference's -D_FILTER_2D; without the key CALES_FILTER_2D decides).
 Per entry: create the context, warm up, time K steps of cales_step between device synchronisations (K from a pilot so that the window is at
 least --window seconds), repeat them with per-kernel events, print ONE JSON line: ms_per_step, the plan string and, per scope of the solve, the ms
 per call and the fraction of the 8 TB/s peak at 2 compulsory words per cell and pass (4 with fillps inside the forward x pass, 9 for the correction
-pass) -- the pricing of DESIGN.md 3. CALES_LIB picks the library, so a job script can alternate two builds."""
+pass) -- the pricing of DESIGN.md 3; under "sgs_scopes" the ms per call of cmpt_sgs and of the passes of the dynamic model. CALES_LIB picks the
+library, so a job script can alternate two builds."""
 import argparse
 import json
 import math
@@ -19,6 +21,7 @@ import time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 PEAK = 8.0e12
+SGS_SCOPES = ["cmpt_sgs_dsmag", "cmpt_sgs_smag", "strain_filter_uvw", "correc_strain_filter_uvw", "lij_mij_filter_contract", "strain_rate"]
 WORDS = {"fillps_fft_x_fwd": 4, "fft_x_fwd": 2, "fft_y_fwd": 2, "gaussel_z": 2, "fft_y_bwd": 2, "fft_x_bwd": 2, "correc_updatep": 9}
 
 
@@ -37,6 +40,10 @@ def load(entry):
     if "sgs" in opts:
         case.sgstype = opts["sgs"]
     case.impdiff = int(opts.get("impdiff", 0))
+    if "filter" in opts:
+        if opts["filter"] not in ("2d", "3d"):
+            raise SystemExit(f"{entry}: filter is 2d or 3d")
+        case.filter2d = opts["filter"] == "2d"
     return case
 
 
@@ -75,10 +82,11 @@ def run(entry, window, warmup):
             per_pass = tot / (3 * K)      # three substeps, one solve (and at most one correction pass) each
             scopes[k] = {"ms_per_call": round(tot / calls, 5), "calls_per_step": round(calls / K, 2), "ms_per_step": round(tot / K, 5),
                          "frac_peak": round(words * ncell * rb / (per_pass * 1e-3) / PEAK, 4)}
+        sgs = {k: {"ms_per_call": round(st[k][1] / st[k][0], 5), "calls_per_step": round(st[k][0] / K, 2)} for k in SGS_SCOPES if st.get(k, (0, 0.))[0]}
         divmax = h.chkdiv()[1]
         pl = h.describe_plan()
         return {"entry": entry, "ng": [int(x) for x in case.ng], "lib": os.path.basename(capi.LIB_PATH), "steps": K, "ms_per_step": round(ms, 5),
-                "divmax": divmax, "plan": ";".join(f"{k}={v}" for k, v in pl.items()), "scopes": scopes}
+                "divmax": divmax, "plan": ";".join(f"{k}={v}" for k, v in pl.items()), "scopes": scopes, "sgs_scopes": sgs}
     finally:
         h.close()
 
