@@ -29,6 +29,15 @@ def filter2d_env() -> bool:
     """CALES_FILTER_2D, the run-time form of the reference's -D_FILTER_2D: set to anything but the empty string or 0."""
     return os.environ.get("CALES_FILTER_2D", "0") not in ("", "0")
 
+# enum cales_sgs_average of include/cales.h, OR-ed onto the two dynamic values: the directions the Germano identity is averaged over (sgs.f90:359-370)
+SGS_AVE = {"planes": 0, "volume": 4, "xlines": 8}      # the reference's hard-wired _CHANNEL | -D_DIT | _DUCT without _CHANNEL
+
+
+def dsmag_average_env() -> str:
+    """CALES_DSMAG_AVERAGE, the run-time form of the reference's _DIT / _CHANNEL / _DUCT: planes (also unset or empty), volume or xlines."""
+    return os.environ.get("CALES_DSMAG_AVERAGE", "") or "planes"
+
+
 FIELDS = dict(u=0, v=1, w=2, p=3, pp=4, visct=5, dudt=6, dvdt=7, dwdt=8, dudto=9, dvdto=10, dwdto=11,
               dudtd=12, dvdtd=13, dwdtd=14)
 
@@ -77,6 +86,12 @@ def make_case(case, nranks: int = 1, rank: int = 0) -> CalesCase:
     f2d = getattr(case, "filter2d", None)
     if case.sgstype == "dsmag" and (filter2d_env() if f2d is None else f2d):      # (the reference ignores the flag for 'none' and 'smag')
         p.sgstype = SGS_DSMAG_FILTER2D
+    if case.sgstype == "dsmag":      # (likewise ignored for 'none' and 'smag')
+        ave = getattr(case, "dsmag_average", None)
+        ave = dsmag_average_env() if ave is None else ave
+        if ave not in SGS_AVE:
+            raise ValueError(f"ERROR: unknown averaging of the dynamic model {ave!r} (planes, volume or xlines)")
+        p.sgstype |= SGS_AVE[ave]
     p.lwm[:] = [int(x) for x in case.lwm.ravel(order="F")]
     p.hwm = float(case.hwm)
     p.impdiff = int(case.impdiff)

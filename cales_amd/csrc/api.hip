@@ -169,7 +169,11 @@ int cales_create(const cales_case *cs, void *stream, cales_ctx **out) {
   cales_ctx *c = new cales_ctx();
   c->C = *cs;
   // 'dsmag' of a -D_FILTER_2D build: normalised once -- the model is 'dsmag' everywhere, the plane filter is a property of its path (SgsPath)
-  if (cs->sgstype == CALES_SGS_DSMAG_FILTER2D) { c->C.sgstype = CALES_SGS_DSMAG; c->sgs.filter2d = true; }
+  // ... and so are the directions the Germano identity is averaged over (enum cales_sgs_average; cales_check_case has refused every other combination)
+  if (cs->sgstype & CALES_SGS_AVE_VOLUME) c->sgs.ave = SgsAve::volume;
+  if (cs->sgstype & CALES_SGS_AVE_XLINES) c->sgs.ave = SgsAve::xlines;
+  c->C.sgstype = cs->sgstype & ~(CALES_SGS_AVE_VOLUME | CALES_SGS_AVE_XLINES);
+  if (c->C.sgstype == CALES_SGS_DSMAG_FILTER2D) { c->C.sgstype = CALES_SGS_DSMAG; c->sgs.filter2d = true; }
   c->fl.read_env();      // the CALES_* switches are fixed for the life of the context
   // zero all device pointers
   for (auto &p : c->f) p = nullptr;
@@ -543,6 +547,7 @@ int cales_describe_plan(cales_ctx *c, char *buf, int buflen) {
   s += std::string(";visct_ghost_cells=") + (pl.visct_ghosts ? "updated" : "zero_field");
   s += std::string(";momentum=") + (c->mom.fused ? "fused_mom_rk" : "mom+rk_update");
   s += std::string(";sgs=") + sgs_path_name(c);
+  if (c->sgs.ave != SgsAve::planes) s += std::string(";sgs_average=") + (c->sgs.ave == SgsAve::volume ? "volume" : "x_lines");
   s += std::string(";solver=") + solver_path_name(c);
   if (c->P > 1) s += ";mode_columns_per_rank=" + std::to_string(solver_mode_columns(c));      // of the pressure solve (padded to whole 128-B lines where that costs 6 % or less: solver_setup)
   s += ";ranks=" + std::to_string(c->P) + ";exchanges=" + (c->P == 1 ? "none" : !c->comm.on ? "unset" : (c->comm_stream && (c->comm.halo_s || c->comm.a2a_part)) ? "second_stream" : "in_order");

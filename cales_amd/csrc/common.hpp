@@ -153,10 +153,13 @@ enum class SgsForm { none, smag_rows, smag_reference, dsmag_tiles, dsmag_referen
 enum class StrainKernel { corr_rows2, corr, yw32, yw64, pair, plain32, plain64, f2d32, f2d64 };      // k_corr_strain_tile<unsigned, TYC(, EXT = 1)> | k_strain_tile<OFF, TYS, YW(, SSF)>, SSF = 1: pair, 2: f2d (SgsPath::filter2d)
 enum class LmfKernel { pair, yw_ucf32, yw_ucf64, yw32, yw64, ucf32, ucf64, plain32, plain64, f2d32, f2d64 };      // k_lmf_tile<OFF, YW, UCF(, SSF)>, SSF = 1: pair, 2: f2d
 enum class SmagKernel { yw32, yw64, plain32, plain64 };      // k_smag_rows<OFF, YW>
+// the directions <Mij Lij>, <Mij Mij> of the dynamic model are averaged over (sgs.f90:359-370): _CHANNEL (hard-wired there) | -D_DIT | _DUCT
+enum class SgsAve { planes, volume, xlines };
 struct SgsPath {
   SgsForm form = SgsForm::none;
   bool pair = false, lazy = false, ucf = false, small = false, yw = false;      // |S|Sij as pair fields (ss2); lazy: |S| straight into visct (homogeneous sgs BCs)
   bool filter2d = false;    // the reference's -D_FILTER_2D (cales_case.sgstype = CALES_SGS_DSMAG_FILTER2D): test filter in the x-y planes only, alph2 = 2.52 everywhere
+  SgsAve ave = SgsAve::planes;      // cales_case.sgstype & CALES_SGS_AVE_*: volume folds the plane sums into one (k_volume_fold), xlines takes the sequence (k_contract_lines)
   bool wraps_x = true;      // reads wrapped interior columns where x is periodic (cales_step may leave the x ghost columns stale)
   // static kernel arguments (y walls: dsmag those this rank owns, smag_rows those of the case -- global distances, the shear reaches every slab)
   int zlo = 0, zhi = 0, wmlo = 0, wmhi = 0, wylo = 0, wyhi = 0, wmylo = 0, wmyhi = 0; real flo = 0., fhi = 0.;

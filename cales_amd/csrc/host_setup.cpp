@@ -283,7 +283,12 @@ int hs_check_case(const cales_case *cs, std::string &msg) {
       if (cs->lwm[5] != 0 && !per_z) ok = ok && h > cs->l[2] - zc[n3] && h < cs->l[2] - zc[1];
       if (!ok) { msg = "invalid wall model height (sanity.f90:224-231)"; return 1; }
     } }
-  if (cs->sgstype < 0 || cs->sgstype > CALES_SGS_DSMAG_FILTER2D) { msg = "unknown SGS model"; return 1; }
+  {
+    const int ave = cs->sgstype & (CALES_SGS_AVE_VOLUME | CALES_SGS_AVE_XLINES), model = cs->sgstype & ~ave;
+    if (cs->sgstype < 0 || model > CALES_SGS_DSMAG_FILTER2D) { msg = "unknown SGS model"; return 1; }
+    if (ave == (CALES_SGS_AVE_VOLUME | CALES_SGS_AVE_XLINES)) { msg = "SGS model: CALES_SGS_AVE_VOLUME and CALES_SGS_AVE_XLINES exclude each other"; return 1; }
+    if (ave && model < CALES_SGS_DSMAG) { msg = "SGS model: an averaging flag (CALES_SGS_AVE_*) goes with the dynamic model only"; return 1; }
+  }
   // (sanity.f90:98-111 refuses static Smagorinsky with more than two subdomains between two opposite walls because every rank measures the
   // wall distance with its local indices and knows only its own walls' shear. Here distances use global rows and the shear planes of the
   // two y walls are handed to every slab, k_sgs.hip wall_shear_y_planes: any number of y slabs gives the one-rank result.)

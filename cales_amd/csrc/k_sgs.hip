@@ -256,6 +256,55 @@ __global__ __launch_bounds__(256) void k_plane_sum(Geom g, const real *__restric
   __syncthreads();
   if (threadIdx.x == 0) p1d[blockIdx.y * g.n3 + blockIdx.x] = sh[0] + sh[1] + sh[2] + sh[3];
 }
+// ave2d_duct(...,1,...) of the two contractions (sgs.f90:328-358,585-612; SgsAve::xlines) without the two fields between them: one wave per x line (j, k),
+// four lines per block. The lanes walk the row in segments of 64 cells from i = 1 -- rows start on a 128-B line there, every load is whole lines -- with
+// the expressions of k_contract in their order, each lane adding its cells in segment order; one DPP sum over the wave, and lane 63 stores the two sums
+// of the line: lines[(k-1) n2 + j-1] and lines[n2 n3 + ...]. 15 words per cell are read and nothing else is written. Loads are unconditional: a lane
+// past n1 reads cell n1 again and adds zero. No LDS, no barrier (a wave without a line leaves at once).
+__global__ __launch_bounds__(256) void k_contract_lines(Geom g, CP6 mij, CP6 lij, const real *__restrict__ uf, const real *__restrict__ vf,
+                                                        const real *__restrict__ wf, real *__restrict__ lines) {
+  const int nl = g.n2 * g.n3, line = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (line >= nl) return;
+  const size_t row = g.ix(0, line % g.n2 + 1, line / g.n2 + 1);
+  real slm = 0., smm = 0.;
+  for (int i0 = 1; i0 <= g.n1; i0 += 64) {
+    const bool in = i0 + lane <= g.n1;
+    const size_t c = row + (in ? i0 + lane : g.n1);
+    real m_[6], l_[6];
+#pragma unroll
+    for (int m = 0; m < 6; ++m) { m_[m] = mij.p[m][c]; l_[m] = lij.p[m][c]; }
+    const real a = uf[c], b = vf[c], d = wf[c];
+    l_[0] -= a * a; l_[1] -= b * b; l_[2] -= d * d; l_[3] -= a * b; l_[4] -= a * d; l_[5] -= b * d;
+    const real lm = m_[0] * l_[0] + m_[1] * l_[1] + m_[2] * l_[2] + (m_[3] * l_[3] + m_[4] * l_[4] + m_[5] * l_[5]) * 2.;
+    const real mm = m_[0] * m_[0] + m_[1] * m_[1] + m_[2] * m_[2] + (m_[3] * m_[3] + m_[4] * m_[4] + m_[5] * m_[5]) * 2.;
+    slm += in ? lm : (real)0.; smm += in ? mm : (real)0.;
+  }
+  slm = wave_sum_lane63(slm); smm = wave_sum_lane63(smm);
+  if (lane == 63) { lines[line] = slm; lines[nl + line] = smm; }
+}
+// visct = max(visct*<LM>(j,k)/<MM>(j,k),0) (sgs.f90:372-380 behind ave2d_duct: gar = dl(1)/l(1), sgs.f90:586,609); the line sums replace the broadcast arrays
+__global__ __launch_bounds__(BX *BY) void k_dsmag_final_lines(Geom g, real gar, const real *__restrict__ lines, const real *s0, real *visct) {
+  const int i = blockIdx.x * BX + threadIdx.x + 1, j = blockIdx.y * BY + threadIdx.y + 1, k = blockIdx.z + 1;
+  if (i > g.n1 || j > g.n2) return;
+  const size_t c = g.ix(i, j, k);
+  const int q = (k - 1) * g.n2 + j - 1;
+  const real lm = lines[q] * gar, mm = lines[g.n2 * g.n3 + q] * gar;
+  real vt = s0[c] * lm / mm;
+  visct[c] = fmax(vt, 0.);
+}
+// ave0d_dit (sgs.f90:388-431; SgsAve::volume) from the plane sums: T = sum over k of p1d(k) dzf(k) of both quantities, written into every plane's slot, so
+// that k_dsmag_coef / k_dsmag_final run as they are (only the ratio enters: gar and 1/l(3) cancel). One block, fixed order; on several slabs every
+// rank folds the same all-reduced vector. All reads of p1d precede the barrier, all writes follow it.
+__global__ __launch_bounds__(256) void k_volume_fold(int n3, const real *__restrict__ dzf, real *p1d) {
+  __shared__ real sh[2][4];
+  real a = 0., b = 0.;
+  for (int k = threadIdx.x; k < n3; k += 256) { const real d = dzf[k + 1]; a += p1d[k] * d; b += p1d[n3 + k] * d; }
+  for (int o = 32; o > 0; o >>= 1) { a += __shfl_down(a, o, 64); b += __shfl_down(b, o, 64); }
+  if ((threadIdx.x & 63) == 0) { sh[0][threadIdx.x >> 6] = a; sh[1][threadIdx.x >> 6] = b; }
+  __syncthreads();
+  const real ta = sh[0][0] + sh[0][1] + sh[0][2] + sh[0][3], tb = sh[1][0] + sh[1][1] + sh[1][2] + sh[1][3];
+  for (int k = threadIdx.x; k < n3; k += 256) { p1d[k] = ta; p1d[n3 + k] = tb; }
+}
 // visct = max(visct*<LM>/<MM>,0) (sgs.f90:372-380); the plane averages replace the broadcast arrays
 __global__ __launch_bounds__(BX *BY) void k_dsmag_final(Geom g, real gar, const real *__restrict__ p1d, const real *s0, real *visct) {
   const int i = blockIdx.x * BX + threadIdx.x + 1, j = blockIdx.y * BY + threadIdx.y + 1, k = blockIdx.z + 1;
@@ -1340,6 +1389,7 @@ void sgs_setup(cales_ctx *c) {
   for (int q = 2; q < 4; ++q) yw = yw || c->is_wall[q] != 0. || c->C.lwm[q] != 0;
   if (c->C.sgstype == 1) P.form = !xw && n[2] >= 3 && n[1] >= 2 && !fl.smag_reference_sequence ? SgsForm::smag_rows : SgsForm::smag_reference;
   // (ducts: the fused last pass knows the wall rule along y from three rows on)
+  else if (P.ave == SgsAve::xlines) P.form = SgsForm::dsmag_reference;      // (no tile form yet: k_lmf_tile hands out plane partials, not rows')
   else if (!P.filter2d) P.form = !xw && !(yw && n[1] < 3) && n[2] >= 3 && !fl.dsmag_reference_sequence ? SgsForm::dsmag_tiles : SgsForm::dsmag_reference;
   else {
     // the plane filter (-D_FILTER_2D): tiles for the channel class -- x periodic (the kernels wrap around), nothing at the y faces, z between two walls (no-slip
@@ -1529,6 +1579,7 @@ static int dsmag_fast(cales_ctx *c, const SgsFold *fold, bool *visct_ghosts_done
     LAUNCH(c, k_plane_fold, dim3(2 * n[2]), dim3(256), 0, c->stream, n[2], L.nblk, c->wk[0], c->d_p1d);
   }
   if (c->P > 1) { if (int e = allreduce_res(c, (int)(c->d_p1d - c->res), 2 * n[2], 0)) return e; }   // sgs.f90:475
+  if (P.ave == SgsAve::volume) LAUNCH(c, k_volume_fold, dim3(1), dim3(256), 0, c->stream, n[2], c->d_dzf, c->d_p1d);      // sgs.f90:360-361
   const real gar = c->dl[0] * c->dl[1] / (c->C.l[0] * c->C.l[1]);
   if (P.lazy) {
     if (!c->d_cs) HIPCHK(c, hipMalloc(&c->d_cs, (n[2] + 2) * sizeof(real)));
@@ -1697,9 +1748,16 @@ int op_cmpt_sgs(cales_ctx *c, const SgsFold *fold, bool *visct_ghosts_done) {
   filter(c->vc, c->vf);
   filter(c->wc, c->wf);
   CP6 clij; for (int m = 0; m < 6; ++m) clij.p[m] = lij[m];
+  if (c->sgs.ave == SgsAve::xlines) {      // sgs.f90:366-367: x is local to a y slab -- nothing to communicate
+    LAUNCH(c, k_contract_lines, dim3((n[1] * n[2] + 3) / 4), dim3(256), 0, c->stream, c->g, cmij, clij, c->uf, c->vf, c->wf, wk[0]);
+    LAUNCH(c, k_dsmag_final_lines, gr, b, 0, c->stream, c->g, c->dl[0] / c->C.l[0], wk[0], visct, visct);
+    LAUNCHCHK(c);
+    return 0;
+  }
   LAUNCH(c, k_contract, gr, b, 0, c->stream, c->g, cmij, clij, c->uf, c->vf, c->wf, wk[0], wk[1]);
   LAUNCH(c, k_plane_sum, dim3(n[2], 2), dim3(256), 0, c->stream, c->g, wk[0], wk[1], c->d_p1d);
   if (c->P > 1) { if (int e = allreduce_res(c, (int)(c->d_p1d - c->res), 2 * n[2], 0)) return e; }   // sgs.f90:475
+  if (c->sgs.ave == SgsAve::volume) LAUNCH(c, k_volume_fold, dim3(1), dim3(256), 0, c->stream, n[2], c->d_dzf, c->d_p1d);      // sgs.f90:360-361
   const real gar = c->dl[0] * c->dl[1] / (c->C.l[0] * c->C.l[1]);
   LAUNCH(c, k_dsmag_final, gr, b, 0, c->stream, c->g, gar, c->d_p1d, visct, visct);
   LAUNCHCHK(c);

@@ -17,6 +17,8 @@
 !                              _IMPDIFF/_IMPDIFF_1D are run-time here); reads ./input.nml
 ! environment: CALES_FILTER_2D (set to anything but 0) = the reference's build switch _FILTER_2D: sgstype = 'dsmag' test-filters in the x-y planes
 !              only and uses alph2 = 2.52 everywhere (src/sgs.f90:236-247,316-327,817-821); no effect on 'none' and 'smag'
+!              CALES_DSMAG_AVERAGE = planes (also unset or empty) | volume | xlines: the reference's _CHANNEL (hard-wired there) | -D_DIT | _DUCT -- the
+!              directions sgstype = 'dsmag' averages the Germano identity over (src/sgs.f90:359-370); no effect on 'none' and 'smag'
 program cales
   use, intrinsic :: iso_c_binding
   use, intrinsic :: iso_fortran_env, only: int64
@@ -58,8 +60,8 @@ program cales
   integer :: myid,nranks,n2l,jlo          ! rank, number of ranks, rows of the slab, global row of local row 1 minus 1
   logical :: is_done,kill,is_chan,is_duct
   character(len=512) :: iomsg,arg
-  character(len=16) :: f2d
-  integer :: f2dlen,f2dstat
+  character(len=16) :: f2d,ave
+  integer :: f2dlen,f2dstat,avelen,avestat
   character(len=100) :: filename
   character(len=7) :: fldnum
   character(len=4) :: chkptnum
@@ -127,6 +129,20 @@ program cales
     cs%sgstype = 2
     call get_environment_variable('CALES_FILTER_2D',f2d,f2dlen,f2dstat)           ! the run-time form of -D_FILTER_2D
     if(f2dstat <= 0 .and. f2dlen > 0 .and. trim(f2d) /= '0') cs%sgstype = 3       ! CALES_SGS_DSMAG_FILTER2D (include/cales.h)
+    call get_environment_variable('CALES_DSMAG_AVERAGE',ave,avelen,avestat)       ! the run-time form of _DIT / _CHANNEL / _DUCT
+    if(avestat == 0 .and. avelen > 0) then
+      select case(trim(ave))
+      case('planes')
+      case('volume'); cs%sgstype = ior(cs%sgstype,CALES_SGS_AVE_VOLUME)
+      case('xlines'); cs%sgstype = ior(cs%sgstype,CALES_SGS_AVE_XLINES)
+      case default
+        if(myid == 0) print*, 'ERROR: unknown CALES_DSMAG_AVERAGE (planes, volume or xlines)'
+        call die
+      end select
+    else if(avestat < 0) then                                                     ! (longer than any of the three words)
+      if(myid == 0) print*, 'ERROR: unknown CALES_DSMAG_AVERAGE (planes, volume or xlines)'
+      call die
+    end if
   case('amd')                                                                  ! src/sgs.f90:381-382
     if(myid == 0) print*, 'ERROR: AMD model not yet implemented'
     call die

@@ -39,7 +39,8 @@ typedef struct cales_case {
   char    cbcvel[18], cbcpre[6], cbcsgs[6];
   cales_real  bcvel[18], bcpre[6], bcsgs[6];
   cales_real  bforce[3]; int32_t is_forced[3]; cales_real velf[3];
-  int32_t sgstype;        /* 0 'none', 1 'smag', 2 'dsmag', 3 'dsmag' of a -D_FILTER_2D build (src/sgs.f90:61-153; enum cales_sgstype below) */
+  int32_t sgstype;        /* 0 'none', 1 'smag', 2 'dsmag', 3 'dsmag' of a -D_FILTER_2D build (src/sgs.f90:61-153; enum cales_sgstype below),
+                           * 2 and 3 optionally OR-ed with one flag of enum cales_sgs_average */
   int32_t lwm[6]; cales_real hwm;
   int32_t impdiff;        /* 0 explicit; 2 = _IMPDIFF + _IMPDIFF_1D (z-implicit); 1 = _IMPDIFF (3-D implicit; periodic or no-slip wall pairs in x and y) */
   int32_t nranks, rank;   /* y-slab decomposition: rank owns rows rank*ng2/nranks+1 ... */
@@ -48,6 +49,12 @@ typedef struct cales_case {
 /* cales_case.sgstype. CALES_SGS_DSMAG_FILTER2D is the reference's 'dsmag' built with -D_FILTER_2D: the test filter of the dynamic model acts in the
  * x-y planes only (filter2d, src/sgs.f90:824-848) and alph2 = 2.52 everywhere (sgs.f90:817-821). The flag changes nothing for 'none' and 'smag'. */
 enum cales_sgstype { CALES_SGS_NONE = 0, CALES_SGS_SMAG = 1, CALES_SGS_DSMAG = 2, CALES_SGS_DSMAG_FILTER2D = 3 };
+/* The directions over which the dynamic model averages <Mij Lij> and <Mij Mij> (the Germano identity, src/sgs.f90:359-370): one flag OR-ed onto
+ * CALES_SGS_DSMAG or CALES_SGS_DSMAG_FILTER2D (sgstype 6, 7 / 10, 11). No flag: the z planes, the reference's hard-wired _CHANNEL (ave1d_channel).
+ * CALES_SGS_AVE_VOLUME: a -D_DIT build, one coefficient for the whole domain, weighted by dzf(k) (ave0d_dit, sgs.f90:388-431).
+ * CALES_SGS_AVE_XLINES: a _DUCT build without _CHANNEL, one coefficient per x line (j, k) (ave2d_duct(...,1,...), sgs.f90:585-612).
+ * cales_check_case refuses both flags together and a flag on 'none' or 'smag'. */
+enum cales_sgs_average { CALES_SGS_AVE_VOLUME = 4, CALES_SGS_AVE_XLINES = 8 };
 
 typedef struct cales_ctx cales_ctx;
 
