@@ -549,6 +549,7 @@ int cales_describe_plan(cales_ctx *c, char *buf, int buflen) {
   s += std::string(";sgs=") + sgs_path_name(c);
   if (c->sgs.ave != SgsAve::planes) s += std::string(";sgs_average=") + (c->sgs.ave == SgsAve::volume ? "volume" : "x_lines");
   s += std::string(";solver=") + solver_path_name(c);
+  if (c->C.impdiff == 1) for (int iv = 0; iv < 3; ++iv) s += std::string(";helmholtz_") + "uvw"[iv] + "=" + helmholtz_path_name(c, iv);
   if (c->P > 1) s += ";mode_columns_per_rank=" + std::to_string(solver_mode_columns(c));      // of the pressure solve (padded to whole 128-B lines where that costs 6 % or less: solver_setup)
   s += ";ranks=" + std::to_string(c->P) + ";exchanges=" + (c->P == 1 ? "none" : !c->comm.on ? "unset" : (c->comm_stream && (c->comm.halo_s || c->comm.a2a_part)) ? "second_stream" : "in_order");
   std::snprintf(buf, buflen, "%s", s.c_str());

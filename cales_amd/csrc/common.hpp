@@ -404,6 +404,7 @@ int op_out2d_duct(cales_ctx *c, real *buf);
 bool solver_can_fuse_fillps(cales_ctx *c);
 int solver_mode_columns(cales_ctx *c);      // complex mode columns per rank of the pressure solve
 std::string solver_path_name(cales_ctx *c);      // which transform / tridiagonal kernels the pressure solve of this context takes (cales_describe_plan)
+std::string helmholtz_path_name(cales_ctx *c, int iv);      // ... and the Helmholtz solve of velocity component iv (0..2) of the 3-D implicit step
 const char *sgs_path_name(const cales_ctx *c);      // likewise for cmpt_sgs (SgsPath)
 void sgs_setup(cales_ctx *c);               // SgsPath: form, flags, static kernel arguments and kernels (needs is_wall)
 int sgs_setup_launches(cales_ctx *c);       // ... and the launch geometry of its tile passes (needs ncu)

@@ -1851,8 +1851,8 @@ __global__ __launch_bounds__(256) void k_gaussel(Geom g, int nz, int ncol, int n
 
 // ------------------------------------------------------------------------------------------ host side
 // The path of one solved field: its transform kinds, the kernel of each direction, its eigenvalues and normalisation -- decided once (the pressure's
-// by solver_setup, a velocity component's of the 3-D implicit step by velocity_path on its first solve) and then only read: solve_field launches
-// it, solver_path_name prints it (cales_describe_plan).
+// by solver_setup, a velocity component's of the 3-D implicit step by velocity_path on its first solve or its first description, whichever comes first:
+// velocity_path_ready) and then only read: solve_field launches it, solver_path_name / helmholtz_path_name print it (cales_describe_plan).
 enum class XKernel { fft_x8, fft_x4, dst1, fft_x };                             // radix-8 | DCT-IV | face-centred | mixed radix
 enum class YKernel { fft_y16, fft_y8, fft_y8r, fft_y4, dst1, fft_y };          // radix-8 (16 | 8 per thread | register ends) | DCT-IV | face-centred | mixed radix
 enum class ZKernel { herm, tile, ri, periodic_real, periodic_cpx };            // k_gaussel_herm | launch_tile | k_gaussel_ri | k_gaussel<real, 1> | k_gaussel<real2, 1>
@@ -1894,7 +1894,8 @@ struct Solver {
   int xodd = 0, yodd = 0;        // the odd factor of an x / y line the radix-8 kernels take (SolvePath::xodd, yodd)
   real *twx = nullptr, *twx_post = nullptr, *twy = nullptr, *twy_post = nullptr, *twyd = nullptr;      // twiddle tables; twy_post, twyd: DCT weights of x, of y
   real *tw4x = nullptr, *tw4y = nullptr, *twy4 = nullptr;         // DCT-IV weights of x and y, twiddles of the N/2-point y lines
-  SolvePath pres, vel[3]; bool vel_ready[3] = {false, false, false};
+  SolvePath pres, vel[3];
+  int vel_state[3] = {0, 0, 0}; std::string vel_err[3];      // a component's path: 0 not built yet, 1 built, 2 refused with vel_err (velocity_path_ready)
   HzPath hz[3];                  // impdiff = 2
   real *d_a = nullptr, *d_b, *d_c, *d_av[3] = {nullptr, nullptr, nullptr}, *d_bv[3], *d_cv[3];      // tridiagonal (a | b | c, n3 each) of the pressure; of the velocity components, unscaled (impdiff)
   real *d_scaled = nullptr;      // 5 n3 reals, see scaled_abc (impdiff)
@@ -2124,7 +2125,7 @@ int solver_setup(cales_ctx *c) {
     HIPCHK(c, hipMemcpy(s.d_av[iv], abc.data(), abc.size() * sizeof(real), hipMemcpyHostToDevice));
   }
   HIPCHK(c, hipMalloc(&s.d_scaled, (size_t)5 * n3 * sizeof(real))); HIPCHK(c, hipMemset(s.d_scaled, 0, (size_t)5 * n3 * sizeof(real)));
-  if (c->C.impdiff == 1) HIPCHK(c, hipMalloc(&s.tab_imp3d, TILE_TAB * sizeof(real)));      // (the paths themselves on their first solve: velocity_path)
+  if (c->C.impdiff == 1) HIPCHK(c, hipMalloc(&s.tab_imp3d, TILE_TAB * sizeof(real)));      // (the paths themselves on first use: velocity_path_ready)
   if (c->C.impdiff != 2) return 0;
   // the z-only sweeps: the in-LDS tile of the pressure solve on the real field (u, dudtd in, u out: 3 words instead of 5) where its nz + q planes fit
   for (int iv = 0; iv < 3; ++iv) {
@@ -2416,18 +2417,29 @@ static int solve_field(cales_ctx *c, const SolvePath &P, real *pp, const real *d
   return 0;
 }
 
-// the kernels the pressure solve of this context takes (cales_describe_plan): its path, by name
-std::string solver_path_name(cales_ctx *c) {
-  if (!c->solver) return "unset";
-  const SolvePath &P = c->solver->pres;
-  static const char *kinds[] = {"PP", "NN", "DD", "ND", "DN"};
-  std::string s = std::string("x:") + kinds[P.xkind] + (P.xk == XKernel::fft_x8 ? "/radix8" : P.xk == XKernel::fft_x4 ? "/dct4" : "/mixed_radix");
+// A path by name (cales_describe_plan). The pressure's string merges what its tests never had to tell apart (the three radix-8 y kernels by kind, the
+// marching z kernels) and stays as it is; a velocity component's (`every`) has one name for every value of XKernel, YKernel and ZKernel, for the three
+// face-centred kinds, for the planes per lane of its tile and for the persistent tile.
+static std::string path_name(const SolvePath &P, bool every) {
+  static const char *kinds[] = {"PP", "NN", "DD", "ND", "DN", "DDf", "NNf", "DNf"};      // 5..7: along the component (RODFT00 | REDFT00 | RODFT01/10)
+  std::string s = std::string("x:") + kinds[P.xkind] + (P.xk == XKernel::fft_x8 ? "/radix8" : P.xk == XKernel::fft_x4 ? "/dct4" : (every && P.xk == XKernel::dst1) ? "/face_centred" : "/mixed_radix");
   if (P.xodd) s += "x" + std::to_string(P.xodd);
-  s += std::string(",y:") + kinds[P.ykind] + (radix8_y(P.yk) ? (P.yodd ? "/radix8x" + std::to_string(P.yodd) : P.ykind ? "/radix8" : "/radix8_register_ends") : P.yk == YKernel::fft_y4 ? "/dct4" : "/mixed_radix");
-  s += std::string(",z:") + (P.zk == ZKernel::herm ? "thomas_hermitian" : P.zk == ZKernel::tile ? (P.zt.PER ? "lds_tile_periodic" : "lds_tile") : "thomas_march");
+  s += std::string(",y:") + kinds[P.ykind];
+  if (every && P.yk == YKernel::fft_y16) s += "/radix8_16_per_thread";
+  else if (every && P.yk == YKernel::dst1) s += "/face_centred";
+  else if (every && radix8_y(P.yk)) s += P.yodd ? "/radix8x" + std::to_string(P.yodd) : P.yk == YKernel::fft_y8 ? "/radix8" : "/radix8_register_ends";
+  else s += radix8_y(P.yk) ? (P.yodd ? "/radix8x" + std::to_string(P.yodd) : P.ykind ? "/radix8" : "/radix8_register_ends") : P.yk == YKernel::fft_y4 ? "/dct4" : "/mixed_radix";
+  s += std::string(",z:") + (P.zk == ZKernel::herm ? "thomas_hermitian" : P.zk == ZKernel::tile ? (P.zt.PER ? "lds_tile_periodic" : "lds_tile")
+                             : (every && P.zk == ZKernel::periodic_real) ? "thomas_periodic_real" : (every && P.zk == ZKernel::periodic_cpx) ? "thomas_periodic_complex" : "thomas_march");
+  if (every && P.zk == ZKernel::tile) s += P.zt.persistent ? "_persistent" : "_m" + std::to_string(P.zt.M);
   if (P.nyq) s += ",modes_0_and_n1/2:one_column";
   if (P.null_switch) s += ",null_mode:reference_order";
   return s;
+}
+// the kernels the pressure solve of this context takes
+std::string solver_path_name(cales_ctx *c) {
+  if (!c->solver) return "unset";
+  return path_name(c->solver->pres, false);
 }
 
 int op_solver(cales_ctx *c, const FusedFill &fill) {
@@ -2581,12 +2593,25 @@ static int velocity_path(cales_ctx *c, Solver &s, int iv, SolvePath &V) {
   tile_setup(c, V, s.tab_imp3d);
   return 0;
 }
+// the one place a component's path is made: by its first solve or by cales_describe_plan, whichever comes first; a refusal is kept and repeated
+static int velocity_path_ready(cales_ctx *c, Solver &s, int iv) {
+  if (s.vel_state[iv] == 0) { s.vel_state[iv] = velocity_path(c, s, iv, s.vel[iv]) ? 2 : 1; if (s.vel_state[iv] == 2) s.vel_err[iv] = c->err; }
+  if (s.vel_state[iv] == 2) { c->err = s.vel_err[iv]; return 1; }
+  return 0;
+}
+// the kernels the Helmholtz solve of velocity component iv takes (3-D implicit diffusion)
+std::string helmholtz_path_name(cales_ctx *c, int iv) {
+  if (!c->solver || c->C.impdiff != 1) return "unset";
+  const std::string err = c->err;
+  if (velocity_path_ready(c, *c->solver, iv)) { c->err = err; return "refused"; }      // (a description fails no call: the solve itself reports why)
+  return path_name(c->solver->vel[iv], true);
+}
 int op_helmholtz(cales_ctx *c, int ivel, real alpha) {
   if (c->C.impdiff != 1) { c->err = "helmholtz needs impdiff = 1"; return 1; }
   Solver *s = c->solver;
   if (!s) { c->err = "solver not initialised"; return 1; }
-  SolvePath &V = s->vel[ivel - 1];
-  if (!s->vel_ready[ivel - 1]) { if (int e = velocity_path(c, *s, ivel - 1, V)) return e; s->vel_ready[ivel - 1] = true; }
+  if (int e = velocity_path_ready(c, *s, ivel - 1)) return e;
+  const SolvePath &V = s->vel[ivel - 1];
   ProfScope ps(c, "helmholtz_xyz");
   const int n3 = c->n[2];
   if (int e = op_rhs_b_velxy(c, ivel, alpha)) return e;      // main.f90:424-431: boundary terms of the x and y faces, then z

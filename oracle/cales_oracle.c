@@ -476,6 +476,14 @@ void o_get_solver(const ostate *s, int which, double *lambdaxy, double *a, doubl
     memcpy(a, s->a, nb); memcpy(b, s->b, nb); memcpy(c, s->c, nb); *normfft = s->normfft;
   } else if (s->av[which-1]) {
     memcpy(a, s->av[which-1], nb); memcpy(b, s->bv[which-1], nb); memcpy(c, s->cv[which-1], nb);
+    /* eigenvalues of the velocity component, as o_solver_helmholtz forms them (face-centred along its own direction; the entry of the face that is
+       no unknown, Dirichlet-Dirichlet, is zero) */
+    const char *bcv = &s->cbcvel[6*(which-1)];
+    double *lx = dalloc(n[0]), *ly = dalloc(n[1]);
+    eigenvalues(n[0], bcv + 0, which == 1 ? 'f' : 'c', lx); for (int i = 0; i < n[0]; i++) lx[i] = lx[i]*(s->dli[0]*s->dli[0]);
+    eigenvalues(n[1], bcv + 2, which == 2 ? 'f' : 'c', ly); for (int j = 0; j < n[1]; j++) ly[j] = ly[j]*(s->dli[1]*s->dli[1]);
+    for (int j = 0; j < n[1]; j++) for (int i = 0; i < n[0]; i++) lambdaxy[i + (size_t)n[0]*j] = lx[i] + ly[j];
+    free(lx); free(ly);
   }
 }
 

@@ -5,7 +5,8 @@ import numpy as np
 import pytest
 
 from oracle.oracle import Oracle
-from tests.util import F, load_golden, relerr
+from tests.util import OPEN_SETS, F, load_golden, relerr
+from tests.util import open_case as _open_case      # (tests/test_helmholtz_reference.py runs the same cases on the CPU)
 
 pytestmark = pytest.mark.gpu
 
@@ -690,39 +691,6 @@ def test_helmholtz_3d_with_walls(name, ng, ivel):
     a = got[1:nn[0] + 1, 1:nn[1] + 1, 1:nn[2] + 1]; b = ref[1:nn[0] + 1, 1:nn[1] + 1, 1:nn[2] + 1]
     assert np.abs(a - b).max() < 1e-12 * np.abs(b).max(), (name, ng, ivel)
     h.close()
-
-
-def _open_case(xset, yset, ng, inflow=True):
-    """devchan_nd with other BC pairs: xset / yset = (pair of the normal velocity, pair of the two tangential ones) in x / y, None = periodic; the
-    pressure takes the complementary pair of the normal velocity (sanity.f90:140-189), z keeps its walls. Dirichlet faces get non-zero values."""
-    g, case = load_golden("devchan_nd")
-    case.ng[:] = ng; case.impdiff = 1; case.sgstype = "none"; case.lwm[:] = 0
-    case.bcvel[:] = 0.; case.bcpre[:] = 0.
-    comp = {"D": "N", "N": "D", "P": "P"}
-    for d, pairs in ((0, xset), (1, yset)):
-        for iv in range(3):
-            pr = "PP" if pairs is None else (pairs[0] if iv == d else pairs[1])
-            for side in (0, 1):
-                case.cbcvel[side, d, iv] = pr[side]
-                if inflow and pr[side] == "D":
-                    case.bcvel[side, d, iv] = (0.7, 0.3, -0.2)[iv] * (1. if side == 0 else -0.5)
-        prn = "PP" if pairs is None else pairs[0]
-        for side in (0, 1):
-            case.cbcpre[side, d] = comp[prn[side]]
-    case.cbcsgs[:] = np.where(case.cbcvel[:, :, 0] == "P", "P", "D")
-    case.is_forced[:] = False; case.bforce[:] = 0.
-    return case
-
-
-OPEN_SETS = [(("DN", "NN"), None, (16, 12, 10)),      # the developing channel: inflow / outflow (RODFT01/10 along u, REDFT10/01 across)
-             (("DN", "DN"), None, (24, 8, 12)),       # tangential components Dirichlet at the inflow (RODFT11)
-             (("ND", "ND"), None, (16, 12, 10)),      # REDFT10/01 with half-integer eigenvalues along u, REDFT11 across
-             (("NN", "DD"), None, (18, 10, 10)),      # REDFT00 along u (2 (n-1)-point extension: 34 = 2 x 17)
-             (None, ("DN", "NN"), (12, 16, 10)),      # the same along y
-             (None, ("ND", "DN"), (12, 24, 10)),
-             (None, ("NN", "ND"), (10, 18, 12)),
-             (("DN", "NN"), ("DD", "DD"), (16, 12, 10)),      # inflow / outflow between side walls
-             (("DD", "DD"), ("DN", "DN"), (12, 16, 10))]
 
 
 @pytest.mark.imp3d_open

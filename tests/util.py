@@ -130,3 +130,168 @@ def triperiodic_bounds(case, fields, p, dt, nsteps, sens):
     C = abs(float(np.asarray(p)[1:-1, 1:-1, 1:-1].mean()))
     dxi = max(float(case.ng[d]) / float(case.l[d]) for d in range(3))
     return [1e-9 + 4. * sens + 100. * eps * C * dt * dxi * 3 * nsteps / max(float(np.abs(f).max()), 1e-300) for f in fields]
+
+
+def open_case(xset, yset, ng, inflow=True):
+    """devchan_nd with other BC pairs: xset / yset = (pair of the normal velocity, pair of the two tangential ones) in x / y, None = periodic; the
+    pressure takes the complementary pair of the normal velocity (sanity.f90:140-189), z keeps its walls. Dirichlet faces get non-zero values."""
+    g, case = load_golden("devchan_nd")
+    case.ng[:] = ng; case.impdiff = 1; case.sgstype = "none"; case.lwm[:] = 0
+    case.bcvel[:] = 0.; case.bcpre[:] = 0.
+    comp = {"D": "N", "N": "D", "P": "P"}
+    for d, pairs in ((0, xset), (1, yset)):
+        for iv in range(3):
+            pr = "PP" if pairs is None else (pairs[0] if iv == d else pairs[1])
+            for side in (0, 1):
+                case.cbcvel[side, d, iv] = pr[side]
+                if inflow and pr[side] == "D":
+                    case.bcvel[side, d, iv] = (0.7, 0.3, -0.2)[iv] * (1. if side == 0 else -0.5)
+        prn = "PP" if pairs is None else pairs[0]
+        for side in (0, 1):
+            case.cbcpre[side, d] = comp[prn[side]]
+    case.cbcsgs[:] = np.where(case.cbcvel[:, :, 0] == "P", "P", "D")
+    case.is_forced[:] = False; case.bforce[:] = 0.
+    return case
+
+
+OPEN_SETS = [(("DN", "NN"), None, (16, 12, 10)),      # the developing channel: inflow / outflow (RODFT01/10 along u, REDFT10/01 across)
+             (("DN", "DN"), None, (24, 8, 12)),       # tangential components Dirichlet at the inflow (RODFT11)
+             (("ND", "ND"), None, (16, 12, 10)),      # REDFT10/01 with half-integer eigenvalues along u, REDFT11 across
+             (("NN", "DD"), None, (18, 10, 10)),      # REDFT00 along u (2 (n-1)-point extension: 34 = 2 x 17)
+             (None, ("DN", "NN"), (12, 16, 10)),      # the same along y
+             (None, ("ND", "DN"), (12, 24, 10)),
+             (None, ("NN", "ND"), (10, 18, 12)),
+             (("DN", "NN"), ("DD", "DD"), (16, 12, 10)),      # inflow / outflow between side walls
+             (("DD", "DD"), ("DN", "DN"), (12, 16, 10))]
+
+
+# ------------------------------------------------------------------ the Helmholtz solve of 3-D implicit diffusion in extended precision
+LD = np.longdouble
+
+
+def helmholtz_pairs(oracle, ivel):
+    """BC pairs ("PP", "DN", ...) of velocity component ivel in x, y, z, as the solve sees them (after initbc)"""
+    bc = oracle.cbcvel()
+    return [str(bc[0, d, ivel - 1]) + str(bc[1, d, ivel - 1]) for d in range(3)]
+
+
+def helmholtz_unknowns(case, oracle, ivel):
+    """points per direction that (1 + alpha L) q = q* solves for: a face that carries a Dirichlet value is no unknown -- the last face of a
+    Dirichlet-Dirichlet direction of the component's own (fft.f90:63-143), the top face of w under a Dirichlet wall (solver.f90:49)"""
+    nn = [int(x) for x in case.ng]; pr = helmholtz_pairs(oracle, ivel)
+    for d in range(2):
+        if d == ivel - 1 and pr[d] == "DD":
+            nn[d] -= 1
+    if ivel == 3 and pr[2][1] == "D":
+        nn[2] -= 1
+    return nn
+
+
+def _line_transform(pair, own, n, whole=False):
+    """One direction of the solve for a BC pair, across the component (cell-centred) or along it (face-centred), find_fft / eigenvalues of
+    fft.f90:192-245 and initsolver.f90:66-98 from their closed forms in extended precision: (forward, backward, eigenvalues per stored mode in
+    units of 1/h^2, divisor of the unnormalised pair, the same eigenvalues in the layout of the n-point line the reference stores). The transforms
+    are FFTW's unnormalised r2r kinds (scipy's default scaling is the same)."""
+    import scipy.fft as sf
+    pi = 4 * np.arctan(LD(1))
+    lam = lambda theta: -4 * np.sin(theta / 2) ** 2      # -2 (1 - cos theta) without the cancellation
+    q = np.arange(n, dtype=LD)
+    if pair == "PP" and whole:      # the second direction: its input may be complex (periodic x before it) -- all n wavenumbers; an r2r kind takes real and imaginary part alike
+        lm = lam(2 * pi * q / n)
+        return (lambda x, ax: sf.fft(x, axis=ax)), (lambda x, ax: sf.ifft(x, axis=ax, norm="forward")), lm, LD(n), lm
+    if pair == "PP":      # R2HC / HC2R: modes 0 .. n/2; half-complex slot q holds wavenumber min(q, n - q)
+        lm = lam(2 * pi * q[:n // 2 + 1] / n)
+        return (lambda x, ax: sf.rfft(x, axis=ax)), (lambda x, ax: sf.irfft(x, n=n, axis=ax, norm="forward")), lm, LD(n), lm[np.minimum(np.arange(n), n - np.arange(n))]
+    dct = lambda t: (lambda x, ax: sf.dct(x, type=t, axis=ax))
+    dst = lambda t: (lambda x, ax: sf.dst(x, type=t, axis=ax))
+    half = lam((2 * q + 1) * pi / (2 * n))
+    if not own:
+        if pair == "NN": return dct(2), dct(3), lam(q * pi / n), LD(2 * n), lam(q * pi / n)                      # REDFT10 / REDFT01
+        if pair == "DD": return dst(2), dst(3), lam((q + 1) * pi / n), LD(2 * n), lam((q + 1) * pi / n)          # RODFT10 / RODFT01
+        if pair == "ND": return dct(4), dct(4), half, LD(2 * n), half                                          # REDFT11
+        if pair == "DN": return dst(4), dst(4), half, LD(2 * n), half                                          # RODFT11
+    else:
+        if pair == "NN": return dct(1), dct(1), lam(q * pi / n), LD(2 * (n - 1)), lam(q * pi / n)                # REDFT00 of n points with eigenvalues of period n (the reference's: not an exact inverse)
+        if pair == "DD":                                                                                       # RODFT00 of n - 1 points
+            lm = lam((q[:n - 1] + 1) * pi / n)
+            return dst(1), dst(1), lm, LD(2 * n), np.concatenate([lm, [LD(0)]])
+        if pair == "ND": return dct(2), dct(3), half, LD(2 * n), half                                          # REDFT10 / REDFT01 with half-integer eigenvalues (the reference's: not exact)
+        if pair == "DN": return dst(3), dst(2), half, LD(2 * n), half                                          # RODFT01 / RODFT10
+    raise ValueError(f"no transform for the BC pair {pair!r}")
+
+
+def helmholtz_reference(case, oracle, ivel, alpha, rhs):
+    """(1 + alpha L) q = q* of 3-D implicit diffusion (main.f90:423-491, solver.f90:20-80) for velocity component ivel in np.longdouble (x87 extended
+    precision, 64-bit significand), independent of the oracle's transforms and of the library: scipy.fft on longdouble input for the transforms of x and y
+    (one per direction, by the component's BC pair and staggering as find_fft defines them), eigenvalues and normalisation from their closed forms, a
+    Thomas sweep over all modes at once for z. `rhs` is the haloed r.h.s. AFTER the boundary terms (updt_rhs_b_vel); the return value holds the unknowns
+    only (helmholtz_unknowns). It follows the reference's algorithm, the two face-centred sets that are no exact inverses of the discrete operator (NN and
+    ND along the component) included. Two things it does not copy: the +eps on every pivot of dgtsv_homebrewed (solver.f90:160-178; the pivots here are
+    >= 1, so that is one more rounding of FP64 size, far below any bar this reference is used at) and periodic z, which no case that needs it has.
+    The tridiagonal a, b, c are grid data and come from the oracle; its eigenvalues are compared with the closed forms here."""
+    pr = helmholtz_pairs(oracle, ivel)
+    if pr[2] == "PP":
+        raise NotImplementedError("helmholtz_reference: periodic z")
+    ng = [int(x) for x in case.ng]; nn = helmholtz_unknowns(case, oracle, ivel); nz = nn[2]
+    lam_o, a, b, c, _ = oracle.solver_operands(ivel)
+    x = np.array(rhs[1:nn[0] + 1, 1:nn[1] + 1, 1:nz + 1], dtype=LD)
+    tr = [_line_transform(pr[d], d == ivel - 1, ng[d], whole=d == 1) for d in range(2)]
+    h2i = [(LD(ng[d]) / LD(float(case.l[d]))) ** 2 for d in range(2)]
+    full = tr[0][4][:, None] * h2i[0] + tr[1][4][None, :] * h2i[1]
+    eps = np.finfo(np.float64).eps
+    assert np.abs(full - lam_o).max() <= 8 * eps * np.abs(full).max(), ("eigenvalues", float(np.abs(full - lam_o).max() / np.abs(full).max()))
+    x = tr[1][0](tr[0][0](x, 0), 1)
+    assert x.dtype in (np.longdouble, np.clongdouble), x.dtype
+    alpha = LD(alpha)
+    lam = tr[0][2][:, None] * h2i[0] + tr[1][2][None, :] * h2i[1]
+    aa = alpha * a[:nz].astype(LD); cc = alpha * c[:nz].astype(LD)
+    bb = 1 + alpha * (b[:nz].astype(LD)[None, None, :] + lam[:, :, None])
+    d = np.empty(bb.shape, dtype=LD)
+    z = 1 / bb[:, :, 0]; d[:, :, 0] = cc[0] * z; x[:, :, 0] = x[:, :, 0] * z
+    for l in range(1, nz):
+        z = 1 / (bb[:, :, l] - aa[l] * d[:, :, l - 1]); d[:, :, l] = cc[l] * z
+        x[:, :, l] = (x[:, :, l] - aa[l] * x[:, :, l - 1]) * z
+    for l in range(nz - 2, -1, -1):
+        x[:, :, l] = x[:, :, l] - d[:, :, l] * x[:, :, l + 1]
+    x = tr[1][1](x, 1)
+    if pr[0] != "PP":
+        x = x.real      # real x modes: the imaginary part a periodic y left is round-off
+    x = tr[0][1](x, 0)
+    assert x.dtype == np.longdouble, x.dtype
+    return x / (tr[0][3] * tr[1][3])
+
+
+def helmholtz_exact_kinds(oracle, ivel):
+    """whether the component's transform set diagonalises the discrete operator exactly: everything but NN and ND along the component"""
+    pr = helmholtz_pairs(oracle, ivel)
+    return all(not (d == ivel - 1 and pr[d] in ("NN", "ND")) for d in range(2))
+
+
+def helmholtz_operator(case, oracle, ivel, alpha, x):
+    """(1 + alpha L_h) x on the unknowns, in x's precision: second differences of the staggered component in x and y -- along the component a Dirichlet
+    face is 0 and no unknown, a Neumann face mirrors its neighbours; across it the ghost cell is -/+ the first interior value (Dirichlet / Neumann) --
+    and the tridiagonal a, b, c of the component in z (initsolver.f90:100-169). For the exact kinds only (helmholtz_exact_kinds)."""
+    pr = helmholtz_pairs(oracle, ivel); ng = [int(v) for v in case.ng]
+    assert helmholtz_exact_kinds(oracle, ivel)
+    _, a, b, c, _ = oracle.solver_operands(ivel)
+    T = x.dtype.type
+    lap = np.zeros_like(x)
+    for d in range(2):
+        h2i = (T(ng[d]) / T(float(case.l[d]))) ** 2
+        if pr[d] == "PP":
+            lap += (np.roll(x, -1, d) - 2 * x + np.roll(x, 1, d)) * h2i
+            continue
+        e = np.pad(x, [(1, 1) if ax == d else (0, 0) for ax in range(3)])
+        at = lambda i: tuple(i if ax == d else slice(None) for ax in range(3))
+        if d == ivel - 1:      # faces
+            if pr[d][0] == "N": e[at(0)] = e[at(2)]
+            if pr[d][1] == "N": e[at(-1)] = e[at(-3)]
+        else:                  # cell centres
+            e[at(0)] = -e[at(1)] if pr[d][0] == "D" else e[at(1)]
+            e[at(-1)] = -e[at(-2)] if pr[d][1] == "D" else e[at(-2)]
+        lap += (e[at(slice(2, None))] - 2 * e[at(slice(1, -1))] + e[at(slice(0, -2))]) * h2i
+    nz = x.shape[2]
+    lz = b[:nz].astype(T)[None, None, :] * x
+    lz[:, :, 1:] += a[1:nz].astype(T)[None, None, :] * x[:, :, :-1]
+    lz[:, :, :-1] += c[:nz - 1].astype(T)[None, None, :] * x[:, :, 1:]
+    return x + T(alpha) * (lap + lz)
