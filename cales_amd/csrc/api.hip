@@ -2,6 +2,7 @@
 // one entry per reference operator, the fused time step (reference src/main.f90:417-508) and the
 // HIP-event kernel timers used by bench.py's roofline line.
 #include "common.hpp"
+#include <atomic>
 
 static thread_local std::string g_create_err;
 
@@ -48,29 +49,49 @@ void prof_flush(cales_ctx *c) {
   c->pending.clear();
 }
 
-// ------------------------------------------------------------------------------------------ helpers
-static int dev_alloc(cales_ctx *c, real **p, size_t n, bool zero = true) {
+// ------------------------------------------------------------------------------------------ device memory (common.hpp)
+static std::atomic<int64_t> g_mem_bytes{0}, g_mem_allocs{0};      // over every context of the process: cales_memory_in_use(NULL)
+static void mem_record(cales_ctx *c, void *base, size_t bytes, bool pinned) {
+  c->mem.push_back({base, bytes, pinned}); c->mem_bytes += (int64_t)bytes; g_mem_bytes += (int64_t)bytes; g_mem_allocs += 1;
+}
+int ctx_alloc(cales_ctx *c, real **p, size_t n, bool zero) {
   HIPCHK(c, hipMalloc(p, (n ? n : 1) * sizeof(real)));
+  mem_record(c, *p, (n ? n : 1) * sizeof(real), false);
   if (zero) HIPCHK(c, hipMemset(*p, 0, (n ? n : 1) * sizeof(real)));
   return 0;
 }
-// 3-D fields: pitch-padded rows, shifted so that element (1,j,k) sits on a 128-B boundary (see cales_create). (Skewing the start of
-// every field by a different number of cache lines, so that the same cell of different fields does not fall on the same L2 set,
-// was measured at 512^3 with six strides and changed no kernel by more than the run-to-run noise.)
-static int field_alloc(cales_ctx *c, real **p) {
-  real *base = nullptr;
-  if (dev_alloc(c, &base, c->ntot + LINE_REALS)) return 1;
-  *p = base + c->field_ofs;
+int ctx_alloc_pinned(cales_ctx *c, real **p, size_t n) {
+  if (hipHostMalloc((void **)p, n * sizeof(real)) != hipSuccess) { c->err = "hipHostMalloc failed"; return 1; }
+  mem_record(c, *p, n * sizeof(real), true);
   return 0;
 }
-static void field_free(cales_ctx *c, real *p) { if (p) hipFree(p - c->field_ofs); }
+void ctx_free(cales_ctx *c, real *p) {
+  for (size_t q = c->mem.size(); p && q-- > 0;) if (c->mem[q].base == p) {
+    const MemBlock b = c->mem[q]; c->mem.erase(c->mem.begin() + q);
+    if (b.pinned) hipHostFree(b.base); else hipFree(b.base);
+    c->mem_bytes -= (int64_t)b.bytes; g_mem_bytes -= (int64_t)b.bytes; g_mem_allocs -= 1;
+    return;
+  }
+}
+void ctx_release_all(cales_ctx *c) { while (!c->mem.empty()) ctx_free(c, (real *)c->mem.back().base); }
+// ------------------------------------------------------------------------------------------ helpers
+// 3-D fields: pitch-padded rows, shifted so that element (1,j,k) sits on a 128-B boundary (see cales_create). (Skewing the start of
+// every field by a different number of cache lines, so that the same cell of different fields does not fall on the same L2 set,
+// was measured at 512^3 with six strides and changed no kernel by more than the run-to-run noise.) width = 2: a field of PAIRS (|S|Sij of the
+// dynamic model, SgsPath::pair), pair (1,j,k) on a 128-B boundary
+static int field_alloc(cales_ctx *c, real **p, int width = 1) {
+  real *base = nullptr;
+  if (ctx_alloc(c, &base, width * (c->ntot + LINE_REALS))) return 1;
+  *p = base + width * c->field_ofs;
+  return 0;
+}
 // k fields in ONE allocation, each right behind the one before: a kernel that addresses the first with 32-bit byte offsets reaches the others with
 // multiples of the constant c->pp_companion_bytes added (the correction pressure and its companions, the velocity and its companion: the second /
-// third ghost rows of k_corr_strain_tile on several slabs). p[0] is what field_free takes.
+// third ghost rows of k_corr_strain_tile on several slabs).
 static int field_alloc_multi(cales_ctx *c, int k, real **p) {
   real *base = nullptr;
   const size_t one = c->ntot + LINE_REALS;
-  if (dev_alloc(c, &base, (size_t)k * one)) return 1;
+  if (ctx_alloc(c, &base, (size_t)k * one)) return 1;
   for (int q = 0; q < k; ++q) p[q] = base + (size_t)q * one + c->field_ofs;
   c->pp_companion_bytes = one * sizeof(real); c->comp_one = one;
   return 0;
@@ -98,15 +119,14 @@ __global__ __launch_bounds__(256) void k_calib_rows(Geom g, long nrows, const re
   }
   if (MODE == 0 && acc == (real)1.2345e30) sink[blockIdx.x] = acc;      // never true: no write traffic
 }
-static int upload_vec(cales_ctx *c, real **p, const std::vector<real> &v) {
-  if (dev_alloc(c, p, v.size(), false)) return 1;
+int ctx_upload(cales_ctx *c, real **p, const std::vector<real> &v) {
+  if (ctx_alloc(c, p, v.size(), false)) return 1;
   HIPCHK(c, hipMemcpy(*p, v.data(), v.size() * sizeof(real), hipMemcpyHostToDevice));
   return 0;
 }
 static int upload_bound(cales_ctx *c, DBound &b, std::vector<real> h[3]) {
-  return upload_vec(c, &b.x, h[0]) || upload_vec(c, &b.y, h[1]) || upload_vec(c, &b.z, h[2]);
+  return ctx_upload(c, &b.x, h[0]) || ctx_upload(c, &b.y, h[1]) || ctx_upload(c, &b.z, h[2]);
 }
-static void free_bound(DBound &b) { hipFree(b.x); hipFree(b.y); hipFree(b.z); }
 
 extern "C" {
 
@@ -134,27 +154,23 @@ int cales_set_device(int dev) { return hipSetDevice(dev) == hipSuccess ? 0 : 1; 
 // ------------------------------------------------------------------------------------------ context
 const char *cales_last_error(const cales_ctx *ctx) { return ctx ? ctx->err.c_str() : g_create_err.c_str(); }
 
+int cales_memory_in_use(const cales_ctx *c, int64_t *bytes, int64_t *allocations) {
+  if (bytes) *bytes = c ? c->mem_bytes : g_mem_bytes.load();
+  if (allocations) *allocations = c ? (int64_t)c->mem.size() : g_mem_allocs.load();
+  return 0;
+}
+
 void cales_destroy(cales_ctx *c) {
   if (!c) return;
   hipStreamSynchronize(c->stream);
   prof_flush(c);
   for (auto &ev : c->evpool) { hipEventDestroy(ev.first); hipEventDestroy(ev.second); }
-  if (c->comm_stream) { hipStreamSynchronize(c->comm_stream); hipStreamDestroy(c->comm_stream); }
   for (auto &e : c->sync_ev) hipEventDestroy(e);
-  solver_teardown(c);
-  for (int q = 0; q < CALES_NFIELDS; ++q) field_free(c, c->f[q]);
-  for (int q = 0; q < 3; ++q) field_free(c, c->f2[q]);
-  hipFree(c->d_dzc); hipFree(c->d_dzf); hipFree(c->d_zc); hipFree(c->d_zf); hipFree(c->d_dzci); hipFree(c->d_dzfi); hipFree(c->d_gvr_c); hipFree(c->d_gvr_f);
-  DBound *bs[11] = {&c->bcu, &c->bcv, &c->bcw, &c->bcp, &c->bcs, &c->bcuf, &c->bcvf, &c->bcwf, &c->bcu_mag, &c->bcv_mag, &c->bcw_mag};
-  for (auto *b : bs) free_bound(*b);
-  for (int d = 0; d < 3; ++d) hipFree(c->rhsbp[d]);
-  field_free(c, c->scr1); hipFree(c->d_red); hipFree(c->d_force); if (c->d_mpart) hipFree(c->d_mpart); if (c->d_cs) hipFree(c->d_cs); if (c->d_stat) hipFree(c->d_stat); if (c->d_stat2) hipFree(c->d_stat2); hipHostFree(c->h_red);
-  field_free(c, c->s0); field_free(c, c->uc); field_free(c, c->vc); field_free(c, c->wc); field_free(c, c->uf); field_free(c, c->vf); field_free(c, c->wf); field_free(c, c->alph2); if (!c->p1d_in_comm) hipFree(c->d_p1d);
-  for (int m = 0; m < 6; ++m) { field_free(c, c->wk[m]); field_free(c, c->sij[m]); field_free(c, c->mij[m]); }
-  for (int m = 0; m < 3; ++m) if (c->ss2[m]) hipFree(c->ss2[m] - 2 * c->field_ofs);
-  cales_comm_release_native(c);
-  hipFree(c->d_del);
+  if (c->comm_stream) { hipStreamSynchronize(c->comm_stream); hipStreamDestroy(c->comm_stream); }
   if (c->own_stream) hipStreamDestroy(c->stream);
+  cales_comm_release_native(c);
+  solver_teardown(c);
+  ctx_release_all(c);
   delete c;
 }
 
@@ -175,20 +191,11 @@ int cales_create(const cales_case *cs, void *stream, cales_ctx **out) {
   c->C.sgstype = cs->sgstype & ~(CALES_SGS_AVE_VOLUME | CALES_SGS_AVE_XLINES);
   if (c->C.sgstype == CALES_SGS_DSMAG_FILTER2D) { c->C.sgstype = CALES_SGS_DSMAG; c->sgs.filter2d = true; }
   c->fl.read_env();      // the CALES_* switches are fixed for the life of the context
-  // zero all device pointers
-  for (auto &p : c->f) p = nullptr;
-  c->d_dzc = c->d_dzf = c->d_zc = c->d_zf = c->d_dzci = c->d_dzfi = c->d_gvr_c = c->d_gvr_f = nullptr;
-  DBound *bs[11] = {&c->bcu, &c->bcv, &c->bcw, &c->bcp, &c->bcs, &c->bcuf, &c->bcvf, &c->bcwf, &c->bcu_mag, &c->bcv_mag, &c->bcw_mag};
-  for (auto *b : bs) b->x = b->y = b->z = nullptr;
-  for (int d = 0; d < 3; ++d) c->rhsbp[d] = nullptr;
-  c->rhsbz_vel = nullptr;
-  c->scr1 = c->scr2 = c->d_red = c->h_red = c->d_force = nullptr;
-  c->s0 = c->uc = c->vc = c->wc = c->uf = c->vf = c->wf = c->alph2 = c->d_p1d = nullptr;
-  for (int m = 0; m < 6; ++m) c->wk[m] = c->sij[m] = c->mij[m] = nullptr;
-  c->sgs_first = true;
+  // (a context is whole at every stage: its members start out null, what it has allocated is in c->mem -- cales_destroy takes it as it is)
   auto fail = [&](int rc) { g_create_err = c->err; cales_destroy(c); return rc; };
-  if (stream) { c->stream = (hipStream_t)stream; c->own_stream = false; }
-  else { c->own_stream = true; if (hipStreamCreate(&c->stream) != hipSuccess) { c->own_stream = false; c->stream = 0; c->err = "hipStreamCreate failed"; return fail(4); } }
+  if (stream) c->stream = (hipStream_t)stream;
+  else if (hipStreamCreate(&c->stream) != hipSuccess) { c->stream = nullptr; c->err = "hipStreamCreate failed"; return fail(4); }
+  else c->own_stream = true;
   // geometry: y-slab of rank `rank`
   const int P = cs->nranks, r = cs->rank;
   c->P = P; c->rank = r; c->per_y = cs->cbcpre[2] == 'P' && cs->cbcpre[3] == 'P';
@@ -199,7 +206,7 @@ int cales_create(const cales_case *cs, void *stream, cales_ctx **out) {
   Geom &g = c->g;
   g.n1 = c->n[0]; g.n2 = c->n[1]; g.n3 = c->n[2];
   // Row pitch: a multiple of one cache line (128 B = 16 doubles / 32 floats) with room for the n1/2+1 complex modes of a row stored from i = 1; with the
-  // one-line-minus-one-element offset of dev_alloc, element i = 1 of every row is 128-B aligned, so kernels whose waves handle 64 consecutive
+  // one-line-minus-one-element offset of field_alloc, element i = 1 of every row is 128-B aligned, so kernels whose waves handle 64 consecutive
   // cells from i = 1 read and write whole cache lines (partial-line writes cost ~1.5x, tools/micro/wrtile.hip).
   g.s1 = (g.n1 + 3 + LINE_REALS - 1) / LINE_REALS * LINE_REALS;
   c->field_ofs = LINE_REALS - 1;
@@ -215,8 +222,8 @@ int cales_create(const cales_case *cs, void *stream, cales_ctx **out) {
     c->gvr_c[k] = c->dl[0] * c->dl[1] * c->dzc[k] / (cs->l[0] * cs->l[1] * cs->l[2]);
     c->gvr_f[k] = c->dl[0] * c->dl[1] * c->dzf[k] / (cs->l[0] * cs->l[1] * cs->l[2]);
   }
-  if (upload_vec(c, &c->d_dzc, c->dzc) || upload_vec(c, &c->d_dzf, c->dzf) || upload_vec(c, &c->d_zc, c->zc) || upload_vec(c, &c->d_zf, c->zf) ||
-      upload_vec(c, &c->d_dzci, c->dzci) || upload_vec(c, &c->d_dzfi, c->dzfi) || upload_vec(c, &c->d_gvr_c, c->gvr_c) || upload_vec(c, &c->d_gvr_f, c->gvr_f))
+  if (ctx_upload(c, &c->d_dzc, c->dzc) || ctx_upload(c, &c->d_dzf, c->dzf) || ctx_upload(c, &c->d_zc, c->zc) || ctx_upload(c, &c->d_zf, c->zf) ||
+      ctx_upload(c, &c->d_dzci, c->dzci) || ctx_upload(c, &c->d_dzfi, c->dzfi) || ctx_upload(c, &c->d_gvr_c, c->gvr_c) || ctx_upload(c, &c->d_gvr_f, c->gvr_f))
     return fail(5);
   // which faces are physical boundaries of this slab (initmpi.f90:201-204 for x-pencils; y is the decomposed direction)
   c->is_bound[0] = c->is_bound[1] = 1;
@@ -226,6 +233,7 @@ int cales_create(const cales_case *cs, void *stream, cales_ctx **out) {
   // boundary-condition tables (bound.f90:726-867)
   std::vector<real> hb[11][3];
   hs_initbc(c, hb);
+  DBound *bs[11] = {&c->bcu, &c->bcv, &c->bcw, &c->bcp, &c->bcs, &c->bcuf, &c->bcvf, &c->bcwf, &c->bcu_mag, &c->bcv_mag, &c->bcw_mag};
   for (int q = 0; q < 11; ++q) if (upload_bound(c, *bs[q], hb[q])) return fail(6);
   // walls (sgs.f90:70-83,154-171); those in y are global properties of the case, not of the slab (distances use global indices)
   for (int d = 1; d <= 3; ++d) for (int s = 0; s <= 1; ++s) c->is_wall[s + 2 * (d - 1)] = (ISB(c, s, d) && CBV(c, s, d, d) == 'D') ? 1. : 0.;
@@ -240,27 +248,20 @@ int cales_create(const cales_case *cs, void *stream, cales_ctx **out) {
     hs_bc_rhs(&cs->cbcpre[0], hb[3][0].data(), n[1], n[2], dx01, dx01, 'c', rx.data());
     hs_bc_rhs(&cs->cbcpre[2], hb[3][1].data(), n[0], n[2], dy01, dy01, 'c', ry.data());
     hs_bc_rhs(&cs->cbcpre[4], hb[3][2].data(), n[0], n[1], dzc01, dzf01, 'c', rz.data());
-    if (upload_vec(c, &c->rhsbp[0], rx) || upload_vec(c, &c->rhsbp[1], ry) || upload_vec(c, &c->rhsbp[2], rz)) return fail(7); }
+    if (ctx_upload(c, &c->rhsbp[0], rx) || ctx_upload(c, &c->rhsbp[1], ry) || ctx_upload(c, &c->rhsbp[2], rz)) return fail(7); }
   // fields (haloed); r.h.s. buffers use the same layout so every kernel shares one index
   const int nfields = cs->impdiff ? CALES_NFIELDS : CALES_DUDTD;
   // several slabs where some plan can take StepPlan::fold_rows2 (three fields under 4 GB, four rows per slab, the one-launch ghost-cell kernel):
   // companions behind u, v, w (both buffer sets) and two behind pp (common.hpp, vel_comp)
   c->vel_comp = P > 1 && fold_correc_possible(c) && c->n[1] >= 4 && 3 * (c->ntot + 2 * LINE_REALS) * sizeof(real) < (1ull << 32) && !c->fl.unmerged_bc;
-  for (int q = 0; q < nfields; ++q) {
-    if (q == CALES_PP) continue;
-    if (c->vel_comp && q <= CALES_W) { real *two[2]; if (field_alloc_multi(c, 2, two)) return fail(8); c->f[q] = two[0]; }
-    else if (field_alloc(c, &c->f[q])) return fail(8);
-  }
-  { real *three[3]; if (field_alloc(c, &c->scr1) || field_alloc_multi(c, c->vel_comp ? 3 : 2, three)) return fail(9);      // (scr2, scr3 live in pp's allocation: freed with it)
+  auto vel_field = [&](real **p) { real *two[2] = {nullptr, nullptr}; const int e = field_alloc_multi(c, c->vel_comp ? 2 : 1, two); *p = two[0]; return e; };
+  for (int q = 0; q < nfields; ++q) if (q != CALES_PP && (q <= CALES_W ? vel_field(&c->f[q]) : field_alloc(c, &c->f[q]))) return fail(8);
+  { real *three[3]; if (field_alloc(c, &c->scr1) || field_alloc_multi(c, c->vel_comp ? 3 : 2, three)) return fail(9);      // (scr2, scr3: pp's companions)
     c->f[CALES_PP] = three[0]; c->scr2 = three[1]; c->scr3 = c->vel_comp ? three[2] : nullptr; }
-  for (int q = 0; q < 3; ++q) {
-    if (c->vel_comp) { real *two[2]; if (field_alloc_multi(c, 2, two)) return fail(9); c->f2[q] = two[0]; }
-    else if (field_alloc(c, &c->f2[q])) return fail(9);
-  }
-  c->red_blocks = 8;
-  if (dev_alloc(c, &c->d_red, 64 + 16 * (size_t)(n3 + 2)) || dev_alloc(c, &c->d_force, 8)) return fail(10);
+  for (int q = 0; q < 3; ++q) if (vel_field(&c->f2[q])) return fail(9);
+  if (ctx_alloc(c, &c->d_red, 64 + 16 * (size_t)(n3 + 2)) || ctx_alloc(c, &c->d_force, 8)) return fail(10);
   c->res = c->d_red;
-  if (hipHostMalloc((void **)&c->h_red, 64 * sizeof(real)) != hipSuccess) { c->err = "hipHostMalloc failed"; return fail(11); }
+  if (ctx_alloc_pinned(c, &c->h_red, 64)) return fail(11);
   // sgs scratch (sgs.f90:70-83,154-171)
   if (c->C.sgstype >= 1) {
     if (field_alloc(c, &c->s0)) return fail(12);
@@ -269,10 +270,10 @@ int cales_create(const cales_case *cs, void *stream, cales_ctx **out) {
   }
   if (c->C.sgstype == 2) {
     if (field_alloc(c, &c->uc) || field_alloc(c, &c->vc) || field_alloc(c, &c->wc) || field_alloc(c, &c->uf) ||
-        field_alloc(c, &c->vf) || field_alloc(c, &c->wf) || (!c->sgs.filter2d && field_alloc(c, &c->alph2)) || dev_alloc(c, &c->d_p1d, 2 * (size_t)n3 + 2))
+        field_alloc(c, &c->vf) || field_alloc(c, &c->wf) || (!c->sgs.filter2d && field_alloc(c, &c->alph2)) || ctx_alloc(c, &c->d_p1d, 2 * (size_t)n3 + 2))
       return fail(13);
     if (c->sgs.pair) {      // |S|Sij as three fields of pairs between K_AC and the fused last pass: the twelve scalar scratch fields of the other forms are not needed
-      for (int m = 0; m < 3; ++m) { real *b = nullptr; if (dev_alloc(c, &b, 2 * c->ntot + 2 * LINE_REALS)) return fail(13); c->ss2[m] = b + 2 * c->field_ofs; }
+      for (int m = 0; m < 3; ++m) if (field_alloc(c, &c->ss2[m], 2)) return fail(13);
     } else
     for (int m = 0; m < 6; ++m) if (field_alloc(c, &c->sij[m]) || field_alloc(c, &c->mij[m])) return fail(13);
   }
@@ -683,9 +684,7 @@ int cales_set_comm(cales_ctx *c, cales_halo_cb halo, cales_alltoall_cb a2a, cale
   // reduction results live in the tail of A so that the host can all-reduce them in place
   const int64_t tail = CALES_RES_TAIL + 2 * (int64_t)(c->n[2] + 2);
   c->res = bufA + (nbuf - tail);
-  if (c->d_p1d && !c->p1d_in_comm) hipFree(c->d_p1d);      // a second call must not free the interior pointer set by the first
   c->d_p1d = c->res + 64;
-  c->p1d_in_comm = true;
   return 0;
 }
 int cales_set_comm_overlap(cales_ctx *c, cales_halo_s_cb halo_s, cales_alltoall_part_cb a2a_part) {
@@ -722,8 +721,9 @@ int cales_calibrate(cales_ctx *c, int reps, real gbps[3], int64_t *bytes_per_str
   const long nrows = (long)(c->n[1] + 2) * (c->n[2] + 2);
   const double bytes = (double)nrows * c->n[0] * sizeof(real);
   if (bytes_per_stream) *bytes_per_stream = (int64_t)bytes;
-  hipEvent_t e0, e1;
-  HIPCHK(c, hipEventCreate(&e0)); HIPCHK(c, hipEventCreate(&e1));
+  struct Event { hipEvent_t e = nullptr; ~Event() { if (e) hipEventDestroy(e); } } ev0, ev1;      // destroyed on every return
+  HIPCHK(c, hipEventCreate(&ev0.e)); HIPCHK(c, hipEventCreate(&ev1.e));
+  const hipEvent_t e0 = ev0.e, e1 = ev1.e;
   const dim3 gr(256 * 16), bl(256);
   const real *a = c->f[CALES_U]; real *b = c->scr1;      // scr1: scratch between operators
   auto run = [&](int mode) {
@@ -741,7 +741,6 @@ int cales_calibrate(cales_ctx *c, int reps, real gbps[3], int64_t *bytes_per_str
     if (hipEventElapsedTime(&ms, e0, e1) != hipSuccess || !(ms > 0.f)) { rc = 1; break; }
     gbps[mode] = (real)((mode == 2 ? 2. : 1.) * bytes * reps / (ms * 1e-3) / 1e9);
   }
-  hipEventDestroy(e0); hipEventDestroy(e1);
   if (rc) { c->err = "cales_calibrate: event timing failed"; return rc; }
   LAUNCHCHK(c);
   return 0;

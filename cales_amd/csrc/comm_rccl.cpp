@@ -156,7 +156,7 @@ int cales_comm_unique_id(void *id_out) {
   return 0;
 }
 
-// Collective over all ranks of the decomposition: joins the RCCL communicator, allocates the two staging buffers and
+// Collective over all ranks of the decomposition: joins the RCCL communicator, allocates the two staging buffers (the context's) and
 // registers the native exchanges (instead of cales_set_comm).
 int cales_comm_init_rccl(cales_ctx *c, const void *id_in) {
   if (!c || !id_in) return 1;
@@ -167,20 +167,17 @@ int cales_comm_init_rccl(cales_ctx *c, const void *id_in) {
   const ncclResult_t r = g_api.CommInitRank(&nc->comm, c->P, id, c->rank);
   if (r != ncclSuccess) { c->err = std::string("ncclCommInitRank: ") + g_api.GetErrorString(r); delete nc; return 1; }
   int64_t n = 0; cales_comm_buffer_doubles(c, &n);
-  if (hipMalloc(&nc->A, n * sizeof(real)) != hipSuccess || hipMalloc(&nc->B, n * sizeof(real)) != hipSuccess) {
-    c->err = "cales_comm_init_rccl: hipMalloc of the staging buffers failed"; g_api.CommDestroy(nc->comm); hipFree(nc->A); delete nc; return 1;
-  }
-  c->native_comm = nc;
+  c->native_comm = nc;      // (from here on cales_destroy releases it)
+  if (ctx_alloc(c, &nc->A, (size_t)n, false) || ctx_alloc(c, &nc->B, (size_t)n, false)) return 1;
   if (int e = cales_set_comm(c, native_halo, native_alltoall, native_allreduce, c, nc->A, nc->B, n)) return e;
   return cales_set_comm_overlap(c, native_halo_s, native_alltoall_part);
 }
 
-// called by cales_destroy
+// called by cales_destroy, before the context's memory (the staging buffers with it) goes
 void cales_comm_release_native(cales_ctx *c) {
   NativeComm *nc = static_cast<NativeComm *>(c->native_comm);
   if (!nc) return;
   if (nc->comm && g_api.CommDestroy) g_api.CommDestroy(nc->comm);
-  hipFree(nc->A); hipFree(nc->B);
   delete nc; c->native_comm = nullptr;
 }
 

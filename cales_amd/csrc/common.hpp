@@ -36,7 +36,7 @@ struct Geom {              // passed by value to kernels
   __host__ __device__ inline size_t ix(int i, int j, int k) const { return (size_t)i + (size_t)s1 * (size_t)j + (size_t)s12 * (size_t)k; }
 };
 
-struct DBound { real *x, *y, *z; };
+struct DBound { real *x = nullptr, *y = nullptr, *z = nullptr; };
 // Boundary term of an inhomogeneous z condition in the r.h.s. of a velocity Helmholtz solve (cmpt_rhs_b / bc_rhs, bound.f90:447-560, times alpha, main.f90:432):
 // one side of one component; `at` evaluates it for column (i, j) with the operations of the reference in their order. Used by k_rhs_b_velz (the term as a
 // pass of its own / as a plane) and by the in-LDS Helmholtz sweep, which adds it while it loads plane 1 / n.
@@ -226,53 +226,52 @@ struct FusedFill { real dtrki = 0.; int mean_mask = 0; };
 
 struct KernelStat { std::string name; int64_t calls = 0; real ms = 0.; };
 struct Solver;      // k_solver.hip
+struct MemBlock { void *base; size_t bytes; bool pinned; };      // one allocation of a context ("who owns device memory")
 
 struct cales_ctx {
-  cales_case C;
+  cales_case C{};
   Flags fl;
   StepPlan plan;      // see StepPlan above
-  Geom g;
-  int n[3], lo[3];
-  real dl[3], dli[3], visc;
-  hipStream_t stream; bool own_stream;
+  Geom g{};
+  int n[3] = {0, 0, 0}, lo[3] = {1, 1, 1};
+  real dl[3] = {0., 0., 0.}, dli[3] = {0., 0., 0.}, visc = 0.;
+  hipStream_t stream = nullptr; bool own_stream = false;
   hipStream_t comm_stream = nullptr;      // exchanges that overlap kernels (created by cales_set_comm_overlap)
   std::vector<hipEvent_t> sync_ev; size_t sync_next = 0;      // ordering events between the two streams (no timing), reused round-robin
   std::string err;
   std::string launch_err;      // first failed kernel launch / attribute call (LAUNCH below): the context is failed from then on
   // host copies of the grid
   std::vector<real> dzc, dzf, zc, zf, dzci, dzfi, gvr_c, gvr_f;
-  char cbcvel[18];
-  int is_bound[6], index_wm[6];
+  char cbcvel[18] = {};
+  int is_bound[6] = {}, index_wm[6] = {};
+  std::vector<MemBlock> mem; int64_t mem_bytes = 0;      // every device and pinned-host allocation of the context, temporaries of a call included (ctx_alloc)
   // device grid (0:n3+1)
-  real *d_dzc, *d_dzf, *d_zc, *d_zf, *d_dzci, *d_dzfi, *d_gvr_c, *d_gvr_f;
+  real *d_dzc = nullptr, *d_dzf = nullptr, *d_zc = nullptr, *d_zf = nullptr, *d_dzci = nullptr, *d_dzfi = nullptr, *d_gvr_c = nullptr, *d_gvr_f = nullptr;
   // fields
-  real *f[CALES_NFIELDS];
+  real *f[CALES_NFIELDS] = {};
   real *f2[3] = {nullptr, nullptr, nullptr};   // second velocity buffers of the fused mom+RK kernel (pointers are swapped with f[U..W])
-  size_t ntot;
+  size_t ntot = 0;
   // BC planes
   DBound bcu, bcv, bcw, bcp, bcs, bcuf, bcvf, bcwf, bcu_mag, bcv_mag, bcw_mag;
-  real *rhsbp[3];        // (na,nb,0:1)
-  real *rhsbz_vel;       // scratch (n1,n2,0:1) for z-implicit Helmholtz r.h.s.
+  real *rhsbp[3] = {nullptr, nullptr, nullptr};        // (na,nb,0:1)
   // solver
-  // k_solver.hip: plans, tables and the path of every solved field; the z solves' coefficients, chunked tables and scratch (solver_setup / solver_teardown)
+  // k_solver.hip: plans, tables and the path of every solved field; the z solves' coefficients, chunked tables and scratch (solver_setup; the device tables are the context's memory)
   Solver *solver = nullptr;
-  real *scr1, *scr2;         // solver scratch (haloed size)
+  real *scr1 = nullptr, *scr2 = nullptr;         // solver scratch (haloed size)
   // reductions
-  real *d_red; real *h_red;       // partial sums / results (pinned host)
-  real *d_force;                    // f(3) + dpdl(3) accumulators on device
-  int red_blocks;
+  real *d_red = nullptr; real *h_red = nullptr;       // partial sums / results (pinned host)
+  real *d_force = nullptr;                    // f(3) + dpdl(3) accumulators on device
   // sgs scratch
   real *ss2[3] = {nullptr, nullptr, nullptr};      // |S|Sij as three pair fields (2 ntot reals each; SgsPath::pair) instead of sij / mij
-  real *s0, *wk[6], *sij[6], *mij[6], *uc, *vc, *wc, *uf, *vf, *wf, *alph2, *d_p1d;
-  real is_wall[6];
+  real *s0 = nullptr, *wk[6] = {}, *sij[6] = {}, *mij[6] = {}, *uc = nullptr, *vc = nullptr, *wc = nullptr, *uf = nullptr, *vf = nullptr, *wf = nullptr, *alph2 = nullptr, *d_p1d = nullptr;
+  real is_wall[6] = {};
   SgsPath sgs;      // see SgsPath above
   BcPath bc;        // see BcPath above
   MomPath mom;      // see MomPath above
-  bool sgs_first;
+  bool sgs_first = true;
   // decomposition
   int P = 1, rank = 0; bool per_y = true; int cw = 0;      // cw: complex mode columns per rank (padded)
   Comm comm;
-  bool p1d_in_comm = false;
   real *res = nullptr;                // reduction results (inside comm.A when comm is on, so they can be all-reduced)
   // profiling
   bool prof = false;
@@ -280,7 +279,7 @@ struct cales_ctx {
   std::vector<std::pair<int, std::pair<hipEvent_t, hipEvent_t>>> pending;
   std::vector<std::pair<hipEvent_t, hipEvent_t>> evpool;
   real *d_del = nullptr;   // Smagorinsky filter width per plane (fast path)
-  void *native_comm = nullptr;   // RCCL communicator + staging buffers when the library does the exchanges itself (comm_rccl.cpp)
+  void *native_comm = nullptr;   // RCCL communicator when the library does the exchanges itself (comm_rccl.cpp)
   bool visct_zero = true;  // CALES_VISCT still holds the zeros it was created / reset with (no SGS model: lets kernels skip it)
   // dynamic model, fast path: the eddy-viscosity field holds |S| and d_cs(0:n3+1) the clipped plane coefficients <LM>/<MM> until somebody
   // other than the fused momentum kernel reads it (materialize_visct); visct = |S| * cs(k) is the same product either way
@@ -365,6 +364,18 @@ struct ProfScope {
   ~ProfScope() { if (slot >= 0) prof_end(c, slot, s); }
 };
 
+// ---- device memory (api.hip): n reals (at least one) until cales_destroy (ctx_release_all), zeroed on request; ctx_free gives one allocation back early
+int  ctx_alloc(cales_ctx *c, real **p, size_t n, bool zero = true);
+int  ctx_alloc_pinned(cales_ctx *c, real **p, size_t n);
+int  ctx_upload(cales_ctx *c, real **p, const std::vector<real> &v);      // ... holding a copy of a host table
+void ctx_free(cales_ctx *c, real *p);
+void ctx_release_all(cales_ctx *c);
+struct CtxTemp {      // n reals for the length of a scope, released on every return (p null: the allocation failed, c->err says why)
+  cales_ctx *c; real *p = nullptr;
+  CtxTemp(cales_ctx *c_, size_t n) : c(c_) { ctx_alloc(c, &p, n, false); }
+  CtxTemp(const CtxTemp &) = delete;
+  ~CtxTemp() { ctx_free(c, p); }
+};
 // ---- host-side set-up (host_setup.cpp)
 void   hs_initgrid(int gtype, int n, real gr, real lz, real *dzc, real *dzf, real *zc, real *zf);
 void   hs_initbc(cales_ctx *c, std::vector<real> hb[11][3]);
@@ -419,7 +430,7 @@ int op_xwrap_zghost(cales_ctx *c, int nf, real **f);      // periodic copy of th
 int op_chkdt(cales_ctx *c, real *dtmax);
 int op_chkdiv(cales_ctx *c, real *divtot, real *divmax);
 int solver_setup(cales_ctx *c);
-void solver_teardown(cales_ctx *c);
+void solver_teardown(cales_ctx *c);      // (the host-side struct; its tables go with the context's memory)
 
 // XCD-aware block order for the one-plane-per-block stencil kernels (grid = x tiles, y tiles, z planes).
 // Workgroups are dealt round-robin to the 8 XCDs, each with its private 4 MiB L2 (MI355X_MICROARCH.md, "Workgroup

@@ -1582,7 +1582,7 @@ static int dsmag_fast(cales_ctx *c, const SgsFold *fold, bool *visct_ghosts_done
   if (P.ave == SgsAve::volume) LAUNCH(c, k_volume_fold, dim3(1), dim3(256), 0, c->stream, n[2], c->d_dzf, c->d_p1d);      // sgs.f90:360-361
   const real gar = c->dl[0] * c->dl[1] / (c->C.l[0] * c->C.l[1]);
   if (P.lazy) {
-    if (!c->d_cs) HIPCHK(c, hipMalloc(&c->d_cs, (n[2] + 2) * sizeof(real)));
+    if (!c->d_cs && ctx_alloc(c, &c->d_cs, n[2] + 2, false)) return 1;
     LAUNCH(c, k_dsmag_coef, dim3(1), dim3(256), 0, c->stream, n[2], gar, c->d_p1d, c->d_cs, P.perz);
     c->visct_lazy = true;
   } else LAUNCH(c, k_dsmag_final, gr, b, 0, c->stream, c->g, gar, c->d_p1d, c->s0, visct);
@@ -1599,7 +1599,7 @@ __global__ void k_smag_del(int n, real dl1, real dl2, const real *__restrict__ d
 // c->d_del, made by the first Smagorinsky pass that needs it
 static int smag_del(cales_ctx *c) {
   if (c->d_del) return 0;
-  HIPCHK(c, hipMalloc(&c->d_del, (c->n[2] + 2) * sizeof(real)));
+  if (ctx_alloc(c, &c->d_del, c->n[2] + 2, false)) return 1;
   LAUNCH(c, k_smag_del, dim3((c->n[2] + 2 + 63) / 64), dim3(64), 0, c->stream, c->n[2] + 2, c->dl[0], c->dl[1], c->d_dzf, c->d_del);
   return 0;
 }

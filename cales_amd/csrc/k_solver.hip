@@ -15,7 +15,7 @@
 #include "common.hpp"
 
 // (aligned to its own size: LDS and global accesses of a complex value are ONE 128-bit operation -- ds_read_b128 at 256 B/clk instead of ds_read2_b64 at
-//  128, MI355X_MICROARCH.md "LDS"; every cpx array here starts on a 16-byte boundary: hipMalloc'ed tables, the __align__(16) dynamic LDS block)
+//  128, MI355X_MICROARCH.md "LDS"; every cpx array here starts on a 16-byte boundary: the context's device tables, the __align__(16) dynamic LDS block)
 struct __attribute__((aligned(2 * sizeof(real)))) cpx { real x, y; };
 __device__ inline cpx cadd(cpx a, cpx b) { return {a.x + b.x, a.y + b.y}; }
 __device__ inline cpx csub(cpx a, cpx b) { return {a.x - b.x, a.y - b.y}; }
@@ -1953,18 +1953,14 @@ static int upload_twiddles(cales_ctx *c, int N, int cnt, real **dev) {
   std::vector<real> t(2 * (size_t)cnt);
   const real pi = std::acos(-1.0);
   for (int q = 0; q < cnt; ++q) { const real ang = -2. * pi * q / N; t[2 * q] = std::cos(ang); t[2 * q + 1] = std::sin(ang); }
-  HIPCHK(c, hipMalloc(dev, t.size() * sizeof(real)));
-  HIPCHK(c, hipMemcpy(*dev, t.data(), t.size() * sizeof(real), hipMemcpyHostToDevice));
-  return 0;
+  return ctx_upload(c, dev, t);
 }
 // DCT-IV weights of n-point lines (k_fft_x4, k_fft_y4): e^{-i pi (4q+1)/(4n)}, then e^{-i pi q/n}, q < n/2
 static int upload_dct4_weights(cales_ctx *c, int n, real **dev) {
   const int nh = n / 2; std::vector<real> t(4 * (size_t)nh); const real pi = std::acos(-1.0);
   for (int q = 0; q < nh; ++q) { const real a1 = -pi * (4. * q + 1.) / (4. * n), a2 = -pi * q / (real)n;
                                  t[2 * q] = std::cos(a1); t[2 * q + 1] = std::sin(a1); t[2 * (nh + q)] = std::cos(a2); t[2 * (nh + q) + 1] = std::sin(a2); }
-  HIPCHK(c, hipMalloc(dev, t.size() * sizeof(real)));
-  HIPCHK(c, hipMemcpy(*dev, t.data(), t.size() * sizeof(real), hipMemcpyHostToDevice));
-  return 0;
+  return ctx_upload(c, dev, t);
 }
 // DCT-IV / DST-IV in y (k_fft_y4): N/2-point lines, two per complex column -- plans and tables made by the first path that needs them
 static int dct4_y_setup(cales_ctx *c, Solver &s, const char *who) {
@@ -2098,19 +2094,18 @@ int solver_setup(cales_ctx *c) {
     P.nyq = P.xkind == 0 && P.ykind <= 1 && s.x8 && s.y8 && !P.periodic_z && (hasd || !c->fl.keep_null_mode) && tile_takes(c, n3, false) && !c->fl.no_nyquist_packing;
     if (P.nyq && P.zk != ZKernel::tile) { c->err = "solver: the packed mode column needs the z solve in the LDS tile"; return 1; }
     P.cw = P.nyq ? (n1 / 2 + c->P - 1) / c->P : c->cw; }
-  HIPCHK(c, hipMalloc(&P.lamx, (n1 + 2) * sizeof(real))); HIPCHK(c, hipMalloc(&P.lamy, n2g * sizeof(real)));
-  HIPCHK(c, hipMemcpy(P.lamx, lx.data(), (n1 + 2) * sizeof(real), hipMemcpyHostToDevice));
-  HIPCHK(c, hipMemcpy(P.lamy, ly.data(), n2g * sizeof(real), hipMemcpyHostToDevice));
+  if (ctx_upload(c, &P.lamx, lx) || ctx_upload(c, &P.lamy, ly)) return 1;
   // tridiagonal (initsolver.f90:127-169), pressure: cell-centred
   std::vector<real> abc(3 * (size_t)n3);      // a | b | c
   hs_tridmatrix(&c->C.cbcpre[4], n3, c->dzci.data(), c->dzfi.data(), 'c', abc.data(), abc.data() + n3, abc.data() + 2 * n3);
-  HIPCHK(c, hipMalloc(&s.d_a, abc.size() * sizeof(real))); s.d_b = s.d_a + n3; s.d_c = s.d_a + 2 * n3;
-  HIPCHK(c, hipMemcpy(s.d_a, abc.data(), abc.size() * sizeof(real), hipMemcpyHostToDevice));
+  if (ctx_upload(c, &s.d_a, abc)) return 1;
+  s.d_b = s.d_a + n3; s.d_c = s.d_a + 2 * n3;
   if (P.zk == ZKernel::tile) {      // the pressure's tile and its table, built here once
-    HIPCHK(c, hipMalloc(&s.tab_pres, TILE_TAB * sizeof(real))); tile_setup(c, P, s.tab_pres);
+    if (ctx_alloc(c, &s.tab_pres, TILE_TAB, false)) return 1;
+    tile_setup(c, P, s.tab_pres);
     tile_table(c, P.zt.M, P.zt.PER ? n3 - 1 : n3, s.d_a, s.d_b, s.d_c, s.tab_pres);
   }
-  if (P.refnull) HIPCHK(c, hipMalloc(&s.d_nullw, (size_t)5 * (n3 + 2) * sizeof(real)));
+  if (P.refnull && ctx_alloc(c, &s.d_nullw, (size_t)5 * (n3 + 2), false)) return 1;
   P.normfft = 1. / ((P.xkind ? 2. : 1.) * (real)n1 * (P.ykind ? 2. : 1.) * (real)n2g);   // fft.f90:99,136,142; find_fft norm = [1,0] (PP) / [2,0] (NN)
   if (upload_twiddles(c, n1 / 2, n1 / 2, &s.twx)) return 1;
   if (upload_twiddles(c, n1, n1 / 2 + 1, &s.twx_post)) return 1;
@@ -2121,11 +2116,11 @@ int solver_setup(cales_ctx *c) {
   if (!c->C.impdiff) return 0;
   for (int iv = 0; iv < 3; ++iv) {
     hs_tridmatrix(&c->cbcvel[6 * iv + 4], n3, c->dzci.data(), c->dzfi.data(), iv == 2 ? 'f' : 'c', abc.data(), abc.data() + n3, abc.data() + 2 * n3);
-    HIPCHK(c, hipMalloc(&s.d_av[iv], abc.size() * sizeof(real))); s.d_bv[iv] = s.d_av[iv] + n3; s.d_cv[iv] = s.d_av[iv] + 2 * n3;
-    HIPCHK(c, hipMemcpy(s.d_av[iv], abc.data(), abc.size() * sizeof(real), hipMemcpyHostToDevice));
+    if (ctx_upload(c, &s.d_av[iv], abc)) return 1;
+    s.d_bv[iv] = s.d_av[iv] + n3; s.d_cv[iv] = s.d_av[iv] + 2 * n3;
   }
-  HIPCHK(c, hipMalloc(&s.d_scaled, (size_t)5 * n3 * sizeof(real))); HIPCHK(c, hipMemset(s.d_scaled, 0, (size_t)5 * n3 * sizeof(real)));
-  if (c->C.impdiff == 1) HIPCHK(c, hipMalloc(&s.tab_imp3d, TILE_TAB * sizeof(real)));      // (the paths themselves on first use: velocity_path_ready)
+  if (ctx_alloc(c, &s.d_scaled, (size_t)5 * n3)) return 1;
+  if (c->C.impdiff == 1 && ctx_alloc(c, &s.tab_imp3d, TILE_TAB, false)) return 1;      // (the paths themselves on first use: velocity_path_ready)
   if (c->C.impdiff != 2) return 0;
   // the z-only sweeps: the in-LDS tile of the pressure solve on the real field (u, dudtd in, u out: 3 words instead of 5) where its nz + q planes fit
   for (int iv = 0; iv < 3; ++iv) {
@@ -2136,18 +2131,11 @@ int solver_setup(cales_ctx *c) {
     if (H.form != HzForm::tile) continue;
     H.T.nolam = 1; H.T.nq = n3; H.zt.M = tile_m(H.nz); H.zt.NV = 2; H.zt.ndbl = n[0]; H.zt.nrow = n[1];
     for (int dud = 0; dud <= 1; ++dud) { H.zt.DUD = dud; tile_attr(c, H.zt); }      // as the operator runs it | inside cales_step, forming its r.h.s.
-    if (!s.tab_hz) HIPCHK(c, hipMalloc(&s.tab_hz, (size_t)12 * TILE_TAB * sizeof(real)));
+    if (!s.tab_hz && ctx_alloc(c, &s.tab_hz, (size_t)12 * TILE_TAB, false)) return 1;
   }
   return 0;
 }
-void solver_teardown(cales_ctx *c) {
-  if (Solver *s = c->solver) {
-    for (const SolvePath *P : {&s->pres, &s->vel[0], &s->vel[1], &s->vel[2]}) { hipFree(P->lamx); hipFree(P->lamy); hipFree(P->tw1x); hipFree(P->tw1y); }
-    for (real *t : {s->twx, s->twx_post, s->twy, s->twy_post, s->twyd, s->tw4x, s->tw4y, s->twy4}) hipFree(t);
-    for (real *t : {s->d_a, s->d_av[0], s->d_av[1], s->d_av[2], s->d_scaled, s->tab_pres, s->tab_imp3d, s->tab_hz, s->d_nullw}) hipFree(t);
-    delete s; c->solver = nullptr;
-  }
-}
+void solver_teardown(cales_ctx *c) { delete c->solver; c->solver = nullptr; }
 
 // CALES_KEEP_NULL_MODE: the zero-eigenvalue column of a singular pressure problem (no Dirichlet condition in z) solved in the REFERENCE's own
 // sequential order -- dgtsv_homebrewed / gaussel_periodic with their +eps pivots, solver.f90:109-179, one operation at a time, no contraction.
@@ -2347,7 +2335,8 @@ static int solve_field(cales_ctx *c, const SolvePath &P, real *pp, const real *d
     F.xwrap = c->step_xskip ? n[0] : 0;
     if (F.mean_mask) {
       const size_t need = 3 * (size_t)xblk_f * NCH;
-      if (c->n_mpart < need) { if (c->d_mpart) hipFree(c->d_mpart); HIPCHK(c, hipMalloc(&c->d_mpart, need * sizeof(real))); c->n_mpart = need; }
+      // (the one buffer that may grow: the pipelined exchange, which cales_set_comm_overlap may switch on between two steps, cuts the rows into other blocks)
+      if (c->n_mpart < need) { ctx_free(c, c->d_mpart); c->d_mpart = nullptr; if (ctx_alloc(c, &c->d_mpart, need, false)) return 1; c->n_mpart = need; }
       F.part = c->d_mpart; if (pipe) F.pstride = (int)(xblocks_c * NCH);
     }
   }
@@ -2571,9 +2560,7 @@ static int velocity_path(cales_ctx *c, Solver &s, int iv, SolvePath &V) {
   for (auto &v : lx) v = v * (c->dli[0] * c->dli[0]);
   for (auto &v : ly) v = v * (c->dli[1] * c->dli[1]);
   if (V.ykind == 2) std::reverse(ly.begin(), ly.end());      // see solver_setup
-  HIPCHK(c, hipMalloc(&V.lamx, (n1 + 2) * sizeof(real))); HIPCHK(c, hipMalloc(&V.lamy, n2g * sizeof(real)));
-  HIPCHK(c, hipMemcpy(V.lamx, lx.data(), (n1 + 2) * sizeof(real), hipMemcpyHostToDevice));
-  HIPCHK(c, hipMemcpy(V.lamy, ly.data(), n2g * sizeof(real), hipMemcpyHostToDevice));
+  if (ctx_upload(c, &V.lamx, lx) || ctx_upload(c, &V.lamy, ly)) return 1;
   // fft.f90:99,136,142: normfft = prod norm(1) (n + norm(2) - ix): 1 n (PP), 2 n ('c' pairs, 'f' ND/DN), 2 (n + 1 - 1) ('f' DD), 2 (n - 1) ('f' NN)
   auto nrm = [](int kd, int nn) -> real { return kd == 0 ? (real)nn : kd == 6 ? 2. * (nn - 1) : 2. * nn; };
   V.normfft = 1. / (nrm(V.xkind, n1) * nrm(V.ykind, n2g));

@@ -520,7 +520,7 @@ int op_stats_chan(cales_ctx *c, real *buf) {
   if (int e = materialize_visct(c)) return e;
   const int nbx = 8, n3 = c->n[2];
   const size_t need = (size_t)NSTAT * n3 * (nbx + 1);
-  if (!c->d_stat) HIPCHK(c, hipMalloc(&c->d_stat, need * sizeof(real)));
+  if (!c->d_stat && ctx_alloc(c, &c->d_stat, need, false)) return 1;
   real *part = c->d_stat, *out = c->d_stat + (size_t)NSTAT * n3 * nbx;
   LAUNCH(c, k_stats_chan_partial, dim3(nbx, n3), dim3(256), 0, c->stream, c->g, c->dl[0], c->dl[1], c->d_dzc, c->d_dzf, c->f[CALES_U], c->f[CALES_V],
                      c->f[CALES_W], c->f[CALES_P], c->f[CALES_VISCT], part);
@@ -640,7 +640,7 @@ __global__ void k_stats_leak_fold(int n3, int nbx, real ratio, const real *__res
 int op_stats_chan_budget(cales_ctx *c, real *budget, real *leak) {
   const int nbx = 8, n3 = c->n[2];
   const size_t need = (size_t)NBUDGET * n3 * (nbx + 1);
-  if (!c->d_stat2) HIPCHK(c, hipMalloc(&c->d_stat2, need * sizeof(real)));
+  if (!c->d_stat2 && ctx_alloc(c, &c->d_stat2, need, false)) return 1;
   real *part = c->d_stat2, *out = c->d_stat2 + (size_t)NBUDGET * n3 * nbx;
   const real ratio = c->dl[0] * c->dl[1] / (c->C.l[0] * c->C.l[1]);
   if (budget) {
@@ -684,14 +684,13 @@ int op_out1d(cales_ctx *c, int field, int idir, int use_dzc, real *buf) {
   if (field < 0 || field >= CALES_NFIELDS || idir < 1 || idir > 3) { c->err = "cales_out1d: bad field or direction"; return 1; }
   if (field == CALES_VISCT) if (int e = materialize_visct(c)) return e;
   const int ne = c->n[idir - 1];
-  real *out = nullptr; HIPCHK(c, hipMalloc(&out, (size_t)ne * sizeof(real)));
+  CtxTemp tmp(c, (size_t)ne); real *out = tmp.p; if (!out) return 1;
   // grid_area_ratio of the reference: dl(1) dl(2) / (l(1) l(2)) along z, dl(1) / (l(1) l(3)) along y, dl(2) / (l(2) l(3)) along x
   const real ratio = idir == 3 ? c->dl[0] * c->dl[1] / (c->C.l[0] * c->C.l[1]) : idir == 2 ? c->dl[0] / (c->C.l[0] * c->C.l[2]) : c->dl[1] / (c->C.l[1] * c->C.l[2]);
   LAUNCH(c, k_out1d, dim3(ne), dim3(256), 0, c->stream, c->g, idir, ratio, use_dzc ? c->d_dzc : c->d_dzf, c->f[field], out);
   LAUNCHCHK(c);
   HIPCHK(c, hipMemcpyAsync(buf, out, (size_t)ne * sizeof(real), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  hipFree(out);
   return 0;
 }
 // out1d_chan (output.f90:317-405, idir = 3): um, vm, wm, u2, v2, w2, uw per plane
@@ -712,12 +711,11 @@ __global__ __launch_bounds__(256) void k_out1d_chan(Geom g, real ratio, const re
 }
 int op_out1d_chan(cales_ctx *c, real *buf) {
   const int n3 = c->n[2];
-  real *out = nullptr; HIPCHK(c, hipMalloc(&out, (size_t)7 * n3 * sizeof(real)));
+  CtxTemp tmp(c, (size_t)7 * n3); real *out = tmp.p; if (!out) return 1;
   LAUNCH(c, k_out1d_chan, dim3(n3), dim3(256), 0, c->stream, c->g, c->dl[0] * c->dl[1] / (c->C.l[0] * c->C.l[1]), c->f[CALES_U], c->f[CALES_V], c->f[CALES_W], out);
   LAUNCHCHK(c);
   HIPCHK(c, hipMemcpyAsync(buf, out, (size_t)7 * n3 * sizeof(real), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  hipFree(out);
   return 0;
 }
 // out2d_duct (output.f90:406-507, streamwise direction x): nine cell-centred averages along x for every (j, k); one wave per (j, k)
@@ -738,12 +736,11 @@ __global__ __launch_bounds__(256) void k_out2d_duct(Geom g, real ratio, const re
 }
 int op_out2d_duct(cales_ctx *c, real *buf) {
   const int n2 = c->n[1], n3 = c->n[2];
-  real *out = nullptr; HIPCHK(c, hipMalloc(&out, (size_t)9 * n2 * n3 * sizeof(real)));
+  CtxTemp tmp(c, (size_t)9 * n2 * n3); real *out = tmp.p; if (!out) return 1;
   LAUNCH(c, k_out2d_duct, dim3((n2 + 3) / 4, n3), dim3(256), 0, c->stream, c->g, c->dl[0] / c->C.l[0], c->f[CALES_U], c->f[CALES_V], c->f[CALES_W], out);
   LAUNCHCHK(c);
   HIPCHK(c, hipMemcpyAsync(buf, out, (size_t)9 * n2 * n3 * sizeof(real), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  hipFree(out);
   return 0;
 }
 

@@ -115,6 +115,9 @@ module cales_c
     integer(c_int) function cales_calibrate(ctx,reps,gbps,nbytes) bind(C,name='cales_calibrate')
       import; type(c_ptr), value :: ctx; integer(c_int), value :: reps; real(c_rp) :: gbps(3); integer(c_int64_t) :: nbytes
     end function
+    integer(c_int) function cales_memory_in_use(ctx,nbytes,nalloc) bind(C,name='cales_memory_in_use')
+      import; type(c_ptr), value :: ctx; integer(c_int64_t) :: nbytes, nalloc
+    end function
     integer(c_int) function cales_fillps(ctx,dtrki) bind(C,name='cales_fillps')
       import; type(c_ptr), value :: ctx; real(c_rp), value :: dtrki
     end function

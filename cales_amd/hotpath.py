@@ -71,6 +71,14 @@ def check_case(case: Case, nranks: int = 1) -> None:
         raise CalesError("*** Simulation aborted due to errors in the input file *** " + buf.value.decode())
 
 
+def memory_in_use(handle=None) -> Tuple[int, int]:
+    """(bytes, allocations) of device and pinned-host memory held by one context, or with no handle by every context of this process."""
+    b, n = C.c_int64(0), C.c_int64(0)
+    if capi.lib().cales_memory_in_use(handle, C.byref(b), C.byref(n)):
+        raise CalesError("cales_memory_in_use failed")
+    return int(b.value), int(n.value)
+
+
 class HotPath:
     def __init__(self, case: Case, nranks: int = 1, rank: int = 0, stream: int | None = None):
         self.case = case
@@ -269,6 +277,10 @@ class HotPath:
             self.L.cales_profile_get(self.h, i, name, 64, C.byref(calls), C.byref(ms))
             out[name.value.decode()] = (calls.value, ms.value)
         return out
+
+    def memory_in_use(self) -> Tuple[int, int]:
+        """(bytes, allocations) this context holds on the device and in pinned host memory right now (cales_memory_in_use)."""
+        return memory_in_use(self.h)
 
     def device_info(self) -> Tuple[str, int]:
         name = C.create_string_buffer(128); b = C.c_int64(0)

@@ -85,6 +85,10 @@ int  cales_create(const cales_case *c, void *stream, cales_ctx **out);
 void cales_destroy(cales_ctx *ctx);
 const char *cales_last_error(const cales_ctx *ctx);    /* ctx may be NULL for create-time errors */
 int  cales_sync(cales_ctx *ctx);
+/* Device and pinned-host memory the context holds right now (every allocation of the library is the context's, the temporaries of a call in flight
+ * included; cales_destroy releases all of it): bytes and number of allocations. ctx may be NULL: the totals over every context of the process.
+ * Either result pointer may be NULL. */
+int  cales_memory_in_use(const cales_ctx *ctx, int64_t *bytes, int64_t *allocations);
 int  cales_local_size(const cales_ctx *ctx, int32_t n[3], int32_t lo[3]);
 
 /* host <-> device (src/main.f90:368 `enter data copyin(u,v,w,p)`, :576-607 `update self`) */

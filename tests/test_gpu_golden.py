@@ -514,7 +514,7 @@ def test_pending_projection_is_completed_by_every_entry_that_looks(monkeypatch):
 # entries that read or write no field (or are the consumer itself): they do not have to complete a pending projection
 _NO_FIELD_ENTRIES = {"cales_destroy", "cales_last_error", "cales_local_size", "cales_get_forcing", "cales_get_dpdl", "cales_get_bcvel", "cales_step", "cales_describe_plan",
                      "cales_profile_enable", "cales_profile_reset", "cales_profile_count", "cales_profile_get", "cales_device_info",
-                     "cales_comm_buffer_doubles", "cales_set_comm", "cales_set_comm_overlap", "cales_comm_init_rccl"}
+                     "cales_comm_buffer_doubles", "cales_set_comm", "cales_set_comm_overlap", "cales_comm_init_rccl", "cales_memory_in_use"}
 
 
 def _entry_calls(h, dt):
