@@ -82,7 +82,7 @@ struct Spec {
 
 // Run-time switches: read from the environment ONCE, by cales_create; the launch path only looks at these fields.
 struct Flags {
-  bool unfolded_correc = false, unfolded_mom = false, eager_projection = false, lazy_projection = false, helmholtz_z_per_column = false, unfused_imp_rhs = false, unfused_correc = false, unfused_forcing = false, unfused_fillps = false, unfused_mean = false, keep_last_rhs = false, wide_offsets = false, dsmag_reference_sequence = false, dsmag_xghosts = false, smag_reference_sequence = false, gaussel_march = false, fft_generic = false, fft_no_odd_radix = false, keep_null_mode = false, unfused_rk = false, overlap = false, xghosts_in_step = false, unmerged_bc = false, no_nyquist_packing = false;
+  bool unfolded_correc = false, unfolded_mom = false, eager_projection = false, lazy_projection = false, helmholtz_z_per_column = false, unfused_imp_rhs = false, unfused_correc = false, unfused_forcing = false, unfused_fillps = false, unfused_mean = false, keep_last_rhs = false, wide_offsets = false, dsmag_reference_sequence = false, dsmag_xghosts = false, smag_reference_sequence = false, gaussel_march = false, fft_generic = false, fft_no_odd_radix = false, keep_null_mode = false, unfused_rk = false, overlap = false, xghosts_in_step = false, unmerged_bc = false, no_nyquist_packing = false, sgs_six_components = false;
   int kchunk = 0; long tile_min_blocks = 2048;
   std::string test_bad_launch;      // CALES_TEST_BAD_LAUNCH: test hook of the launch check (LAUNCH below)
   void read_env() {
@@ -101,6 +101,7 @@ struct Flags {
     wide_offsets = getenv("CALES_WIDE_OFFSETS") != nullptr;
     dsmag_reference_sequence = getenv("CALES_DSMAG_REFERENCE_SEQUENCE") != nullptr;
     dsmag_xghosts = getenv("CALES_DSMAG_XGHOSTS") != nullptr;
+    sgs_six_components = getenv("CALES_SGS_SIX_COMPONENTS") != nullptr;      // dynamic model in cales_step on one rank: all six |S|Sij travel between the strain-rate pass and the last pass (default: five, the third from the trace -- SgsPath::five)
     smag_reference_sequence = getenv("CALES_SMAG_REFERENCE_SEQUENCE") != nullptr;
     gaussel_march = getenv("CALES_GAUSSEL_MARCH") != nullptr;
     no_nyquist_packing = getenv("CALES_NO_NYQUIST_PACKING") != nullptr;      // periodic x, periodic or Neumann y: the real modes 0 and n1/2 in columns of their own (n1/2 + 1 mode columns) instead of sharing column 0
@@ -150,14 +151,18 @@ struct TileGeom { dim3 block, grid; int kchunk = 0; BandMap bm{0, 0, 0, 0}; };
 enum class SgsForm { none, smag_rows, smag_reference, dsmag_tiles, dsmag_reference };
 // the instantiation of each launch site (32 / 64: unsigned / size_t byte offsets; yw: walls or wall-model faces in y; ucf: the last pass forms the
 // cell-centred velocity). Pair fields imply x and y periodic, 32-bit offsets and ucf: one instantiation each.
-enum class StrainKernel { corr_rows2, corr, yw32, yw64, pair, plain32, plain64, f2d32, f2d64 };      // k_corr_strain_tile<unsigned, TYC(, EXT = 1)> | k_strain_tile<OFF, TYS, YW(, SSF)>, SSF = 1: pair, 2: f2d (SgsPath::filter2d)
-enum class LmfKernel { pair, yw_ucf32, yw_ucf64, yw32, yw64, ucf32, ucf64, plain32, plain64, f2d32, f2d64 };      // k_lmf_tile<OFF, YW, UCF(, SSF)>, SSF = 1: pair, 2: f2d
+enum class StrainKernel { corr_rows2, corr, corr5, yw32, yw64, pair, plain32, plain64, f2d32, f2d64 };      // k_corr_strain_tile<unsigned, TYC(, 1: EXT, 2: FIVE)> | k_strain_tile<OFF, TYS, YW(, SSF)>, SSF = 1: pair, 2: f2d (SgsPath::filter2d)
+enum class LmfKernel { pair, pair5, yw_ucf32, yw_ucf64, yw32, yw64, ucf32, ucf64, plain32, plain64, f2d32, f2d64 };      // k_lmf_tile<OFF, YW, UCF(, PAIR)>, PAIR = 1: pair, 2: pair5 (five components) | k_lmf_plane_tile<OFF>: f2d
 enum class SmagKernel { yw32, yw64, plain32, plain64 };      // k_smag_rows<OFF, YW>
 // the directions <Mij Lij>, <Mij Mij> of the dynamic model are averaged over (sgs.f90:359-370): _CHANNEL (hard-wired there) | -D_DIT | _DUCT
 enum class SgsAve { planes, volume, xlines };
 struct SgsPath {
   SgsForm form = SgsForm::none;
   bool pair = false, lazy = false, ucf = false, small = false, yw = false;      // |S|Sij as pair fields (ss2); lazy: |S| straight into visct (homogeneous sgs BCs)
+  // five: inside cales_step with the projection folded into the strain-rate pass on ONE rank, five |S|Sij travel (two pair fields and S12 plain) and the last
+  // pass takes |S|S33 = -(|S|S11 + |S|S22): the trace of the strain rate of a velocity that pass has just projected is the divergence the solve left. Calls
+  // without the fold (start-up, operator level, CALES_UNFOLDED_CORREC), slabs and every other form keep six (CALES_SGS_SIX_COMPONENTS: everywhere)
+  bool five = false;
   bool filter2d = false;    // the reference's -D_FILTER_2D (cales_case.sgstype = CALES_SGS_DSMAG_FILTER2D): test filter in the x-y planes only, alph2 = 2.52 everywhere
   SgsAve ave = SgsAve::planes;      // cales_case.sgstype & CALES_SGS_AVE_*: volume folds the plane sums into one (k_volume_fold), xlines takes the sequence (k_contract_lines)
   bool wraps_x = true;      // reads wrapped interior columns where x is periodic (cales_step may leave the x ghost columns stale)

@@ -396,7 +396,7 @@ struct LijMijArgs {
 #define TYLF 8      // tile height of the instantiations without y walls (their LDS leaves room for twelve rows: six filtered quantities instead of nine)
 #endif
 #define LMF_TY(YW) ((YW) ? TYL : TYLF)
-struct LmfArgs { LijMijArgs L; const real *ss[6]; const real2 *ss2[3]; int by0; BandMap bm; int gx; };      // ss2: |S|Sij as three fields of pairs (PAIR = 1), ss: six fields      // bm: block map of this launch (bm.gx = 0: plain 3-D grid); gx: x tiles of the whole field      // by0: first y tile of this launch (interior and edge tiles of a slab are launched apart)
+struct LmfArgs { LijMijArgs L; const real *ss[6]; const real2 *ss2[3]; int by0; BandMap bm; int gx; };      // ss2: |S|Sij as three fields of pairs (PAIR = 1; PAIR = 2: two of pairs, S12 plain at the head of ss2[1]), ss: six fields      // bm: block map of this launch (bm.gx = 0: plain 3-D grid); gx: x tiles of the whole field      // by0: first y tile of this launch (interior and edge tiles of a slab are launched apart)
 // Every global access of the plane loop is UNCONDITIONAL (out-of-range lanes, rows and planes are clamped onto valid cells whose values are
 // never used): a load inside a divergent branch makes the compiler wait with s_waitcnt vmcnt(0) at the next use of ANY loaded value -- it
 // cannot count the operations in flight across the branch -- and that drained, right behind the barrier of every plane, the six loads of
@@ -410,6 +410,11 @@ constexpr int LMF_KMAX = 256;      // longest k chunk (block sums of a chunk in 
 // bound by its writes) -- x periodic, z walls or periodic, y periodic / slab neighbours / walls; otherwise UCF = 0 reads the stored fields.
 // PAIR = 1: K_AC stored |S|Sij as three fields of PAIRS (S11,S22), (S33,S12), (S13,S23) per cell: nine 16-byte loads per plane instead of eighteen
 // 8-byte ones. The pass is bound by what its ten waves issue, not by bytes: 3.95 -> 3.45 ms at 512^3 (K_AC's paired stores cost 0.28 of the 0.5 back).
+// PAIR = 2: FIVE components, as k_corr_strain_tile<.., FIVE> left them -- the pairs (S11,S22) in ss2[0] and (S13,S23) in ss2[2], S12 as a plain field at the
+// head of ss2[1] -- and |S|S33 not at all: the velocity that pass differenced was the one it had just projected, so S11 + S22 + S33 is the divergence the
+// solve left (round-off; chkdiv watches it) and |S|S33 = -(|S|S11 + |S|S22). The test filter with its wall rules is linear: the filtered sixth component is
+// the negated sum of the two filtered diagonal ones, formed after the z combination. Fifteen row loads per plane instead of eighteen (six of 16 bytes, three
+// of 8), five rolling values per plane instead of six; 11 compulsory words per cell instead of 12. Only inside cales_step (SgsPath::five).
 template <typename OFF, int YW, int UCF, int PAIR = 0>      // YW = 1: walls or wall-model faces in y (ducts); 0: the channel instantiation carries none of that logic
 __global__ __launch_bounds__(64 * (LMF_TY(YW) + 2)) void k_lmf_tile(Geom g, LmfArgs B) {
   const LijMijArgs &A = B.L;
@@ -486,7 +491,17 @@ __global__ __launch_bounds__(64 * (LMF_TY(YW) + 2)) void k_lmf_tile(Geom g, LmfA
   }
   // |S|Sij: y and x combination of one plane (three rows in, lanes beside by DPP)
   auto ssload = [&](int kk, real (*raw)[3]) {
-    if (PAIR) {
+    if (PAIR == 2) {      // slots: S11, S22 | S12 | S13, S23
+      const OFF o1 = c0s + (OFF)kk * sk, o = 2 * o1, s2 = 2 * sj;
+#pragma unroll
+      for (int q = 0; q < 2; ++q) {
+        const char *f = (const char *)B.ss2[2 * q];
+        const real2 a = *(const real2 *)(f + (o - s2)), b = *(const real2 *)(f + o), c_ = *(const real2 *)(f + (o + s2));
+        raw[3 * q][0] = a.x; raw[3 * q + 1][0] = a.y; raw[3 * q][1] = b.x; raw[3 * q + 1][1] = b.y; raw[3 * q][2] = c_.x; raw[3 * q + 1][2] = c_.y;
+      }
+      const real *f12 = (const real *)B.ss2[1];
+      raw[2][0] = ldb(f12, o1 - sj); raw[2][1] = ldb(f12, o1); raw[2][2] = ldb(f12, o1 + sj);
+    } else if (PAIR) {
 #pragma unroll
       for (int q = 0; q < 3; ++q) {
         const OFF o = 2 * (c0s + (OFF)kk * sk), s2 = 2 * sj;      // a pair field is twice as wide: byte offsets double
@@ -500,14 +515,15 @@ __global__ __launch_bounds__(64 * (LMF_TY(YW) + 2)) void k_lmf_tile(Geom g, LmfA
       raw[q][0] = ldb(B.ss[q], o - sj); raw[q][1] = ldb(B.ss[q], o); raw[q][2] = ldb(B.ss[q], o + sj);
     }
   };
+  constexpr int NSS = PAIR == 2 ? 5 : 6;      // |S|Sij components that travel
   auto sscomb = [&](const real (*raw)[3], real *X) {
 #pragma unroll
-    for (int q = 0; q < 6; ++q) {
+    for (int q = 0; q < NSS; ++q) {
       const real Y = (ylo ? 2. * raw[q][1] - raw[q][2] : raw[q][0]) + 2. * raw[q][1] + (yhi ? 2. * raw[q][1] - raw[q][0] : raw[q][2]);
       X[q] = lane_prev(Y) + 2. * Y + lane_next(Y);
     }
   };
-  real xm[6], xc[6], xp[6], rw[6][3];
+  real xm[NSS], xc[NSS], xp[NSS], rw[NSS][3];
   // the ghost plane below a wall is never used (LO planes take 4 xc); it is read all the same when the chunk starts inside the field
   ssload(kbeg - 1, rw); sscomb(rw, xm);
   ssload(kbeg, rw); sscomb(rw, xc);
@@ -596,7 +612,9 @@ __global__ __launch_bounds__(64 * (LMF_TY(YW) + 2)) void k_lmf_tile(Geom g, LmfA
       real m[6];
 #pragma unroll
       for (int q = 0; q < 6; ++q) {
-        const real G = (LO || HI) ? 4. * xc[q] : xm[q] + 2. * xc[q] + xp[q];      // filter(|S|Sij) * 64
+        auto zc3 = [&](int s) { return (LO || HI) ? 4. * xc[s] : xm[s] + 2. * xc[s] + xp[s]; };      // filter(|S|Sij) * 64
+        // (five components: slot of component q, and the third one from the trace after the full 27-point combination)
+        const real G = (PAIR == 2 && q == 2) ? -(zc3(0) + zc3(1)) : zc3(PAIR == 2 && q > 2 ? q - 1 : q);
         m[q] = 2. * (G * (1. / 64.) - a2s0 * sij[q]);                             // Mij, sgs.f90:261-272
       }
       lm = m[0] * l0 + m[1] * l1 + m[2] * l2 + (m[3] * l3 + m[4] * l4 + m[5] * l5) * 2.;       // sgs.f90:344-349
@@ -608,7 +626,7 @@ __global__ __launch_bounds__(64 * (LMF_TY(YW) + 2)) void k_lmf_tile(Geom g, LmfA
 #pragma unroll
     for (int q = 0; q < 3; ++q) { sm[q] = sc[q]; sc[q] = sp[q]; sp[q] = sn[q]; }
 #pragma unroll
-    for (int q = 0; q < 6; ++q) { xm[q] = xc[q]; xc[q] = xp[q]; }
+    for (int q = 0; q < NSS; ++q) { xm[q] = xc[q]; xc[q] = xp[q]; }
     zcm = zcc; zcc = zcn; zfc = zfn;
   };
   {
@@ -978,8 +996,14 @@ __global__ __launch_bounds__(64 * (TY + 2)) void k_strain_tile(Geom g, StrainTil
 // it writes -- corrected u, v, w, p + pp, |S|, |S|Sij, the filtered velocity, and v_c of those two rows for the last pass (A.vcg) -- from a SECOND ghost
 // row of the prediction (rows -1 / n2+2: the ghost rows 0 / n2+1 of the companion field that sits A.ppd bytes behind every velocity field) and a third of
 // pp (row n2+3: its second companion): nothing this pass produces travels between the slabs afterwards.
-template <typename OFF, int TY, int EXT = 0>
+// FIVE (one rank, SgsPath::five): |S|S33 is not stored -- S11 + S22 + S33 is the divergence of the velocity this very pass has projected, round-off of the
+// solve, so the last pass takes |S|S33 = -(|S|S11 + |S|S22) (k_lmf_tile, PAIR = 2) -- and |S|S12, left without a partner, goes as a plain field to the head of
+// ss2[1]: 13 words written per cell instead of 14, 18 words in all instead of 19. |S| itself is formed from the true S33, in registers, as before. Valid only
+// HERE: cmpt_sgs outside the step (start-up, operator-level calls) sees a velocity nobody has projected and keeps six components.
+// (EXT and FIVE: the values 1 and 2 of one template parameter, as in k_strain_tile -- slabs keep six components.)
+template <typename OFF, int TY, int ROWS = 0>
 __global__ __launch_bounds__(64 * (TY + 2)) void k_corr_strain_tile(Geom g, StrainTileArgs A) {
+  constexpr int EXT = ROWS == 1, FIVE = ROWS == 2;
   __shared__ real ring[3][3][TY + 2][66];      // rows: x-halo cell, 64 own cells, x-halo cell
   __shared__ real shs[3][TY + 2][64];
   // pp of the tile's cells, planes k+1 / k+2 (by parity), column 64 = the x-halo cell right of the row: the correction of a cell needs pp(i+1) (the lane
@@ -1175,7 +1199,8 @@ __global__ __launch_bounds__(64 * (TY + 2)) void k_corr_strain_tile(Geom g, Stra
       const OFF i2 = 2 * idx;      // |S|Sij (sgs.f90:198-210), two components per 16-byte store
       typedef real v2 __attribute__((ext_vector_type(2)));
       __builtin_nontemporal_store(v2{s0v * s11, s0v * s22}, (v2 *)((char *)A.ss2[0] + i2));
-      __builtin_nontemporal_store(v2{s0v * s33, s0v * s12}, (v2 *)((char *)A.ss2[1] + i2));
+      if (FIVE) __builtin_nontemporal_store(s0v * s12, (real *)((char *)A.ss2[1] + idx));
+      else __builtin_nontemporal_store(v2{s0v * s33, s0v * s12}, (v2 *)((char *)A.ss2[1] + i2));
       __builtin_nontemporal_store(v2{s0v * s13, s0v * s23}, (v2 *)((char *)A.ss2[2] + i2));
       // (the cell-centred velocity is not stored: the last pass forms it from u, v, w itself -- the only form this pass serves, dsmag_fast)
       // EXT: v_c of the two ghost rows, which the last pass reads from A.vcg (row 0: its lower neighbour v(-1) is in this tile's ring, nowhere else);
@@ -1422,6 +1447,9 @@ void sgs_setup(cales_ctx *c) {
   // |S|Sij as three fields of pairs between K_AC and the fused last pass: ucf, and y periodic (the one-launch ghost-cell kernel takes a pair field as a
   // field of twice the width), 32-bit byte offsets still enough for a field twice as long
   P.pair = !P.filter2d && P.ucf && CBP(c, 0, 2) == 'P' && CBP(c, 1, 2) == 'P' && !fl.wide_offsets && !fl.unmerged_bc && (2 * c->ntot + 64) * sizeof(real) < (1ull << 32);
+  // five |S|Sij instead of six wherever the strain-rate pass projects the velocity itself (make_plan: fold_correc needs pair fields) on one rank -- on slabs the
+  // scratch rows travel in counted planes and keep six
+  P.five = P.pair && c->P == 1 && !fl.sgs_six_components;
   P.lmf_ty = P.yw ? TYL : TYLF;
   P.strain = P.pair ? StrainKernel::pair : P.yw ? (P.small ? StrainKernel::yw32 : StrainKernel::yw64) : (P.small ? StrainKernel::plain32 : StrainKernel::plain64);
   static const LmfKernel lmf[2][2][2] = {{{LmfKernel::plain64, LmfKernel::plain32}, {LmfKernel::ucf64, LmfKernel::ucf32}},
@@ -1463,12 +1491,17 @@ static int dsmag_fast(cales_ctx *c, const SgsFold *fold, bool *visct_ghosts_done
   // are extrapolated through the z walls, w on the faces is not, sgs.f90:705-710); fold (pair fields, make_plan): with the projection folded in, ext:
   // from two ghost rows of the prediction, forming the ghost rows of its outputs too
   const bool ext = fold && fold->rows2;
+  const bool five = fold && !ext && P.five;      // (the identity holds for the velocity this call projects, not for one it is handed)
+  // five components: S12 as a plain field in the buffer of the pair field (S33,S12), placed like every field -- cell (1, j, k) at the head of a 128-B line
+  // (field_alloc: a pair field starts 2 field_ofs reals into its allocation, a field field_ofs; 8 bytes off, every wave's 512-B store touches a fifth line)
+  real *const s12 = five ? c->ss2[1] - c->field_ofs : nullptr;
   { ProfScope ps(c, fold ? "correc_strain_filter_uvw" : "strain_filter_uvw");
     const TileGeom &t = !fold ? P.strain_geo : ext ? P.corr_rows2_geo : P.corr_geo;
     StrainTileArgs S;
     S.u[0] = f[CALES_U]; S.u[1] = f[CALES_V]; S.u[2] = f[CALES_W]; S.s0 = P.lazy ? visct : c->s0;
     for (int m = 0; m < 6; ++m) S.ssij[m] = ssij[m];
     for (int m = 0; m < 3; ++m) S.ss2[m] = reinterpret_cast<real2 *>(c->ss2[m]);
+    if (five) S.ss2[1] = reinterpret_cast<real2 *>(s12);
     S.uc[0] = P.ucf ? nullptr : c->uc; S.uc[1] = P.ucf ? nullptr : c->vc; S.uc[2] = P.ucf ? nullptr : c->wc; S.uf[0] = c->uf; S.uf[1] = c->vf; S.uf[2] = c->wf;
     S.dzci = c->d_dzci; S.dzfi = c->d_dzfi; S.dxi = c->dli[0]; S.dyi = c->dli[1]; S.kchunk = t.kchunk; S.zlo = P.zlo; S.zhi = P.zhi; S.wmlo = P.wmlo; S.wmhi = P.wmhi; S.flo = P.flo; S.fhi = P.fhi;
     S.wylo = P.wylo; S.wyhi = P.wyhi; S.wmylo = P.wmylo; S.wmyhi = P.wmyhi; S.twy = nullptr; S.dl2 = c->dl[1];
@@ -1482,8 +1515,9 @@ static int dsmag_fast(cales_ctx *c, const SgsFold *fold, bool *visct_ghosts_done
       S.bcz[0][0] = c->bcu.z; S.bcz[0][1] = c->bcu.z + pl; S.bcz[1][0] = c->bcv.z; S.bcz[1][1] = c->bcv.z + pl;
       S.vcg = c->vc;
     }
-    switch (!fold ? P.strain : ext ? StrainKernel::corr_rows2 : StrainKernel::corr) {
+    switch (!fold ? P.strain : ext ? StrainKernel::corr_rows2 : five ? StrainKernel::corr5 : StrainKernel::corr) {
     case StrainKernel::corr_rows2: LAUNCH(c, (k_corr_strain_tile<unsigned, TYC, 1>), t.grid, t.block, 0, c->stream, c->g, S); break;
+    case StrainKernel::corr5: LAUNCH(c, (k_corr_strain_tile<unsigned, TYC, 2>), t.grid, t.block, 0, c->stream, c->g, S); break;
     case StrainKernel::corr: LAUNCH(c, (k_corr_strain_tile<unsigned, TYC>), t.grid, t.block, 0, c->stream, c->g, S); break;
     case StrainKernel::yw32: LAUNCH(c, (k_strain_tile<unsigned, TYS, 1>), t.grid, t.block, 0, c->stream, c->g, S); break;
     case StrainKernel::yw64: LAUNCH(c, (k_strain_tile<size_t, TYS, 1>), t.grid, t.block, 0, c->stream, c->g, S); break;
@@ -1524,13 +1558,16 @@ static int dsmag_fast(cales_ctx *c, const SgsFold *fold, bool *visct_ghosts_done
   if (ext) bc.rows_current = true;      // the ghost rows of every field below were formed by the strain-rate pass: their x and z ghost cells only
   else if (c->P > 1) bc.collect = &rows;
   BcCall bz = bc; bz.skip = P.perx;      // (the filtered velocity: its z ghost planes are read)
-  if (int e = P.pair ? op_boundp_wide(c, 3, c->ss2, 1, bc) : op_boundp_multi(c, 6, ssij, 1, bc)) return e;
+  // (five components: the pair fields (S11,S22) and (S13,S23); S12, a plain field at the head of ss2[1], goes with v_c below -- no launch more)
+  real *ssp[3] = {c->ss2[0], five ? c->ss2[2] : c->ss2[1], c->ss2[2]};
+  if (int e = P.pair ? op_boundp_wide(c, five ? 2 : 3, ssp, 1, bc) : op_boundp_multi(c, 6, ssij, 1, bc)) return e;
   if (int e = op_bounduvw(c, c->bcuf, c->bcvf, c->bcwf, 0, 0, c->uf, c->vf, c->wf, bz)) return e;
   if (!P.ucf) { real *cc[3] = {c->uc, c->vc, c->wc}; if (int e = op_boundp_multi(c, 3, cc, 1, bc)) return e; }
   else if (ext) { if (int e = op_boundp(c, c->vc, 1, bc)) return e; }      // (v_c of the two ghost rows came from the strain-rate pass)
   else if (!(P.wylo && P.wyhi)) {      // v_c of the rows 1 and n2 only: their copies in the ghost rows (periodic wrap or the slab neighbours') are what the last pass reads for row 0
     LAUNCH(c, k_vc_edge_rows, dim3((n[0] + 2 + 63) / 64, (n[2] + 2 + 3) / 4), dim3(64, 4), 0, c->stream, c->g, f[CALES_V], c->vc);
-    if (int e = op_boundp(c, c->vc, 1, bc)) return e; }
+    real *two[2] = {c->vc, s12};
+    if (int e = op_boundp_multi(c, five ? 2 : 1, two, 1, bc)) return e; }
   if (P.lazy && visct_ghosts_done && c->P > 1) {      // inside cales_step |S| is final (K_AC wrote it): its rows travel along
     BcCall bv = bc; bv.skip = 0;
     if (int e = op_boundp(c, visct, 1, bv)) return e;
@@ -1550,12 +1587,14 @@ static int dsmag_fast(cales_ctx *c, const SgsFold *fold, bool *visct_ghosts_done
     L.kchunk = t.kchunk; L.nblk = t.grid.x * t.grid.y;
     LmfArgs B; B.L = L; for (int m = 0; m < 6; ++m) B.ss[m] = ssij[m];
     for (int m = 0; m < 3; ++m) B.ss2[m] = reinterpret_cast<const real2 *>(c->ss2[m]);
+    if (five) B.ss2[1] = reinterpret_cast<const real2 *>(s12);
     B.gx = t.grid.x;
     auto launch = [&](int by0, int nby) {      // the y tiles by0 .. by0 + nby - 1
       if (nby <= 0) return;
       TileGeom s = t; s.grid.y = nby; s = with_bands(s);
       B.by0 = by0; B.bm = s.bm;
-      switch (P.lmf) {
+      switch (five ? LmfKernel::pair5 : P.lmf) {
+      case LmfKernel::pair5: LAUNCH(c, (k_lmf_tile<unsigned, 0, 1, 2>), s.grid, s.block, 0, c->stream, c->g, B); break;
       case LmfKernel::pair: LAUNCH(c, (k_lmf_tile<unsigned, 0, 1, 1>), s.grid, s.block, 0, c->stream, c->g, B); break;
       case LmfKernel::yw_ucf32: LAUNCH(c, (k_lmf_tile<unsigned, 1, 1>), s.grid, s.block, 0, c->stream, c->g, B); break;
       case LmfKernel::yw_ucf64: LAUNCH(c, (k_lmf_tile<size_t, 1, 1>), s.grid, s.block, 0, c->stream, c->g, B); break;
