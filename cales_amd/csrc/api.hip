@@ -337,7 +337,7 @@ int cales_get_bcvel(cales_ctx *c, int ivel, real *x, real *y, real *z) {
 
 // ------------------------------------------------------------------------------------------ operators
 int cales_bounduvw(cales_ctx *c, int is_updt_wm, int is_correc) {
-  ENTRY(c, op_bounduvw(c, c->bcu, c->bcv, c->bcw, is_updt_wm, is_correc, c->f[CALES_U], c->f[CALES_V], c->f[CALES_W]));
+  ENTRY(c, op_bounduvw(c, VelSet::state, is_updt_wm, is_correc));
 }
 int cales_boundp(cales_ctx *c, int field, int which) {
   if (field < 0 || field >= CALES_NFIELDS || !c->f[field]) { c->err = "bad field id"; return 1; }
@@ -415,7 +415,7 @@ static int project_now(cales_ctx *c, real dtrk, real alpha, int fmask) {
   // the pressure is final once the fused correction has run: its ghost cells ride along with those of the velocity (one launch, one slab exchange)
   BcCall b;
   if (fuse_cu) b.rider(c->f[CALES_P], 0);
-  if (int e = op_bounduvw(c, c->bcu, c->bcv, c->bcw, 1, 1, c->f[CALES_U], c->f[CALES_V], c->f[CALES_W], b)) return e;
+  if (int e = op_bounduvw(c, VelSet::state, 1, 1, b)) return e;
   if (!fuse_cu) { if (int e = op_updatep(c, alpha)) return e; if (int e = op_boundp(c, c->f[CALES_P], 0)) return e; }
   return 0;
 }
@@ -426,7 +426,7 @@ static int end_of_step_refresh(cales_ctx *c) {
   c->step_xskip = false;
   BcCall b; b.rows_current = true;      // (only the x ghost columns are stale)
   b.rider(c->f[CALES_P], 0); b.rider(c->f[CALES_PP], 0); b.rider(c->f[CALES_VISCT], 1);
-  if (int e = op_bounduvw(c, c->bcu, c->bcv, c->bcw, 0, 1, c->f[CALES_U], c->f[CALES_V], c->f[CALES_W], b)) return e;
+  if (int e = op_bounduvw(c, VelSet::state, 0, 1, b)) return e;
   if (!(CBV(c, 0, 3, 3) == 'P' && CBV(c, 1, 3, 3) == 'P')) { if (int e = op_xwrap_zghost(c, 3, c->f + CALES_U)) return e; }      // (periodic z: the z copies of the launch above cover the corners)
   return 0;
 }
@@ -443,7 +443,7 @@ static int finish_pending(cales_ctx *c) {
   int e = 0;
   if (due && pj.p_done) {      // (z-implicit diffusion: the pressure is up to date, ghost cells included)
     e = op_correc(c, pj.dtrk, pj.fmask);
-    if (!e) e = op_bounduvw(c, c->bcu, c->bcv, c->bcw, 1, 1, c->f[CALES_U], c->f[CALES_V], c->f[CALES_W]);
+    if (!e) e = op_bounduvw(c, VelSet::state, 1, 1);
   } else if (due) e = project_now(c, pj.dtrk, 0., pj.fmask);
   if (!e) e = end_of_step_refresh(c);      // (the completion ends with the refresh)
   if (e) { c->launch_err = std::string(due ? "completing a pending projection" : "refreshing the x ghost columns") + " failed (" + c->err + "): the context is unusable"; return e; }
@@ -607,7 +607,7 @@ static int step_body(cales_ctx *c, real dt) {
       if (p_ghosts_due) b.rider(c->f[CALES_P], 0);
       // (two ghost rows of the prediction, fold_rows2: the rows 2 / n2-1 travel to the neighbours' companion fields in the same message as the rows 1 / n2)
       HaloBatch rows; if (pl.fold_rows2) b.collect = &rows;
-      if (int e = op_bounduvw(c, c->bcu, c->bcv, c->bcw, 1, 0, c->f[CALES_U], c->f[CALES_V], c->f[CALES_W], b)) return e;
+      if (int e = op_bounduvw(c, VelSet::state, 1, 0, b)) return e;
       if (pl.fold_rows2) {
         if (int e = halo_y_rows(c, 3, c->f + CALES_U, 2, b)) return e;
         if (int e = halo_flush_deferred(c, rows, false)) return e;
@@ -644,7 +644,7 @@ static int step_body(cales_ctx *c, real dt) {
         pend.p_done = true;
       }
       BcCall b; b.view_dtrk = pend.dtrk; b.view_fmask = pend.fmask;
-      if (int e = op_bounduvw(c, c->bcu, c->bcv, c->bcw, 1, 1, c->f[CALES_U], c->f[CALES_V], c->f[CALES_W], b)) return e;
+      if (int e = op_bounduvw(c, VelSet::state, 1, 1, b)) return e;
     } else if (int e = project_now(c, dtrk, alpha, fmask)) return e;
     bool visct_ghosts_done = false;
     if (int e = op_cmpt_sgs(c, pl.fold_correc ? &fold : nullptr, &visct_ghosts_done)) return e;

@@ -191,12 +191,24 @@ struct MomPath {
 // be formed in ghost cells), only the velocity is pending. xskip: the step that left it left the x ghost columns alone (step_xskip)
 struct PendingProjection { real dtrk = 0.; int fmask = 0; bool p_done = false, xskip = false; };
 
-// The form each BC set of the case takes in the ghost-cell operators (k_bound.hip), decided once by cales_create (bc_setup) from the BC types, is_bound
-// and Flags, and only read after. No job tables here: they hold field pointers, which the f / f2 swaps change.
+// One direction of one field in the ghost-cell operators (k_bound.hip): the type of each end ('P' at both: periodic, one copy serves both; 'D'; 'N'; 0: this
+// end is left alone), cen = 0: face-centred along this direction, and per end the spacing of the Neumann rule and the plane of boundary values. k_bc_all
+// takes it as it stands.
+struct BcRule { char t0, t1, cen; real dr0, dr1; const real *bc0, *bc1; };
+// ... the three directions of one field. wm[d]: bit 0 / 1 -- the lower / upper end of direction d is a wall-model face of this rank and the field a
+// tangential velocity component: bounduvw leaves that end to the update that follows the wall model
+struct BcRules { BcRule d[3]; unsigned char wm[3]; };
+enum class VelSet { state = 0, filtered = 1 };      // u, v, w with bcu/bcv/bcw | the dynamic model's filtered velocity uf, vf, wf with bcuf/bcvf/bcwf
+// What the case fixes about the ghost-cell operators (k_bound.hip), worked out once by cales_create (bc_setup) from the BC types, is_bound, the wall-model
+// faces, the grid and Flags, and only read after: the kernel form of every BC set and the rules of every (field kind, direction, end) as this rank applies
+// them -- 'P' where the direction is periodic, 0 at an end the slab does not own and for a periodic y on several slabs (the rows are exchanged). The
+// tables hold everything about the case and nothing about a call: no field pointers (the f / f2 swaps change them), and the plane pointers are stable
+// (the wall model rewrites what the planes hold). What a call changes is bc_rule's business.
 enum class BcForm { merged, all, by_direction };      // k_bc_merged (x, y periodic) | k_bc_all (any pointwise set) | one k_set_bc launch per direction
 struct BcPath {
   BcForm vel = BcForm::by_direction, wm = BcForm::by_direction, cell[2] = {BcForm::by_direction, BcForm::by_direction};      // velocity set; tangential set of the wall-model faces; pressure [0] / sgs [1] set
-  // the one thing a call decides: k_bc_all does not serve a Neumann condition on face-centred data. Bit d-1: the normal component has one in direction d
+  BcRules rules_vel[2][3] = {}, rules_cell[2] = {};      // [VelSet][component]; pressure [0] / sgs [1] set
+  // the one thing a call decides about the form: k_bc_all does not serve a Neumann condition on face-centred data. Bit d-1: the normal component has one in direction d
   // on this rank (never with is_correc, which leaves a non-periodic normal direction alone) -- the velocity set takes `all` in calls that skip every such direction
   int vel_fcn = 0;
   bool ride[2] = {false, false};      // cell-centred fields with the pressure / sgs set can join the velocity's launch (BcCall::ride)
@@ -204,7 +216,8 @@ struct BcPath {
 // y-halo rows collected over several ghost-cell calls and exchanged in ONE message by halo_flush_deferred: a local of the caller (sixteen planes are what
 // the staging buffers hold). kind: 0 a field, 1 a pair field, 2 / 3 the second / third rows of a field into its first / second companion
 struct HaloBatch { int n = 0; real *p[16]; unsigned char kind[16]; };
-// What a caller inside cales_step asks of ONE call of a ghost-cell operator; default-constructed: the operator as the C-ABI entry runs it
+// What a caller inside cales_step asks of ONE call of a ghost-cell operator; default-constructed: the operator as the C-ABI entry runs it. The operator
+// turns it, with BcPath's tables, into the rules of the call (bc_rule) and the exchange that goes with them
 struct BcCall {
   int skip = 0;                  // bit d-1: leave direction d alone (the call's consumers do not read it)
   // bounduvw leaves the wall-model update and the tangential ghost cells of wall-model faces alone: those of the first bounduvw of a substep are rewritten
@@ -391,8 +404,8 @@ int    hs_check_case(const cales_case *cs, std::string &msg);
 void   hs_bc_rhs(const char *cbc2, const real *bc, int na, int nb, const real *dlc, const real *dlf, char c_or_f, real *rhs);
 
 // ---- device operators (k_*.hip); all asynchronous on c->stream
-void bc_setup(cales_ctx *c);                // BcPath (needs is_bound, cbcvel)
-int op_bounduvw(cales_ctx *c, DBound &bu, DBound &bv, DBound &bw, int is_updt_wm, int is_correc, real *u, real *v, real *w, const BcCall &b = BcCall());
+void bc_setup(cales_ctx *c);                // BcPath (needs is_bound, cbcvel, the grid and the BC planes)
+int op_bounduvw(cales_ctx *c, VelSet set, int is_updt_wm, int is_correc, const BcCall &b = BcCall());      // the set's fields are read at call time (the f / f2 swaps)
 int op_boundp(cales_ctx *c, real *p, int which, const BcCall &b = BcCall());
 int op_boundp_multi(cales_ctx *c, int nf, real **p, int which, const BcCall &b = BcCall());
 int halo_flush_deferred(cales_ctx *c, HaloBatch &rows, bool overlapped = true);

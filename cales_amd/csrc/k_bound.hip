@@ -1,10 +1,14 @@
-// Ghost-cell kernels: bounduvw / boundp / set_bc (reference src/bound.f90:18-399), the single-rank
-// image of updthalo (src/bound.f90:619-696), updt_rhs_b (src/bound.f90:562-617) and the log-law /
-// laminar wall model (src/wmodel.f90:19-335).
+// Ghost-cell operators: bounduvw / boundp / set_bc (reference src/bound.f90:18-399), the single-rank image of updthalo (src/bound.f90:619-696),
+// updt_rhs_b (src/bound.f90:562-617) and the log-law / laminar wall model (src/wmodel.f90:19-335).
 //
-// The reference issues one tiny `!$acc kernels` region per face and field (39 regions). Here all faces
-// of one direction (up to 3 fields x 2 sides) go into ONE launch; the x -> y -> z order of the
-// reference is kept because corner ghosts depend on it.
+// The reference issues one tiny `!$acc kernels` region per face and field (39 regions), x, then y, then z: corner ghosts depend on that order. Here a
+// ghost-cell update is a list of entries {field, rules, view} (BcEntry) that takes one of three kernel forms (BcForm, chosen per BC set by bc_setup):
+//   k_bc_merged   x and y periodic, any pointwise z condition: all directions of up to eight fields in one launch;
+//   k_bc_all      any set of pointwise conditions but Neumann on face-centred data: all directions of up to six fields in one launch;
+//   k_set_bc      one launch per direction in the reference's order, up to six (field, end) jobs each: what the others do not serve, CALES_UNMERGED_BC.
+// What the case fixes about every (field kind, direction, end) sits in BcPath's tables (bc_setup), what a call changes is applied by bc_rule, and every
+// operator -- bounduvw with its riders and wall-model faces, boundp of one or several fields, pair fields -- goes through bc_update: the slab exchange,
+// one builder per form, one launch site per kernel.
 #include "common.hpp"
 
 // Corrected view (cales_step, projection folded into the next momentum pass): a source cell that is an INTERIOR cell (1..n in all three directions) is
@@ -82,10 +86,6 @@ static inline const real *plane(const DBound &b, int idir, int ibound, const int
   const real *base = idir == 1 ? b.x : idir == 2 ? b.y : b.z;
   return base + (size_t)ibound * pl;
 }
-static inline void add_job(BcJobs &J, real *p, char ctype, int ibound, int centered, const real *bc, real dr) {
-  BcJob &j = J.job[J.njobs++];
-  j.p = p; j.bc = bc; j.dr = dr; j.ctype = ctype; j.centered = (char)centered; j.ibound = (char)ibound; j.vcomp = 0;
-}
 
 // ---- all three directions in ONE launch, for the common BC sets: x periodic, y periodic (or exchanged between slabs), any
 // pointwise z condition. The reference applies x, then y, then z, and later directions also fill the corner ghosts of earlier ones
@@ -128,9 +128,8 @@ __global__ __launch_bounds__(256) void k_bc_merged(Geom g, MJobs J) {
     p[g.ix(i, 0, k)] = S(i, n2, k); p[g.ix(i, n2 + 1, k)] = S(i, 1, k);
   }
 }
-static int launch_merged(cales_ctx *c, MJobs &J, const Geom *gg = nullptr) {
+static int launch_merged(cales_ctx *c, MJobs &J, const Geom &G) {      // (G: the context's geometry or its doubled-width view, wide_geom)
   if (!J.nf) return 0;
-  const Geom &G = gg ? *gg : c->g;
   const int n[3] = {G.n1, G.n2, G.n3};
   // one grid for the three regions: region 0 needs (n1+2) x (n2+2), region 1 (n2+2) x n3, region 2 n1 x n3 threads
   const int ex = std::max(n[0] + 2, n[1] + 2), ey = std::max(n[1] + 2, n[2] + 2);
@@ -147,7 +146,7 @@ static int launch_merged(cales_ctx *c, MJobs &J, const Geom *gg = nullptr) {
 // takes it (the plane entry of the cell being set, ghost positions included). A thread computes its cell from stored cells no thread writes: no
 // ordering between the directions is left. Not served: Neumann on face-centred data (outflow: set_bc copies the OLD boundary value into the ghost
 // cell while it rewrites the boundary value itself) -- such sets keep the launch per direction.
-struct ADir { char t0, t1, cen; real dr0, dr1; const real *bc0, *bc1; };      // t = 0: this end is left alone; 'P': both ends; cen = 0: face-centred along this direction
+using ADir = BcRule;      // (common.hpp; t = 0: this end is left alone; 'P': both ends; cen = 0: face-centred along this direction)
 struct AField { real *p; ADir d[3]; char vcomp; };      // vcomp != 0: stored cells through the corrected view of this velocity component
 struct AJobs { int nf; AField f[6]; CorrView V; };
 __device__ inline bool a_set(const ADir &R, int idx, int n) {
@@ -228,16 +227,16 @@ static int launch_all(cales_ctx *c, AJobs &J) {
   LAUNCHCHK(c);
   return 0;
 }
-// one direction of one field: the types of its two ends as the reference's loops over idir / ibound would apply them on this rank
-static void a_dir(cales_ctx *c, const BcCall &b, ADir &D, int idir, char c0, char c1, int centered, const real *bc0, const real *bc1, real dr0, real dr1) {
-  D.t0 = D.t1 = 0; D.cen = (char)centered; D.dr0 = dr0; D.dr1 = dr1; D.bc0 = bc0; D.bc1 = bc1;
-  if ((bc_skipped(c, b) >> (idir - 1) & 1) && !(idir == 3 && c0 == 'P' && c1 == 'P')) return;      // (a periodic z is copied even where z is "skipped": the skip is for wall planes nobody reads)
-  if (c0 == 'P' && c1 == 'P') {
-    if (idir == 2 && c->P > 1) return;                // rows exchanged between the slabs (halo_y_comm, before the launch)
-    D.t0 = D.t1 = 'P'; return;                        // (x and z are never decomposed: a local copy)
-  }
-  if (ISB(c, 0, idir)) D.t0 = c0;
-  if (ISB(c, 1, idir)) D.t1 = c1;
+// BcPath's entry for one direction of one field: the types of its two ends as the reference's loops over idir / ibound apply them on this rank
+static BcRule table_rule(const cales_ctx *c, int idir, char c0, char c1, int cen, const DBound &bc) {
+  const int n3 = c->n[2];
+  BcRule R{};
+  R.cen = (char)cen;
+  R.dr0 = idir < 3 ? c->dl[idir - 1] : cen ? c->dzc[0] : c->dzf[0]; R.dr1 = idir < 3 ? c->dl[idir - 1] : cen ? c->dzc[n3] : c->dzf[n3];
+  R.bc0 = plane(bc, idir, 0, c->n); R.bc1 = plane(bc, idir, 1, c->n);
+  if (c0 == 'P' && c1 == 'P') { if (!(idir == 2 && c->P > 1)) R.t0 = R.t1 = 'P'; }      // (y on several slabs: the rows are exchanged; x and z are never decomposed: a local copy)
+  else { if (ISB(c, 0, idir)) R.t0 = c0; if (ISB(c, 1, idir)) R.t1 = c1; }
+  return R;
 }
 // x periodic, y periodic on one rank or exchanged between slabs, z pointwise
 static bool merged_ok(const cales_ctx *c, const char *cbx, const char *cby) {
@@ -246,7 +245,7 @@ static bool merged_ok(const cales_ctx *c, const char *cbx, const char *cby) {
   if (!(cby[0] == 'P' && cby[1] == 'P')) return false;
   return true;
 }
-// BcPath: the form of every BC set of the case (cales_create)
+// BcPath: the form of every BC set of the case and the rules of every field kind (cales_create)
 void bc_setup(cales_ctx *c) {
   BcPath &B = c->bc;
   const BcForm other = c->fl.unmerged_bc ? BcForm::by_direction : BcForm::all;
@@ -262,6 +261,15 @@ void bc_setup(cales_ctx *c) {
   for (int d = 1; d <= 3; ++d) for (int sd = 0; sd <= 1; ++sd) if (ISB(c, sd, d) && CBV(c, sd, d, d) == 'N') B.vel_fcn |= 1 << (d - 1);
   // the periodic kernel takes riders whose own set is periodic in x and y, the all-directions kernel any cell-centred set
   for (int w = 0; w < 2; ++w) B.ride[w] = merged ? B.cell[w] == BcForm::merged : B.vel == BcForm::all;
+  const DBound *bvel[2][3] = {{&c->bcu, &c->bcv, &c->bcw}, {&c->bcuf, &c->bcvf, &c->bcwf}};
+  for (int d = 1; d <= 3; ++d) {
+    const int wm = (ISB(c, 0, d) && LWM(c, 0, d) != 0 ? 1 : 0) | (ISB(c, 1, d) && LWM(c, 1, d) != 0 ? 2 : 0);
+    for (int s = 0; s < 2; ++s) for (int iv = 1; iv <= 3; ++iv) {
+      B.rules_vel[s][iv - 1].d[d - 1] = table_rule(c, d, CBV(c, 0, d, iv), CBV(c, 1, d, iv), iv != d, *bvel[s][iv - 1]);
+      B.rules_vel[s][iv - 1].wm[d - 1] = iv != d ? (unsigned char)wm : 0;
+    }
+    for (int w = 0; w < 2; ++w) B.rules_cell[w].d[d - 1] = w ? table_rule(c, d, CBS(c, 0, d), CBS(c, 1, d), 1, c->bcs) : table_rule(c, d, CBP(c, 0, d), CBP(c, 1, d), 1, c->bcp);
+  }
 }
 
 // y-slab neighbours (bound.f90:619-696 for idir = 2): pack the first/last interior rows of nf fields into the
@@ -294,19 +302,19 @@ __global__ __launch_bounds__(256) void k_unpack_y(Geom g, HaloFields H, const re
 // A field of PAIRS (two values per cell, SgsPath::pair) is, for every operation that copies whole rows or planes, a field of twice the width:
 // 2 (n1 + 2) values per row, pitches doubled. Its x ghost "columns" mean nothing in that view -- the callers skip direction x.
 static Geom wide_geom(const cales_ctx *c) { Geom g = c->g; g.n1 = 2 * c->g.n1 + 2; g.s1 = 2 * c->g.s1; g.s12 = 2 * c->g.s12; return g; }
-// (wide[q] != 0: field q is a pair field; nullptr: none is)
-static int halo_y_on(cales_ctx *c, const BcCall &b, int nf, real **flds, hipStream_t st, bool overlapped, const unsigned char *wide = nullptr) {
+// kind[q]: 0 a field, 1 a pair field, 2 / 3 the second / third rows of a field into its first / second companion (nullptr: fields); vcomp[q] != 0 in a
+// call that carries a corrected view: the rows of field q that leave are those of this component of the projected velocity (nullptr: none)
+static int halo_y_on(cales_ctx *c, const BcCall &b, int nf, real **flds, hipStream_t st, bool overlapped, const unsigned char *kinds = nullptr, const unsigned char *vcomp = nullptr) {
   const Geom &G = c->g;
   HaloFields H; H.nf = nf; int planes = 0, anyw = 0;
-  // (wide[q]: 0 a field, 1 a pair field, 2 / 3 the second / third rows of a field into its first / second companion)
   for (int q = 0; q < nf; ++q) {
-    const int kind = wide ? wide[q] : 0;
+    const int kind = kinds ? kinds[q] : 0;
     H.p[q] = flds[q]; H.wide[q] = kind == 1; H.off[q] = planes; planes += 1 + H.wide[q]; anyw |= H.wide[q]; H.vcomp[q] = 0;
     H.rofs[q] = kind >= 2 ? (unsigned char)(kind - 1) : 0; H.dst[q] = kind >= 2 ? flds[q] + (size_t)(kind - 1) * c->comp_one : flds[q];
   }
-  if (b.view_dtrk != 0.) {      // op_bounduvw through the corrected view: the velocity rows that leave are those of the projected velocity
+  if (b.view_dtrk != 0. && vcomp) {      // op_bounduvw through the corrected view
     H.V = corr_view(c, b);
-    for (int q = 0; q < nf; ++q) for (int iv = 0; iv < 3; ++iv) if (flds[q] == c->f[CALES_U + iv] && !H.rofs[q]) H.vcomp[q] = (unsigned char)(iv + 1);
+    for (int q = 0; q < nf; ++q) if (!H.rofs[q]) H.vcomp[q] = vcomp[q];
   }
   const int64_t cnt = (int64_t)G.s1 * (c->n[2] + 2) * planes;
   if (4 * cnt > c->comm.nbuf) { c->err = "halo staging buffer too small"; return 1; }
@@ -321,7 +329,8 @@ static int halo_y_on(cales_ctx *c, const BcCall &b, int nf, real **flds, hipStre
   return 0;
 }
 // the rows of nf fields of one kind: into the caller's batch (BcCall::collect, exchanged later by halo_flush_deferred) or exchanged now
-static int halo_y_kind(cales_ctx *c, const BcCall &b, int nf, real **flds, int kind) {
+// (a batch is flushed without a view: vcomp goes with an exchange made now)
+static int halo_y_kind(cales_ctx *c, const BcCall &b, int nf, real **flds, int kind, const unsigned char *vcomp = nullptr) {
   if (b.collect) {
     HaloBatch &R = *b.collect;
     if (R.n + nf > 16) { c->err = "halo batch full"; return 1; }
@@ -329,17 +338,17 @@ static int halo_y_kind(cales_ctx *c, const BcCall &b, int nf, real **flds, int k
     return 0;
   }
   unsigned char w[16]; for (int q = 0; q < nf && q < 16; ++q) w[q] = (unsigned char)kind;
-  return halo_y_on(c, b, nf, flds, c->stream, false, w);
+  return halo_y_on(c, b, nf, flds, c->stream, false, w, vcomp);
 }
 int halo_y_rows(cales_ctx *c, int nf, real **flds, int kind, const BcCall &b) {
   if (!c->comm.on) { c->err = "nranks > 1 but no communication hooks registered (cales_set_comm)"; return 1; }
   if (!c->comp_one || kind < 2 || kind > 3) { c->err = "halo_y_rows: no companion fields"; return 1; }
   return halo_y_kind(c, b, nf, flds, kind);
 }
-static int halo_y_comm(cales_ctx *c, const BcCall &b, int nf, real **flds, bool wide = false) {
+static int halo_y_comm(cales_ctx *c, const BcCall &b, int nf, real **flds, int kind, const unsigned char *vcomp) {
   if (!c->comm.on) { c->err = "nranks > 1 but no communication hooks registered (cales_set_comm)"; return 1; }
   if (b.rows_current) return 0;
-  return halo_y_kind(c, b, nf, flds, wide ? 1 : 0);
+  return halo_y_kind(c, b, nf, flds, kind, vcomp);
 }
 // The y-halo rows of the fields collected in `rows` (BcCall::collect) travel on the second stream, after everything queued on the
 // context's stream so far (their ghost-cell kernels included: what those wrote into the ghost rows is overwritten by the rows
@@ -358,101 +367,110 @@ int halo_flush_deferred(cales_ctx *c, HaloBatch &rows, bool overlapped) {
   rows.n = 0;
   return 0;
 }
-// halo exchange in the non-pencil directions: y across slabs (or a periodic copy on one rank), z always local
-static int halo_self(cales_ctx *c, const BcCall &b, int nf, real **flds) {
-  if (c->P > 1) { if (int e = halo_y_comm(c, b, nf, flds)) return e; }
-  for (int idir = (c->P > 1 ? 3 : 2); idir <= 3; ++idir) {
-    const bool periodic = idir == 2 ? c->per_y : !ISB(c, 0, 3);
-    if (!periodic) continue;             // not periodic: neighbours are MPI_PROC_NULL
-    BcJobs J; J.njobs = 0; J.idir = idir;
-    const bool view = b.view_dtrk != 0.;      // op_bounduvw through the corrected view: the periodic copies are those of the projected velocity
-    if (view) J.V = corr_view(c, b);
-    for (int q = 0; q < nf; ++q) {
-      if (J.njobs == 6) { if (int e = launch_jobs(c, J)) return e; J.njobs = 0; }
-      add_job(J, flds[q], 'P', 0, 1, nullptr, 0.);
-      if (view) for (int iv = 0; iv < 3; ++iv) if (flds[q] == c->f[CALES_U + iv]) J.job[J.njobs - 1].vcomp = (char)(iv + 1);
+// ------------------------------------------------------------------------------------------ one ghost-cell update
+// An entry of an update: the field, its rules in BcPath's tables and, in a call that carries a corrected view, the velocity component the field holds
+// the prediction of (0: plain reads) -- stated by whoever lists the entry, never inferred from the pointer
+struct BcEntry { real *p; const BcRules *r; char vcomp; };
+// What one update takes from its call: the skipped directions (bc_skipped), bounduvw's is_correc, the update of the wall-model faces that follows the
+// wall model instead of the main one, a pair field in the doubled-width view
+struct BcUse { int skipped = 0; bool is_correc = false, wm_faces = false, wide = false; };
+// does the update serve direction d (0..2) at all? A periodic z is copied even where z is "skipped": the skip is for wall planes nobody reads. Pair fields:
+// direction x is the consumers' business (they wrap around) and pointwise z conditions would need the BC planes in the doubled view (the callers skip z at walls)
+static bool dir_on(const BcUse &u, int d, bool periodic) {
+  if (u.wide && (d == 0 || (d == 2 && !periodic))) return false;
+  return !(u.skipped >> d & 1) || (d == 2 && periodic);
+}
+// THE place where a call changes a rule of the tables: direction d of field T as this update applies it
+static BcRule bc_rule(const BcRules &T, int d, const BcUse &u) {
+  BcRule R = T.d[d];
+  const bool periodic = R.t0 == 'P';
+  int off = T.wm[d];                                                              // main update: the wall-model ends are set afterwards, from the wall-model stress
+  if (u.wm_faces) off = ~T.wm[d];                                                 // ... by this update: those ends and nothing else (bound.f90:125-148)
+  else if (!dir_on(u, d, periodic) || (u.is_correc && !R.cen && !periodic)) off = 3;      // the corrected normal velocity keeps its wall value (bound.f90:60-75)
+  if (off & 1) R.t0 = 0;
+  if (off & 2) R.t1 = 0;
+  return R;
+}
+// x, y periodic: every entry in one launch (k_bc_merged). The three flags are what the call leaves on of each direction
+static int update_merged(cales_ctx *c, int ne, const BcEntry *e, const BcUse &u, const CorrView &V) {
+  MJobs J; J.nf = ne; J.V = V;
+  J.do_x = dir_on(u, 0, true); J.wrap_y = c->P == 1 && dir_on(u, 1, true); J.do_z = dir_on(u, 2, e[0].r->d[2].t0 == 'P');
+  if (u.wide && !J.wrap_y && !J.do_z) return 0;
+  for (int q = 0; q < ne; ++q) {
+    const BcRule z = bc_rule(*e[q].r, 2, u);
+    MField &F = J.f[q]; F.p = e[q].p; F.bc0 = z.bc0; F.bc1 = z.bc1; F.dr0 = z.dr0; F.dr1 = z.dr1; F.t0 = z.t0; F.t1 = z.t1; F.centered = z.cen; F.vcomp = e[q].vcomp;
+  }
+  return launch_merged(c, J, u.wide ? wide_geom(c) : c->g);
+}
+// any pointwise set: six entries per launch (k_bc_all); the update of the wall-model faces only where some end is on
+static int update_all(cales_ctx *c, int ne, const BcEntry *e, const BcUse &u, const CorrView &V) {
+  for (int q0 = 0; q0 < ne; q0 += 6) {
+    AJobs J; J.nf = std::min(6, ne - q0); J.V = V; bool any = false;
+    for (int q = 0; q < J.nf; ++q) {
+      AField &F = J.f[q]; F.p = e[q0 + q].p; F.vcomp = e[q0 + q].vcomp;
+      for (int d = 0; d < 3; ++d) { F.d[d] = bc_rule(*e[q0 + q].r, d, u); any = any || F.d[d].t0 || F.d[d].t1; }
     }
-    if (int e = launch_jobs(c, J)) return e;
+    if (u.wm_faces && !any) continue;
+    if (int er = launch_all(c, J)) return er;
   }
   return 0;
+}
+// the reference's order, one k_set_bc launch per direction and at most six jobs per launch: first the periodic copies of y (one rank) and z, the image of
+// updthalo (bound.f90:619-696: neighbours of the non-pencil directions), then x -> y -> z for everything else. A 'P' is one job for both ends; the
+// two ends of an entry stay in one launch
+static int update_by_direction(cales_ctx *c, int ne, const BcEntry *e, const BcUse &u, const CorrView &V) {
+  for (int pass = 0; pass < 2; ++pass)
+    for (int d = pass ? 0 : 1; d < 3; ++d) {
+      BcJobs J; J.njobs = 0; J.idir = d + 1; J.V = V;
+      for (int q = 0; q < ne; ++q) {
+        const BcRule R = bc_rule(*e[q].r, d, u);
+        const bool copy = d > 0 && R.t0 == 'P';
+        if (copy != (pass == 0)) continue;
+        if (J.njobs + (copy ? 1 : 2) > 6) { if (int er = launch_jobs(c, J)) return er; J.njobs = 0; }
+        auto add = [&](char t, int ib, const real *bc, real dr) {
+          BcJob &j = J.job[J.njobs++];
+          j.p = e[q].p; j.bc = bc; j.dr = dr; j.ctype = t; j.centered = R.cen; j.ibound = (char)ib; j.vcomp = e[q].vcomp;
+        };
+        if (R.t0 == 'P') { add('P', 0, nullptr, 0.); continue; }
+        if (R.t0) add(R.t0, 0, R.bc0, R.dr0);
+        if (R.t1) add(R.t1, 1, R.bc1, R.dr1);
+      }
+      if (int er = launch_jobs(c, J)) return er;
+    }
+  return 0;
+}
+// ne <= 8 entries in the form `form`: the rows of the slab neighbours (in one exchange; not for the wall-model faces, which follow an update that had
+// it), then the ghost cells in as few launches as the form's job table allows
+static int bc_update(cales_ctx *c, int ne, const BcEntry *e, BcForm form, const BcUse &u, const BcCall &b) {
+  if (ne > 8) { c->err = "a ghost-cell update takes at most eight fields"; return 1; }
+  if (c->P > 1 && !u.wm_faces) {
+    real *p[8]; unsigned char vc[8];
+    for (int q = 0; q < ne; ++q) { p[q] = e[q].p; vc[q] = (unsigned char)e[q].vcomp; }
+    if (int er = halo_y_comm(c, b, ne, p, u.wide ? 1 : 0, vc)) return er;
+  }
+  // corrected view (cales_step, fold_mom): the fields hold the prediction, the ghost cells receive the values of the projected velocity
+  const CorrView V = b.view_dtrk != 0. ? corr_view(c, b) : CorrView{};
+  return form == BcForm::merged ? update_merged(c, ne, e, u, V) : form == BcForm::all ? update_all(c, ne, e, u, V) : update_by_direction(c, ne, e, u, V);
 }
 
-// a cell-centred field with the pressure (which = 0) or the sgs (1) BC set as one entry of the one-launch kernel
-static void merged_pfield(cales_ctx *c, MField &F, real *p, int which) {
-  const char *cbc = which == 0 ? c->C.cbcpre : c->C.cbcsgs; const DBound &bc = which == 0 ? c->bcp : c->bcs;
-  const bool per_z = cbc[4] == 'P' && cbc[5] == 'P';
-  F.p = p; F.centered = 1;
-  F.t0 = per_z ? 'P' : cbc[4]; F.t1 = per_z ? 'P' : cbc[5];
-  F.bc0 = plane(bc, 3, 0, c->n); F.bc1 = plane(bc, 3, 1, c->n); F.dr0 = c->dzc[0]; F.dr1 = c->dzc[c->n[2]];
-}
-// a cell-centred field with the pressure (which = 0) or the sgs (1) BC set as one entry of the all-directions kernel
-static void all_pfield(cales_ctx *c, const BcCall &b, AField &F, real *p, int which) {
-  const char *cbc = which == 0 ? c->C.cbcpre : c->C.cbcsgs; const DBound &bc = which == 0 ? c->bcp : c->bcs;
-  F.p = p; F.vcomp = 0;
-  for (int idir = 1; idir <= 3; ++idir) {
-    const real dr0 = idir < 3 ? c->dl[idir - 1] : c->dzc[0], dr1 = idir < 3 ? c->dl[idir - 1] : c->dzc[c->n[2]];
-    a_dir(c, b, F.d[idir - 1], idir, cbc[2 * (idir - 1)], cbc[2 * (idir - 1) + 1], 1, plane(bc, idir, 0, c->n), plane(bc, idir, 1, c->n), dr0, dr1);
-  }
-}
 // ------------------------------------------------------------------------------------------ boundp (bound.f90:156-200)
-// pair fields (x and y periodic only: SgsPath::pair): the y rows (wrapped on one rank, exchanged between slabs) and the z ghost planes through the
-// one-launch kernel in the doubled-width view; direction x is the consumers' business (they wrap around)
+static int cell_update(cales_ctx *c, int nf, real **p, int which, const BcCall &b, bool wide) {
+  BcEntry e[8];
+  for (int q = 0; q < nf && q < 8; ++q) e[q] = BcEntry{p[q], &c->bc.rules_cell[which], 0};
+  BcUse u; u.skipped = bc_skipped(c, b); u.wide = wide;
+  return bc_update(c, nf, e, c->bc.cell[which], u, b);
+}
+// pair fields (x and y periodic only: SgsPath::pair): the y rows (wrapped on one rank, exchanged between slabs) and the z ghost planes where z is periodic,
+// through the one-launch kernel in the doubled-width view
 int op_boundp_wide(cales_ctx *c, int nf, real **p2, int which, const BcCall &b) {
   ProfScope ps(c, "boundp");
-  const char *cbc = which == 0 ? c->C.cbcpre : c->C.cbcsgs;
   if (c->bc.cell[which] != BcForm::merged || nf > 8 || !(bc_skipped(c, b) & 1)) { c->err = "pair fields need periodic x and y and a caller that skips direction x"; return 1; }
-  if (c->P > 1) { if (int e = halo_y_comm(c, b, nf, p2, true)) return e; }
-  const bool per_z = cbc[4] == 'P' && cbc[5] == 'P';
-  const Geom G = wide_geom(c);
-  MJobs J; J.nf = nf; J.do_x = 0; J.wrap_y = c->P == 1; J.do_z = per_z || !(bc_skipped(c, b) & 4);
-  if (!J.wrap_y && !J.do_z) return 0;
-  for (int q = 0; q < nf; ++q) {
-    merged_pfield(c, J.f[q], p2[q], which);
-    if (!per_z) { J.f[q].t0 = 0; J.f[q].t1 = 0; }      // (pointwise z conditions would need the BC planes in the doubled view: the callers skip z at walls)
-  }
-  if (!per_z) J.do_z = 0;
-  if (!J.wrap_y && !J.do_z) return 0;
-  return launch_merged(c, J, &G);
+  return cell_update(c, nf, p2, which, b, true);
 }
-// nf <= 8 fields with the same BC set in one halo exchange and as few launches as the job table allows
+// nf <= 8 fields with the same BC set (which: 0 pressure, 1 sgs) in one halo exchange and as few launches as the job table allows
 int op_boundp_multi(cales_ctx *c, int nf, real **p, int which, const BcCall &b) {
   ProfScope ps(c, "boundp");
-  const char *cbc = which == 0 ? c->C.cbcpre : c->C.cbcsgs; const DBound &bc = which == 0 ? c->bcp : c->bcs;
-  const BcForm form = c->bc.cell[which];
-  if (form == BcForm::merged && nf <= 8) {      // x, y periodic: all three directions in one launch (k_bc_merged)
-    if (c->P > 1) { if (int e = halo_y_comm(c, b, nf, p)) return e; }
-    const bool per_z = cbc[4] == 'P' && cbc[5] == 'P';
-    MJobs J; J.nf = nf; J.do_x = !(bc_skipped(c, b) & 1); J.wrap_y = c->P == 1; J.do_z = per_z || !(bc_skipped(c, b) & 4);
-    for (int q = 0; q < nf; ++q) merged_pfield(c, J.f[q], p[q], which);
-    return launch_merged(c, J);
-  }
-  if (form != BcForm::by_direction) {      // every other set of a cell-centred field: all directions in one launch (k_bc_all), six fields at a time
-    if (c->P > 1) { if (int e = halo_y_comm(c, b, nf, p)) return e; }
-    for (int q0 = 0; q0 < nf; q0 += 6) {
-      AJobs J; J.nf = std::min(6, nf - q0); J.V = CorrView{};
-      for (int q = 0; q < J.nf; ++q) all_pfield(c, b, J.f[q], p[q0 + q], which);
-      if (int e = launch_all(c, J)) return e;
-    }
-    return 0;
-  }
-  if (int e = halo_self(c, b, nf, p)) return e;
-  for (int idir = 1; idir <= 3; ++idir) {
-    if (!ISB(c, 0, idir) && !ISB(c, 1, idir)) continue;
-    if (bc_skipped(c, b) >> (idir - 1) & 1) continue;
-    BcJobs J; J.njobs = 0; J.idir = idir;
-    const real dr0 = idir < 3 ? c->dl[idir - 1] : c->dzc[0], dr1 = idir < 3 ? c->dl[idir - 1] : c->dzc[c->n[2]];
-    const char c0 = cbc[0 + 2 * (idir - 1)], c1 = cbc[1 + 2 * (idir - 1)];
-    for (int q = 0; q < nf; ++q) {
-      if (J.njobs + 2 > 6) { if (int e = launch_jobs(c, J)) return e; J.njobs = 0; }
-      if (c0 == 'P') add_job(J, p[q], 'P', 0, 1, nullptr, 0.);      // both ends in one job (identical result to the two calls)
-      else {
-        if (ISB(c, 0, idir)) add_job(J, p[q], c0, 0, 1, plane(bc, idir, 0, c->n), dr0);
-        if (ISB(c, 1, idir)) add_job(J, p[q], c1, 1, 1, plane(bc, idir, 1, c->n), dr1);
-      }
-    }
-    if (J.njobs) { if (int e = launch_jobs(c, J)) return e; }
-  }
-  return 0;
+  return cell_update(c, nf, p, which, b, false);
 }
 int op_boundp(cales_ctx *c, real *p, int which, const BcCall &b) { real *fl[1] = {p}; return op_boundp_multi(c, 1, fl, which, b); }
 
@@ -599,136 +617,40 @@ static int updt_wallmodelbc(cales_ctx *c, DBound &bu, DBound &bv, DBound &bw, co
 }
 
 // ------------------------------------------------------------------------------------------ bounduvw (bound.f90:18-154)
-// rode: the riders of the call (BcCall::ride) went with the velocity's launch
-static int bounduvw_launches(cales_ctx *c, DBound &bu, DBound &bv, DBound &bw, int is_updt_wm, int is_correc, real *u, real *v, real *w, const BcCall &b, bool &rode) {
-  ProfScope ps(c, "bounduvw");
-  const int *n = c->n;
-  real *fl[3] = {u, v, w};
-  DBound *bnd[3] = {&bu, &bv, &bw};
-  // corrected view (cales_step, fold_mom): the fields hold the prediction, the ghost cells receive the values of the projected velocity
-  const bool view = b.view_dtrk != 0.;
-  const CorrView V = view ? corr_view(c, b) : CorrView{};
-  const int skipped = bc_skipped(c, b);
+// The three components of a velocity set, face-centred along their own direction, plus the call's riders; then, unless the call leaves the wall model
+// alone, the wall-model stress (is_updt_wm) and the tangential ghost cells of the wall-model faces from it. Riders that cannot join (BcPath::ride, a
+// skipped z, the per-direction form) get their own update right after.
+int op_bounduvw(cales_ctx *c, VelSet set, int is_updt_wm, int is_correc, const BcCall &b) {
+  const BcPath &B = c->bc;
+  const bool state = set == VelSet::state, view = b.view_dtrk != 0.;
+  real *fl[3] = {state ? c->f[CALES_U] : c->uf, state ? c->f[CALES_V] : c->vf, state ? c->f[CALES_W] : c->wf};
+  BcEntry e[6];
+  for (int iv = 0; iv < 3; ++iv) e[iv] = BcEntry{fl[iv], &B.rules_vel[(int)set][iv], (char)(state && view ? iv + 1 : 0)};
+  BcUse u; u.skipped = bc_skipped(c, b); u.is_correc = is_correc != 0;
   // the form of the velocity set (BcPath): k_bc_all only while no direction of this call holds a Neumann condition on the normal component
-  BcForm form = c->bc.vel;
-  if (form == BcForm::all && !is_correc && (c->bc.vel_fcn & ~skipped)) form = BcForm::by_direction;
+  BcForm form = B.vel;
+  if (form == BcForm::all && !is_correc && (B.vel_fcn & ~u.skipped)) form = BcForm::by_direction;
   // riders: cell-centred fields join the velocity's launch -- and its slab exchange
   int nr = 0;
-  if (b.nride > 0 && form != BcForm::by_direction && !(skipped & 4)) {
+  if (b.nride > 0 && form != BcForm::by_direction && !(u.skipped & 4)) {
     nr = b.nride;
-    for (int q = 0; q < b.nride; ++q) if (!c->bc.ride[b.ride_which[q]]) nr = 0;
+    for (int q = 0; q < b.nride; ++q) if (!B.ride[b.ride_which[q]]) nr = 0;
   }
-  rode = nr > 0;
-  real *all[6] = {fl[0], fl[1], fl[2], nullptr, nullptr, nullptr};
-  for (int q = 0; q < nr; ++q) all[3 + q] = b.ride[q];
-  if (form == BcForm::merged) {
-    if (c->P > 1) { if (int e = halo_y_comm(c, b, 3 + nr, all)) return e; }
-    const bool per_z = CBV(c, 0, 3, 3) == 'P' && CBV(c, 1, 3, 3) == 'P';
-    MJobs J; J.nf = 3 + nr; J.do_x = !(skipped & 1); J.wrap_y = c->P == 1; J.do_z = per_z || !(skipped & 4);
-    for (int q = 0; q < nr; ++q) merged_pfield(c, J.f[3 + q], b.ride[q], b.ride_which[q]);
-    J.V = V;
-    for (int ivel = 1; ivel <= 3; ++ivel) {
-      MField &F = J.f[ivel - 1]; F.p = fl[ivel - 1]; F.vcomp = view ? (char)ivel : 0;
-      const bool normal = ivel == 3;
-      F.centered = normal ? 0 : 1;
-      F.bc0 = plane(*bnd[ivel - 1], 3, 0, n); F.bc1 = plane(*bnd[ivel - 1], 3, 1, n);
-      F.dr0 = normal ? c->dzf[0] : c->dzc[0]; F.dr1 = normal ? c->dzf[n[2]] : c->dzc[n[2]];
-      if (per_z) { F.t0 = F.t1 = 'P'; continue; }
-      F.t0 = CBV(c, 0, 3, ivel); F.t1 = CBV(c, 1, 3, ivel);
-      if (normal && is_correc) F.t0 = F.t1 = 0;                                 // the corrected normal velocity keeps its wall value (bound.f90:60-75)
-      if (!normal) { if (LWM(c, 0, 3) != 0) F.t0 = 0; if (LWM(c, 1, 3) != 0) F.t1 = 0; }      // set below from the wall-model stress
-    }
-    if (int e = launch_merged(c, J)) return e;
-  } else if (form == BcForm::all) {
-    // every other pointwise set: the three directions of the three components (and of the riders) in ONE launch (k_bc_all), types of every (component,
-    // direction, end) as the loops of the per-direction form would apply them
-    AJobs JA; JA.nf = 3 + nr; JA.V = V;
-    for (int ivel = 1; ivel <= 3; ++ivel) {
-      AField &F = JA.f[ivel - 1]; F.p = fl[ivel - 1]; F.vcomp = view ? (char)ivel : 0;
-      for (int idir = 1; idir <= 3; ++idir) {
-        const bool periodic = CBV(c, 0, idir, idir) == 'P' && CBV(c, 1, idir, idir) == 'P', normal = ivel == idir;
-        const real dr0 = idir < 3 ? c->dl[idir - 1] : (normal ? c->dzf[0] : c->dzc[0]), dr1 = idir < 3 ? c->dl[idir - 1] : (normal ? c->dzf[n[2]] : c->dzc[n[2]]);
-        char c0 = CBV(c, 0, idir, ivel), c1 = CBV(c, 1, idir, ivel);
-        if (normal && is_correc && !periodic) c0 = c1 = 0;      // the corrected normal velocity keeps its wall value (bound.f90:60-75)
-        a_dir(c, b, F.d[idir - 1], idir, c0, c1, normal ? 0 : 1, plane(*bnd[ivel - 1], idir, 0, n), plane(*bnd[ivel - 1], idir, 1, n), dr0, dr1);
-        if (!c0 && !c1) F.d[idir - 1].t0 = F.d[idir - 1].t1 = 0;
-        if (!normal) { if (LWM(c, 0, idir) != 0) F.d[idir - 1].t0 = 0; if (LWM(c, 1, idir) != 0) F.d[idir - 1].t1 = 0; }      // set below from the wall-model stress
-      }
-    }
-    for (int q = 0; q < nr; ++q) all_pfield(c, b, JA.f[3 + q], b.ride[q], b.ride_which[q]);
-    if (c->P > 1) { if (int e = halo_y_comm(c, b, 3 + nr, all)) return e; }
-    if (int e = launch_all(c, JA)) return e;
-  } else {
-  if (int e = halo_self(c, b, 3, fl)) return e;
-  for (int idir = 1; idir <= 3; ++idir) {
-    if (!ISB(c, 0, idir) && !ISB(c, 1, idir)) continue;
-    if (skipped >> (idir - 1) & 1) continue;
-    BcJobs J; J.njobs = 0; J.idir = idir;
-    const bool periodic = CBV(c, 0, idir, idir) == 'P' && CBV(c, 1, idir, idir) == 'P';
-    const bool impose_norm = (!is_correc) || periodic;
-    const real drn0 = idir < 3 ? c->dl[idir - 1] : c->dzf[0], drn1 = idir < 3 ? c->dl[idir - 1] : c->dzf[n[2]];
-    const real drt0 = idir < 3 ? c->dl[idir - 1] : c->dzc[0], drt1 = idir < 3 ? c->dl[idir - 1] : c->dzc[n[2]];
-    J.V = V;
-    for (int ivel = 1; ivel <= 3; ++ivel) {
-      real *p = fl[ivel - 1];
-      const bool normal = ivel == idir;
-      const char c0 = CBV(c, 0, idir, ivel), c1 = CBV(c, 1, idir, ivel);
-      const int first = J.njobs;
-      struct SetView { BcJobs &J; int first, comp; ~SetView() { for (int q = first; q < J.njobs; ++q) J.job[q].vcomp = (char)comp; } } setview{J, first, view ? ivel : 0};
-      if (normal) {
-        if (!impose_norm) continue;
-        if (c0 == 'P') add_job(J, p, 'P', 0, 0, nullptr, 0.);
-        else {
-          if (ISB(c, 0, idir)) add_job(J, p, c0, 0, 0, plane(*bnd[ivel - 1], idir, 0, n), drn0);
-          if (ISB(c, 1, idir)) add_job(J, p, c1, 1, 0, plane(*bnd[ivel - 1], idir, 1, n), drn1);
-        }
-      } else {
-        if (c0 == 'P' && LWM(c, 0, idir) == 0) { add_job(J, p, 'P', 0, 1, nullptr, 0.); continue; }
-        if (ISB(c, 0, idir) && LWM(c, 0, idir) == 0) add_job(J, p, c0, 0, 1, plane(*bnd[ivel - 1], idir, 0, n), drt0);
-        if (ISB(c, 1, idir) && LWM(c, 1, idir) == 0) add_job(J, p, c1, 1, 1, plane(*bnd[ivel - 1], idir, 1, n), drt1);
-      }
-    }
-    if (int e = launch_jobs(c, J)) return e;
-  }
-  }
-  if (b.skip_wm) return 0;
-  if (is_updt_wm) if (int e = updt_wallmodelbc(c, bu, bv, bw, u, v, w)) return e;
-  if (c->bc.wm == BcForm::all) {      // tangential Neumann BCs carrying the wall-model stress (bound.f90:125-148): every wall-model face in one launch
-    AJobs JW; JW.nf = 3; JW.V = V; bool any = false;
-    for (int ivel = 1; ivel <= 3; ++ivel) {
-      AField &F = JW.f[ivel - 1]; F.p = fl[ivel - 1]; F.vcomp = view ? (char)ivel : 0;
-      for (int idir = 1; idir <= 3; ++idir) {
-        ADir &D = F.d[idir - 1]; D.t0 = D.t1 = 0; D.cen = 1; D.dr0 = idir < 3 ? c->dl[idir - 1] : c->dzc[0]; D.dr1 = idir < 3 ? c->dl[idir - 1] : c->dzc[n[2]];
-        D.bc0 = plane(*bnd[ivel - 1], idir, 0, n); D.bc1 = plane(*bnd[ivel - 1], idir, 1, n);
-        if (ivel == idir) continue;
-        if (ISB(c, 0, idir) && LWM(c, 0, idir) != 0) { D.t0 = CBV(c, 0, idir, ivel); any = true; }
-        if (ISB(c, 1, idir) && LWM(c, 1, idir) != 0) { D.t1 = CBV(c, 1, idir, ivel); any = true; }
-      }
-    }
-    return any ? launch_all(c, JW) : 0;
-  }
-  for (int idir = 1; idir <= 3; ++idir) {   // ... or one launch per direction
-    BcJobs J; J.njobs = 0; J.idir = idir;
-    const real drt0 = idir < 3 ? c->dl[idir - 1] : c->dzc[0], drt1 = idir < 3 ? c->dl[idir - 1] : c->dzc[n[2]];
-    for (int ib = 0; ib <= 1; ++ib) {
-      if (!(ISB(c, ib, idir) && LWM(c, ib, idir) != 0)) continue;
-      for (int ivel = 1; ivel <= 3; ++ivel) if (ivel != idir)
-        add_job(J, fl[ivel - 1], CBV(c, ib, idir, ivel), ib, 1, plane(*bnd[ivel - 1], idir, ib, n), ib ? drt1 : drt0);
-    }
-    if (int e = launch_jobs(c, J)) return e;
-  }
-  return 0;
-}
-int op_bounduvw(cales_ctx *c, DBound &bu, DBound &bv, DBound &bw, int is_updt_wm, int is_correc, real *u, real *v, real *w, const BcCall &b) {
-  bool rode = false;
-  if (int e = bounduvw_launches(c, bu, bv, bw, is_updt_wm, is_correc, u, v, w, b, rode)) return e;
-  if (!b.nride || rode) return 0;
-  // the riders could not join (BcPath::ride, a skipped z, CALES_UNMERGED_BC): their ghost cells now, consecutive riders of one BC set together
+  for (int q = 0; q < nr; ++q) e[3 + q] = BcEntry{b.ride[q], &B.rules_cell[b.ride_which[q]], 0};
+  { ProfScope ps(c, "bounduvw");
+    if (int er = bc_update(c, 3 + nr, e, form, u, b)) return er;
+    if (!b.skip_wm) {
+      if (is_updt_wm) { if (int er = state ? updt_wallmodelbc(c, c->bcu, c->bcv, c->bcw, fl[0], fl[1], fl[2]) : updt_wallmodelbc(c, c->bcuf, c->bcvf, c->bcwf, fl[0], fl[1], fl[2])) return er; }
+      BcUse w; w.wm_faces = true;      // tangential Neumann BCs carrying the wall-model stress (bound.f90:125-148)
+      if (int er = bc_update(c, 3, e, B.wm, w, b)) return er;
+    } }
+  if (!b.nride || nr) return 0;
+  // the riders could not join: their ghost cells now, consecutive riders of one BC set together
   BcCall alone = b; alone.nride = 0;
   for (int q0 = 0, q1; q0 < b.nride; q0 = q1) {
     real *p[3];
     for (q1 = q0; q1 < b.nride && b.ride_which[q1] == b.ride_which[q0]; ++q1) p[q1 - q0] = b.ride[q1];
-    if (int e = op_boundp_multi(c, q1 - q0, p, b.ride_which[q0], alone)) return e;
+    if (int er = op_boundp_multi(c, q1 - q0, p, b.ride_which[q0], alone)) return er;
   }
   return 0;
 }
@@ -741,7 +663,7 @@ __global__ __launch_bounds__(256) void k_updt_rhs_b(Geom g, RhsJob J) {
   const size_t q = J.idir == 1 ? g.ix(J.pos, a, b) : J.idir == 2 ? g.ix(a, J.pos, b) : g.ix(a, b, J.pos);
   J.p[q] += J.rhs[(a - 1) + (size_t)J.na * (b - 1)];
 }
-static int rhs_b_dir(cales_ctx *c, real *p, int idir, const char *cbc6, const char *cf, const real *rhs, real scale_unused) {
+static int rhs_b_dir(cales_ctx *c, real *p, int idir, const char *cbc6, const char *cf, const real *rhs) {
   const int *n = c->n;
   const int na = idir == 1 ? n[1] : n[0], nb = idir == 3 ? n[1] : n[2];
   const int q = (cf[idir - 1] == 'f' && cbc6[1 + 2 * (idir - 1)] == 'D') ? 1 : 0;
@@ -753,7 +675,6 @@ static int rhs_b_dir(cales_ctx *c, real *p, int idir, const char *cbc6, const ch
   LAUNCHCHK(c);
   return 0;
 }
-static bool plane_all_zero(const cales_ctx *c, int idir) { (void)c; (void)idir; return false; }
 
 int op_updt_rhs_b(cales_ctx *c) {
   ProfScope ps(c, "updt_rhs_b");
@@ -761,8 +682,8 @@ int op_updt_rhs_b(cales_ctx *c) {
   for (int idir = 1; idir <= 3; ++idir) {
     const bool zero = (c->C.bcpre[0 + 2 * (idir - 1)] == 0. && c->C.bcpre[1 + 2 * (idir - 1)] == 0.) ||
                       (CBP(c, 0, idir) == 'P');
-    if (zero || plane_all_zero(c, idir)) continue;
-    if (int e = rhs_b_dir(c, c->f[CALES_PP], idir, c->C.cbcpre, "ccc", c->rhsbp[idir - 1], 1.)) return e;
+    if (zero) continue;
+    if (int e = rhs_b_dir(c, c->f[CALES_PP], idir, c->C.cbcpre, "ccc", c->rhsbp[idir - 1])) return e;
   }
   return 0;
 }
@@ -810,8 +731,8 @@ int op_rhs_b_velxy(cales_ctx *c, int ivel, real alpha) {
   LAUNCHCHK(c);
   return 0;
 }
-// planes != nullptr: the two contributions go to planes[0 / n1*n2] instead of being added to the field; has[ib] tells which exist
-// the two sides as arguments of the in-LDS sweep (no launch): has[ib] as below
+// the two sides as arguments of the in-LDS sweep (no launch); has[ib]: the side exists on this rank and is not periodic
+// (bound.f90:479-482: dzc01_c=[dzc(0),dzc(n)], dzf01_c=[dzf(1),dzf(n)]; dzc01_f=[dzc(1),dzc(n-1)], dzf01_f=[dzf(1),dzf(n)])
 void rhs_b_velz_args(cales_ctx *c, int ivel, real alpha, RhsBz *R, int *has) {
   const int *n = c->n; const int n3 = n[2];
   const char cf = ivel == 3 ? 'f' : 'c';
@@ -827,21 +748,17 @@ void rhs_b_velz_args(cales_ctx *c, int ivel, real alpha, RhsBz *R, int *has) {
     R[ib] = RhsBz{plane(bc, 3, ib, n), cbc[ib], cf, dlc, dlf, ib == 0 ? (real)1. : (real)-1., alpha};
   }
 }
+// ... as a pass of its own. planes != nullptr: the two contributions go to planes[0 / n1*n2] instead of being added to the field; has[ib] tells which exist
 int op_rhs_b_velz(cales_ctx *c, int ivel, real alpha, real *planes, int *has) {
-  const int *n = c->n; const int n3 = n[2];
-  const char cf = ivel == 3 ? 'f' : 'c';
-  const DBound &bc = ivel == 1 ? c->bcu : ivel == 2 ? c->bcv : c->bcw;
-  const char *cbc = &c->cbcvel[6 * (ivel - 1) + 4];
-  const int q = (cf == 'f' && cbc[1] == 'D') ? 1 : 0;
-  // bound.f90:479-482: dzc01_c=[dzc(0),dzc(n)], dzf01_c=[dzf(1),dzf(n)]; dzc01_f=[dzc(1),dzc(n-1)], dzf01_f=[dzf(1),dzf(n)]
-  if (has) has[0] = has[1] = 0;
+  const int *n = c->n;
+  RhsBz R[2]; int on[2];
+  rhs_b_velz_args(c, ivel, alpha, R, on);
+  if (has) { has[0] = on[0]; has[1] = on[1]; }
   for (int ib = 0; ib <= 1; ++ib) {
-    if (!ISB(c, ib, 3) || cbc[ib] == 'P') continue;
-    if (has) has[ib] = 1;
-    const real dlc = cf == 'c' ? (ib ? c->dzc[n3] : c->dzc[0]) : (ib ? c->dzc[n3 - 1] : c->dzc[1]);
-    const real dlf = ib ? c->dzf[n3] : c->dzf[1];
+    if (!on[ib]) continue;
+    const int pos = ib ? n[2] - ((R[ib].cf == 'f' && R[ib].ctype == 'D') ? 1 : 0) : 1;      // face-centred Dirichlet data: the last unknown plane is n3 - 1
     LAUNCH(c, k_rhs_b_velz, dim3((n[0] + 63) / 64, (n[1] + 3) / 4), dim3(64, 4), 0, c->stream, c->g, c->f[CALES_U + ivel - 1],
-                       plane(bc, 3, ib, n), ib, cbc[ib], cf, dlc, dlf, alpha, ib ? n3 - q : 1, planes ? planes + (size_t)ib * n[0] * n[1] : nullptr);
+                       R[ib].bc, ib, R[ib].ctype, R[ib].cf, R[ib].dlc, R[ib].dlf, alpha, pos, planes ? planes + (size_t)ib * n[0] * n[1] : nullptr);
   }
   LAUNCHCHK(c);
   return 0;

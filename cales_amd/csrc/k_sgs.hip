@@ -1541,7 +1541,7 @@ static int dsmag_fast(cales_ctx *c, const SgsFold *fold, bool *visct_ghosts_done
       LAUNCH(c, k_fold_ghost_rows, dim3((n[0] + 63) / 64, (n[2] + 3) / 4, 2), dim3(64, 4), 0, c->stream, c->g, c->f2[0], c->f2[1], c->f2[2], c->f[CALES_U], c->f[CALES_V],
              c->f[CALES_W], f[CALES_PP], c->scr2, f[CALES_P], c->d_force, fold->fmask, fold->dtrk * c->dli[0], fold->dtrk * c->dli[1], fold->dtrk, c->d_dzci, c->step_xskip ? 1 : 0);
     BcCall bc; bc.rows_current = c->P > 1; bc.rider(f[CALES_P], 0);
-    if (int e = op_bounduvw(c, c->bcu, c->bcv, c->bcw, 1, 1, c->f[CALES_U], c->f[CALES_V], c->f[CALES_W], bc)) return e;
+    if (int e = op_bounduvw(c, VelSet::state, 1, 1, bc)) return e;
   }
   // sgs-type ghost cells: only the periodic exchange matters (products of ghosts = ghosts of products; the wall ghosts are
   // replaced by the extrapolation rule inside the filters)
@@ -1561,7 +1561,7 @@ static int dsmag_fast(cales_ctx *c, const SgsFold *fold, bool *visct_ghosts_done
   // (five components: the pair fields (S11,S22) and (S13,S23); S12, a plain field at the head of ss2[1], goes with v_c below -- no launch more)
   real *ssp[3] = {c->ss2[0], five ? c->ss2[2] : c->ss2[1], c->ss2[2]};
   if (int e = P.pair ? op_boundp_wide(c, five ? 2 : 3, ssp, 1, bc) : op_boundp_multi(c, 6, ssij, 1, bc)) return e;
-  if (int e = op_bounduvw(c, c->bcuf, c->bcvf, c->bcwf, 0, 0, c->uf, c->vf, c->wf, bz)) return e;
+  if (int e = op_bounduvw(c, VelSet::filtered, 0, 0, bz)) return e;
   if (!P.ucf) { real *cc[3] = {c->uc, c->vc, c->wc}; if (int e = op_boundp_multi(c, 3, cc, 1, bc)) return e; }
   else if (ext) { if (int e = op_boundp(c, c->vc, 1, bc)) return e; }      // (v_c of the two ghost rows came from the strain-rate pass)
   else if (!(P.wylo && P.wyhi)) {      // v_c of the rows 1 and n2 only: their copies in the ghost rows (periodic wrap or the slab neighbours') are what the last pass reads for row 0
@@ -1768,7 +1768,7 @@ int op_cmpt_sgs(cales_ctx *c, const SgsFold *fold, bool *visct_ghosts_done) {
   filter(f2d ? f[CALES_U] : wk[0], c->uf);
   filter(f2d ? f[CALES_V] : wk[1], c->vf);
   filter(f2d ? f[CALES_W] : wk[2], c->wf);
-  if (int e = op_bounduvw(c, c->bcuf, c->bcvf, c->bcwf, 0, 0, c->uf, c->vf, c->wf)) return e;
+  if (int e = op_bounduvw(c, VelSet::filtered, 0, 0)) return e;
   real *ff[3] = {c->uf, c->vf, c->wf};
   if (int e = extrapolate(c, 3, ff, if123, 0)) return e;
   if (int e = strain_rate(c, c->uf, c->vf, c->wf, c->s0, sij)) return e;
