@@ -124,6 +124,11 @@ int ctx_upload(cales_ctx *c, real **p, const std::vector<real> &v) {
   HIPCHK(c, hipMemcpy(*p, v.data(), v.size() * sizeof(real), hipMemcpyHostToDevice));
   return 0;
 }
+// the views of RedLayout: result slots and plane sums in the tail of staging buffer A once hooks are registered (the host all-reduces them in place), in d_red otherwise
+static void red_place(cales_ctx *c) {
+  c->res = c->comm.on ? c->comm.A + (c->comm.nbuf - c->red.comm_tail) : c->d_red;
+  c->d_p1d = c->res + c->red.p1d;
+}
 static int upload_bound(cales_ctx *c, DBound &b, std::vector<real> h[3]) {
   return ctx_upload(c, &b.x, h[0]) || ctx_upload(c, &b.y, h[1]) || ctx_upload(c, &b.z, h[2]);
 }
@@ -259,9 +264,10 @@ int cales_create(const cales_case *cs, void *stream, cales_ctx **out) {
   { real *three[3]; if (field_alloc(c, &c->scr1) || field_alloc_multi(c, c->vel_comp ? 3 : 2, three)) return fail(9);      // (scr2, scr3: pp's companions)
     c->f[CALES_PP] = three[0]; c->scr2 = three[1]; c->scr3 = c->vel_comp ? three[2] : nullptr; }
   for (int q = 0; q < 3; ++q) if (vel_field(&c->f2[q])) return fail(9);
-  if (ctx_alloc(c, &c->d_red, 64 + 16 * (size_t)(n3 + 2)) || ctx_alloc(c, &c->d_force, 8)) return fail(10);
-  c->res = c->d_red;
-  if (ctx_alloc_pinned(c, &c->h_red, 64)) return fail(11);
+  c->red = RedLayout::of(n3);
+  if (ctx_alloc(c, &c->d_red, (size_t)c->red.total) || ctx_alloc(c, &c->d_force, 8)) return fail(10);
+  red_place(c);
+  if (ctx_alloc_pinned(c, &c->h_red, RedLayout::NHOST)) return fail(11);
   // sgs scratch (sgs.f90:70-83,154-171)
   if (c->C.sgstype >= 1) {
     if (field_alloc(c, &c->s0)) return fail(12);
@@ -270,7 +276,7 @@ int cales_create(const cales_case *cs, void *stream, cales_ctx **out) {
   }
   if (c->C.sgstype == 2) {
     if (field_alloc(c, &c->uc) || field_alloc(c, &c->vc) || field_alloc(c, &c->wc) || field_alloc(c, &c->uf) ||
-        field_alloc(c, &c->vf) || field_alloc(c, &c->wf) || (!c->sgs.filter2d && field_alloc(c, &c->alph2)) || ctx_alloc(c, &c->d_p1d, 2 * (size_t)n3 + 2))
+        field_alloc(c, &c->vf) || field_alloc(c, &c->wf) || (!c->sgs.filter2d && field_alloc(c, &c->alph2)))
       return fail(13);
     if (c->sgs.pair) {      // |S|Sij as three fields of pairs between K_AC and the fused last pass: the twelve scalar scratch fields of the other forms are not needed
       for (int m = 0; m < 3; ++m) if (field_alloc(c, &c->ss2[m], 2)) return fail(13);
@@ -311,9 +317,7 @@ int cales_get_field(cales_ctx *c, int field, real *host) {
   const dim3 b(64, 4, 1), gr((c->n[0] + 2 + 63) / 64, (c->n[1] + 2 + 3) / 4, c->n[2] + 2);
   LAUNCH(c, k_repack, gr, b, 0, c->stream, c->g, 0, c->f[field], c->scr1);
   LAUNCHCHK(c);
-  HIPCHK(c, hipMemcpyAsync(host, c->scr1, nh * sizeof(real), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return 0;
+  return read_back(c, host, c->scr1, nh);
 }
 int cales_upload_state(cales_ctx *c, const real *u, const real *v, const real *w, const real *p) {
   return cales_set_field(c, CALES_U, u) || cales_set_field(c, CALES_V, v) || cales_set_field(c, CALES_W, w) || cales_set_field(c, CALES_P, p);
@@ -355,19 +359,17 @@ int cales_rk_par(cales_ctx *c, const real rkpar[2], real dt, real f_out[3]) {
 }
 int cales_bulk_forcing(cales_ctx *c) { ENTRY(c, op_bulk_forcing(c)); }
 int cales_get_forcing(cales_ctx *c, real f[3]) {
-  HIPCHK(c, hipMemcpyAsync(c->h_red + 32, c->d_force, 3 * sizeof(real), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  for (int q = 0; q < 3; ++q) f[q] = c->h_red[32 + q];
+  if (int e = read_back(c, c->h_red + RedLayout::H_FORCE, c->d_force, 3)) return e;
+  for (int q = 0; q < 3; ++q) f[q] = c->h_red[RedLayout::H_FORCE + q];
   return 0;
 }
 int cales_bulk_mean(cales_ctx *c, int field, int c_or_f, real *mean) {
   if (field < 0 || field >= CALES_NFIELDS || !c->f[field]) { c->err = "bad field id"; return 1; }
   ENTER(c);
-  if (int e = op_bulk_mean_dev(c, c->f[field], c_or_f, nullptr)) return e;
+  if (int e = op_bulk_mean_dev(c, c->f[field], c_or_f)) return e;
   LAUNCHCHK(c);
-  HIPCHK(c, hipMemcpyAsync(c->h_red + 16, c->res + 16, sizeof(real), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  *mean = c->h_red[16];
+  if (int e = read_back(c, c->h_red + RedLayout::H_BULK_MEAN, c->res + RedLayout::BULK_MEAN, 1)) return e;
+  *mean = c->h_red[RedLayout::H_BULK_MEAN];
   return 0;
 }
 int cales_fillps(cales_ctx *c, real dtrki) { ENTRY(c, op_fillps(c, dtrki)); }
@@ -387,7 +389,6 @@ int cales_out1d_chan(cales_ctx *c, real *buf) { if (!c || !buf) return 1; ENTRY(
 int cales_out2d_duct(cales_ctx *c, real *buf) { if (!c || !buf) return 1; ENTRY(c, op_out2d_duct(c, buf)); }
 
 // ------------------------------------------------------------------------------------------ time step (main.f90:412-508)
-__global__ void k_zero6(real *f, int first) { if ((int)threadIdx.x >= first && threadIdx.x < 6) f[threadIdx.x] = 0.; }      // first = 3: dpdl only (the increments f(0:2) of a pending projection are still needed)
 __global__ __launch_bounds__(256) void k_row2_to_companion(Geom g, const real *__restrict__ pp, real *__restrict__ comp) {
   const int i = blockIdx.x * 64 + threadIdx.x, k = blockIdx.y * 4 + threadIdx.y;
   if (i > g.n1 + 1 || k > g.n3 + 1) return;
@@ -570,14 +571,13 @@ int cales_step(cales_ctx *c, real dt) {
 // One time step, src/main.f90:417-508. WHICH form every operator takes is the plan's (make_plan); what is left here is the sequence, and the plan's
 // decisions go to the operators as arguments of each call.
 static int step_body(cales_ctx *c, real dt) {
-  static const real rk[3][2] = {{32. / 60., 0.}, {25. / 60., -17. / 60.}, {45. / 60., -25. / 60.}};
   const StepPlan pl = current_plan(c);      // (a copy: the plan of THIS step, whatever the step does to the state it was made from)
   if (c->pend.dtrk != 0. && !pl.fold_mom) { if (int e = finish_pending(c)) return e; }      // (the conditions changed between two steps: a field was set by hand)
   // The pending projection is this step's from here on: the one the step before left to this step's first momentum pass, then that of every substep that
   // folds. It goes back to the context in one place, at the end of a step that succeeded -- an error return leaves none behind
   PendingProjection pend = c->pend;
   c->pend = PendingProjection();
-  LAUNCH(c, k_zero6, dim3(1), dim3(64), 0, c->stream, c->d_force, pend.dtrk != 0. ? 3 : 0);     // dpdl(:) = 0
+  op_zero_force(c, pend.dtrk != 0. ? 3 : 0, 6);     // dpdl(:) = 0, and f(:) unless a pending projection still needs its increments
   c->in_step = true;
   StepMode mode{c};
   if (c->pend_xrefresh && !pl.xskip) {      // the step before left the x ghost columns stale and this one reads them
@@ -588,7 +588,7 @@ static int step_body(cales_ctx *c, real dt) {
   const int fmask = pl.defer_force ? pl.force_mask : 0;      // the components whose bulk-forcing increment the projection adds
   SgsFold fold{0., pl.fold_rows2, fmask};      // (pl.fold_correc: the projection each substep leaves to cmpt_sgs)
   for (int irk = 1; irk <= 3; ++irk) {
-    const real dtrk = (rk[irk - 1][0] + rk[irk - 1][1]) * dt, dtrki = 1. / dtrk;
+    const real dtrk = (RKPAR[irk - 1][0] + RKPAR[irk - 1][1]) * dt, dtrki = 1. / dtrk;
     real alpha = 0.;
     const bool p_ghosts_due = pend.dtrk != 0. && !pend.p_done;      // the momentum pass below stores p + pp of the interior cells: its ghost cells ride along with those of the prediction
     { RkOpts o; o.mean_mask = pl.mean_mask; o.rhs_in_sweep = pl.defer_imp_rhs; o.store_rhs = irk < 3 || pl.keep_last_rhs; o.pending = pend.dtrk != 0. ? &pend : nullptr;
@@ -597,7 +597,7 @@ static int step_body(cales_ctx *c, real dt) {
     if (!pl.defer_force && !pl.defer_imp_rhs) { if (int e = op_bulk_forcing(c)) return e; }
     if (c->C.impdiff == 2) {
       alpha = -.5 * c->visc * dtrk;
-      const real hf12 = .5 * (rk[irk - 1][0] * dt + rk[irk - 1][1] * dt);      // (rounded as rk rounds the factor of its own implicit part)
+      const real hf12 = .5 * (RKPAR[irk - 1][0] * dt + RKPAR[irk - 1][1] * dt);      // (rounded as rk rounds the factor of its own implicit part)
       for (int iv = 1; iv <= 3; ++iv) if (int e = op_helmholtz_z(c, iv, alpha, pl.defer_imp_rhs, hf12)) return e;
     } else if (c->C.impdiff == 1) {
       alpha = -.5 * c->visc * dtrk;
@@ -653,24 +653,21 @@ static int step_body(cales_ctx *c, real dt) {
   if (pend.dtrk != 0.) c->pend = pend;      // (lazy_last) the last projection is the next step's (or finish_pending's), the refresh with it
   else if (c->step_xskip && !c->fl.eager_projection) c->pend_xrefresh = true;      // the x ghost columns wait for the first caller that is not the next step (finish_pending)
   else if (int e = end_of_step_refresh(c)) return e;
-  c->h_red[40] = dt;
+  c->step_dt = dt;
   return 0;
 }
 int cales_get_dpdl(cales_ctx *c, real dpdl[3]) {
-  HIPCHK(c, hipMemcpyAsync(c->h_red + 32, c->d_force, 6 * sizeof(real), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  const real dti = 1. / c->h_red[40];
-  for (int q = 0; q < 3; ++q) dpdl[q] = -c->h_red[35 + q] * dti;
+  if (int e = read_back(c, c->h_red + RedLayout::H_FORCE, c->d_force, 6)) return e;      // (f and dpdl, back to back)
+  const real dti = 1. / c->step_dt;
+  for (int q = 0; q < 3; ++q) dpdl[q] = -c->h_red[RedLayout::H_DPDL + q] * dti;
   return 0;
 }
 
 // ------------------------------------------------------------------------------------------ multi-GPU hooks
-#define CALES_RES_TAIL 4096
 int cales_comm_buffer_doubles(const cales_ctx *c, int64_t *n) {
   const int64_t a2a = 2 * (int64_t)c->P * c->n[2] * c->n[1] * c->cw;                 // [peer][k][jl][mm] complex
   const int64_t halo = 4 * 16 * (int64_t)c->g.s1 * (c->n[2] + 2);                    // lo|hi x up to 16 field planes (send in A, recv in B)
-  const int64_t tail = CALES_RES_TAIL + 2 * (int64_t)(c->n[2] + 2);
-  *n = std::max(a2a, halo) + tail;
+  *n = std::max(a2a, halo) + c->red.comm_tail;
   return 0;
 }
 int cales_set_comm(cales_ctx *c, cales_halo_cb halo, cales_alltoall_cb a2a, cales_allreduce_cb allred, void *user,
@@ -681,10 +678,7 @@ int cales_set_comm(cales_ctx *c, cales_halo_cb halo, cales_alltoall_cb a2a, cale
   c->comm.A = bufA; c->comm.B = bufB; c->comm.nbuf = nbuf; c->comm.on = true;
   HIPCHK(c, hipMemsetAsync(bufA, 0, nbuf * sizeof(real), c->stream));
   HIPCHK(c, hipMemsetAsync(bufB, 0, nbuf * sizeof(real), c->stream));
-  // reduction results live in the tail of A so that the host can all-reduce them in place
-  const int64_t tail = CALES_RES_TAIL + 2 * (int64_t)(c->n[2] + 2);
-  c->res = bufA + (nbuf - tail);
-  c->d_p1d = c->res + 64;
+  red_place(c);      // the reduction results move into the tail of A, where the host can all-reduce them in place
   return 0;
 }
 int cales_set_comm_overlap(cales_ctx *c, cales_halo_s_cb halo_s, cales_alltoall_part_cb a2a_part) {
@@ -727,9 +721,8 @@ int cales_calibrate(cales_ctx *c, int reps, real gbps[3], int64_t *bytes_per_str
   const dim3 gr(256 * 16), bl(256);
   const real *a = c->f[CALES_U]; real *b = c->scr1;      // scr1: scratch between operators
   auto run = [&](int mode) {
-    if (mode == 0) LAUNCH(c, k_calib_rows<0>, gr, bl, 0, c->stream, c->g, nrows, a, b, c->d_red);
-    else if (mode == 1) LAUNCH(c, k_calib_rows<1>, gr, bl, 0, c->stream, c->g, nrows, a, b, c->d_red);
-    else LAUNCH(c, k_calib_rows<2>, gr, bl, 0, c->stream, c->g, nrows, a, b, c->d_red);
+    const auto k_calib_rows_mode = mode == 0 ? k_calib_rows<0> : mode == 1 ? k_calib_rows<1> : k_calib_rows<2>;
+    LAUNCH(c, k_calib_rows_mode, gr, bl, 0, c->stream, c->g, nrows, a, b, c->d_red + c->red.part);      // (sink: the reductions' partials, never written)
   };
   int rc = 0;
   for (int mode = 0; mode < 3 && !rc; ++mode) {

@@ -242,6 +242,20 @@ struct RkOpts { int mean_mask = 0; bool rhs_in_sweep = false, store_rhs = true; 
 // dtrki != 0: the forward x transform of the pressure solve forms pp = div(u*)/dtrk itself and sums the bulk means of the components in mean_mask
 struct FusedFill { real dtrki = 0.; int mean_mask = 0; };
 
+// Where the scalar reductions live (bulk means and forcing, chkdt, chkdiv, the dynamic model's plane sums), the same with and without communication:
+// result slots, then the plane sums p1d, then the per-block partial sums. Results and p1d are what the slabs all-reduce: views into the tail of staging buffer A
+// once hooks are registered, into the head of the context's own d_red (which always holds the partials) otherwise -- red_place (api.hip) places both
+struct RedLayout {
+  enum Slot { CHECK = 0, FORCE = 8, BULK_MEAN = 16, NSLOT = 64 };      // res[]: chkdt's two maxima | chkdiv's sum and maximum; FORCE + component: its bulk mean (rk.f90:197-222); cales_bulk_mean
+  enum Host { H_CHECK = 0, H_BULK_MEAN = 16, H_FORCE = 32, H_DPDL = 35, NHOST = 64 };      // h_red[]: H_FORCE and H_DPDL are d_force's f(3) and dpdl(3), back to back
+  int64_t p1d = NSLOT, np1d = 0, part = 0, npart = 0, total = 0;      // offset and length of p1d (2 n3 and two to spare) and of the partials (sixteen blocks per plane, or two arrays of eight); reals of d_red
+  int64_t comm_tail = 0;      // reals at the end of the staging buffers that no exchange uses: results and p1d live there, with room to spare
+  static RedLayout of(int n3) {
+    RedLayout L; L.np1d = 2 * (int64_t)n3 + 2; L.part = L.p1d + L.np1d; L.npart = 16 * (int64_t)(n3 + 2); L.total = L.part + L.npart; L.comm_tail = 4096 + L.np1d + 2;
+    return L;
+  }
+};
+constexpr real RKPAR[3][2] = {{32. / 60., 0.}, {25. / 60., -17. / 60.}, {45. / 60., -25. / 60.}};      // the three substeps' coefficients, param.f90:27-29
 struct KernelStat { std::string name; int64_t calls = 0; real ms = 0.; };
 struct Solver;      // k_solver.hip
 struct MemBlock { void *base; size_t bytes; bool pinned; };      // one allocation of a context ("who owns device memory")
@@ -276,12 +290,14 @@ struct cales_ctx {
   // k_solver.hip: plans, tables and the path of every solved field; the z solves' coefficients, chunked tables and scratch (solver_setup; the device tables are the context's memory)
   Solver *solver = nullptr;
   real *scr1 = nullptr, *scr2 = nullptr;         // solver scratch (haloed size)
-  // reductions
-  real *d_red = nullptr; real *h_red = nullptr;       // partial sums / results (pinned host)
+  RedLayout red;      // reductions (RedLayout above)
+  real *d_red = nullptr; real *h_red = nullptr;       // the context's own buffer of red.total reals | results on the host (pinned, RedLayout::Host)
+  real *res = nullptr, *d_p1d = nullptr;              // views placed by red_place: result slots and plane sums, in d_red or in the tail of comm.A
+  real step_dt = 0.;                                  // dt of the last cales_step (cales_get_dpdl divides by it)
   real *d_force = nullptr;                    // f(3) + dpdl(3) accumulators on device
   // sgs scratch
   real *ss2[3] = {nullptr, nullptr, nullptr};      // |S|Sij as three pair fields (2 ntot reals each; SgsPath::pair) instead of sij / mij
-  real *s0 = nullptr, *wk[6] = {}, *sij[6] = {}, *mij[6] = {}, *uc = nullptr, *vc = nullptr, *wc = nullptr, *uf = nullptr, *vf = nullptr, *wf = nullptr, *alph2 = nullptr, *d_p1d = nullptr;
+  real *s0 = nullptr, *wk[6] = {}, *sij[6] = {}, *mij[6] = {}, *uc = nullptr, *vc = nullptr, *wc = nullptr, *uf = nullptr, *vf = nullptr, *wf = nullptr, *alph2 = nullptr;
   real is_wall[6] = {};
   SgsPath sgs;      // see SgsPath above
   BcPath bc;        // see BcPath above
@@ -290,7 +306,6 @@ struct cales_ctx {
   // decomposition
   int P = 1, rank = 0; bool per_y = true; int cw = 0;      // cw: complex mode columns per rank (padded)
   Comm comm;
-  real *res = nullptr;                // reduction results (inside comm.A when comm is on, so they can be all-reduced)
   // profiling
   bool prof = false;
   std::vector<KernelStat> stats;
@@ -305,8 +320,6 @@ struct cales_ctx {
   // The mode of the step in progress, read by the host side of nearly every operator. Everything else a step decides reaches the operators as
   // arguments (BcCall, RkOpts, FusedFill, SgsFold, ...)
   bool in_step = false;             // inside cales_step: the operator order is known, dead ghost work can be dropped
-  real *d_stat2 = nullptr;
-  real *d_stat = nullptr;      // partial sums and result of the plane statistics
   bool force_zeroed = false;
   int ncu = 0;      // compute units of the device (balanced_kchunk)
   real *d_mpart = nullptr; size_t n_mpart = 0;      // partial sums of the bulk means the forward x transform forms (FusedFill::mean_mask)
@@ -416,7 +429,11 @@ int op_rk_par(cales_ctx *c, real rkpar1, real rkpar2, real dt, const RkOpts &o =
 int op_momrk(cales_ctx *c, real f1, real f2, real f12, const RkOpts &o = RkOpts());
 void mom_setup(cales_ctx *c);               // MomPath (needs ncu)
 int op_bulk_forcing(cales_ctx *c);
-int op_bulk_mean_dev(cales_ctx *c, const real *p, int c_or_f, real *d_out);   // result to device scalar
+int op_bulk_mean_dev(cales_ctx *c, const real *p, int c_or_f);   // result to res[RedLayout::BULK_MEAN]
+real *red_partials(cales_ctx *c, size_t need);      // room for `need` partial sums (RedLayout); nullptr and c->err where the layout has less
+int allreduce_dev(cales_ctx *c, real *p, int64_t count, int op);      // [p, p + count) over the slabs, in place (op: 0 sum, 1 max): nothing on one rank; the range must lie in staging buffer A
+int read_back(cales_ctx *c, real *host, const real *dev, size_t n);      // n reals to the host on the context's stream, complete on return
+int op_zero_force(cales_ctx *c, int first, int last);      // d_force[first, last) = 0 (f(3), dpdl(3))
 int op_fillps(cales_ctx *c, real dtrki);
 int op_updt_rhs_b(cales_ctx *c);
 int op_solver(cales_ctx *c, const FusedFill &fill = FusedFill());

@@ -1364,7 +1364,6 @@ __global__ __launch_bounds__(256) void k_plane_fold(int n3, int nblk, const real
   (void)n3;
 }
 
-int allreduce_res(cales_ctx *c, int slot, int count, int op);
 // v_c = (v(j) + v(j-1))/2 of the rows j = 1 and j = n2 (all i, k, ghost columns and planes included): the two rows whose copies the ghost-cell update /
 // the slab exchange puts into the ghost rows 0 and n2+1 of `vc` -- k_lmf_tile<.., UCF = 1> reads row 0 from there
 __global__ __launch_bounds__(256) void k_vc_edge_rows(Geom g, const real *__restrict__ v, real *__restrict__ vc) {
@@ -1617,7 +1616,7 @@ static int dsmag_fast(cales_ctx *c, const SgsFold *fold, bool *visct_ghosts_done
     } else launch(0, (int)t.grid.y);
     LAUNCH(c, k_plane_fold, dim3(2 * n[2]), dim3(256), 0, c->stream, n[2], L.nblk, c->wk[0], c->d_p1d);
   }
-  if (c->P > 1) { if (int e = allreduce_res(c, (int)(c->d_p1d - c->res), 2 * n[2], 0)) return e; }   // sgs.f90:475
+  if (c->P > 1) { if (int e = allreduce_dev(c, c->d_p1d, 2 * n[2], 0)) return e; }   // sgs.f90:475
   if (P.ave == SgsAve::volume) LAUNCH(c, k_volume_fold, dim3(1), dim3(256), 0, c->stream, n[2], c->d_dzf, c->d_p1d);      // sgs.f90:360-361
   const real gar = c->dl[0] * c->dl[1] / (c->C.l[0] * c->C.l[1]);
   if (P.lazy) {
@@ -1653,7 +1652,7 @@ static int wall_shear_y_planes(cales_ctx *c, int wylo, int wyhi, const real **ou
   real *twy = c->wk[0];
   if (c->P > 1) {
     if (!c->comm.on) { c->err = "nranks > 1 but no communication hooks registered (cales_set_comm)"; return 1; }
-    if ((int64_t)cnt > c->res - c->comm.A) { c->err = "smag: staging buffer too small for the wall-shear planes"; return 1; }
+    if ((int64_t)cnt > c->comm.nbuf - c->red.comm_tail) { c->err = "smag: staging buffer too small for the wall-shear planes"; return 1; }      // (the tail holds the reduction results)
     twy = c->comm.A;
     if (c->comm_stream) if (int e = stream_after(c, c->stream, c->comm_stream)) return e;      // nothing of an overlapped exchange may still use A
     HIPCHK(c, hipMemsetAsync(twy, 0, cnt * sizeof(real), c->stream));
@@ -1662,7 +1661,7 @@ static int wall_shear_y_planes(cales_ctx *c, int wylo, int wyhi, const real **ou
   if (lo || hi)
     LAUNCH(c, k_wall_shear_y, dim3((n[0] + 63) / 64, (n[2] + 3) / 4), dim3(64, 4), 0, c->stream, c->g, c->f[CALES_U], c->f[CALES_W], c->visc, c->dli[1], lo, hi, twy, c->step_xskip ? 1 : 0);
   LAUNCHCHK(c);
-  if (c->P > 1 && c->comm.allred(c->comm.user, 0, (int64_t)cnt, 0)) { c->err = "allreduce callback failed (wall-shear planes)"; return 1; }
+  if (int e = allreduce_dev(c, twy, (int64_t)cnt, 0)) return e;
   *out = twy;
   return 0;
 }
@@ -1795,7 +1794,7 @@ int op_cmpt_sgs(cales_ctx *c, const SgsFold *fold, bool *visct_ghosts_done) {
   }
   LAUNCH(c, k_contract, gr, b, 0, c->stream, c->g, cmij, clij, c->uf, c->vf, c->wf, wk[0], wk[1]);
   LAUNCH(c, k_plane_sum, dim3(n[2], 2), dim3(256), 0, c->stream, c->g, wk[0], wk[1], c->d_p1d);
-  if (c->P > 1) { if (int e = allreduce_res(c, (int)(c->d_p1d - c->res), 2 * n[2], 0)) return e; }   // sgs.f90:475
+  if (c->P > 1) { if (int e = allreduce_dev(c, c->d_p1d, 2 * n[2], 0)) return e; }   // sgs.f90:475
   if (c->sgs.ave == SgsAve::volume) LAUNCH(c, k_volume_fold, dim3(1), dim3(256), 0, c->stream, n[2], c->d_dzf, c->d_p1d);      // sgs.f90:360-361
   const real gar = c->dl[0] * c->dl[1] / (c->C.l[0] * c->C.l[1]);
   LAUNCH(c, k_dsmag_final, gr, b, 0, c->stream, c->g, gar, c->d_p1d, visct, visct);

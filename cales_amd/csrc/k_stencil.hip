@@ -203,59 +203,69 @@ __global__ __launch_bounds__(256) void k_fold_force(const real *__restrict__ par
 __global__ void k_force_finish(const real *__restrict__ res, int slot, real velf, real *__restrict__ force, int comp) {
   if (threadIdx.x == 0) { const real f = velf - res[slot]; force[comp] = f; force[3 + comp] += f; }
 }
-// all-reduce of res[slot..slot+count) across the slabs (utils.f90:46, chkdiv.f90:50-51, chkdt.f90:98, sgs.f90:475)
-int allreduce_res(cales_ctx *c, int slot, int count, int op) {
-  if (c->P == 1) return 0;
+// ---- host side of every scalar reduction (RedLayout, common.hpp): room for partials, all-reduce by pointer, readback, the one fold path
+real *red_partials(cales_ctx *c, size_t need) {
+  if ((int64_t)need > c->red.npart) { c->err = "reduction: " + std::to_string(need) + " partial sums do not fit the " + std::to_string(c->red.npart) + " of the layout"; return nullptr; }
+  return c->d_red + c->red.part;
+}
+int allreduce_dev(cales_ctx *c, real *p, int64_t count, int op) {
+  if (c->P == 1) return 0;      // (utils.f90:46, chkdiv.f90:50-51, chkdt.f90:98, sgs.f90:475)
   if (!c->comm.on) { c->err = "nranks > 1 but no communication hooks registered (cales_set_comm)"; return 1; }
-  const int64_t off = (c->res - c->comm.A) + slot;
-  if (c->comm.allred(c->comm.user, off, count, op)) { c->err = "allreduce callback failed"; return 1; }
+  const uintptr_t lo = (uintptr_t)c->comm.A, hi = (uintptr_t)(c->comm.A + c->comm.nbuf), a = (uintptr_t)p;
+  if (count < 0 || a < lo || a > hi || (uint64_t)count > (hi - a) / sizeof(real)) { c->err = "allreduce: the values do not lie in the staging buffer the hooks were registered with"; return 1; }
+  if (c->comm.allred(c->comm.user, p - c->comm.A, count, op)) { c->err = "allreduce callback failed"; return 1; }
   return 0;
 }
-
-int op_bulk_mean_dev(cales_ctx *c, const real *p, int c_or_f, real *d_out) {
-  (void)d_out;
-  ProfScope ps(c, "bulk_mean");
-  const int nbx = 16;      // (partials: 16 (n3 + 2) of d_red, cales_create)
-  dim3 gr(nbx, c->n[2]);
-  LAUNCH(c, k_bulk_mean_partial, gr, dim3(64, 4), 0, c->stream, c->g, p, c_or_f ? c->d_gvr_f : c->d_gvr_c, c->d_red + 64);
-  LAUNCH(c, k_fold, dim3(1), dim3(256), 0, c->stream, c->d_red + 64, nbx * c->n[2], 0, c->res, 16);
-  LAUNCHCHK(c);
-  return allreduce_res(c, 16, 1, 0);
+int read_back(cales_ctx *c, real *host, const real *dev, size_t n) {
+  HIPCHK(c, hipMemcpyAsync(host, dev, n * sizeof(real), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return 0;
+}
+// partials -> result slot -> the slabs: res[slot] = op0 over np partials; with op1 also res[slot + 1] = op1 over the np behind them. Then over the ranks: ONE
+// all-reduce of both values where the operations agree, one per slot in their order otherwise (the hosts see exactly these calls)
+static int fold_results(cales_ctx *c, const real *part, int np, int slot, int op0, int op1 = -1) {
+  LAUNCH(c, k_fold, dim3(1), dim3(256), 0, c->stream, part, np, op0, c->res, slot);
+  if (op1 >= 0) LAUNCH(c, k_fold, dim3(1), dim3(256), 0, c->stream, part + np, np, op1, c->res, slot + 1);
+  if (op1 < 0 || op1 == op0) return allreduce_dev(c, c->res + slot, op1 < 0 ? 1 : 2, op0);
+  if (int e = allreduce_dev(c, c->res + slot, 1, op0)) return e;
+  return allreduce_dev(c, c->res + slot + 1, 1, op1);
+}
+// partials of a bulk mean -> the forcing increment of component comp (cmpt_bulk_forcing, rk.f90:197-222): one launch on one rank, fold + all-reduce + finish on several
+static int force_from_partials(cales_ctx *c, const real *part, int np, int comp) {
+  const int slot = RedLayout::FORCE + comp;
+  if (c->P == 1) { LAUNCH(c, k_fold_force, dim3(1), dim3(256), 0, c->stream, part, np, c->C.velf[comp], c->res, slot, c->d_force, comp); return 0; }
+  if (int e = fold_results(c, part, np, slot, 0)) return e;
+  LAUNCH(c, k_force_finish, dim3(1), dim3(64), 0, c->stream, c->res, slot, c->C.velf[comp], c->d_force, comp);
+  return 0;
+}
+// the partial sums of a bulk mean of p (16 blocks per plane) in the layout's partials; returns their number, 0 on error
+static int bulk_mean_partials(cales_ctx *c, const real *p, int c_or_f, real **part) {
+  const int nbx = 16, np = nbx * c->n[2];
+  if (!(*part = red_partials(c, np))) return 0;
+  LAUNCH(c, k_bulk_mean_partial, dim3(nbx, c->n[2]), dim3(64, 4), 0, c->stream, c->g, p, c_or_f ? c->d_gvr_f : c->d_gvr_c, *part);
+  return np;
 }
 
-static int forcing_component(cales_ctx *c, int comp) {   // cmpt_bulk_forcing, rk.f90:197-222
-  const int nbx = 16;
-  dim3 gr(nbx, c->n[2]);
-  const real *p = c->f[CALES_U + comp];
-  LAUNCH(c, k_bulk_mean_partial, gr, dim3(64, 4), 0, c->stream, c->g, p, comp == 2 ? c->d_gvr_c : c->d_gvr_f, c->d_red + 64);
-  if (c->P == 1) LAUNCH(c, k_fold_force, dim3(1), dim3(256), 0, c->stream, c->d_red + 64, nbx * c->n[2], c->C.velf[comp], c->res, 8 + comp, c->d_force, comp);
-  else {
-    LAUNCH(c, k_fold, dim3(1), dim3(256), 0, c->stream, c->d_red + 64, nbx * c->n[2], 0, c->res, 8 + comp);
-    if (int e = allreduce_res(c, 8 + comp, 1, 0)) return e;
-    LAUNCH(c, k_force_finish, dim3(1), dim3(64), 0, c->stream, c->res, 8 + comp, c->C.velf[comp], c->d_force, comp);
-  }
+int op_bulk_mean_dev(cales_ctx *c, const real *p, int c_or_f) {
+  ProfScope ps(c, "bulk_mean");
+  real *part; const int np = bulk_mean_partials(c, p, c_or_f, &part);
+  if (!np || fold_results(c, part, np, RedLayout::BULK_MEAN, 0)) return 1;
   LAUNCHCHK(c);
   return 0;
 }
 
 // the same from per-block partial sums made by another pass (k_fft_x8<0,KIND,1>): part[comp*nblk + b]
 int op_force_from_partials(cales_ctx *c, int mask, const real *part, int nblk) {
-  for (int comp = 0; comp < 3; ++comp) {
-    if (!(mask >> comp & 1)) continue;
-    if (c->P == 1) { LAUNCH(c, k_fold_force, dim3(1), dim3(256), 0, c->stream, part + (size_t)comp * nblk, nblk, c->C.velf[comp], c->res, 8 + comp, c->d_force, comp); continue; }
-    LAUNCH(c, k_fold, dim3(1), dim3(256), 0, c->stream, part + (size_t)comp * nblk, nblk, 0, c->res, 8 + comp);
-    if (int e = allreduce_res(c, 8 + comp, 1, 0)) return e;
-    LAUNCH(c, k_force_finish, dim3(1), dim3(64), 0, c->stream, c->res, 8 + comp, c->C.velf[comp], c->d_force, comp);
-  }
+  for (int comp = 0; comp < 3; ++comp) if (mask >> comp & 1) if (int e = force_from_partials(c, part + (size_t)comp * nblk, nblk, comp)) return e;
   LAUNCHCHK(c);
   return 0;
 }
 
-__global__ void k_zero_force(real *force) { if (threadIdx.x < 3) force[threadIdx.x] = 0.; }
+__global__ void k_zero_force(real *force, int first, int last) { if ((int)threadIdx.x >= first && (int)threadIdx.x < last) force[threadIdx.x] = 0.; }
+int op_zero_force(cales_ctx *c, int first, int last) { LAUNCH(c, k_zero_force, dim3(1), dim3(64), 0, c->stream, c->d_force, first, last); return 0; }
 
 int op_rk(cales_ctx *c, int irk, real dt, const RkOpts &o) {
-  static const real rk[3][2] = {{32. / 60., 0.}, {25. / 60., -17. / 60.}, {45. / 60., -25. / 60.}};   // param.f90:27-29
-  return op_rk_par(c, rk[irk - 1][0], rk[irk - 1][1], dt, o);
+  return op_rk_par(c, RKPAR[irk - 1][0], RKPAR[irk - 1][1], dt, o);
 }
 // rk(rkpar, ..., dt, ...) of rk.f90:17 with the caller's coefficients
 int op_rk_par(cales_ctx *c, real rkpar1, real rkpar2, real dt, const RkOpts &o) {
@@ -277,8 +287,10 @@ int op_rk_par(cales_ctx *c, real rkpar1, real rkpar2, real dt, const RkOpts &o) 
   }
   for (int q = 0; q < 3; ++q) std::swap(f[CALES_DUDT + q], f[CALES_DUDTO + q]);     // swap, rk.f90:98-100
   if (!(c->C.is_forced[0] && c->C.is_forced[1] && c->C.is_forced[2]) && !c->force_zeroed) {      // unforced components stay zero for good
-    LAUNCH(c, k_zero_force, dim3(1), dim3(64), 0, c->stream, c->d_force); c->force_zeroed = true; }
-  for (int q = 0; q < 3; ++q) if (c->C.is_forced[q] && !(o.mean_mask >> q & 1)) if (int e = forcing_component(c, q)) return e;
+    op_zero_force(c, 0, 3); c->force_zeroed = true; }
+  for (int q = 0; q < 3; ++q) if (c->C.is_forced[q] && !(o.mean_mask >> q & 1)) {      // cmpt_bulk_forcing of the components whose mean no other pass sums
+    real *part; const int np = bulk_mean_partials(c, f[CALES_U + q], q != 2, &part);
+    if (!np || force_from_partials(c, part, np, q)) return 1; }
   if (c->C.impdiff && !o.rhs_in_sweep) {
     ProfScope ps(c, "rk_imp_rhs");
     LAUNCH(c, k_rk_imp_rhs, gr, b, 0, c->stream, c->g, .5 * f12, f[CALES_U], f[CALES_V], f[CALES_W], f[CALES_DUDTD], f[CALES_DVDTD], f[CALES_DWDTD]);
@@ -449,15 +461,12 @@ __global__ __launch_bounds__(256) void k_chkdiv_partial(Geom g, real dxi, real d
 }
 int op_chkdiv(cales_ctx *c, real *divtot, real *divmax) {
   const int nbx = 8, np = nbx * c->n[2];
+  real *part = red_partials(c, 2 * (size_t)np), *h = c->h_red + RedLayout::H_CHECK; if (!part) return 1;
   LAUNCH(c, k_chkdiv_partial, dim3(nbx, c->n[2]), dim3(64, 4), 0, c->stream, c->g, c->dli[0], c->dli[1], c->d_dzfi, c->f[CALES_U],
-                     c->f[CALES_V], c->f[CALES_W], c->d_red + 64, c->d_red + 64 + np);
-  LAUNCH(c, k_fold, dim3(1), dim3(256), 0, c->stream, c->d_red + 64, np, 0, c->res, 0);
-  LAUNCH(c, k_fold, dim3(1), dim3(256), 0, c->stream, c->d_red + 64 + np, np, 1, c->res, 1);
-  if (int e = allreduce_res(c, 0, 1, 0)) return e;
-  if (int e = allreduce_res(c, 1, 1, 1)) return e;
-  HIPCHK(c, hipMemcpyAsync(c->h_red, c->res, 2 * sizeof(real), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  *divtot = c->h_red[0]; *divmax = c->h_red[1];
+                     c->f[CALES_V], c->f[CALES_W], part, part + np);
+  if (int e = fold_results(c, part, np, RedLayout::CHECK, 0, 1)) return e;      // sum, maximum
+  if (int e = read_back(c, h, c->res + RedLayout::CHECK, 2)) return e;
+  *divtot = h[0]; *divmax = h[1];
   return 0;
 }
 
@@ -507,29 +516,27 @@ __global__ __launch_bounds__(256) void k_stats_chan_partial(Geom g, real dx, rea
     if (threadIdx.x == 0) part[((size_t)blockIdx.y * gridDim.x + blockIdx.x) * NSTAT + q] = r;
   }
 }
-__global__ void k_stats_fold(int n3, int nbx, real ratio, const real *__restrict__ part, real *__restrict__ out) {
+// out[q, k] = ratio * the sum over the nbx blocks of plane k, for the nstat sums of a plane (both statistics blocks)
+__global__ void k_stats_fold_n(int nstat, int n3, int nbx, real ratio, const real *__restrict__ part, real *__restrict__ out) {
   const int t = blockIdx.x * 256 + threadIdx.x;
-  if (t >= NSTAT * n3) return;
-  const int q = t % NSTAT, k = t / NSTAT;
+  if (t >= nstat * n3) return;
+  const int q = t % nstat, k = t / nstat;
   real a = 0.;
-  for (int bx = 0; bx < nbx; ++bx) a += part[((size_t)k * nbx + bx) * NSTAT + q];
+  for (int bx = 0; bx < nbx; ++bx) a += part[((size_t)k * nbx + bx) * nstat + q];
   out[t] = a * ratio;
 }
 // buf: (27, n3) column-major on the host; with several ranks the sums of THIS rank's rows (the caller adds the ranks, output.f90:691)
 int op_stats_chan(cales_ctx *c, real *buf) {
   if (int e = materialize_visct(c)) return e;
   const int nbx = 8, n3 = c->n[2];
-  const size_t need = (size_t)NSTAT * n3 * (nbx + 1);
-  if (!c->d_stat && ctx_alloc(c, &c->d_stat, need, false)) return 1;
-  real *part = c->d_stat, *out = c->d_stat + (size_t)NSTAT * n3 * nbx;
+  CtxTemp tmp(c, (size_t)NSTAT * n3 * (nbx + 1)); if (!tmp.p) return 1;
+  real *part = tmp.p, *out = tmp.p + (size_t)NSTAT * n3 * nbx;
   LAUNCH(c, k_stats_chan_partial, dim3(nbx, n3), dim3(256), 0, c->stream, c->g, c->dl[0], c->dl[1], c->d_dzc, c->d_dzf, c->f[CALES_U], c->f[CALES_V],
                      c->f[CALES_W], c->f[CALES_P], c->f[CALES_VISCT], part);
   const real ratio = c->dl[0] * c->dl[1] / (c->C.l[0] * c->C.l[1]);
-  LAUNCH(c, k_stats_fold, dim3((NSTAT * n3 + 255) / 256), dim3(256), 0, c->stream, n3, nbx, ratio, part, out);
+  LAUNCH(c, k_stats_fold_n, dim3((NSTAT * n3 + 255) / 256), dim3(256), 0, c->stream, NSTAT, n3, nbx, ratio, part, out);
   LAUNCHCHK(c);
-  HIPCHK(c, hipMemcpyAsync(buf, out, (size_t)NSTAT * n3 * sizeof(real), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return 0;
+  return read_back(c, buf, out, (size_t)NSTAT * n3);
 }
 
 // Second block of out1d_single_point_chan (output.f90:700-1001): the 38 plane sums of the mean-kinetic-energy and Reynolds-stress
@@ -619,14 +626,6 @@ __global__ __launch_bounds__(256) void k_stats_leak_partial(Geom g, real dx, rea
   const real rm = block_reduce<1>(mx, sh), ra = block_reduce<0>(sa, sh), rd = block_reduce<0>(sd, sh);
   if (threadIdx.x == 0) { real *o = part + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 3; o[0] = rm; o[1] = ra; o[2] = rd; }
 }
-__global__ void k_stats_fold_n(int nstat, int n3, int nbx, real ratio, const real *__restrict__ part, real *__restrict__ out) {
-  const int t = blockIdx.x * 256 + threadIdx.x;
-  if (t >= nstat * n3) return;
-  const int q = t % nstat, k = t / nstat;
-  real a = 0.;
-  for (int bx = 0; bx < nbx; ++bx) a += part[((size_t)k * nbx + bx) * nstat + q];
-  out[t] = a * ratio;
-}
 __global__ void k_stats_leak_fold(int n3, int nbx, real ratio, const real *__restrict__ dzf, const real *__restrict__ part, real *__restrict__ out) {
   const int k = blockIdx.x * 64 + threadIdx.x;      // plane k+1
   if (k >= n3) return;
@@ -639,22 +638,21 @@ __global__ void k_stats_leak_fold(int n3, int nbx, real ratio, const real *__res
 // budget: (38, n3), leak: (6, n3), column-major on the host (either may be NULL); this rank's rows when there are several ranks
 int op_stats_chan_budget(cales_ctx *c, real *budget, real *leak) {
   const int nbx = 8, n3 = c->n[2];
-  const size_t need = (size_t)NBUDGET * n3 * (nbx + 1);
-  if (!c->d_stat2 && ctx_alloc(c, &c->d_stat2, need, false)) return 1;
-  real *part = c->d_stat2, *out = c->d_stat2 + (size_t)NBUDGET * n3 * nbx;
   const real ratio = c->dl[0] * c->dl[1] / (c->C.l[0] * c->C.l[1]);
   if (budget) {
+    CtxTemp tmp(c, (size_t)NBUDGET * n3 * (nbx + 1)); if (!tmp.p) return 1;
+    real *part = tmp.p, *out = tmp.p + (size_t)NBUDGET * n3 * nbx;
     LAUNCH(c, k_stats_budget_partial, dim3(nbx, n3), dim3(256), 0, c->stream, c->g, c->dl[0], c->dl[1], c->d_dzc, c->d_dzf, c->f[CALES_U], c->f[CALES_V],
                        c->f[CALES_W], c->f[CALES_P], part);
     LAUNCH(c, k_stats_fold_n, dim3((NBUDGET * n3 + 255) / 256), dim3(256), 0, c->stream, NBUDGET, n3, nbx, ratio, part, out);
-    HIPCHK(c, hipMemcpyAsync(budget, out, (size_t)NBUDGET * n3 * sizeof(real), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (int e = read_back(c, budget, out, (size_t)NBUDGET * n3)) return e;
   }
   if (leak) {
+    CtxTemp tmp(c, (size_t)3 * nbx * n3 + (size_t)6 * n3); if (!tmp.p) return 1;
+    real *part = tmp.p, *out = tmp.p + (size_t)3 * nbx * n3;
     LAUNCH(c, k_stats_leak_partial, dim3(nbx, n3), dim3(256), 0, c->stream, c->g, c->dl[0], c->dl[1], c->d_dzf, c->f[CALES_U], c->f[CALES_V], c->f[CALES_W], part);
     LAUNCH(c, k_stats_leak_fold, dim3((n3 + 63) / 64), dim3(64), 0, c->stream, n3, nbx, ratio, c->d_dzf, part, out);
-    HIPCHK(c, hipMemcpyAsync(leak, out, (size_t)6 * n3 * sizeof(real), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (int e = read_back(c, leak, out, (size_t)6 * n3)) return e;
   }
   LAUNCHCHK(c);
   return 0;
@@ -689,9 +687,7 @@ int op_out1d(cales_ctx *c, int field, int idir, int use_dzc, real *buf) {
   const real ratio = idir == 3 ? c->dl[0] * c->dl[1] / (c->C.l[0] * c->C.l[1]) : idir == 2 ? c->dl[0] / (c->C.l[0] * c->C.l[2]) : c->dl[1] / (c->C.l[1] * c->C.l[2]);
   LAUNCH(c, k_out1d, dim3(ne), dim3(256), 0, c->stream, c->g, idir, ratio, use_dzc ? c->d_dzc : c->d_dzf, c->f[field], out);
   LAUNCHCHK(c);
-  HIPCHK(c, hipMemcpyAsync(buf, out, (size_t)ne * sizeof(real), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return 0;
+  return read_back(c, buf, out, (size_t)ne);
 }
 // out1d_chan (output.f90:317-405, idir = 3): um, vm, wm, u2, v2, w2, uw per plane
 __global__ __launch_bounds__(256) void k_out1d_chan(Geom g, real ratio, const real *__restrict__ u, const real *__restrict__ v, const real *__restrict__ w, real *__restrict__ out) {
@@ -714,9 +710,7 @@ int op_out1d_chan(cales_ctx *c, real *buf) {
   CtxTemp tmp(c, (size_t)7 * n3); real *out = tmp.p; if (!out) return 1;
   LAUNCH(c, k_out1d_chan, dim3(n3), dim3(256), 0, c->stream, c->g, c->dl[0] * c->dl[1] / (c->C.l[0] * c->C.l[1]), c->f[CALES_U], c->f[CALES_V], c->f[CALES_W], out);
   LAUNCHCHK(c);
-  HIPCHK(c, hipMemcpyAsync(buf, out, (size_t)7 * n3 * sizeof(real), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return 0;
+  return read_back(c, buf, out, (size_t)7 * n3);
 }
 // out2d_duct (output.f90:406-507, streamwise direction x): nine cell-centred averages along x for every (j, k); one wave per (j, k)
 __global__ __launch_bounds__(256) void k_out2d_duct(Geom g, real ratio, const real *__restrict__ u, const real *__restrict__ v, const real *__restrict__ w, real *__restrict__ out) {
@@ -739,9 +733,7 @@ int op_out2d_duct(cales_ctx *c, real *buf) {
   CtxTemp tmp(c, (size_t)9 * n2 * n3); real *out = tmp.p; if (!out) return 1;
   LAUNCH(c, k_out2d_duct, dim3((n2 + 3) / 4, n3), dim3(256), 0, c->stream, c->g, c->dl[0] / c->C.l[0], c->f[CALES_U], c->f[CALES_V], c->f[CALES_W], out);
   LAUNCHCHK(c);
-  HIPCHK(c, hipMemcpyAsync(buf, out, (size_t)9 * n2 * n3 * sizeof(real), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return 0;
+  return read_back(c, buf, out, (size_t)9 * n2 * n3);
 }
 
 // ------------------------------------------------------------------------------------------ chkdt (chkdt.f90:50-98)
@@ -779,16 +771,13 @@ __global__ __launch_bounds__(256) void k_chkdt_partial(Geom g, real dxi, real dy
 int op_chkdt(cales_ctx *c, real *dtmax) {
   if (int e = materialize_visct(c)) return e;
   const int nbx = 8, np = nbx * c->n[2];
-  real **f = c->f;
+  real **f = c->f, *part = red_partials(c, 2 * (size_t)np), *h = c->h_red + RedLayout::H_CHECK; if (!part) return 1;
   const auto k_chkdt_partial_imp = c->C.impdiff == 2 ? k_chkdt_partial<2> : c->C.impdiff == 1 ? k_chkdt_partial<1> : k_chkdt_partial<0>;
   LAUNCH(c, k_chkdt_partial_imp, dim3(nbx, c->n[2]), dim3(64, 4), 0, c->stream, c->g, 1. / c->dl[0], 1. / c->dl[1], c->visc, c->d_dzci,
-                     c->d_dzfi, f[CALES_VISCT], f[CALES_U], f[CALES_V], f[CALES_W], c->d_red + 64, c->d_red + 64 + np);
-  LAUNCH(c, k_fold, dim3(1), dim3(256), 0, c->stream, c->d_red + 64, np, 1, c->res, 0);
-  LAUNCH(c, k_fold, dim3(1), dim3(256), 0, c->stream, c->d_red + 64 + np, np, 1, c->res, 1);
-  if (int e = allreduce_res(c, 0, 2, 1)) return e;
-  HIPCHK(c, hipMemcpyAsync(c->h_red, c->res, 2 * sizeof(real), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  real dti = c->h_red[0], dtid = c->h_red[1];
+                     c->d_dzfi, f[CALES_VISCT], f[CALES_U], f[CALES_V], f[CALES_W], part, part + np);
+  if (int e = fold_results(c, part, np, RedLayout::CHECK, 1, 1)) return e;      // two maxima
+  if (int e = read_back(c, h, c->res + RedLayout::CHECK, 2)) return e;
+  real dti = h[0], dtid = h[1];
   if (dti == 0.) dti = 1.;
   if (dtid == 0.) dtid = CALES_EPS;
   *dtmax = std::fmin(0.4125 / dtid, 1.732 / dti);

@@ -15,9 +15,12 @@ SP = ["-DCALES_SINGLE", "-Wno-c++11-narrowing", "-Wno-implicit-const-int-float-c
 def kernels(path):
     """{symbol: (instruction lines, .amdhsa_ lines)}"""
     body, res, cur, hsa = {}, {}, None, None
-    for line in open(path):
+    lines = open(path).readlines()
+    names = {l.split()[1] for l in lines if l.strip().startswith(".amdhsa_kernel")}      # (kernels inside extern "C" keep their plain names)
+    for line in lines:
         t = re.sub(r"\.LBB\d+_", ".LBB_", line.split(";")[0]).strip()
-        m = re.match(r"(_Z\w+):$", t)
+        m = re.match(r"(\w+):$", t)
+        if m and m.group(1) not in names: m = None
         if t.startswith(".amdhsa_kernel"): hsa = t.split()[1]; res[hsa] = []      # (the descriptor sits between the label and .Lfunc_end)
         elif t.startswith(".end_amdhsa_kernel"): hsa = None
         elif hsa is not None: res[hsa].append(t)
