@@ -122,6 +122,19 @@ END_ONLY = {
     "tgv_ppp_x64": ("dns/triperiodic/input.nml",
                     {r"ng\(1:3\) = .*": "ng(1:3) = 64, 16, 16", r"l\(1:3\) = .*": "l(1:3) = 6.283185307179586, 6.283185307179586, 6.283185307179586",
                      r"visci = .*": "visci = 1600.", r"inivel = .*": "inivel = 'tgv'"}, 0),
+    # bulk forcing in y and z and a body force (rk.f90:82-86,209-221: v with the face weights, w with the centre weights; bforce acts in the directions that
+    # are not forced -- a forced one's increment cancels it): every other case forces x alone and has bforce = 0. A channel with a spanwise bulk velocity
+    # and a body force along x and z, the same with x and y forced under the dynamic model, the triply periodic box forced in y and z
+    "chan_smag_fy_x64": ("les/_manuscript_turbulent_channel/input.nml",
+                         {r"ng\(1:3\) = .*": "ng(1:3) = 64, 16, 12", r"gr = 5\.": "gr = 2.", r"is_forced\(1:3\) = .*": "is_forced(1:3) = F, T, F",
+                          r"velf\(1:3\) = .*": "velf(1:3) = 1., 0.3, 0.", r"bforce\(1:3\) = .*": "bforce(1:3) = 0.7, 0., 0.05"}, 0),
+    "chan_dsmag_fxy_x64": ("les/_manuscript_turbulent_channel/input.nml",
+                           {r"ng\(1:3\) = .*": "ng(1:3) = 64, 16, 12", r"gr = 5\.": "gr = 2.", r"sgstype = 'smag'": "sgstype = 'dsmag'",
+                            r"is_forced\(1:3\) = .*": "is_forced(1:3) = T, T, F", r"velf\(1:3\) = .*": "velf(1:3) = 1., 0.3, 0."}, 0),
+    "tgv_fyz_x64": ("dns/triperiodic/input.nml",
+                    {r"ng\(1:3\) = .*": "ng(1:3) = 64, 16, 16", r"l\(1:3\) = .*": "l(1:3) = 6.283185307179586, 6.283185307179586, 6.283185307179586",
+                     r"visci = .*": "visci = 1600.", r"inivel = .*": "inivel = 'tgv'", r"is_forced\(1:3\) = .*": "is_forced(1:3) = F, T, T",
+                     r"velf\(1:3\) = .*": "velf(1:3) = 0., 0.2, -0.15", r"bforce\(1:3\) = .*": "bforce(1:3) = 0.05, 0., 0."}, 0),
 }
 END_KEYS = ("input_nml", "impdiff", "dt", "dt_cfl", "dpdl", "r3_div", "s0raw_u", "s0raw_v", "s0raw_w", "s0raw_p", "r3_s7_u", "r3_s7_v", "r3_s7_w", "r3_s8_p", "r3_s9_visct")
 CASES.update(END_ONLY)
@@ -384,7 +397,21 @@ def run_initflow(out):
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--case", default=None)
+    ap.add_argument("--check", default=None, metavar="NAME", help="run case NAME again and compare every array with the committed file (max |diff| = 0); writes nothing here")
     a = ap.parse_args()
+    if a.check:
+        # the recipe is unchanged: the same reference build and the same sequence give the committed vectors back, to the last bit
+        new = os.path.join(tempfile.mkdtemp(prefix="goldchk_"), a.check + ".npz")
+        run_case(a.check, new)
+        old, new = np.load(os.path.join(HERE, a.check + ".npz")), np.load(new)
+        assert sorted(old.files) == sorted(new.files), (sorted(old.files), sorted(new.files))
+        for k in old.files:
+            if old[k].dtype.kind in "fiu":
+                assert old[k].shape == new[k].shape and np.abs(np.asarray(new[k], dtype=np.float64) - old[k]).max() == 0., k
+            else:
+                assert np.array_equal(old[k], new[k]), k
+        print("check:", a.check, "max |diff| = 0 over", len(old.files), "arrays")
+        sys.exit(0)
     if a.case == "grids":
         run_grids(os.path.join(HERE, "grids.npz"))
     elif a.case == "outstats":

@@ -92,6 +92,17 @@ def test_slab_ranks_match_single_rank_at_baseline_sizes(key, P):
     _slabs_against_single_rank(case, P, 2)
 
 
+@pytest.mark.parametrize("name,ng,P,fset", [("chan_dsmag", (64, 32, 24), 4, "B"), ("chan_smag", (32, 24, 16), 3, "A"), ("tgv_dsmag_ppp", (32, 24, 16), 2, "D")])
+def test_slab_ranks_forced_in_y_and_z(name, ng, P, fset):
+    """Bulk forcing in y and z and a body force on several slabs (tests/util.py FORCING_SETS; every case above forces x alone): the bulk means of v and w folded
+    per rank, all-reduced and finished (k_force_finish) for components 1 and 2, dpdl on every rank -- against the one-rank run, which tests/test_gpu_forcing.py
+    holds to the oracle. (Not reached by these: the one-row form of the folded projection, slabs of three rows and fewer, whose ghost rows k_fold_ghost_rows
+    forms with the increments.)"""
+    from tests.util import forced_case
+    case = forced_case(name, ng, fset)
+    _slabs_against_single_rank(case, P, 2)
+
+
 def _slabs_against_single_rank(case, P, nsteps):
     from cales_amd.decomp import run_loopback
     u, v, w, p, visct, dt, div, dpdl = _single(case, nsteps)

@@ -141,7 +141,8 @@ def test_fused_step_matches_operator_sequence(name):
 @pytest.mark.parametrize("keep_x", [False, True], ids=["wrap", "xghosts"])
 @pytest.mark.parametrize("name", ["chan_dsmag_p2", "chan_smag_p2", "duct_dsmag_p2", "tgv_ppp_p2", "chan_dsmag_x64", "chan_dsmag_x128", "tgv_dsmag_ppp_x64",
                                   "chan_smag_wm_x64", "duct_smag_wm_x64", "duct_smag_wm_imp1d_x64",
-                                  "chan_nosgs_x64", "cavity_nnn_x64", "halfchan_imp1d_x64", "duct_dsmag_x64", "tgv_ppp_x64"])
+                                  "chan_nosgs_x64", "cavity_nnn_x64", "halfchan_imp1d_x64", "duct_dsmag_x64", "tgv_ppp_x64",
+                                  "chan_smag_fy_x64", "chan_dsmag_fxy_x64", "tgv_fyz_x64"])      # (forcing in y and z, a body force)
 def test_fused_step_at_power_of_two_rows(name, keep_x, monkeypatch):
     """Reference-made end-of-step states at power-of-two row lengths: radix-8 transforms, fillps inside the forward x pass, the x ghost columns left
     alone until the step returns (and, with CALES_XGHOSTS_IN_STEP, updated by every ghost-cell operator as at the operator level)."""

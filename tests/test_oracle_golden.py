@@ -215,7 +215,9 @@ def test_solver_operands_and_z_sweep(name):
 
 
 END_CASES = ["chan_dsmag_p2", "chan_smag_p2", "duct_dsmag_p2", "tgv_ppp_p2", "chan_dsmag_x64", "chan_dsmag_x128", "tgv_dsmag_ppp_x64", "chan_smag_wm_x64", "duct_smag_wm_x64", "duct_smag_wm_imp1d_x64",
-             "chan_nosgs_x64", "cavity_nnn_x64", "halfchan_imp1d_x64", "duct_dsmag_x64", "tgv_ppp_x64"]
+             "chan_nosgs_x64", "cavity_nnn_x64", "halfchan_imp1d_x64", "duct_dsmag_x64", "tgv_ppp_x64",
+             # bulk forcing in y and z, a body force (rk.f90:82-86,209-221): a spanwise bulk velocity with bforce along x and z, x and y forced, the box forced in y and z
+             "chan_smag_fy_x64", "chan_dsmag_fxy_x64", "tgv_fyz_x64"]
 
 
 @pytest.mark.parametrize("name", END_CASES)
@@ -236,6 +238,17 @@ def test_step_at_power_of_two_rows(name):
     assert relerr(p, pg) < 1e-11 or relerr(p - p[1:-1, 1:-1, 1:-1].mean(), pg - pg[1:-1, 1:-1, 1:-1].mean()) < 1e-11
     assert relerr(visct, g["r3_s9_visct"]) < 1e-10
     assert np.abs(dpdl - g["dpdl"]).max() < 1e-10 * max(1., np.abs(g["dpdl"]).max())
+
+
+def test_golden_recipe_is_unchanged():
+    """The vectors added later come from the recipe that made the earlier ones: gen_golden.py --check runs a committed case again through the compiled
+    reference and finds every array unchanged, max |diff| = 0. Needs the reference build (oracle/ref/Makefile), which exists only where the reference does."""
+    import subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    if not os.path.exists(os.path.join(root, "oracle", "_ref", "libcales_ref.so")):
+        pytest.skip("no reference build on this machine")
+    r = subprocess.run([sys.executable, os.path.join(root, "tests", "golden", "gen_golden.py"), "--check", "chan_dsmag_x64"], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0 and "max |diff| = 0" in r.stdout, r.stdout[-2000:] + r.stderr[-3000:]
 
 
 def test_manifest_lists_every_golden_file():

@@ -295,3 +295,108 @@ def helmholtz_operator(case, oracle, ivel, alpha, x):
     lz[:, :, 1:] += a[1:nz].astype(T)[None, None, :] * x[:, :, :-1]
     lz[:, :, :-1] += c[:nz - 1].astype(T)[None, None, :] * x[:, :, 1:]
     return x + T(alpha) * (lap + lz)
+
+
+# ------------------------------------------------------------------ bulk forcing in y and z, body force (rk.f90:82-86,209-221; mom.f90:311-335)
+# is_forced, velf (None: the case's own), bforce. bforce acts only in a direction that is NOT forced -- a forced direction's increment cancels it --, so no
+# set has both in one direction.
+FORCING_SETS = {"A": ((False, True, False), (None, 0.3, None), (0.7, 0., 0.05)),
+                "B": ((True, True, False), (None, 0.3, None), (0., 0., 0.)),
+                "C": ((False, True, True), (None, 0.2, -0.15), (0.05, 0., 0.)),
+                "D": ((True, True, True), (0.1, 0.2, -0.15), (0., 0., 0.)),
+                "E": ((False, False, False), (None, None, None), (1., 0., 0.))}
+
+# case, grid, sets, steps, what cales_describe_plan must say (the path the row is there for), switches of the row
+FORCING_STEPS = [
+    ("chan_smag", (24, 20, 12), "AB", 3, {"fillps": "own_pass", "bulk_forcing": "in_correction(means_own_pass)"}, {}),
+    ("chan_smag", (64, 18, 12), "AB", 2, {"bulk_forcing": "in_correction(means_in_x_transform)"}, {}),
+    ("chan_dsmag", (64, 20, 12), "AB", 2, {"projection": "in_strain_rate_pass", "bulk_forcing": "in_correction(means_in_x_transform)"}, {}),
+    ("chan_dsmag", (128, 12, 20), "B", 2, {"projection": "in_strain_rate_pass", "bulk_forcing": "in_correction(means_in_x_transform)"}, {}),      # two x tiles, several k chunks
+    ("chan_nosgs_x64", (64, 24, 16), "AB", 2, {"projection": "in_next_momentum_pass(substeps_1_2)", "bulk_forcing": "in_correction(means_in_x_transform)"}, {}),
+    # (the increment rides in the pending projection over the step boundary)
+    ("chan_nosgs_x64", (64, 24, 16), "AB", 3, {"projection": "in_next_momentum_pass(all_substeps)", "bulk_forcing": "in_correction(means_in_x_transform)"}, {"CALES_LAZY_PROJECTION": "1"}),
+    ("chan_smag_wm", (32, 16, 16), "B", 3, {"first_wall_model_update": "skipped", "bulk_forcing": "in_correction(means_in_x_transform)"}, {}),
+    ("chan_smag_wm", (32, 16, 8), "A", 3, {"first_wall_model_update": "skipped", "bulk_forcing": "in_correction(means_in_x_transform)"}, {}),
+    # the first wall-model update kept, hence the forcing as a pass of its own before it. A sampling height inside the first cell would do that, but
+    # cales_check_case refuses every such case (sanity.f90:224-231: hwm above the first cell centre), as it does at this grid's zc(1) = 0.057 < hwm = 0.1;
+    # of make_plan's conditions only the reference's full ghost-cell sequence is left to reach the fragment
+    ("chan_smag_wm", (32, 16, 8), "A", 3, {"first_wall_model_update": "kept", "bulk_forcing": "own_pass"}, {"CALES_UNMERGED_BC": "1"}),
+    ("chan_dsmag_wm", (64, 16, 12), "B", 2, {"sgs": "dsmag_tiles*", "first_wall_model_update": "*"}, {}),      # ("*": any value that starts so)
+    ("halfchan_imp1d", (16, 16, 16), "AB", 3, {"bulk_forcing": "in_helmholtz_sweep", "implicit_rhs": "in_helmholtz_sweep"}, {}),
+    ("halfchan_imp1d", (16, 16, 16), "AB", 3, {"bulk_forcing": "own_pass", "implicit_rhs": "own_pass"}, {"CALES_UNFUSED_IMP_RHS": "1"}),
+    ("couette_imp3d_ops", (16, 16, 16), "AB", 3, {"bulk_forcing": "own_pass"}, {}),
+    # periodic z: w weighted with the cell-centre weights (three steps at the 64-cell rows for the reason given below)
+    ("tgv_ppp", (32, 24, 16), "CD", 3, {"projection": "in_next_momentum_pass(substeps_1_2)", "bulk_forcing": "in_correction(means_in_x_transform)"}, {}),
+    ("tgv_ppp", (64, 16, 16), "CD", 3, {"projection": "in_next_momentum_pass(substeps_1_2)", "bulk_forcing": "in_correction(means_in_x_transform)"}, {}),
+    # the strain-rate fold with the increments of v and w, of u, v and w (three steps: the body force of set C moves u by bforce x elapsed time, 1e-2 of
+    # its maximum after two steps of these grids and 1.4e-2 after three)
+    ("tgv_dsmag_ppp", (64, 16, 24), "CD", 3, {"projection": "in_strain_rate_pass", "bulk_forcing": "in_correction(means_in_x_transform)"}, {}),
+    ("tgv_dsmag_ppp", (64, 16, 32), "CD", 3, {"projection": "in_strain_rate_pass", "bulk_forcing": "in_correction(means_in_x_transform)"}, {}),
+    # body force only, nothing forced
+    ("duct_smag_wm", (16, 24, 24), "E", 3, {"bulk_forcing": "none"}, {}),
+    ("duct_dsmag", (64, 18, 20), "E", 2, {"bulk_forcing": "none"}, {}),
+] + [
+    # sets A and B through the forms behind the switches, at the 64-cell rows
+    (name, ng, "AB", 2, expect, {env: "1"})
+    for name, ng in (("chan_smag", (64, 18, 12)), ("chan_dsmag", (64, 20, 12)))
+    for env, expect in (("CALES_UNFUSED_FORCING", {"bulk_forcing": "own_pass"}), ("CALES_UNFUSED_MEAN", {"bulk_forcing": "in_correction(means_own_pass)"}),
+                        ("CALES_UNFOLDED_CORREC", {"projection": "own_pass(correc+updatep)"}), ("CALES_UNFOLDED_MOM", {"projection": "own_pass(correc+updatep)" if name == "chan_smag" else "in_strain_rate_pass"}),
+                        ("CALES_UNFUSED_CORREC", {"projection": "own_passes", "bulk_forcing": "own_pass"}), ("CALES_XGHOSTS_IN_STEP", {"x_ghost_columns": "maintained"}))]
+FORCING_STEP_PARAMS = [(name, ng, s, nsteps, expect, env) for name, ng, sets, nsteps, expect, env in FORCING_STEPS for s in sets]
+
+
+def forcing_id(v):
+    return "x".join(str(x) for x in v) if isinstance(v, tuple) else str(v)
+
+
+FORCING_STEP_IDS = ["-".join([name, forcing_id(ng), s] + [k[6:] for k in env]) for name, ng, s, _, _, env in FORCING_STEP_PARAMS]
+
+
+def forced_case(name, ng, fset):
+    """golden case `name` on the grid `ng` with the forcing set `fset` of FORCING_SETS"""
+    g, case = load_golden(name)
+    case.ng[:] = ng
+    is_forced, velf, bforce = FORCING_SETS[fset]
+    case.is_forced[:] = is_forced
+    for d in range(3):
+        if velf[d] is not None:
+            case.velf[d] = velf[d]
+    case.bforce[:] = bforce
+    return case
+
+
+def perturbed_start(case, o, seed=1):
+    """initflow plus 2 % noise, the start-up of main.f90:370-375 on the oracle `o`, dt = half the bound of chkdt; returns (u, v, w, p, visct, pp, dt) and a raw copy of u, v, w, p"""
+    from cales_amd.hotpath import initflow
+    ng = tuple(int(x) for x in case.ng)
+    u, v, w, p = initflow(case)
+    rng = np.random.RandomState(seed)
+    for a in (u, v, w):
+        a[1:-1, 1:-1, 1:-1] += 0.02 * (rng.rand(*ng) - 0.5)
+    raw = [a.copy(order="F") for a in (u, v, w, p)]
+    visct, pp = o.zeros(), o.zeros()
+    o.bounduvw(u, v, w, True, False); o.boundp(p, 0); o.cmpt_sgs(u, v, w, visct); o.boundp(visct, 1)
+    dt = 0.5 * o.chkdt(visct, u, v, w)
+    return (u, v, w, p, visct, pp, dt), raw
+
+
+def oracle_forcing_of_substeps(o, case, dt, u, v, w, p, pp, visct):
+    """One step of the oracle operator by operator (the sequence of o_step, main.f90:417-508), on the caller's arrays; returns the forcing f of every substep"""
+    fs = []
+    for irk in (1, 2, 3):
+        dtrk = (RK[irk - 1][0] + RK[irk - 1][1]) * dt; alpha = 0.
+        f = o.rk(irk, dt, p, visct, u, v, w); fs.append(f.copy())
+        o.bulk_forcing(f, u, v, w)
+        if case.impdiff:
+            alpha = -.5 * case.visc * dtrk
+            for iv, q in ((1, u), (2, v), (3, w)):
+                if case.impdiff == 2:
+                    o.updt_rhs_b_velz(iv, alpha, q); o.solver_gaussel_z(iv, alpha, q)
+                else:
+                    o.updt_rhs_b_vel(iv, alpha, q); o.solver_helmholtz(iv, alpha, q)
+        o.bounduvw(u, v, w, True, False)
+        o.fillps(1. / dtrk, u, v, w, pp); o.updt_rhs_b_p(pp); o.solver(pp); o.boundp(pp, 0)
+        o.correc(dtrk, pp, u, v, w); o.bounduvw(u, v, w, True, True)
+        o.updatep(alpha, pp, p); o.boundp(p, 0)
+        o.cmpt_sgs(u, v, w, visct); o.boundp(visct, 1)
+    return fs
