@@ -17,10 +17,15 @@ static int finish_pending(cales_ctx *c);
 #define ENTRY(c, expr) do { ENTER(c); const int e_ = (expr); if (e_) return e_; LAUNCHCHK(c); return 0; } while (0)
 
 // ------------------------------------------------------------------------------------------ profiling
+int mark_stream(cales_ctx *c, hipStream_t s, hipEvent_t *e) {
+  if (c->sync_ev.size() < 64) { hipEvent_t ne; HIPCHK(c, hipEventCreateWithFlags(&ne, hipEventDisableTiming)); c->sync_ev.push_back(ne); c->sync_next = c->sync_ev.size() - 1; }
+  *e = c->sync_ev[c->sync_next]; c->sync_next = (c->sync_next + 1) % c->sync_ev.size();
+  HIPCHK(c, hipEventRecord(*e, s));
+  return 0;
+}
 int stream_after(cales_ctx *c, hipStream_t later, hipStream_t earlier) {
-  if (c->sync_ev.size() < 64) { hipEvent_t e; HIPCHK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming)); c->sync_ev.push_back(e); c->sync_next = c->sync_ev.size() - 1; }
-  hipEvent_t e = c->sync_ev[c->sync_next]; c->sync_next = (c->sync_next + 1) % c->sync_ev.size();
-  HIPCHK(c, hipEventRecord(e, earlier));
+  hipEvent_t e;
+  if (int err = mark_stream(c, earlier, &e)) return err;
   HIPCHK(c, hipStreamWaitEvent(later, e, 0));
   return 0;
 }
@@ -283,8 +288,8 @@ int cales_create(const cales_case *cs, void *stream, cales_ctx **out) {
     } else
     for (int m = 0; m < 6; ++m) if (field_alloc(c, &c->sij[m]) || field_alloc(c, &c->mij[m])) return fail(13);
   }
+  { hipDeviceProp_t pr; int dev = 0; if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&pr, dev) == hipSuccess) c->ncu = pr.multiProcessorCount; }      // (before solver_setup: its schedule counts on it)
   if (solver_setup(c)) return fail(14);
-  { hipDeviceProp_t pr; int dev = 0; if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&pr, dev) == hipSuccess) c->ncu = pr.multiProcessorCount; }
   if (sgs_setup_launches(c)) return fail(14);
   mom_setup(c);
   if (hipStreamSynchronize(c->stream) != hipSuccess) { c->err = "sync failed"; return fail(15); }
@@ -679,7 +684,7 @@ int cales_set_comm(cales_ctx *c, cales_halo_cb halo, cales_alltoall_cb a2a, cale
   HIPCHK(c, hipMemsetAsync(bufA, 0, nbuf * sizeof(real), c->stream));
   HIPCHK(c, hipMemsetAsync(bufB, 0, nbuf * sizeof(real), c->stream));
   red_place(c);      // the reduction results move into the tail of A, where the host can all-reduce them in place
-  return 0;
+  return solver_comm_changed(c);
 }
 int cales_set_comm_overlap(cales_ctx *c, cales_halo_s_cb halo_s, cales_alltoall_part_cb a2a_part) {
   if (!c->comm.on) { c->err = "cales_set_comm_overlap: call cales_set_comm first"; return 1; }
@@ -690,7 +695,7 @@ int cales_set_comm_overlap(cales_ctx *c, cales_halo_s_cb halo_s, cales_alltoall_
     HIPCHK(c, hipStreamCreateWithPriority(&c->comm_stream, hipStreamNonBlocking, greatest));
   }
   c->comm.halo_s = halo_s; c->comm.a2a_part = a2a_part;
-  return 0;
+  return solver_comm_changed(c);
 }
 int cales_initflow_slab(const cales_case *cs, const char *inivel, int is_wallturb, real *u, real *v, real *w, real *p) {
   if (!cs || !inivel || !u || !v || !w || !p) return 1;

@@ -322,7 +322,6 @@ struct cales_ctx {
   bool in_step = false;             // inside cales_step: the operator order is known, dead ghost work can be dropped
   bool force_zeroed = false;
   int ncu = 0;      // compute units of the device (balanced_kchunk)
-  real *d_mpart = nullptr; size_t n_mpart = 0;      // partial sums of the bulk means the forward x transform forms (FusedFill::mean_mask)
   // cales_step with periodic x: the x ghost columns are not maintained between the operators of a step -- every kernel of the step reads the wrapped
   // interior column instead (a ghost-column update touches two cache lines per row and field for two values: 1.2 of 45 ms per step at 512^3) -- and
   // are brought up to date once, when the step returns
@@ -385,6 +384,8 @@ void launch_failed(cales_ctx *c, const char *what, hipError_t e);
 // profiling bracket: PROF_BEGIN(ctx,"name"); launch...; PROF_END(ctx)
 int  prof_begin(cales_ctx *c, const char *name, hipStream_t s = nullptr);
 void prof_end(cales_ctx *c, int slot, hipStream_t s = nullptr);
+// the next ordering event of the context's pool (cales_ctx::sync_ev, round robin), recorded on `s`
+int  mark_stream(cales_ctx *c, hipStream_t s, hipEvent_t *e);
 // `later` waits for everything queued on `earlier` so far
 int  stream_after(cales_ctx *c, hipStream_t later, hipStream_t earlier);
 void prof_flush(cales_ctx *c);
@@ -465,6 +466,7 @@ int op_xwrap_zghost(cales_ctx *c, int nf, real **f);      // periodic copy of th
 int op_chkdt(cales_ctx *c, real *dtmax);
 int op_chkdiv(cales_ctx *c, real *divtot, real *divmax);
 int solver_setup(cales_ctx *c);
+int solver_comm_changed(cales_ctx *c);      // cales_set_comm, cales_set_comm_overlap: the staging buffers and the exchange form of the solves' schedules
 void solver_teardown(cales_ctx *c);      // (the host-side struct; its tables go with the context's memory)
 
 // XCD-aware block order for the one-plane-per-block stencil kernels (grid = x tiles, y tiles, z planes).

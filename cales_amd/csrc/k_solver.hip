@@ -1880,6 +1880,17 @@ struct SolvePath {
   real *lamx = nullptr, *lamy = nullptr; real normfft = 1.;      // eigenvalues per stored spectral index; scale of the inverse transforms
   FftPlan p1x, p1y; real *tw1x = nullptr, *tw1y = nullptr;      // k_dst1 (face-centred kinds)
 };
+// How a path is launched: the chunks of its exchange and the geometry of every pass, made by solve_sched with the path and again when the communication hooks
+// change (solver_comm_changed); solve_field only reads it. Chunk ch is the rows [ch rows, (ch + 1) rows) of the (j,k) row list, the planes ch kpc + 1 .. (ch + 1) kpc.
+struct SolveSched {
+  real2 *slab_spec = nullptr, *mode_spec = nullptr;      // the spectrum by rows | by mode columns: the staging buffers A | B, or null, in place: the modes of row (j,k) from i = 1 of the field (one rank; spec_of)
+  int nch = 1, kpc = 0; long rows = 0;                   // chunks (1: the exchange in order on the context's stream; 2, 4: pipelined on the second one), planes and rows of a chunk
+  unsigned xblk_f = 0, xblk_b = 0; int xit_f = 1, xit_b = 1, ykc = 1;      // k_fft_x8 forward | backward: blocks of a chunk, row groups per block; planes per block of the radix-8 y kernels
+  int ncol = 0, ncol_y = 0, mofs = 0, nmodes = 0;        // complex mode columns: here, those the radix-8 y kernels transform, the index of the first, in all
+  int64_t a2a_stride = 0, a2a_chunk = 0; int npart = 0;      // all-to-all: values of a peer's block, a chunk's share; bulk-mean partial sums per component (a block of the forward x pass each: their stride too)
+  Spec S; TileMap T{}; dim3 gz;                          // gz: grid of the marching z kernel (ZKernel::herm, ri, periodic_real, periodic_cpx; the tile's follows from ZTile: launch_tile)
+};
+static real2 *spec_of(real2 *staged, real *pp) { return staged ? staged : reinterpret_cast<real2 *>(pp + 1); }      // (the field is the call's: a step swaps the velocity buffers)
 // A z-only Helmholtz sweep of the z-implicit step (op_helmholtz_z), one per velocity component: nz = n3 - q unknowns (q = 1: w under a Dirichlet top) and their form
 enum class HzForm { thomas_periodic, thomas_per_column, tile, cols };      // k_gaussel<real, 1> | k_gaussel<real, 0> (CALES_HELMHOLTZ_Z_PER_COLUMN) | the LDS tile on the real field | k_thomas_coef + k_gaussel_cols(_rhs): shared pivots
 struct HzPath {
@@ -1894,7 +1905,8 @@ struct Solver {
   int xodd = 0, yodd = 0;        // the odd factor of an x / y line the radix-8 kernels take (SolvePath::xodd, yodd)
   real *twx = nullptr, *twx_post = nullptr, *twy = nullptr, *twy_post = nullptr, *twyd = nullptr;      // twiddle tables; twy_post, twyd: DCT weights of x, of y
   real *tw4x = nullptr, *tw4y = nullptr, *twy4 = nullptr;         // DCT-IV weights of x and y, twiddles of the N/2-point y lines
-  SolvePath pres, vel[3];
+  SolvePath pres, vel[3]; SolveSched sched_pres, sched_vel[3];
+  real *d_mpart = nullptr;       // 3 npart partial sums of the bulk means the pressure's forward x transform forms (FusedFill::mean_mask; solver_comm_changed)
   int vel_state[3] = {0, 0, 0}; std::string vel_err[3];      // a component's path: 0 not built yet, 1 built, 2 refused with vel_err (velocity_path_ready)
   HzPath hz[3];                  // impdiff = 2
   real *d_a = nullptr, *d_b, *d_c, *d_av[3] = {nullptr, nullptr, nullptr}, *d_bv[3], *d_cv[3];      // tridiagonal (a | b | c, n3 each) of the pressure; of the velocity components, unscaled (impdiff)
@@ -1943,6 +1955,40 @@ static void launch_nyq(cales_ctx *c, const ZTile &Z, bool herm, int nz, int N, i
   const NyqKernel k_gaussel_nyq_form = forms[Z.M == 2 ? 0 : Z.M == 4 ? 1 : Z.M == 8 ? 2 : 3][herm ? 1 : 0];
   LAUNCH(c, k_gaussel_nyq_form, dim3(herm ? N / 2 + 1 : N / 2), dim3(256), 4 * (64 * (Z.M + 1) + GT_PAD) * 8, c->stream, c->g, nz, N, nh, lscale, Z.tab, lamx, lamy, p, fixnull, S,
          (const real *)nullptr, (const real *)nullptr, (const real *)nullptr);
+}
+__global__ void k_null_column(Geom, Spec, int, int, const real *, const real *, const real *, const real *, const real *, real2 *, real *, int);
+// the z solve of a path on the spectrum by mode columns of pp: the kernel of P.zk in the schedule's geometry, and what goes around it
+static void launch_z(cales_ctx *c, const SolvePath &P, const SolveSched &D, real *pp, const real *da, const real *db, const real *dc, real lscale) {
+  const int n2g = c->C.ng[1], nh = c->C.ng[0] / 2, mh = c->n[0] / 2 + 1, nz = P.nz; real2 *mode_spec = spec_of(D.mode_spec, pp);
+  // CALES_KEEP_NULL_MODE: the singular column in the reference's sequential order (k_null_column); the rank that holds mode 0 does it
+  const bool refnull = P.refnull && D.mofs == 0;
+  if (refnull) LAUNCH(c, k_null_column, dim3(1), dim3(64), 0, c->stream, c->g, D.S, nz, P.periodic_z ? 1 : 0, da, db, dc, P.lamx, P.lamy, mode_spec, c->solver->d_nullw, 0);
+  { ProfScope ps(c, "gaussel_z");
+    const dim3 b(64, 4); real *ms = (real *)mode_spec;
+    switch (P.zk) {
+    case ZKernel::herm:
+      LAUNCH(c, k_gaussel_herm, D.gz, dim3(256), 0, c->stream, c->g, nz, D.ncol, n2g, D.mofs, nh, D.S, lscale, da, db, dc, P.lamx, P.lamy, ms, c->scr1, P.fixnull);
+      break;
+    case ZKernel::tile:
+      // the pressure's operands never change, its table is solver_setup's; a Helmholtz solve rescales its operands with the call's alpha: the table anew
+      if (!P.poisson) tile_table(c, P.zt.M, P.zt.PER ? nz - 1 : nz, da, db, dc, P.zt.tab);
+      launch_tile(c, P.zt, nz, lscale, da, db, dc, P.lamx, P.lamy, ms, P.fixnull, D.T);
+      break;
+    case ZKernel::ri:
+      LAUNCH(c, k_gaussel_ri, D.gz, dim3(256), 0, c->stream, c->g, nz, D.ncol, n2g, D.mofs, P.xkind ? nh : mh, D.S, lscale, da, db, dc, P.lamx, P.lamy, ms, c->scr1, P.fixnull, P.xkind ? 1 : 0);
+      break;
+    case ZKernel::periodic_real:      // real x modes (one eigenvalue each) with the periodic-z closure: scalar columns of the in-place spectrum, one rank
+      LAUNCH(c, (k_gaussel<real, 1>), D.gz, b, 0, c->stream, c->g, nz, 2 * nh, n2g, 1, 0, 2 * nh, D.S, lscale, da, db, dc, P.lamx, P.lamy, pp, c->scr1, c->scr2, P.fixnull);
+      break;
+    case ZKernel::periodic_cpx:
+      LAUNCH(c, (k_gaussel<real2, 1>), D.gz, b, 0, c->stream, c->g, nz, D.ncol, n2g, 0, D.mofs, mh, D.S, lscale, da, db, dc, P.lamx, P.lamy, ms, c->scr1, c->scr2, P.fixnull);
+      break;
+    } }
+  if (P.nyq && D.mofs == 0) {      // the packed column of the modes 0 and n1/2, which the tile left out (the path takes the tile: solver_setup)
+    ProfScope ps(c, "gaussel_z");
+    launch_nyq(c, P.zt, P.ykind == 0, nz, n2g, nh, lscale, P.lamx, P.lamy, mode_spec, P.fixnull, D.S);
+  }
+  if (refnull) LAUNCH(c, k_null_column, dim3(1), dim3(64), 0, c->stream, c->g, D.S, nz, P.periodic_z ? 1 : 0, da, db, dc, P.lamx, P.lamy, mode_spec, c->solver->d_nullw, 1);
 }
 
 bool solver_can_fuse_fillps(cales_ctx *c) { return c->solver && c->solver->x8; }
@@ -2000,6 +2046,65 @@ static void tile_setup(cales_ctx *c, SolvePath &P, real *tab) {
   Z.ndbl = c->P > 1 ? 2 * P.cw * c->n[1] : P.xkind ? 2 * (c->C.ng[0] / 2) : 2 * (P.nyq ? c->n[0] / 2 : c->n[0] / 2 + 1); Z.nrow = c->P > 1 ? c->P : c->C.ng[1];
   Z.persistent = !Z.PER && Z.NV == 1 && P.nz == 1024 && Z.ndbl % 16 == 0;      // full tiles of full chunks only (k_gaussel_tile_p)
   tile_attr(c, Z);
+}
+// ... and its schedule, for a path that is complete: from the path, the decomposition and the hooks registered so far
+static SolveSched solve_sched(const cales_ctx *c, const SolvePath &P) {
+  SolveSched D;
+  const int *n = c->n, mh = n[0] / 2 + 1, n2g = c->C.ng[1], nh = c->C.ng[0] / 2, cw = P.cw, Rx8 = P.xrows, CB8 = P.ycols;
+  const bool dist = c->P > 1, use8x = P.xk == XKernel::fft_x8, use8y = radix8_y(P.yk), use16y = P.yk == YKernel::fft_y16;
+  if (dist) { D.slab_spec = reinterpret_cast<real2 *>(c->comm.A); D.mode_spec = reinterpret_cast<real2 *>(c->comm.B); }
+  D.nmodes = P.nyq ? n[0] / 2 : mh; D.ncol = dist ? cw : D.nmodes; D.mofs = dist ? c->rank * cw : 0;
+  // real x modes (Neumann in x) fill the complex columns 0 .. n1/2 - 1: the slot of "mode n1/2" is never written by the x pass nor read back by it
+  D.ncol_y = (!dist && P.xkind == 1 && use8y) ? nh : D.ncol;
+  D.S.blocked = dist ? 1 : 0; D.S.cw = cw; D.S.n2l = n[1]; D.S.n3 = n[2]; D.S.nyq = P.nyq ? 1 : 0;
+  D.T.blocked = dist ? 1 : 0; D.T.cw = cw; D.T.n2l = n[1]; D.T.mofs = D.mofs; D.T.nmode = P.xkind ? nh : D.nmodes; D.T.nyq = P.nyq ? 1 : 0; D.T.kstride = (size_t)2 * cw * n[1]; D.T.segstride = D.T.kstride * n[2];
+  D.gz = P.zk == ZKernel::herm ? dim3((unsigned)(((long)4 * D.ncol * (n2g / 2 + 1) + 255) / 256)) : P.zk == ZKernel::ri ? dim3((unsigned)(((long)2 * D.ncol * n2g + 255) / 256))
+       : dim3(((P.zk == ZKernel::periodic_real ? 2 * nh : D.ncol) + 63) / 64, (n2g + 3) / 4);
+  // ---- pipelined exchange (cales_set_comm_overlap): the spectrum travels in k-chunks on the second stream while the x transforms of
+  // the next chunk and the y transforms of the previous one run on the context's stream (the reference's cuDecomp pipelined
+  // transposes, src/initmpi.f90:94-139). Radix-8 periodic / Neumann-Neumann transforms only; everything else keeps the single exchange,
+  // which is the same sequence with one chunk.
+  if (dist && c->comm.a2a_part && c->comm_stream && use8x && use8y) { if (n[2] % 4 == 0 && n[2] >= 32) D.nch = 4; else if (n[2] % 2 == 0 && n[2] >= 8) D.nch = 2; }
+  const bool pipe = D.nch > 1;
+  D.kpc = n[2] / D.nch; D.rows = (long)n[1] * D.kpc;
+  D.a2a_stride = (int64_t)n[2] * n[1] * cw * 2; D.a2a_chunk = (int64_t)D.kpc * n[1] * cw * 2;
+  // persistent blocks: several row groups / planes per block so that the register prefetch overlaps the transforms
+  const long xgroups = (D.rows + Rx8 - 1) / Rx8;
+  int xiters = 1; while (xiters < 8 && xgroups / (xiters * 2) >= 2048 / D.nch) xiters *= 2;
+  // measured (round 6, one box, row groups per block 1 / 2 / 4 / 8): forward pass with fillps 512 x 256 x 256 0.672 / 0.690 / 0.723 / 0.748 ms per step but
+  // 512^3 3.15 / 2.90 / 2.84 / 2.77 and 1024^3 25.3 / 23.2 / 22.9 / 21.2 -- persistent blocks pay from ~16 000 row groups; inverse periodic pass 512^3
+  // 1.36 / 1.41 / 1.44 / 1.50 (one group per block), inverse Neumann pass 1024^3 12.6 / 12.0 / 11.4 / 10.8 (eight). In order only: a chunk keeps its count
+  if (!pipe && xgroups <= 8192) xiters = 1;
+  D.xit_f = xiters; D.xit_b = (!pipe && P.xkind == 0 && nh <= 256) ? 1 : xiters;
+  D.xblk_f = (unsigned)((xgroups + D.xit_f - 1) / D.xit_f); D.xblk_b = (unsigned)((xgroups + D.xit_b - 1) / D.xit_b); D.npart = (int)(D.xblk_f * D.nch);
+  // planes per block of the eight-elements-per-thread y kernels: measured at 512^3 (round 6, in the step, planes per block 1 / 2 / 8): y passes 2.77 / 2.69 / 2.94 ms
+  // per step -- many short blocks beat long persistent ones; from 8192 blocks on (in order; of the chunks, from 2048 blocks in all)
+  { const long cg = (D.ncol + CB8 - 1) / CB8, from = pipe ? 2048 / D.nch : 8192;
+    while (D.ykc < 8 && cg * (D.kpc / (D.ykc * 2)) >= from && D.kpc % (D.ykc * 2) == 0) D.ykc *= 2; }
+  // k_fft_y16 holds 1 / 2 / 4 blocks per CU (1024 / 512 / 256 points): a launch runs in ceil(blocks / slots) rounds of (planes per block + ~1.5 planes of
+  // set-up: tables, the first plane's latency) each -- the chunk length that minimises that product (512^3: 7 planes, 5 rounds of 8.5 against 5 of 9.5
+  // with 8; 512 x 256 x 256: 3 planes; 1024^3: 32)
+  if (use16y) {
+    const long slots = (long)(c->ncu > 0 ? c->ncu : 256) * (n2g >= 1024 ? 1 : n2g >= 512 ? 2 : 4), tiles = (D.ncol_y + 7) / 8;
+    double best = 1e300;
+    for (int kc = 1; kc <= 32 && kc <= D.kpc; ++kc) {
+      const long nb = tiles * ((D.kpc + kc - 1) / kc);
+      const double cost = (double)((nb + slots - 1) / slots) * (kc + 1.5);
+      if (cost < best) { best = cost; D.ykc = kc; }
+    }
+  }
+  return D;
+}
+// solver_setup, cales_set_comm, cales_set_comm_overlap: the schedules of the paths that exist, with the staging buffers and the second stream as they are now (a
+// velocity path built later finds them), and the partial sums of the bulk means sized with the pressure's: only a forward k_fft_x8 of a forced case sums any
+int solver_comm_changed(cales_ctx *c) {
+  Solver *s = c->solver;
+  if (!s) return 0;
+  s->sched_pres = solve_sched(c, s->pres);
+  for (int iv = 0; iv < 3; ++iv) if (s->vel_state[iv] == 1) s->sched_vel[iv] = solve_sched(c, s->vel[iv]);
+  ctx_free(c, s->d_mpart); s->d_mpart = nullptr;
+  const bool forced = c->C.is_forced[0] || c->C.is_forced[1] || c->C.is_forced[2];
+  return (forced && s->pres.xk == XKernel::fft_x8) ? ctx_alloc(c, &s->d_mpart, 3 * (size_t)s->sched_pres.npart, false) : 0;
 }
 
 int solver_setup(cales_ctx *c) {
@@ -2113,6 +2218,7 @@ int solver_setup(cales_ctx *c) {
   if (upload_twiddles(c, 4 * n1, n1 / 2 + 1, &s.twy_post)) return 1;      // DCT weights e^{-i pi k/(2 n1)}, k = 0..n1/2 (x)
   if (upload_twiddles(c, 4 * n2g, n2g, &s.twyd)) return 1;               // e^{-i pi k/(2 n2)}, k = 0..n2-1 (y)
   if (P.xkind >= 3 && upload_dct4_weights(c, n1, &s.tw4x)) return 1;    // DCT-IV weights (k_fft_x4)
+  if (solver_comm_changed(c)) return 1;
   if (!c->C.impdiff) return 0;
   for (int iv = 0; iv < 3; ++iv) {
     hs_tridmatrix(&c->cbcvel[6 * iv + 4], n3, c->dzci.data(), c->dzfi.data(), iv == 2 ? 'f' : 'c', abc.data(), abc.data() + n3, abc.data() + 2 * n3);
@@ -2193,9 +2299,9 @@ __global__ void k_null_column(Geom g, Spec S, int nz, int periodic, const real *
   for (int l = 0; l < nz; ++l) p[S.at_mode(g, 0, 1, l + 1)].x = col[l];
 }
 
-// The transform passes of a path. x: the rows [rb, re) of the (j,k) row list (re < 0: all), the radix-8 kernel in `blocks` blocks of `iters` row groups,
-// F (forward only): the pass forms pp = div(u*)/dtrk itself (fillps). y: the planes k0+1..k1 (k1 < 0: all), the radix-8 kernels `kchunk` planes per block.
-// The other kernels take the whole field in a geometry of their own.
+// The transform passes of a path over chunk ch of its schedule. x: the chunk's rows, the radix-8 kernel in the schedule's blocks and row groups per block;
+// F (forward only): the pass forms pp = div(u*)/dtrk itself (fillps). y: the chunk's planes, the radix-8 kernels D.ykc planes per block.
+// The other kernels take the whole field in a geometry of their own (their schedules have one chunk).
 template <int INV, int KIND, int FILL>
 static void launch_x8(cales_ctx *c, const Solver &s, bool odd, unsigned blocks, int iters, real *pp, real scale, const Spec &S, real2 *spec, const FillArgs &F, long rb, long re) {
   if (odd) LAUNCH(c, (k_fft_x8<INV, KIND, FILL, 1>), dim3(blocks), dim3(s.x8_threads), s.shx8, c->stream, c->g, c->C.ng[0] / 2, iters, (const cpx *)s.twx, (const cpx *)s.twx_post,
@@ -2204,11 +2310,12 @@ static void launch_x8(cales_ctx *c, const Solver &s, bool odd, unsigned blocks, 
          (const cpx *)s.twy_post, pp, scale, S, spec, F, rb, re);
 }
 template <int INV>
-static void fft_x(cales_ctx *c, const SolvePath &P, real *pp, const Spec &S, real2 *spec, unsigned blocks, int iters, const FillArgs *F, long rb, long re) {
+static void fft_x(cales_ctx *c, const SolvePath &P, const SolveSched &D, int ch, real *pp, const FillArgs *F = nullptr) {
   const Solver &s = *c->solver;
   const real scale = INV ? P.normfft : (real)1.;
-  const long nrows = (long)c->n[1] * c->n[2];
+  const long nrows = (long)c->n[1] * c->n[2], rb = D.rows * ch, re = rb + D.rows; const unsigned blocks = INV ? D.xblk_b : D.xblk_f; const int iters = INV ? D.xit_b : D.xit_f;
   const dim3 gx((unsigned)((nrows + s.Rx - 1) / s.Rx));
+  const Spec &S = D.S; real2 *spec = spec_of(D.slab_spec, pp);
   if (P.xk == XKernel::fft_x8) {
     if constexpr (INV == 0) if (F) { if (P.xkind) launch_x8<0, 1, 1>(c, s, P.xodd != 0, blocks, iters, pp, scale, S, spec, *F, rb, re); else launch_x8<0, 0, 1>(c, s, P.xodd != 0, blocks, iters, pp, scale, S, spec, *F, rb, re); return; }
     if (P.xkind) launch_x8<INV, 1, 0>(c, s, P.xodd != 0, blocks, iters, pp, scale, S, spec, FillArgs{}, rb, re); else launch_x8<INV, 0, 0>(c, s, P.xodd != 0, blocks, iters, pp, scale, S, spec, FillArgs{}, rb, re);
@@ -2223,12 +2330,12 @@ static void fft_y16(cales_ctx *c, const Solver &s, dim3 gy, int ncols, int kchun
   if constexpr (N > 256) if (c->C.ng[1] < N) return fft_y16<INV, KIND, N / 2>(c, s, gy, ncols, kchunk, S, spec, k0, k1);
   LAUNCH(c, (k_fft_y16<N, INV, KIND>), gy, dim3(N / 2), s.shy16, c->stream, c->g, ncols, kchunk, (const cpx *)s.twy, (const cpx *)s.twyd, S, spec, k0, k1);
 }
-// ncol_y: the columns the radix-8 y kernels transform (see solve_field)
 template <int INV>
-static void fft_y(cales_ctx *c, const SolvePath &P, real *pp, const Spec &S, real2 *spec, int ncol, int ncol_y, int kchunk, int k0, int k1) {
+static void fft_y(cales_ctx *c, const SolvePath &P, const SolveSched &D, int ch, real *pp) {
   const Solver &s = *c->solver;
-  const int n2g = c->C.ng[1], n3 = c->n[2];
-  const dim3 gy((ncol_y + P.ycols - 1) / P.ycols, ((k1 < 0 ? n3 : k1) - k0 + kchunk - 1) / kchunk);
+  const int n2g = c->C.ng[1], n3 = c->n[2], ncol = D.ncol, ncol_y = D.ncol_y, kchunk = D.ykc, k0 = D.kpc * ch, k1 = k0 + D.kpc;
+  const dim3 gy((ncol_y + P.ycols - 1) / P.ycols, (D.kpc + kchunk - 1) / kchunk);
+  const Spec &S = D.S; real2 *spec = spec_of(D.mode_spec, pp);
   switch (P.yk) {
   case YKernel::dst1:
     LAUNCH(c, k_dst1<1>, dim3(ncol, n3), dim3(256), (size_t)2 * (P.p1y.N + 1) * sizeof(cpx), c->stream, c->g, P.p1y, ncol, (const cpx *)P.tw1y, pp, 1., S, spec, P.ykind, INV); break;
@@ -2251,156 +2358,48 @@ static void fft_y(cales_ctx *c, const SolvePath &P, real *pp, const Spec &S, rea
   }
 }
 
-// FFT x, FFT y, tridiagonal z, and back, in place on `pp` along path P; (da,db,dc,lscale) = (a,b,c,1) for the pressure Poisson equation,
-// (alpha a, alpha b + 1, alpha c, alpha) for the Helmholtz equation of a velocity component (main.f90:435-445)
-static int solve_field(cales_ctx *c, const SolvePath &P, real *pp, const real *da, const real *db, const real *dc, real lscale, const FusedFill &ff = FusedFill()) {
-  const int *n = c->n;
-  const int mh = n[0] / 2 + 1, n2g = c->C.ng[1], nh = c->C.ng[0] / 2, nz = P.nz;
-  const long nrows = (long)n[1] * n[2];
-  const bool dist = c->P > 1;
+// FFT x, FFT y, tridiagonal z, and back, in place on `pp` along path P with its schedule D; (da,db,dc,lscale) = (a,b,c,1) for the pressure Poisson equation,
+// (alpha a, alpha b + 1, alpha c, alpha) for the Helmholtz equation of a velocity component (main.f90:435-445). One sequence over the chunks of D: the exchange
+// of a chunk follows its transform, in order on the context's stream (one chunk) or on the second stream, where `arrived` then holds the chunk's event
+static int solve_field(cales_ctx *c, const SolvePath &P, const SolveSched &D, real *pp, const real *da, const real *db, const real *dc, real lscale, const FusedFill &ff = FusedFill()) {
+  const bool dist = c->P > 1, pipe = D.nch > 1;
   if (dist && !c->comm.on) { c->err = "solver: nranks > 1 but no communication hooks registered (cales_set_comm)"; return 1; }
-  const int cw = P.cw, nmodes = P.nyq ? n[0] / 2 : mh;      // complex mode columns: per rank, in all
-  Spec S; S.blocked = dist ? 1 : 0; S.cw = cw; S.n2l = n[1]; S.n3 = n[2]; S.nyq = P.nyq ? 1 : 0;
-  real2 *slab_spec = dist ? reinterpret_cast<real2 *>(c->comm.A) : reinterpret_cast<real2 *>(pp + 1);   // in place: modes of row (j,k) from i = 1
-  real2 *mode_spec = dist ? reinterpret_cast<real2 *>(c->comm.B) : reinterpret_cast<real2 *>(pp + 1);
-  const int ncol = dist ? cw : nmodes, mofs = dist ? c->rank * cw : 0;
-  const int64_t a2a_count = (int64_t)n[2] * n[1] * cw * 2;
-  const bool use8x = P.xk == XKernel::fft_x8, use8y = radix8_y(P.yk), use16y = P.yk == YKernel::fft_y16;
-  const int Rx8 = P.xrows, CB8 = P.ycols;
-  // real x modes (Neumann in x) fill the complex columns 0 .. n1/2 - 1: the slot of "mode n1/2" is never written by the x pass nor read back by it
-  const int ncol_y = (!dist && P.xkind == 1 && use8y) ? nh : ncol;
-  // persistent blocks: several row groups / planes per block so that the register prefetch overlaps the transforms
-  const long xgroups = (nrows + Rx8 - 1) / Rx8;
-  int xiters = 1; while (xiters < 8 && xgroups / (xiters * 2) >= 2048) xiters *= 2;
-  // measured (round 6, one box, row groups per block 1 / 2 / 4 / 8): forward pass with fillps 512 x 256 x 256 0.672 / 0.690 / 0.723 / 0.748 ms per step but
-  // 512^3 3.15 / 2.90 / 2.84 / 2.77 and 1024^3 25.3 / 23.2 / 22.9 / 21.2 -- persistent blocks pay from ~16 000 row groups; inverse periodic pass 512^3
-  // 1.36 / 1.41 / 1.44 / 1.50 (one group per block), inverse Neumann pass 1024^3 12.6 / 12.0 / 11.4 / 10.8 (eight)
-  if (xgroups <= 8192) xiters = 1;
-  const unsigned xblocks = (unsigned)((xgroups + xiters - 1) / xiters);
-  const int xiters_b = (P.xkind == 0 && nh <= 256) ? 1 : xiters;
-  const unsigned xblocks_b = (unsigned)((xgroups + xiters_b - 1) / xiters_b);
-  // planes per block of the eight-elements-per-thread y kernels: measured at 512^3 (round 6, in the step, planes per block 1 / 2 / 8): y passes 2.77 / 2.69 / 2.94 ms
-  // per step -- many short blocks beat long persistent ones; from 8192 blocks on
-  int ykchunk = 1; { const long cg = (ncol + CB8 - 1) / CB8; while (ykchunk < 8 && cg * (n[2] / (ykchunk * 2)) >= 8192 && n[2] % (ykchunk * 2) == 0) ykchunk *= 2; }
-  // k_fft_y16 holds 1 / 2 / 4 blocks per CU (1024 / 512 / 256 points): a launch runs in ceil(blocks / slots) rounds of (planes per block + ~1.5 planes of
-  // set-up: tables, the first plane's latency) each -- the chunk length that minimises that product (512^3: 7 planes, 5 rounds of 8.5 against 5 of 9.5
-  // with 8; 512 x 256 x 256: 3 planes; 1024^3: 32)
-  auto y16_chunk = [&](int planes) {
-    const long slots = (long)(c->ncu > 0 ? c->ncu : 256) * (n2g >= 1024 ? 1 : n2g >= 512 ? 2 : 4), tiles = (ncol_y + 7) / 8;
-    double best = 1e300; int bk = 1;
-    for (int kc = 1; kc <= 32 && kc <= planes; ++kc) {
-      const long nb = tiles * ((planes + kc - 1) / kc);
-      const double cost = (double)((nb + slots - 1) / slots) * (kc + 1.5);
-      if (cost < best) { best = cost; bk = kc; }
-    }
-    return bk;
-  };
-  if (use16y) ykchunk = y16_chunk(n[2]);
-  // ---- pipelined exchange (cales_set_comm_overlap): the spectrum travels in k-chunks on the second stream while the x transforms of
-  // the next chunk and the y transforms of the previous one run on the context's stream (the reference's cuDecomp pipelined
-  // transposes, src/initmpi.f90:94-139). Radix-8 periodic / Neumann-Neumann transforms only; everything else keeps the single exchange,
-  // which is the same sequence with one chunk and the geometry above.
-  int NCH = 1;
-  if (dist && c->comm.a2a_part && c->comm_stream && use8x && use8y) { if (n[2] % 4 == 0 && n[2] >= 32) NCH = 4; else if (n[2] % 2 == 0 && n[2] >= 8) NCH = 2; }
-  const bool pipe = NCH > 1;
-  const int kpc = n[2] / NCH;                                   // planes per chunk
-  const int64_t a2a_stride = a2a_count, a2a_chunk = (int64_t)kpc * n[1] * cw * 2;
-  const long rows_c = (long)n[1] * kpc, xgroups_c = (rows_c + Rx8 - 1) / Rx8;
-  int xiters_c = 1; while (xiters_c < 8 && xgroups_c / (xiters_c * 2) >= 2048 / NCH) xiters_c *= 2;
-  const unsigned xblocks_c = (unsigned)((xgroups_c + xiters_c - 1) / xiters_c);
-  int ykchunk_c = 1; { const long cg = (ncol + CB8 - 1) / CB8; while (ykchunk_c < 8 && cg * (kpc / (ykchunk_c * 2)) >= 2048 / NCH && kpc % (ykchunk_c * 2) == 0) ykchunk_c *= 2; }
-  if (use16y) ykchunk_c = y16_chunk(kpc);
-  const unsigned xblk_f = pipe ? xblocks_c : xblocks, xblk_b = pipe ? xblocks_c : xblocks_b;
-  const int xit_f = pipe ? xiters_c : xiters, xit_b = pipe ? xiters_c : xiters_b, ykc = pipe ? ykchunk_c : ykchunk;
-  auto rows_of = [&](int ch, long &rb, long &re) { rb = pipe ? (long)n[1] * kpc * ch : 0; re = pipe ? rb + rows_c : -1; };
-  auto k0_of = [&](int ch) { return pipe ? kpc * ch : 0; };
-  auto k1_of = [&](int ch) { return pipe ? kpc * (ch + 1) : -1; };
-  hipEvent_t ev_arrived[4];
-  auto mark = [&](hipStream_t st, hipEvent_t &e) -> int {
-    if (c->sync_ev.size() < 64) { hipEvent_t ne; HIPCHK(c, hipEventCreateWithFlags(&ne, hipEventDisableTiming)); c->sync_ev.push_back(ne); c->sync_next = c->sync_ev.size() - 1; }
-    e = c->sync_ev[c->sync_next]; c->sync_next = (c->sync_next + 1) % c->sync_ev.size();
-    HIPCHK(c, hipEventRecord(e, st)); return 0; };
-  auto exchange_chunk = [&](int dir, int ch) -> int {          // comm stream: after everything queued on the context's stream so far
-    if (int e = stream_after(c, c->comm_stream, c->stream)) return e;
+  hipEvent_t arrived[4] = {nullptr, nullptr, nullptr, nullptr};
+  auto exchange = [&](int dir, int ch) -> int {
+    if (!dist) return 0;
+    if (!pipe) { ProfScope ps(c, "alltoall"); if (c->comm.a2a(c->comm.user, dir, D.a2a_stride)) { c->err = "alltoall callback failed"; return 1; } return 0; }
+    if (int e = stream_after(c, c->comm_stream, c->stream)) return e;      // comm stream: after everything queued on the context's stream so far
     { ProfScope ps(c, "alltoall", c->comm_stream);
-      if (c->comm.a2a_part(c->comm.user, dir, a2a_stride, (int64_t)ch * a2a_chunk, a2a_chunk, (void *)c->comm_stream)) { c->err = "alltoall_part callback failed"; return 1; } }
-    return mark(c->comm_stream, ev_arrived[ch]); };
+      if (c->comm.a2a_part(c->comm.user, dir, D.a2a_stride, (int64_t)ch * D.a2a_chunk, D.a2a_chunk, (void *)c->comm_stream)) { c->err = "alltoall_part callback failed"; return 1; } }
+    return mark_stream(c, c->comm_stream, &arrived[ch]); };
+  auto wait_for = [&](int ch) -> int { if (arrived[ch]) HIPCHK(c, hipStreamWaitEvent(c->stream, arrived[ch], 0)); return 0; };
   // fillps inside the forward x transform; the bulk means it sums: several ranks all-reduce them on the context's stream, and RCCL orders the operations of
   // one communicator across streams -- issued between the chunk exchanges it would hold the y transforms back, so the pipelined solve reduces them after the z sweep
-  const bool fill = P.poisson && ff.dtrki != 0. && use8x;
-  FillArgs F{};
+  const bool fill = P.poisson && ff.dtrki != 0. && P.xk == XKernel::fft_x8; FillArgs F{};
   if (fill) {
-    const real dti = ff.dtrki;
-    F = FillArgs{c->f[CALES_U], c->f[CALES_V], c->f[CALES_W], c->d_dzfi, dti, dti * c->dli[0], dti * c->dli[1], ff.mean_mask, c->d_gvr_f, c->d_gvr_c, nullptr};
-    F.xwrap = c->step_xskip ? n[0] : 0;
-    if (F.mean_mask) {
-      const size_t need = 3 * (size_t)xblk_f * NCH;
-      // (the one buffer that may grow: the pipelined exchange, which cales_set_comm_overlap may switch on between two steps, cuts the rows into other blocks)
-      if (c->n_mpart < need) { ctx_free(c, c->d_mpart); c->d_mpart = nullptr; if (ctx_alloc(c, &c->d_mpart, need, false)) return 1; c->n_mpart = need; }
-      F.part = c->d_mpart; if (pipe) F.pstride = (int)(xblocks_c * NCH);
-    }
+    F = FillArgs{c->f[CALES_U], c->f[CALES_V], c->f[CALES_W], c->d_dzfi, ff.dtrki, ff.dtrki * c->dli[0], ff.dtrki * c->dli[1], ff.mean_mask, c->d_gvr_f, c->d_gvr_c, c->solver->d_mpart};
+    F.xwrap = c->step_xskip ? c->n[0] : 0; F.pstride = D.npart;
+    if (F.mean_mask && !F.part) { c->err = "solver: bulk means asked of a case without forcing"; return 1; }
   }
-  for (int ch = 0; ch < NCH; ++ch) {
-    long rb, re; rows_of(ch, rb, re);
+  for (int ch = 0; ch < D.nch; ++ch) {
     { ProfScope ps(c, fill ? "fillps_fft_x_fwd" : "fft_x_fwd");
-      F.pofs = (int)(xblk_f * ch);
-      fft_x<0>(c, P, pp, S, slab_spec, xblk_f, xit_f, fill ? &F : nullptr, rb, re);
-      if (F.mean_mask && !pipe) if (int e = op_force_from_partials(c, F.mean_mask, F.part, (int)xblk_f)) return e; }
-    if (pipe) if (int e = exchange_chunk(0, ch)) return e;
+      F.pofs = (int)(D.xblk_f * ch); fft_x<0>(c, P, D, ch, pp, fill ? &F : nullptr);
+      if (F.mean_mask && !pipe) if (int e = op_force_from_partials(c, F.mean_mask, F.part, D.npart)) return e; }
+    if (int e = exchange(0, ch)) return e;
   }
-  if (dist && !pipe) { ProfScope ps(c, "alltoall"); if (c->comm.a2a(c->comm.user, 0, a2a_count)) { c->err = "alltoall callback failed"; return 1; } }
-  for (int ch = 0; ch < NCH; ++ch) {
-    if (pipe) HIPCHK(c, hipStreamWaitEvent(c->stream, ev_arrived[ch], 0));
-    ProfScope ps(c, "fft_y_fwd");
-    fft_y<0>(c, P, pp, S, mode_spec, ncol, ncol_y, ykc, k0_of(ch), k1_of(ch));
+  for (int ch = 0; ch < D.nch; ++ch) {
+    if (int e = wait_for(ch)) return e;
+    ProfScope ps(c, "fft_y_fwd"); fft_y<0>(c, P, D, ch, pp);
   }
-  // CALES_KEEP_NULL_MODE: the singular column in the reference's sequential order (k_null_column); the rank that holds mode 0 does it
-  const bool refnull = P.refnull && mofs == 0;
-  if (refnull) LAUNCH(c, k_null_column, dim3(1), dim3(64), 0, c->stream, c->g, S, nz, P.periodic_z ? 1 : 0, da, db, dc, P.lamx, P.lamy, mode_spec, c->solver->d_nullw, 0);
-  { ProfScope ps(c, "gaussel_z");
-    const dim3 b(64, 4), gr((ncol + 63) / 64, (n2g + 3) / 4);
-    real *ms = (real *)mode_spec;
-    switch (P.zk) {
-    case ZKernel::herm:
-      LAUNCH(c, k_gaussel_herm, dim3((unsigned)(((long)4 * ncol * (n2g / 2 + 1) + 255) / 256)), dim3(256), 0, c->stream, c->g, nz, ncol, n2g, mofs, nh, S, lscale,
-             da, db, dc, P.lamx, P.lamy, ms, c->scr1, P.fixnull);
-      break;
-    case ZKernel::tile: {
-      TileMap T{}; T.blocked = dist ? 1 : 0; T.cw = cw; T.n2l = n[1]; T.mofs = mofs; T.nmode = P.xkind ? nh : nmodes; T.nyq = P.nyq ? 1 : 0;
-      T.kstride = (size_t)2 * cw * n[1]; T.segstride = T.kstride * n[2];
-      // the pressure's operands never change, its table is solver_setup's; a Helmholtz solve rescales its operands with the call's alpha: the table anew
-      if (!P.poisson) tile_table(c, P.zt.M, P.zt.PER ? nz - 1 : nz, da, db, dc, P.zt.tab);
-      launch_tile(c, P.zt, nz, lscale, da, db, dc, P.lamx, P.lamy, ms, P.fixnull, T);
-      break; }
-    case ZKernel::ri:
-      LAUNCH(c, k_gaussel_ri, dim3((unsigned)(((long)2 * ncol * n2g + 255) / 256)), dim3(256), 0, c->stream, c->g, nz, ncol, n2g, mofs, P.xkind ? nh : mh, S, lscale,
-             da, db, dc, P.lamx, P.lamy, ms, c->scr1, P.fixnull, P.xkind ? 1 : 0);
-      break;
-    case ZKernel::periodic_real:      // real x modes (one eigenvalue each) with the periodic-z closure: scalar columns of the in-place spectrum, one rank
-      LAUNCH(c, (k_gaussel<real, 1>), dim3((2 * nh + 63) / 64, (n2g + 3) / 4), b, 0, c->stream, c->g, nz, 2 * nh, n2g, 1, 0, 2 * nh, S, lscale,
-             da, db, dc, P.lamx, P.lamy, pp, c->scr1, c->scr2, P.fixnull);
-      break;
-    case ZKernel::periodic_cpx:
-      LAUNCH(c, (k_gaussel<real2, 1>), gr, b, 0, c->stream, c->g, nz, ncol, n2g, 0, mofs, mh, S, lscale, da, db, dc, P.lamx, P.lamy, ms, c->scr1, c->scr2, P.fixnull);
-      break;
-    } }
-  if (P.nyq && mofs == 0) {      // the packed column of the modes 0 and n1/2, which the tile left out (the path takes the tile: solver_setup)
-    ProfScope ps(c, "gaussel_z");
-    launch_nyq(c, P.zt, P.ykind == 0, nz, n2g, nh, lscale, P.lamx, P.lamy, mode_spec, P.fixnull, S);
+  launch_z(c, P, D, pp, da, db, dc, lscale);
+  if (F.mean_mask && pipe) if (int e = op_force_from_partials(c, F.mean_mask, F.part, D.npart)) return e;
+  for (int ch = 0; ch < D.nch; ++ch) {
+    { ProfScope ps(c, "fft_y_bwd"); fft_y<1>(c, P, D, ch, pp); }
+    if (int e = exchange(1, ch)) return e;
   }
-  if (refnull) LAUNCH(c, k_null_column, dim3(1), dim3(64), 0, c->stream, c->g, S, nz, P.periodic_z ? 1 : 0, da, db, dc, P.lamx, P.lamy, mode_spec, c->solver->d_nullw, 1);
-  if (F.mean_mask && pipe) if (int e = op_force_from_partials(c, F.mean_mask, F.part, (int)(xblocks_c * NCH))) return e;
-  for (int ch = 0; ch < NCH; ++ch) {
-    { ProfScope ps(c, "fft_y_bwd");
-      fft_y<1>(c, P, pp, S, mode_spec, ncol, ncol_y, ykc, k0_of(ch), k1_of(ch)); }
-    if (pipe) if (int e = exchange_chunk(1, ch)) return e;
-  }
-  if (dist && !pipe) { ProfScope ps(c, "alltoall"); if (c->comm.a2a(c->comm.user, 1, a2a_count)) { c->err = "alltoall callback failed"; return 1; } }
-  for (int ch = 0; ch < NCH; ++ch) {
-    if (pipe) HIPCHK(c, hipStreamWaitEvent(c->stream, ev_arrived[ch], 0));
-    long rb, re; rows_of(ch, rb, re);
-    ProfScope ps(c, "fft_x_bwd");
-    fft_x<1>(c, P, pp, S, slab_spec, xblk_b, xit_b, nullptr, rb, re);
+  for (int ch = 0; ch < D.nch; ++ch) {
+    if (int e = wait_for(ch)) return e;
+    ProfScope ps(c, "fft_x_bwd"); fft_x<1>(c, P, D, ch, pp);
   }
   LAUNCHCHK(c);
   return 0;
@@ -2433,7 +2432,7 @@ std::string solver_path_name(cales_ctx *c) {
 
 int op_solver(cales_ctx *c, const FusedFill &fill) {
   if (!c->solver) { c->err = "solver not initialised"; return 1; }
-  return solve_field(c, c->solver->pres, c->f[CALES_PP], c->solver->d_a, c->solver->d_b, c->solver->d_c, 1., fill);
+  return solve_field(c, c->solver->pres, c->solver->sched_pres, c->f[CALES_PP], c->solver->d_a, c->solver->d_b, c->solver->d_c, 1., fill);
 }
 
 // z-only Helmholtz systems have the same matrix for every column (no eigenvalue shift): the pivots z_l and c'_l of the
@@ -2578,6 +2577,7 @@ static int velocity_path(cales_ctx *c, Solver &s, int iv, SolvePath &V) {
   V.cw = c->cw;
   choose_kernels(c, s, V);
   tile_setup(c, V, s.tab_imp3d);
+  s.sched_vel[iv] = solve_sched(c, V);
   return 0;
 }
 // the one place a component's path is made: by its first solve or by cales_describe_plan, whichever comes first; a refusal is kept and repeated
@@ -2605,5 +2605,5 @@ int op_helmholtz(cales_ctx *c, int ivel, real alpha) {
   if (int e = op_rhs_b_velz(c, ivel, alpha)) return e;
   const ScaledAbc A = scaled_abc(c);
   LAUNCH(c, k_scale_abc, dim3((n3 + 63) / 64), dim3(64), 0, c->stream, n3, alpha, s->d_av[ivel - 1], s->d_bv[ivel - 1], s->d_cv[ivel - 1], A.a, A.b, A.c);
-  return solve_field(c, V, c->f[CALES_U + ivel - 1], A.a, A.b, A.c, alpha);
+  return solve_field(c, V, s->sched_vel[ivel - 1], c->f[CALES_U + ivel - 1], A.a, A.b, A.c, alpha);
 }
