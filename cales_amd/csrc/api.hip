@@ -131,8 +131,26 @@ int ctx_upload(cales_ctx *c, real **p, const std::vector<real> &v) {
 }
 // the views of RedLayout: result slots and plane sums in the tail of staging buffer A once hooks are registered (the host all-reduces them in place), in d_red otherwise
 static void red_place(cales_ctx *c) {
-  c->res = c->comm.on ? c->comm.A + (c->comm.nbuf - c->red.comm_tail) : c->d_red;
+  c->res = c->comm.on ? c->comm.A + c->stage.tail : c->d_red;
   c->d_p1d = c->res + c->red.p1d;
+}
+// THE place where a change of the hooks reaches everything that depends on them (cales_create, cales_set_comm, cales_set_comm_overlap): Comm's record of what
+// they imply, the views of the reductions, the plan of a step (re-made by the next reader) and the schedules of the solves
+static int comm_changed(cales_ctx *c) {
+  Comm &m = c->comm;
+  const bool second = c->P > 1 && m.on && c->comm_stream;
+  m.halo_second_stream = second && m.halo_s; m.a2a_second_stream = second && m.a2a_part;
+  m.has_lo = c->per_y || c->rank > 0; m.has_hi = c->per_y || c->rank < c->P - 1;
+  red_place(c);
+  c->plan.valid = false;
+  return solver_comm_changed(c);
+}
+// n reals at the head of staging buffer A for a caller between two exchanges: below the tail, and after whatever the second stream still does with the buffer
+real *stage_borrow(cales_ctx *c, int64_t n) {
+  if (require_hooks(c)) return nullptr;
+  if (n > c->stage.borrow) { c->err = "staging buffer too small for the " + std::to_string(n) + " reals a caller borrows"; return nullptr; }
+  if (c->comm_stream && stream_after(c, c->stream, c->comm_stream)) return nullptr;
+  return c->comm.A;
 }
 static int upload_bound(cales_ctx *c, DBound &b, std::vector<real> h[3]) {
   return ctx_upload(c, &b.x, h[0]) || ctx_upload(c, &b.y, h[1]) || ctx_upload(c, &b.z, h[2]);
@@ -271,7 +289,6 @@ int cales_create(const cales_case *cs, void *stream, cales_ctx **out) {
   for (int q = 0; q < 3; ++q) if (vel_field(&c->f2[q])) return fail(9);
   c->red = RedLayout::of(n3);
   if (ctx_alloc(c, &c->d_red, (size_t)c->red.total) || ctx_alloc(c, &c->d_force, 8)) return fail(10);
-  red_place(c);
   if (ctx_alloc_pinned(c, &c->h_red, RedLayout::NHOST)) return fail(11);
   // sgs scratch (sgs.f90:70-83,154-171)
   if (c->C.sgstype >= 1) {
@@ -290,6 +307,8 @@ int cales_create(const cales_case *cs, void *stream, cales_ctx **out) {
   }
   { hipDeviceProp_t pr; int dev = 0; if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&pr, dev) == hipSuccess) c->ncu = pr.multiProcessorCount; }      // (before solver_setup: its schedule counts on it)
   if (solver_setup(c)) return fail(14);
+  c->stage = StageLayout::of(c->g.s1, n3, c->n[1], c->cw, P, c->red);      // (the mode columns per rank are the solver's)
+  if (comm_changed(c)) return fail(14);      // no hooks yet: the reductions in d_red, the solves' schedules without staging buffers
   if (sgs_setup_launches(c)) return fail(14);
   mom_setup(c);
   if (hipStreamSynchronize(c->stream) != hipSuccess) { c->err = "sync failed"; return fail(15); }
@@ -488,7 +507,7 @@ static bool fold_correc_possible(const cales_ctx *c) {
 static void make_plan(cales_ctx *c) {
   StepPlan pl;
   pl.valid = true;
-  pl.in_visct_zero = c->visct_zero; pl.in_sgs_first = c->sgs_first; pl.in_comm_on = c->comm.on; pl.in_overlap = c->comm_stream != nullptr;
+  pl.in_visct_zero = c->visct_zero; pl.in_sgs_first = c->sgs_first;
   const Flags &fl = c->fl;
   pl.any_wm = any_wm(c);
   // (fuse_fill: the transform then also sums the bulk means of the forced components, whose increment only the correction kernel needs)
@@ -537,7 +556,7 @@ static void make_plan(cales_ctx *c) {
 }
 static const StepPlan &current_plan(cales_ctx *c) {
   const StepPlan &pl = c->plan;
-  if (!pl.valid || pl.in_visct_zero != c->visct_zero || pl.in_sgs_first != c->sgs_first || pl.in_comm_on != c->comm.on || pl.in_overlap != (c->comm_stream != nullptr)) make_plan(c);
+  if (!pl.valid || pl.in_visct_zero != c->visct_zero || pl.in_sgs_first != c->sgs_first) make_plan(c);
   return c->plan;
 }
 int cales_describe_plan(cales_ctx *c, char *buf, int buflen) {
@@ -558,7 +577,7 @@ int cales_describe_plan(cales_ctx *c, char *buf, int buflen) {
   s += std::string(";solver=") + solver_path_name(c);
   if (c->C.impdiff == 1) for (int iv = 0; iv < 3; ++iv) s += std::string(";helmholtz_") + "uvw"[iv] + "=" + helmholtz_path_name(c, iv);
   if (c->P > 1) s += ";mode_columns_per_rank=" + std::to_string(solver_mode_columns(c));      // of the pressure solve (padded to whole 128-B lines where that costs 6 % or less: solver_setup)
-  s += ";ranks=" + std::to_string(c->P) + ";exchanges=" + (c->P == 1 ? "none" : !c->comm.on ? "unset" : (c->comm_stream && (c->comm.halo_s || c->comm.a2a_part)) ? "second_stream" : "in_order");
+  s += ";ranks=" + std::to_string(c->P) + ";exchanges=" + (c->P == 1 ? "none" : !c->comm.on ? "unset" : (c->comm.halo_second_stream || c->comm.a2a_second_stream) ? "second_stream" : "in_order");
   std::snprintf(buf, buflen, "%s", s.c_str());
   return (int)s.size() < buflen ? 0 : 2;      // 2: truncated
 }
@@ -614,8 +633,8 @@ static int step_body(cales_ctx *c, real dt) {
       HaloBatch rows; if (pl.fold_rows2) b.collect = &rows;
       if (int e = op_bounduvw(c, VelSet::state, 1, 0, b)) return e;
       if (pl.fold_rows2) {
-        if (int e = halo_y_rows(c, 3, c->f + CALES_U, 2, b)) return e;
-        if (int e = halo_flush_deferred(c, rows, false)) return e;
+        if (int e = halo_rows(c, 3, c->f + CALES_U, HaloRows::second_rows, b)) return e;
+        if (int e = halo_flush(c, rows, false)) return e;
       } }
     if (!pl.fuse_fill) { if (int e = op_fillps(c, dtrki)) return e; if (int e = op_updt_rhs_b(c)) return e; }
     if (int e = op_solver(c, pl.fuse_fill ? FusedFill{dtrki, pl.mean_mask} : FusedFill())) return e;
@@ -625,9 +644,9 @@ static int step_body(cales_ctx *c, real dt) {
       HaloBatch rows; BcCall b; b.collect = &rows;
       real *one[1] = {c->f[CALES_PP]};
       if (int e = op_boundp(c, c->f[CALES_PP], 0, b)) return e;
-      if (int e = halo_y_rows(c, 1, one, 2, b)) return e;
-      if (int e = halo_y_rows(c, 1, one, 3, b)) return e;
-      if (int e = halo_flush_deferred(c, rows, false)) return e;
+      if (int e = halo_rows(c, 1, one, HaloRows::second_rows, b)) return e;
+      if (int e = halo_rows(c, 1, one, HaloRows::third_rows, b)) return e;
+      if (int e = halo_flush(c, rows, false)) return e;
     } else
     if (pl.fold_correc && c->P > 1) {
       // the folded projection corrects v in the ghost row n2+1 too and needs pp one row further out: row 2 of every slab goes to row 1 of pp's companion
@@ -670,21 +689,17 @@ int cales_get_dpdl(cales_ctx *c, real dpdl[3]) {
 
 // ------------------------------------------------------------------------------------------ multi-GPU hooks
 int cales_comm_buffer_doubles(const cales_ctx *c, int64_t *n) {
-  const int64_t a2a = 2 * (int64_t)c->P * c->n[2] * c->n[1] * c->cw;                 // [peer][k][jl][mm] complex
-  const int64_t halo = 4 * 16 * (int64_t)c->g.s1 * (c->n[2] + 2);                    // lo|hi x up to 16 field planes (send in A, recv in B)
-  *n = std::max(a2a, halo) + c->red.comm_tail;
+  *n = c->stage.total;      // (StageLayout, common.hpp)
   return 0;
 }
 int cales_set_comm(cales_ctx *c, cales_halo_cb halo, cales_alltoall_cb a2a, cales_allreduce_cb allred, void *user,
                    real *bufA, real *bufB, int64_t nbuf) {
-  int64_t need = 0; cales_comm_buffer_doubles(c, &need);
-  if (!halo || !a2a || !allred || !bufA || !bufB || nbuf < need) { c->err = "cales_set_comm: missing callback/buffer or buffers too small"; return 1; }
+  if (!halo || !a2a || !allred || !bufA || !bufB || nbuf < c->stage.total) { c->err = "cales_set_comm: missing callback/buffer or buffers too small"; return 1; }
   c->comm.halo = halo; c->comm.a2a = a2a; c->comm.allred = allred; c->comm.user = user;
   c->comm.A = bufA; c->comm.B = bufB; c->comm.nbuf = nbuf; c->comm.on = true;
   HIPCHK(c, hipMemsetAsync(bufA, 0, nbuf * sizeof(real), c->stream));
   HIPCHK(c, hipMemsetAsync(bufB, 0, nbuf * sizeof(real), c->stream));
-  red_place(c);      // the reduction results move into the tail of A, where the host can all-reduce them in place
-  return solver_comm_changed(c);
+  return comm_changed(c);      // (the reduction results move into the tail of A, where the host can all-reduce them in place)
 }
 int cales_set_comm_overlap(cales_ctx *c, cales_halo_s_cb halo_s, cales_alltoall_part_cb a2a_part) {
   if (!c->comm.on) { c->err = "cales_set_comm_overlap: call cales_set_comm first"; return 1; }
@@ -695,7 +710,7 @@ int cales_set_comm_overlap(cales_ctx *c, cales_halo_s_cb halo_s, cales_alltoall_
     HIPCHK(c, hipStreamCreateWithPriority(&c->comm_stream, hipStreamNonBlocking, greatest));
   }
   c->comm.halo_s = halo_s; c->comm.a2a_part = a2a_part;
-  return solver_comm_changed(c);
+  return comm_changed(c);
 }
 int cales_initflow_slab(const cales_case *cs, const char *inivel, int is_wallturb, real *u, real *v, real *w, real *p) {
   if (!cs || !inivel || !u || !v || !w || !p) return 1;

@@ -67,7 +67,7 @@ bool load_api() {
   return ok;
 }
 
-struct NativeComm { ncclComm_t comm = nullptr; real *A = nullptr, *B = nullptr; };
+struct NativeComm { ncclComm_t comm = nullptr; };      // (the staging buffers: Comm::A / B, the context's memory)
 
 #define NCHK(c, call)                                                                                     \
   do {                                                                                                    \
@@ -75,28 +75,23 @@ struct NativeComm { ncclComm_t comm = nullptr; real *A = nullptr, *B = nullptr; 
     if (r_ != ncclSuccess) { (c)->err = std::string("RCCL: ") + g_api.GetErrorString(r_) + " in " #call; return 1; } \
   } while (0)
 
-// y neighbours (MPI_PROC_NULL at a non-periodic end, src/initmpi.f90:201-204)
-inline void neighbours(const cales_ctx *c, int &lo, int &hi) {
-  lo = (c->per_y || c->rank > 0) ? (c->rank - 1 + c->P) % c->P : -1;
-  hi = (c->per_y || c->rank < c->P - 1) ? (c->rank + 1) % c->P : -1;
-}
-
 int native_halo_on(void *user, int64_t off_slo, int64_t off_shi, int64_t off_rlo, int64_t off_rhi, int64_t count, hipStream_t st) {
   cales_ctx *c = static_cast<cales_ctx *>(user);
   NativeComm *nc = static_cast<NativeComm *>(c->native_comm);
-  int lo, hi; neighbours(c, lo, hi);
+  const Comm &m = c->comm;
+  const int lo = m.has_lo ? (c->rank - 1 + c->P) % c->P : -1, hi = m.has_hi ? (c->rank + 1) % c->P : -1;      // y neighbours (Comm: which exist)
   // With two ranks and periodic y both neighbours are the same peer: the k-th send to a peer pairs with its k-th receive
   // from us, so "my lowest row" must be sent first and "its lowest row" (my upper ghost) received first.
   NCHK(c, g_api.GroupStart());
   // an error inside the group must still close it: an open group would queue every later collective of this thread for ever
   ncclResult_t rc = ncclSuccess;
   auto add = [&](ncclResult_t r) { if (rc == ncclSuccess) rc = r; };
-  if (lo >= 0) add(g_api.Send(nc->A + off_slo, (size_t)count, NCCL_REAL, lo, nc->comm, st));
+  if (lo >= 0) add(g_api.Send(m.A + off_slo, (size_t)count, NCCL_REAL, lo, nc->comm, st));
   if (hi >= 0) {
-    add(g_api.Recv(nc->B + off_rhi, (size_t)count, NCCL_REAL, hi, nc->comm, st));
-    add(g_api.Send(nc->A + off_shi, (size_t)count, NCCL_REAL, hi, nc->comm, st));
+    add(g_api.Recv(m.B + off_rhi, (size_t)count, NCCL_REAL, hi, nc->comm, st));
+    add(g_api.Send(m.A + off_shi, (size_t)count, NCCL_REAL, hi, nc->comm, st));
   }
-  if (lo >= 0) add(g_api.Recv(nc->B + off_rlo, (size_t)count, NCCL_REAL, lo, nc->comm, st));
+  if (lo >= 0) add(g_api.Recv(m.B + off_rlo, (size_t)count, NCCL_REAL, lo, nc->comm, st));
   add(g_api.GroupEnd());
   if (rc != ncclSuccess) { c->err = std::string("RCCL: ") + g_api.GetErrorString(rc) + " in the halo exchange"; return 1; }
   return 0;
@@ -112,7 +107,7 @@ int native_halo_s(void *user, int64_t off_slo, int64_t off_shi, int64_t off_rlo,
 int native_alltoall_part(void *user, int dir, int64_t peer_stride, int64_t off, int64_t count, void *stream) {
   cales_ctx *c = static_cast<cales_ctx *>(user);
   NativeComm *nc = static_cast<NativeComm *>(c->native_comm);
-  const real *src = dir == 0 ? nc->A : nc->B; real *dst = dir == 0 ? nc->B : nc->A;
+  const real *src = dir == 0 ? c->comm.A : c->comm.B; real *dst = dir == 0 ? c->comm.B : c->comm.A;
   hipStream_t st = static_cast<hipStream_t>(stream);
   NCHK(c, g_api.GroupStart());
   ncclResult_t rc = ncclSuccess;
@@ -129,7 +124,7 @@ int native_alltoall_part(void *user, int dir, int64_t peer_stride, int64_t off, 
 int native_alltoall(void *user, int dir, int64_t count) {
   cales_ctx *c = static_cast<cales_ctx *>(user);
   NativeComm *nc = static_cast<NativeComm *>(c->native_comm);
-  const real *src = dir == 0 ? nc->A : nc->B; real *dst = dir == 0 ? nc->B : nc->A;
+  const real *src = dir == 0 ? c->comm.A : c->comm.B; real *dst = dir == 0 ? c->comm.B : c->comm.A;
   NCHK(c, g_api.AllToAll(src, dst, (size_t)count, NCCL_REAL, nc->comm, c->stream));
   return 0;
 }
@@ -137,7 +132,7 @@ int native_allreduce(void *user, int64_t off, int64_t count, int op) {
   cales_ctx *c = static_cast<cales_ctx *>(user);
   NativeComm *nc = static_cast<NativeComm *>(c->native_comm);
   const ncclRedOp_t rop = op == 0 ? ncclSum : (op == 1 ? ncclMax : ncclMin);
-  NCHK(c, g_api.AllReduce(nc->A + off, nc->A + off, (size_t)count, NCCL_REAL, rop, nc->comm, c->stream));
+  NCHK(c, g_api.AllReduce(c->comm.A + off, c->comm.A + off, (size_t)count, NCCL_REAL, rop, nc->comm, c->stream));
   return 0;
 }
 }  // namespace
@@ -166,10 +161,10 @@ int cales_comm_init_rccl(cales_ctx *c, const void *id_in) {
   ncclUniqueId id; std::memcpy(&id, id_in, sizeof(id));
   const ncclResult_t r = g_api.CommInitRank(&nc->comm, c->P, id, c->rank);
   if (r != ncclSuccess) { c->err = std::string("ncclCommInitRank: ") + g_api.GetErrorString(r); delete nc; return 1; }
-  int64_t n = 0; cales_comm_buffer_doubles(c, &n);
+  const int64_t n = c->stage.total; real *A = nullptr, *B = nullptr;
   c->native_comm = nc;      // (from here on cales_destroy releases it)
-  if (ctx_alloc(c, &nc->A, (size_t)n, false) || ctx_alloc(c, &nc->B, (size_t)n, false)) return 1;
-  if (int e = cales_set_comm(c, native_halo, native_alltoall, native_allreduce, c, nc->A, nc->B, n)) return e;
+  if (ctx_alloc(c, &A, (size_t)n, false) || ctx_alloc(c, &B, (size_t)n, false)) return 1;
+  if (int e = cales_set_comm(c, native_halo, native_alltoall, native_allreduce, c, A, B, n)) return e;
   return cales_set_comm_overlap(c, native_halo_s, native_alltoall_part);
 }
 

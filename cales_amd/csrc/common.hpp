@@ -57,6 +57,10 @@ struct Comm {
   real *A = nullptr, *B = nullptr; int64_t nbuf = 0;   // two device staging buffers owned by the host (doubles)
   bool on = false;
   cales_halo_s_cb halo_s = nullptr; cales_alltoall_part_cb a2a_part = nullptr;   // exchanges on the second stream (cales_set_comm_overlap)
+  // What the registered hooks imply, fixed by comm_changed (api.hip) at the end of cales_set_comm / cales_set_comm_overlap and only read after: which
+  // exchanges go on the second stream (its hook and the stream both exist), and which y neighbours this slab has (MPI_PROC_NULL at a non-periodic
+  // end, src/initmpi.f90:201-204)
+  bool halo_second_stream = false, a2a_second_stream = false, has_lo = false, has_hi = false;
 };
 
 // Where the spectral (after the x transform) data of the Poisson solve lives.
@@ -125,7 +129,7 @@ struct Flags {
 // golden tests assert it next to the profile counters.
 struct StepPlan {
   bool valid = false;
-  bool in_visct_zero = false, in_sgs_first = false, in_comm_on = false, in_overlap = false;      // the state the plan was made from
+  bool in_visct_zero = false, in_sgs_first = false;      // the state the plan was made from (a change of the hooks invalidates it: comm_changed)
   bool xskip = false;            // periodic x: the step's kernels wrap around, the x ghost columns are left alone until somebody else reads them
   bool fold_correc = false;      // dynamic model: projection + pressure update inside the strain-rate pass of the substep's cmpt_sgs (k_corr_strain_tile)
   bool fold_rows2 = false;       // ... on several slabs with TWO ghost rows of the prediction (three of pp): the pass also forms the ghost rows of everything it writes,
@@ -213,9 +217,10 @@ struct BcPath {
   int vel_fcn = 0;
   bool ride[2] = {false, false};      // cell-centred fields with the pressure / sgs set can join the velocity's launch (BcCall::ride)
 };
-// y-halo rows collected over several ghost-cell calls and exchanged in ONE message by halo_flush_deferred: a local of the caller (sixteen planes are what
-// the staging buffers hold). kind: 0 a field, 1 a pair field, 2 / 3 the second / third rows of a field into its first / second companion
-struct HaloBatch { int n = 0; real *p[16]; unsigned char kind[16]; };
+// What travels between y slabs for one field: its rows 1 / n2 into the neighbours' ghost rows (a field; a pair field, rows twice as long), or its rows
+// 2 / n2-1 (3 / n2-2) into the ghost rows of the neighbours' first (second) companion field (cales_ctx::vel_comp)
+enum class HaloRows : unsigned char { field, pair, second_rows, third_rows };
+struct HaloBatch;      // (below, with StageLayout)
 // What a caller inside cales_step asks of ONE call of a ghost-cell operator; default-constructed: the operator as the C-ABI entry runs it. The operator
 // turns it, with BcPath's tables, into the rules of the call (bc_rule) and the exchange that goes with them
 struct BcCall {
@@ -226,7 +231,7 @@ struct BcCall {
   // the ghost rows already hold the neighbours' rows, no slab exchange (end-of-step refresh: only the x ghost columns are stale, the rows the neighbours
   // sent are complete but for their two ends, which the local copies fill; folded strain-rate pass: it formed the ghost rows itself)
   bool rows_current = false;
-  HaloBatch *collect = nullptr;  // the y-halo rows are collected here instead of exchanged (the caller flushes: halo_flush_deferred)
+  HaloBatch *collect = nullptr;  // the y-halo rows are collected here instead of exchanged (the caller flushes: halo_flush)
   // corrected view (StepPlan::fold_mom): the fields hold the prediction, sources that are interior cells are read as (u* + f) - dtrk grad(pp); fmask: the
   // components whose bulk-forcing increment the pending projection adds
   real view_dtrk = 0.; int view_fmask = 0;
@@ -255,6 +260,30 @@ struct RedLayout {
     return L;
   }
 };
+// Where the regions of the two staging buffers live (Comm::A and Comm::B: the host's memory, `total` reals each), worked out once by cales_create
+// and only read after. Halo exchange: the lo | hi rows that leave at the head of A, those that arrive at the head of B, n planes each (blocks). All-to-all: P peer
+// blocks from the head of both, slabs in A, mode blocks in B. Between two exchanges a caller may borrow the head of A (stage_borrow). The tail of A holds the
+// reductions' results and plane sums (RedLayout::comm_tail), and no exchange or borrower reaches it.
+struct StageLayout {
+  static constexpr int MAXPLANES = 16;      // row planes of one block (lo or hi) of one halo exchange; a pair field takes two
+  // the total counts FOUR blocks of MAXPLANES planes per buffer where the offsets use two (send and receive sit in different buffers): twice the room the
+  // halo region needs, kept because the hosts size their memory by the total
+  static constexpr int HALO_SIZED_FOR = 2;
+  int64_t plane = 0;       // reals of one row plane, x and z ghost cells included: s1 (n3 + 2)
+  int64_t halo = 0;        // the halo region [0, halo) of A (send) and of B (receive): two blocks of MAXPLANES planes
+  int64_t a2a = 0;         // all-to-all capacity: reals of the P peer blocks of n3 n2l cw complex values
+  int64_t borrow = 0;      // [0, borrow) of A may be borrowed between two exchanges: everything below the tail
+  int64_t tail = 0, total = 0;      // offset of the tail (RedLayout::comm_tail reals) | reals of each buffer (cales_comm_buffer_doubles)
+  struct Blocks { int64_t lo, hi, count; };      // offsets of the lo | hi block of an exchange of n planes (the same in A and B) and the reals of each
+  Blocks blocks(int n) const { return Blocks{0, n * plane, n * plane}; }
+  static StageLayout of(int s1, int n3, int n2l, int cw, int P, const RedLayout &red) {
+    StageLayout L; L.plane = (int64_t)s1 * (n3 + 2); L.halo = 2 * MAXPLANES * L.plane; L.a2a = 2 * (int64_t)P * n3 * n2l * cw;
+    L.tail = L.borrow = L.a2a > HALO_SIZED_FOR * L.halo ? L.a2a : HALO_SIZED_FOR * L.halo; L.total = L.tail + red.comm_tail;
+    return L;
+  }
+};
+// y-halo rows collected over several ghost-cell calls and exchanged in ONE message by halo_flush: a local of the caller
+struct HaloBatch { int n = 0; real *p[StageLayout::MAXPLANES]; HaloRows kind[StageLayout::MAXPLANES]; };
 constexpr real RKPAR[3][2] = {{32. / 60., 0.}, {25. / 60., -17. / 60.}, {45. / 60., -25. / 60.}};      // the three substeps' coefficients, param.f90:27-29
 struct KernelStat { std::string name; int64_t calls = 0; real ms = 0.; };
 struct Solver;      // k_solver.hip
@@ -306,6 +335,7 @@ struct cales_ctx {
   // decomposition
   int P = 1, rank = 0; bool per_y = true; int cw = 0;      // cw: complex mode columns per rank (padded)
   Comm comm;
+  StageLayout stage;      // the regions of comm.A / comm.B (StageLayout above)
   // profiling
   bool prof = false;
   std::vector<KernelStat> stats;
@@ -422,8 +452,10 @@ void bc_setup(cales_ctx *c);                // BcPath (needs is_bound, cbcvel, t
 int op_bounduvw(cales_ctx *c, VelSet set, int is_updt_wm, int is_correc, const BcCall &b = BcCall());      // the set's fields are read at call time (the f / f2 swaps)
 int op_boundp(cales_ctx *c, real *p, int which, const BcCall &b = BcCall());
 int op_boundp_multi(cales_ctx *c, int nf, real **p, int which, const BcCall &b = BcCall());
-int halo_flush_deferred(cales_ctx *c, HaloBatch &rows, bool overlapped = true);
-int halo_y_rows(cales_ctx *c, int nf, real **flds, int kind, const BcCall &b = BcCall());      // kind 2 / 3: rows 2, n2-1 (3, n2-2) of the neighbours into the ghost rows of the fields' first (second) companions
+// the two entries of the slab exchange of rows (k_bound.hip): the rows of nf fields of one kind into the caller's batch (BcCall::collect) or exchanged now --
+// vcomp: the corrected-view components of a call that carries a view, with the "now" case only --, and a batch flushed in order or on the second stream
+int halo_rows(cales_ctx *c, int nf, real **flds, HaloRows kind, const BcCall &b, const unsigned char *vcomp = nullptr);
+int halo_flush(cales_ctx *c, HaloBatch &rows, bool second_stream);
 int op_mom(cales_ctx *c);
 int op_rk(cales_ctx *c, int irk, real dt, const RkOpts &o = RkOpts());
 int op_rk_par(cales_ctx *c, real rkpar1, real rkpar2, real dt, const RkOpts &o = RkOpts());
@@ -432,7 +464,8 @@ void mom_setup(cales_ctx *c);               // MomPath (needs ncu)
 int op_bulk_forcing(cales_ctx *c);
 int op_bulk_mean_dev(cales_ctx *c, const real *p, int c_or_f);   // result to res[RedLayout::BULK_MEAN]
 real *red_partials(cales_ctx *c, size_t need);      // room for `need` partial sums (RedLayout); nullptr and c->err where the layout has less
-int allreduce_dev(cales_ctx *c, real *p, int64_t count, int op);      // [p, p + count) over the slabs, in place (op: 0 sum, 1 max): nothing on one rank; the range must lie in staging buffer A
+int allreduce_dev(cales_ctx *c, real *p, int64_t count, int op);      // [p, p + count) over the slabs, in place (op: 0 sum, 1 max): nothing on one rank; the range must lie in the tail of staging buffer A or in its borrowed head
+real *stage_borrow(cales_ctx *c, int64_t n);      // n reals at the head of staging buffer A, free of every exchange queued so far (StageLayout::borrow); nullptr and c->err otherwise
 int read_back(cales_ctx *c, real *host, const real *dev, size_t n);      // n reals to the host on the context's stream, complete on return
 int op_zero_force(cales_ctx *c, int first, int last);      // d_force[first, last) = 0 (f(3), dpdl(3))
 int op_fillps(cales_ctx *c, real dtrki);
@@ -466,7 +499,7 @@ int op_xwrap_zghost(cales_ctx *c, int nf, real **f);      // periodic copy of th
 int op_chkdt(cales_ctx *c, real *dtmax);
 int op_chkdiv(cales_ctx *c, real *divtot, real *divmax);
 int solver_setup(cales_ctx *c);
-int solver_comm_changed(cales_ctx *c);      // cales_set_comm, cales_set_comm_overlap: the staging buffers and the exchange form of the solves' schedules
+int solver_comm_changed(cales_ctx *c);      // comm_changed (api.hip): the staging buffers and the exchange form of the solves' schedules
 void solver_teardown(cales_ctx *c);      // (the host-side struct; its tables go with the context's memory)
 
 // XCD-aware block order for the one-plane-per-block stencil kernels (grid = x tiles, y tiles, z planes).
@@ -605,6 +638,11 @@ static inline bool wm_samples_ghost(const cales_ctx *c) {
     if (!(first < h)) return true;
   }
   return false;
+}
+// several slabs need the hooks: THE sentence of every call that finds none (who: the caller's prefix)
+static inline int require_hooks(cales_ctx *c, const char *who = "") {
+  if (!c->comm.on) c->err = std::string(who) + "nranks > 1 but no communication hooks registered (cales_set_comm)";
+  return c->comm.on ? 0 : 1;
 }
 static inline int bc_skipped(const cales_ctx *c, const BcCall &b) { return b.skip | (c->step_xskip ? 1 : 0); }
 static inline dim3 grid3(int nx, int ny, int nz, dim3 b) { return dim3((nx + b.x - 1) / b.x, (ny + b.y - 1) / b.y, (nz + b.z - 1) / b.z); }

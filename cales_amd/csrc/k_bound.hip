@@ -274,7 +274,8 @@ void bc_setup(cales_ctx *c) {
 
 // y-slab neighbours (bound.f90:619-696 for idir = 2): pack the first/last interior rows of nf fields into the
 // staging buffer A, let the host exchange them, unpack into the ghost rows. Planes include the x/z ghosts.
-struct HaloFields { int nf; real *p[16]; unsigned char wide[16]; int off[16]; unsigned char vcomp[16]; unsigned char rofs[16]; real *dst[16]; CorrView V; };      // rofs / dst: rows 1 + rofs and n2 - rofs leave, into the ghost rows of dst (a companion field; rofs = 0: the field itself)      // vcomp != 0: the rows that leave are read through the corrected view      // wide: a pair field (rows twice as long); off: first staging plane of the field, in planes of s1 (n3+2) values
+constexpr int HP = StageLayout::MAXPLANES;
+struct HaloFields { int nf; real *p[HP]; unsigned char wide[HP]; int off[HP]; unsigned char vcomp[HP]; unsigned char rofs[HP]; real *dst[HP]; CorrView V; };      // rofs / dst: rows 1 + rofs and n2 - rofs leave, into the ghost rows of dst (a companion field; rofs = 0: the field itself)      // vcomp != 0: the rows that leave are read through the corrected view      // wide: a pair field (rows twice as long); off: first staging plane of the field, in planes of s1 (n3+2) values
 // x ghost columns of the two z ghost planes, rows 0..n2+1: the corners the velocity update after the projection leaves alone (bounduvw with
 // is_correc does not touch the z ghost planes of w, and the periodic copies of the step's earlier calls were skipped: cales_step, step_xskip)
 __global__ __launch_bounds__(256) void k_xwrap_zghost(Geom g, HaloFields H) {
@@ -302,66 +303,63 @@ __global__ __launch_bounds__(256) void k_unpack_y(Geom g, HaloFields H, const re
 // A field of PAIRS (two values per cell, SgsPath::pair) is, for every operation that copies whole rows or planes, a field of twice the width:
 // 2 (n1 + 2) values per row, pitches doubled. Its x ghost "columns" mean nothing in that view -- the callers skip direction x.
 static Geom wide_geom(const cales_ctx *c) { Geom g = c->g; g.n1 = 2 * c->g.n1 + 2; g.s1 = 2 * c->g.s1; g.s12 = 2 * c->g.s12; return g; }
-// kind[q]: 0 a field, 1 a pair field, 2 / 3 the second / third rows of a field into its first / second companion (nullptr: fields); vcomp[q] != 0 in a
-// call that carries a corrected view: the rows of field q that leave are those of this component of the projected velocity (nullptr: none)
-static int halo_y_on(cales_ctx *c, const BcCall &b, int nf, real **flds, hipStream_t st, bool overlapped, const unsigned char *kinds = nullptr, const unsigned char *vcomp = nullptr) {
-  const Geom &G = c->g;
+// the staging planes a field of this kind takes in each block, and the companion whose ghost rows its rows arrive in (0: the field's own)
+static int halo_planes(HaloRows k) { return k == HaloRows::pair ? 2 : 1; }
+static int halo_companion(HaloRows k) { return k == HaloRows::second_rows ? 1 : k == HaloRows::third_rows ? 2 : 0; }
+// ONE exchange of the rows of nf entries: pack into the lo | hi blocks of A, the hook -- in order on the context's stream, or its second-stream form on the
+// second stream --, unpack the blocks of B into the ghost rows (StageLayout::blocks). vcomp[q] != 0 in a call that carries a corrected view: the rows of field q
+// that leave are those of this component of the projected velocity (nullptr: none)
+static int halo_exchange(cales_ctx *c, int nf, real *const *flds, const HaloRows *kinds, bool second_stream, const BcCall &b = BcCall(), const unsigned char *vcomp = nullptr) {
+  const Geom &G = c->g; const Comm &m = c->comm;
   HaloFields H; H.nf = nf; int planes = 0, anyw = 0;
-  for (int q = 0; q < nf; ++q) {
-    const int kind = kinds ? kinds[q] : 0;
-    H.p[q] = flds[q]; H.wide[q] = kind == 1; H.off[q] = planes; planes += 1 + H.wide[q]; anyw |= H.wide[q]; H.vcomp[q] = 0;
-    H.rofs[q] = kind >= 2 ? (unsigned char)(kind - 1) : 0; H.dst[q] = kind >= 2 ? flds[q] + (size_t)(kind - 1) * c->comp_one : flds[q];
+  for (int q = 0; q < nf; ++q) planes += halo_planes(kinds[q]);
+  if (planes > StageLayout::MAXPLANES) { c->err = "halo staging buffer too small"; return 1; }      // (the arrays of HaloFields and the blocks of the layout)
+  for (int q = 0, at = 0; q < nf; at += halo_planes(kinds[q++])) {
+    const int comp = halo_companion(kinds[q]);
+    H.p[q] = flds[q]; H.wide[q] = kinds[q] == HaloRows::pair; H.off[q] = at; anyw |= H.wide[q]; H.vcomp[q] = 0;
+    H.rofs[q] = (unsigned char)comp; H.dst[q] = flds[q] + (size_t)comp * c->comp_one;
   }
   if (b.view_dtrk != 0. && vcomp) {      // op_bounduvw through the corrected view
     H.V = corr_view(c, b);
     for (int q = 0; q < nf; ++q) if (!H.rofs[q]) H.vcomp[q] = vcomp[q];
   }
-  const int64_t cnt = (int64_t)G.s1 * (c->n[2] + 2) * planes;
-  if (4 * cnt > c->comm.nbuf) { c->err = "halo staging buffer too small"; return 1; }
+  const StageLayout::Blocks S = c->stage.blocks(planes);
+  const hipStream_t st = second_stream ? c->comm_stream : c->stream;
   dim3 blk(64, 4, 1), gr(((G.s1 << anyw) + 63) / 64, (c->n[2] + 2 + 3) / 4, nf);
-  LAUNCH(c, k_pack_y, gr, blk, 0, st, G, H, c->comm.A, c->comm.A + cnt);
+  LAUNCH(c, k_pack_y, gr, blk, 0, st, G, H, m.A + S.lo, m.A + S.hi);
   { ProfScope ps(c, "halo_exchange", st);
-    const int rc = overlapped ? c->comm.halo_s(c->comm.user, 0, cnt, 0, cnt, cnt, (void *)st) : c->comm.halo(c->comm.user, 0, cnt, 0, cnt, cnt);
+    const int rc = second_stream ? m.halo_s(m.user, S.lo, S.hi, S.lo, S.hi, S.count, (void *)st) : m.halo(m.user, S.lo, S.hi, S.lo, S.hi, S.count);
     if (rc) { c->err = "halo callback failed"; return 1; } }
-  const int has_lo = (c->per_y || c->rank > 0) ? 1 : 0, has_hi = (c->per_y || c->rank < c->P - 1) ? 1 : 0;
-  LAUNCH(c, k_unpack_y, gr, blk, 0, st, G, H, c->comm.B, c->comm.B + cnt, has_lo, has_hi);
+  LAUNCH(c, k_unpack_y, gr, blk, 0, st, G, H, m.B + S.lo, m.B + S.hi, m.has_lo ? 1 : 0, m.has_hi ? 1 : 0);
   LAUNCHCHK(c);
   return 0;
 }
-// the rows of nf fields of one kind: into the caller's batch (BcCall::collect, exchanged later by halo_flush_deferred) or exchanged now
-// (a batch is flushed without a view: vcomp goes with an exchange made now)
-static int halo_y_kind(cales_ctx *c, const BcCall &b, int nf, real **flds, int kind, const unsigned char *vcomp = nullptr) {
+// The rows of nf fields of one kind: nothing where the ghost rows already hold them (BcCall::rows_current), into the caller's batch (BcCall::collect, exchanged
+// later by halo_flush -- without a view: vcomp goes with an exchange made now), or exchanged now, in order
+int halo_rows(cales_ctx *c, int nf, real **flds, HaloRows kind, const BcCall &b, const unsigned char *vcomp) {
+  if (int e = require_hooks(c)) return e;
+  if (halo_companion(kind) && !c->comp_one) { c->err = "halo_rows: no companion fields"; return 1; }
+  if (b.rows_current) return 0;
+  if ((b.collect ? b.collect->n : 0) + nf > StageLayout::MAXPLANES) { c->err = "halo batch full"; return 1; }
   if (b.collect) {
     HaloBatch &R = *b.collect;
-    if (R.n + nf > 16) { c->err = "halo batch full"; return 1; }
-    for (int q = 0; q < nf; ++q) { R.p[R.n] = flds[q]; R.kind[R.n++] = (unsigned char)kind; }
+    for (int q = 0; q < nf; ++q) { R.p[R.n] = flds[q]; R.kind[R.n++] = kind; }
     return 0;
   }
-  unsigned char w[16]; for (int q = 0; q < nf && q < 16; ++q) w[q] = (unsigned char)kind;
-  return halo_y_on(c, b, nf, flds, c->stream, false, w, vcomp);
+  HaloRows k[StageLayout::MAXPLANES]; for (int q = 0; q < nf; ++q) k[q] = kind;
+  return halo_exchange(c, nf, flds, k, false, b, vcomp);
 }
-int halo_y_rows(cales_ctx *c, int nf, real **flds, int kind, const BcCall &b) {
-  if (!c->comm.on) { c->err = "nranks > 1 but no communication hooks registered (cales_set_comm)"; return 1; }
-  if (!c->comp_one || kind < 2 || kind > 3) { c->err = "halo_y_rows: no companion fields"; return 1; }
-  return halo_y_kind(c, b, nf, flds, kind);
-}
-static int halo_y_comm(cales_ctx *c, const BcCall &b, int nf, real **flds, int kind, const unsigned char *vcomp) {
-  if (!c->comm.on) { c->err = "nranks > 1 but no communication hooks registered (cales_set_comm)"; return 1; }
-  if (b.rows_current) return 0;
-  return halo_y_kind(c, b, nf, flds, kind, vcomp);
-}
-// The y-halo rows of the fields collected in `rows` (BcCall::collect) travel on the second stream, after everything queued on the
-// context's stream so far (their ghost-cell kernels included: what those wrote into the ghost rows is overwritten by the rows
-// that arrive, whose own x/z ghost cells the neighbour has already set -- the same values the in-order sequence produces).
-// The caller makes the context's stream wait (stream_after) before the first kernel that reads those ghost rows.
-// overlapped = false: the same batching in order on the context's stream -- one exchange for up to twelve fields instead of one per call.
-int halo_flush_deferred(cales_ctx *c, HaloBatch &rows, bool overlapped) {
+// The rows collected in `rows` (BcCall::collect), as many fields per exchange as the staging buffers hold. second_stream: they travel on the second stream,
+// after everything queued on the context's stream so far (their ghost-cell kernels included: what those wrote into the ghost rows is overwritten by the rows
+// that arrive, whose own x/z ghost cells the neighbour has already set -- the same values the in-order sequence produces), and the caller makes the
+// context's stream wait (stream_after) before the first kernel that reads those ghost rows. Otherwise the same batching in order on the context's stream
+int halo_flush(cales_ctx *c, HaloBatch &rows, bool second_stream) {
   if (!rows.n) return 0;
-  if (overlapped) { if (int e = stream_after(c, c->comm_stream, c->stream)) return e; }
-  for (int q0 = 0; q0 < rows.n;) {      // as many fields per exchange as the staging buffers hold: sixteen planes, a pair field takes two
+  if (second_stream) { if (int e = stream_after(c, c->comm_stream, c->stream)) return e; }
+  for (int q0 = 0; q0 < rows.n;) {
     int nf = 0, planes = 0;
-    while (q0 + nf < rows.n && planes + 1 + (rows.kind[q0 + nf] == 1) <= 16) { planes += 1 + (rows.kind[q0 + nf] == 1); ++nf; }
-    if (int e = halo_y_on(c, BcCall(), nf, rows.p + q0, overlapped ? c->comm_stream : c->stream, overlapped, rows.kind + q0)) return e;
+    while (q0 + nf < rows.n && planes + halo_planes(rows.kind[q0 + nf]) <= StageLayout::MAXPLANES) planes += halo_planes(rows.kind[q0 + nf++]);
+    if (int e = halo_exchange(c, nf, rows.p + q0, rows.kind + q0, second_stream)) return e;
     q0 += nf;
   }
   rows.n = 0;
@@ -446,7 +444,7 @@ static int bc_update(cales_ctx *c, int ne, const BcEntry *e, BcForm form, const 
   if (c->P > 1 && !u.wm_faces) {
     real *p[8]; unsigned char vc[8];
     for (int q = 0; q < ne; ++q) { p[q] = e[q].p; vc[q] = (unsigned char)e[q].vcomp; }
-    if (int er = halo_y_comm(c, b, ne, p, u.wide ? 1 : 0, vc)) return er;
+    if (int er = halo_rows(c, ne, p, u.wide ? HaloRows::pair : HaloRows::field, b, vc)) return er;
   }
   // corrected view (cales_step, fold_mom): the fields hold the prediction, the ghost cells receive the values of the projected velocity
   const CorrView V = b.view_dtrk != 0. ? corr_view(c, b) : CorrView{};

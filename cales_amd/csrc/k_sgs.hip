@@ -1548,7 +1548,7 @@ static int dsmag_fast(cales_ctx *c, const SgsFold *fold, bool *visct_ghosts_done
   // kernels wrap around instead; an x ghost update touches four cache lines per row for two values), and the z ghost planes
   // of the quantities the wall rule covers are never read (skipz).
   // several ranks with the second stream: the y-halo rows of the twelve scratch fields travel while the interior tiles of the last pass run
-  const bool overlap = c->P > 1 && c->comm.halo_s && c->comm_stream && !ext;      // (ext: no row of these fields travels)
+  const bool overlap = c->comm.halo_second_stream && !ext;      // (ext: no row of these fields travels)
   // several ranks: ONE exchange for the y-halo rows of all these fields (six |S|Sij, three filtered velocities, v_c, and |S| itself in the lazy form
   // inside cales_step) instead of one per ghost-cell call; their ghost-cell kernels run first, the rows that then arrive carry the neighbour's
   // x/z ghost cells
@@ -1571,7 +1571,7 @@ static int dsmag_fast(cales_ctx *c, const SgsFold *fold, bool *visct_ghosts_done
     BcCall bv = bc; bv.skip = 0;
     if (int e = op_boundp(c, visct, 1, bv)) return e;
     *visct_ghosts_done = true; }
-  if (int e = halo_flush_deferred(c, rows, overlap)) return e;
+  if (int e = halo_flush(c, rows, overlap)) return e;
   LijMijArgs L;
   L.uc[0] = P.ucf ? f[CALES_U] : c->uc; L.uc[1] = P.ucf ? f[CALES_V] : c->vc; L.uc[2] = P.ucf ? f[CALES_W] : c->wc; L.uf[0] = c->uf; L.uf[1] = c->vf; L.uf[2] = c->wf;
   L.vcg = c->vc; L.perz = P.perz; L.xwrap = c->step_xskip ? 1 : 0;
@@ -1651,10 +1651,7 @@ static int wall_shear_y_planes(cales_ctx *c, int wylo, int wyhi, const real **ou
   const size_t cnt = (size_t)2 * (n[2] + 2) * c->g.s1;
   real *twy = c->wk[0];
   if (c->P > 1) {
-    if (!c->comm.on) { c->err = "nranks > 1 but no communication hooks registered (cales_set_comm)"; return 1; }
-    if ((int64_t)cnt > c->comm.nbuf - c->red.comm_tail) { c->err = "smag: staging buffer too small for the wall-shear planes"; return 1; }      // (the tail holds the reduction results)
-    twy = c->comm.A;
-    if (c->comm_stream) if (int e = stream_after(c, c->stream, c->comm_stream)) return e;      // nothing of an overlapped exchange may still use A
+    if (!(twy = stage_borrow(c, (int64_t)cnt))) return 1;
     HIPCHK(c, hipMemsetAsync(twy, 0, cnt * sizeof(real), c->stream));
   } else if (cnt > c->ntot) { c->err = "smag: wall-shear scratch too small"; return 1; }
   const int lo = wylo && ISB(c, 0, 2) ? 1 : 0, hi = wyhi && ISB(c, 1, 2) ? 1 : 0;

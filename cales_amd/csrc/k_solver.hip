@@ -2047,9 +2047,10 @@ static void tile_setup(cales_ctx *c, SolvePath &P, real *tab) {
   Z.persistent = !Z.PER && Z.NV == 1 && P.nz == 1024 && Z.ndbl % 16 == 0;      // full tiles of full chunks only (k_gaussel_tile_p)
   tile_attr(c, Z);
 }
-// ... and its schedule, for a path that is complete: from the path, the decomposition and the hooks registered so far
-static SolveSched solve_sched(const cales_ctx *c, const SolvePath &P) {
-  SolveSched D;
+// ... and its schedule, for a path that is complete: from the path, the decomposition and what the hooks registered so far imply (Comm). Refused where the P
+// peer blocks of the path's all-to-all would not fit what the staging buffers were sized for (StageLayout::a2a)
+static int solve_sched(cales_ctx *c, const SolvePath &P, SolveSched &D) {
+  D = SolveSched();
   const int *n = c->n, mh = n[0] / 2 + 1, n2g = c->C.ng[1], nh = c->C.ng[0] / 2, cw = P.cw, Rx8 = P.xrows, CB8 = P.ycols;
   const bool dist = c->P > 1, use8x = P.xk == XKernel::fft_x8, use8y = radix8_y(P.yk), use16y = P.yk == YKernel::fft_y16;
   if (dist) { D.slab_spec = reinterpret_cast<real2 *>(c->comm.A); D.mode_spec = reinterpret_cast<real2 *>(c->comm.B); }
@@ -2064,10 +2065,14 @@ static SolveSched solve_sched(const cales_ctx *c, const SolvePath &P) {
   // the next chunk and the y transforms of the previous one run on the context's stream (the reference's cuDecomp pipelined
   // transposes, src/initmpi.f90:94-139). Radix-8 periodic / Neumann-Neumann transforms only; everything else keeps the single exchange,
   // which is the same sequence with one chunk.
-  if (dist && c->comm.a2a_part && c->comm_stream && use8x && use8y) { if (n[2] % 4 == 0 && n[2] >= 32) D.nch = 4; else if (n[2] % 2 == 0 && n[2] >= 8) D.nch = 2; }
+  if (c->comm.a2a_second_stream && use8x && use8y) { if (n[2] % 4 == 0 && n[2] >= 32) D.nch = 4; else if (n[2] % 2 == 0 && n[2] >= 8) D.nch = 2; }
   const bool pipe = D.nch > 1;
   D.kpc = n[2] / D.nch; D.rows = (long)n[1] * D.kpc;
   D.a2a_stride = (int64_t)n[2] * n[1] * cw * 2; D.a2a_chunk = (int64_t)D.kpc * n[1] * cw * 2;
+  if (dist && c->P * D.a2a_stride > c->stage.a2a) {
+    c->err = "solver: an all-to-all of " + std::to_string(c->P) + " blocks of " + std::to_string(D.a2a_stride) + " reals does not fit the " + std::to_string(c->stage.a2a) + " the staging buffers were sized for";
+    return 1;
+  }
   // persistent blocks: several row groups / planes per block so that the register prefetch overlaps the transforms
   const long xgroups = (D.rows + Rx8 - 1) / Rx8;
   int xiters = 1; while (xiters < 8 && xgroups / (xiters * 2) >= 2048 / D.nch) xiters *= 2;
@@ -2093,15 +2098,15 @@ static SolveSched solve_sched(const cales_ctx *c, const SolvePath &P) {
       if (cost < best) { best = cost; D.ykc = kc; }
     }
   }
-  return D;
+  return 0;
 }
-// solver_setup, cales_set_comm, cales_set_comm_overlap: the schedules of the paths that exist, with the staging buffers and the second stream as they are now (a
-// velocity path built later finds them), and the partial sums of the bulk means sized with the pressure's: only a forward k_fft_x8 of a forced case sums any
+// comm_changed (api.hip; cales_create, cales_set_comm, cales_set_comm_overlap): the schedules of the paths that exist, with the staging buffers and the second stream
+// as they are now (a velocity path built later finds them), and the partial sums of the bulk means sized with the pressure's: only a forward k_fft_x8 of a forced case sums any
 int solver_comm_changed(cales_ctx *c) {
   Solver *s = c->solver;
   if (!s) return 0;
-  s->sched_pres = solve_sched(c, s->pres);
-  for (int iv = 0; iv < 3; ++iv) if (s->vel_state[iv] == 1) s->sched_vel[iv] = solve_sched(c, s->vel[iv]);
+  if (solve_sched(c, s->pres, s->sched_pres)) return 1;
+  for (int iv = 0; iv < 3; ++iv) if (s->vel_state[iv] == 1 && solve_sched(c, s->vel[iv], s->sched_vel[iv])) return 1;
   ctx_free(c, s->d_mpart); s->d_mpart = nullptr;
   const bool forced = c->C.is_forced[0] || c->C.is_forced[1] || c->C.is_forced[2];
   return (forced && s->pres.xk == XKernel::fft_x8) ? ctx_alloc(c, &s->d_mpart, 3 * (size_t)s->sched_pres.npart, false) : 0;
@@ -2218,8 +2223,7 @@ int solver_setup(cales_ctx *c) {
   if (upload_twiddles(c, 4 * n1, n1 / 2 + 1, &s.twy_post)) return 1;      // DCT weights e^{-i pi k/(2 n1)}, k = 0..n1/2 (x)
   if (upload_twiddles(c, 4 * n2g, n2g, &s.twyd)) return 1;               // e^{-i pi k/(2 n2)}, k = 0..n2-1 (y)
   if (P.xkind >= 3 && upload_dct4_weights(c, n1, &s.tw4x)) return 1;    // DCT-IV weights (k_fft_x4)
-  if (solver_comm_changed(c)) return 1;
-  if (!c->C.impdiff) return 0;
+  if (!c->C.impdiff) return 0;      // (the schedules: solver_comm_changed, once cales_create has laid the staging buffers out)
   for (int iv = 0; iv < 3; ++iv) {
     hs_tridmatrix(&c->cbcvel[6 * iv + 4], n3, c->dzci.data(), c->dzfi.data(), iv == 2 ? 'f' : 'c', abc.data(), abc.data() + n3, abc.data() + 2 * n3);
     if (ctx_upload(c, &s.d_av[iv], abc)) return 1;
@@ -2363,7 +2367,7 @@ static void fft_y(cales_ctx *c, const SolvePath &P, const SolveSched &D, int ch,
 // of a chunk follows its transform, in order on the context's stream (one chunk) or on the second stream, where `arrived` then holds the chunk's event
 static int solve_field(cales_ctx *c, const SolvePath &P, const SolveSched &D, real *pp, const real *da, const real *db, const real *dc, real lscale, const FusedFill &ff = FusedFill()) {
   const bool dist = c->P > 1, pipe = D.nch > 1;
-  if (dist && !c->comm.on) { c->err = "solver: nranks > 1 but no communication hooks registered (cales_set_comm)"; return 1; }
+  if (dist) if (int e = require_hooks(c, "solver: ")) return e;
   hipEvent_t arrived[4] = {nullptr, nullptr, nullptr, nullptr};
   auto exchange = [&](int dir, int ch) -> int {
     if (!dist) return 0;
@@ -2577,8 +2581,7 @@ static int velocity_path(cales_ctx *c, Solver &s, int iv, SolvePath &V) {
   V.cw = c->cw;
   choose_kernels(c, s, V);
   tile_setup(c, V, s.tab_imp3d);
-  s.sched_vel[iv] = solve_sched(c, V);
-  return 0;
+  return solve_sched(c, V, s.sched_vel[iv]);
 }
 // the one place a component's path is made: by its first solve or by cales_describe_plan, whichever comes first; a refusal is kept and repeated
 static int velocity_path_ready(cales_ctx *c, Solver &s, int iv) {

@@ -210,9 +210,11 @@ real *red_partials(cales_ctx *c, size_t need) {
 }
 int allreduce_dev(cales_ctx *c, real *p, int64_t count, int op) {
   if (c->P == 1) return 0;      // (utils.f90:46, chkdiv.f90:50-51, chkdt.f90:98, sgs.f90:475)
-  if (!c->comm.on) { c->err = "nranks > 1 but no communication hooks registered (cales_set_comm)"; return 1; }
-  const uintptr_t lo = (uintptr_t)c->comm.A, hi = (uintptr_t)(c->comm.A + c->comm.nbuf), a = (uintptr_t)p;
-  if (count < 0 || a < lo || a > hi || (uint64_t)count > (hi - a) / sizeof(real)) { c->err = "allreduce: the values do not lie in the staging buffer the hooks were registered with"; return 1; }
+  if (int e = require_hooks(c)) return e;
+  // the tail of A (results and plane sums) or its borrowed head (StageLayout); compared as addresses: p may point anywhere
+  const StageLayout &L = c->stage;
+  const uintptr_t a = (uintptr_t)p, head = (uintptr_t)c->comm.A, tail = (uintptr_t)(c->comm.A + L.tail), end = (uintptr_t)(c->comm.A + L.total), hi = a >= tail ? end : tail;
+  if (count < 0 || a < head || a > hi || (uint64_t)count > (hi - a) / sizeof(real)) { c->err = "allreduce: the values do not lie in the staging buffer the hooks were registered with"; return 1; }
   if (c->comm.allred(c->comm.user, p - c->comm.A, count, op)) { c->err = "allreduce callback failed"; return 1; }
   return 0;
 }

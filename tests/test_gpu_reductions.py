@@ -133,6 +133,8 @@ def test_two_ranks_without_hooks_and_with():
         bare.append(h.memory_in_use())
         with pytest.raises(CalesError, match="no communication hooks registered"):
             h.chkdiv()
+        with pytest.raises(CalesError, match="no communication hooks registered"):      # ... and so does a step, at its first exchange
+            h.step(1e-3)
         h.close()
 
     def body(h, r):
