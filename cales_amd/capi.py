@@ -1,4 +1,4 @@
-"""ctypes binding of libcales_hip.so (C-ABI declared in include/cales.h).
+"""ctypes binding of libcales_hip.so (C-ABI declared in include/cales.h and include/cales_post.h).
 
 There is no CPU fallback: if the HIP library has not been built, importing the symbols raises.
 """
@@ -51,6 +51,10 @@ SYMBOLS = ["cales_real_size", "cales_initgrid", "cales_initflow", "cales_check_c
            "cales_profile_count", "cales_profile_get", "cales_device_info", "cales_comm_buffer_doubles", "cales_set_comm",
            "cales_initflow_slab", "cales_comm_unique_id", "cales_comm_init_rccl", "cales_comm_selftest",
            "cales_device_count", "cales_set_device", "cales_set_comm_overlap", "cales_rk_par", "cales_describe_plan", "cales_calibrate", "cales_memory_in_use"]
+
+# every symbol include/cales_post.h declares, the output side of the C-ABI (planes, boxes and strided samples of a field read from the device); a list of
+# its own, as the header is a header of its own (tests/test_box_reads_host.py checks it against that header)
+POST_SYMBOLS = ["cales_box_share", "cales_read_box", "cales_out2d", "cales_out3d"]
 
 
 class CalesCase(C.Structure):
@@ -156,5 +160,14 @@ def lib() -> C.CDLL:
             fn = getattr(L, name)
             fn.argtypes = args
             fn.restype = None if name == "cales_destroy" else C.c_int
+        for name, args in {      # include/cales_post.h (POST_SYMBOLS)
+            "cales_box_share": [C.POINTER(CalesCase), dp, dp, dp, dp, dp],
+            "cales_read_box": [C.c_void_p, C.c_int, dp, dp, dp, dp, dp],
+            "cales_out2d": [C.c_void_p, C.c_int, C.c_int, C.c_int, dp, dp],
+            "cales_out3d": [C.c_void_p, C.c_int, dp, dp, dp],
+        }.items():
+            fn = getattr(L, name)
+            fn.argtypes = args
+            fn.restype = C.c_int
         _lib = L
     return _lib

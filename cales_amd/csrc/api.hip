@@ -2,6 +2,8 @@
 // one entry per reference operator, the fused time step (reference src/main.f90:417-508) and the
 // HIP-event kernel timers used by bench.py's roofline line.
 #include "common.hpp"
+#include "../../include/cales_post.h"
+#include <algorithm>
 #include <atomic>
 
 static thread_local std::string g_create_err;
@@ -107,6 +109,18 @@ __global__ __launch_bounds__(256) void k_repack(Geom g, int to_device, real *__r
   if (i > g.n1 + 1 || j > g.n2 + 1) return;
   const size_t h = (size_t)i + (size_t)(g.n1 + 2) * ((size_t)j + (size_t)(g.n2 + 2) * k);
   if (to_device) dev[g.ix(i, j, k)] = packed[h]; else packed[h] = dev[g.ix(i, j, k)];
+}
+// A strided box of a field (include/cales_post.h), packed in Fortran order: one thread per OUTPUT element, numbered as the packed array is stored, so the
+// stores of a wave are contiguous whatever the box -- its lanes run along the fastest direction of the output that has more than one point. The loads are
+// what the box makes them: row segments with nskip(1) = 1, one element per row (one 128-B line per lane) for a y-z plane. The points are first + m * skip
+// in LOCAL haloed indices; the host has checked them against the field (box_share below).
+struct BoxRead { int first[3], skip[3], count[3]; };
+__global__ __launch_bounds__(256) void k_box_read(Geom g, BoxRead b, size_t total, const real *__restrict__ dev, real *__restrict__ packed) {
+  const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (t >= total) return;
+  const size_t r = t / (size_t)b.count[0];
+  const int m0 = (int)(t - r * (size_t)b.count[0]), m2 = (int)(r / (size_t)b.count[1]), m1 = (int)(r - (size_t)m2 * (size_t)b.count[1]);
+  packed[t] = dev[g.ix(b.first[0] + m0 * b.skip[0], b.first[1] + m1 * b.skip[1], b.first[2] + m2 * b.skip[2])];
 }
 // Same-box calibration (bench.py "calibration"): three streams over the rows of the context's own fields in the library's layout
 // (padded rows, element 1 of every row on a 128-B boundary, 8 B per lane -- what the FP64 passes do), timed with HIP events on the context's stream.
@@ -361,6 +375,62 @@ int cales_get_bcvel(cales_ctx *c, int ivel, real *x, real *y, real *z) {
   HIPCHK(c, hipMemcpy(y, b.y, sizeof(real) * (size_t)(n[0] + 2) * (n[2] + 2) * 2, hipMemcpyDeviceToHost));
   HIPCHK(c, hipMemcpy(z, b.z, sizeof(real) * (size_t)(n[0] + 2) * (n[1] + 2) * 2, hipMemcpyDeviceToHost));
   return 0;
+}
+
+// ------------------------------------------------------------------------------------------ parts of a field (include/cales_post.h: out2d / out3d)
+// the share of rank cs->rank in the box lo : hi : nskip of global haloed indices: first point and number of points per direction
+static int box_share(const cales_case *cs, const int32_t *lo, const int32_t *hi, const int32_t *nskip, int32_t *first, int32_t *count, std::string &err) {
+  if (!cs || !lo || !hi || !nskip || !first || !count) { err = "box: null argument"; return 1; }
+  if (cs->nranks < 1 || cs->rank < 0 || cs->rank >= cs->nranks || cs->ng[1] % cs->nranks) { err = "box: bad rank / number of ranks"; return 1; }
+  for (int d = 0; d < 3; ++d) {
+    const char x = "xyz"[d];
+    if (nskip[d] < 1) { err = std::string("box: nskip < 1 in ") + x; return 1; }
+    if (lo[d] < 0) { err = std::string("box: lo < 0 in ") + x; return 1; }
+    if (hi[d] > cs->ng[d] + 1) { err = std::string("box: hi > ng+1 in ") + x; return 1; }
+    if (lo[d] > hi[d]) { err = std::string("box: lo > hi in ") + x; return 1; }
+    first[d] = lo[d]; count[d] = (hi[d] - lo[d]) / nskip[d] + 1;
+  }
+  // y: the rows the rank owns, with the global ghost row 0 on the first rank and ng2+1 on the last
+  const int n2 = cs->ng[1] / cs->nranks;
+  const int a = cs->rank == 0 ? 0 : cs->rank * n2 + 1, b = std::min((int)hi[1], cs->rank == cs->nranks - 1 ? cs->ng[1] + 1 : (cs->rank + 1) * n2);
+  const int m0 = a > lo[1] ? (a - lo[1] + nskip[1] - 1) / nskip[1] : 0;      // first point at or above a
+  first[1] = lo[1] + m0 * nskip[1];
+  count[1] = first[1] <= b ? (b - first[1]) / nskip[1] + 1 : 0;
+  return 0;
+}
+int cales_box_share(const cales_case *cs, const int32_t lo[3], const int32_t hi[3], const int32_t nskip[3], int32_t first[3], int32_t count[3]) {
+  return box_share(cs, lo, hi, nskip, first, count, g_create_err);
+}
+int cales_read_box(cales_ctx *c, int field, const int32_t lo[3], const int32_t hi[3], const int32_t nskip[3], real *buf, int32_t count[3]) {
+  ENTER(c);
+  if (field < 0 || field >= CALES_NFIELDS || !c->f[field]) { c->err = "bad field id"; return 1; }
+  int32_t first[3], cnt[3];
+  if (int e = box_share(&c->C, lo, hi, nskip, first, cnt, c->err)) return e;
+  if (count) for (int d = 0; d < 3; ++d) count[d] = cnt[d];
+  const size_t total = (size_t)cnt[0] * (size_t)cnt[1] * (size_t)cnt[2];      // (never more than a field: the points of a share are distinct cells of the slab)
+  if (total == 0) return 0;
+  if (!buf) { c->err = "box: buf is NULL"; return 1; }
+  if (field == CALES_VISCT) if (int e = materialize_visct(c)) return e;
+  BoxRead b;
+  for (int d = 0; d < 3; ++d) { b.first[d] = first[d]; b.skip[d] = nskip[d]; b.count[d] = cnt[d]; }
+  b.first[1] -= c->g.jlo;      // global row -> row of the slab
+  { ProfScope ps(c, "box_read");
+    LAUNCH(c, k_box_read, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, c->stream, c->g, b, total, c->f[field], c->scr1); }     // scr1: scratch between operators
+  LAUNCHCHK(c);
+  return read_back(c, buf, c->scr1, total);
+}
+int cales_out2d(cales_ctx *c, int field, int inorm, int islice, real *buf, int32_t count[3]) {
+  ENTER(c);
+  if (inorm < 1 || inorm > 3) { c->err = "out2d: inorm must be 1..3"; return 1; }
+  if (islice < 1 || islice > c->C.ng[inorm - 1]) { c->err = "out2d: islice outside 1..ng"; return 1; }
+  int32_t lo[3] = {1, 1, 1}, hi[3] = {c->C.ng[0], c->C.ng[1], c->C.ng[2]};
+  const int32_t one[3] = {1, 1, 1};
+  lo[inorm - 1] = hi[inorm - 1] = islice;
+  return cales_read_box(c, field, lo, hi, one, buf, count);
+}
+int cales_out3d(cales_ctx *c, int field, const int32_t nskip[3], real *buf, int32_t count[3]) {
+  const int32_t lo[3] = {1, 1, 1};
+  return cales_read_box(c, field, lo, c->C.ng, nskip, buf, count);
 }
 
 // ------------------------------------------------------------------------------------------ operators

@@ -1,4 +1,4 @@
-! ISO_C_BINDING view of include/cales.h -- what a Fortran host (the reference's own language) binds to.
+! ISO_C_BINDING view of include/cales.h and include/cales_post.h -- what a Fortran host (the reference's own language) binds to.
 ! `type(cales_case)` mirrors `struct cales_case`; character and multi-dimensional members keep the
 ! storage order of the reference's namelist variables (src/param.f90:37-76), so they are copied unchanged.
 module cales_c
@@ -160,6 +160,22 @@ module cales_c
     integer(c_int) function cales_initflow_slab(c,inivel,is_wallturb,u,v,w,p) bind(C,name='cales_initflow_slab')
       import; type(cales_case), intent(in) :: c; character(kind=c_char) :: inivel(*); integer(c_int), value :: is_wallturb
       real(c_rp) :: u(*),v(*),w(*),p(*)
+    end function
+    ! ---- include/cales_post.h: parts of a field read from the device (out2d / out3d, src/output.f90:164-242). A box is the points lo + m*nskip <= hi
+    ! of GLOBAL haloed indices 0:ng+1; a rank's share of it is packed in Fortran order count(1) x count(2) x count(3), first = its first global point
+    integer(c_int) function cales_box_share(c,lo,hi,nskip,first,count) bind(C,name='cales_box_share')      ! host only
+      import; type(cales_case), intent(in) :: c; integer(c_int32_t), intent(in) :: lo(3),hi(3),nskip(3); integer(c_int32_t) :: first(3),count(3)
+    end function
+    integer(c_int) function cales_read_box(ctx,field,lo,hi,nskip,buf,count) bind(C,name='cales_read_box')
+      import; type(c_ptr), value :: ctx; integer(c_int), value :: field; integer(c_int32_t), intent(in) :: lo(3),hi(3),nskip(3)
+      real(c_rp) :: buf(*); integer(c_int32_t) :: count(3)
+    end function
+    integer(c_int) function cales_out2d(ctx,field,inorm,islice,buf,count) bind(C,name='cales_out2d')
+      import; type(c_ptr), value :: ctx; integer(c_int), value :: field,inorm,islice; real(c_rp) :: buf(*); integer(c_int32_t) :: count(3)
+    end function
+    integer(c_int) function cales_out3d(ctx,field,nskip,buf,count) bind(C,name='cales_out3d')
+      import; type(c_ptr), value :: ctx; integer(c_int), value :: field; integer(c_int32_t), intent(in) :: nskip(3)
+      real(c_rp) :: buf(*); integer(c_int32_t) :: count(3)
     end function
   end interface
 end module cales_c

@@ -19,6 +19,8 @@
 !              only and uses alph2 = 2.52 everywhere (src/sgs.f90:236-247,316-327,817-821); no effect on 'none' and 'smag'
 !              CALES_DSMAG_AVERAGE = planes (also unset or empty) | volume | xlines: the reference's _CHANNEL (hard-wired there) | -D_DIT | _DUCT -- the
 !              directions sgstype = 'dsmag' averages the Germano identity over (src/sgs.f90:359-370); no effect on 'none' and 'smag'
+!              CALES_OUT3D_NSKIP = "a,b,c": the nskip of the volume dumps, which the reference hard-codes as [1,1,1] in its out3d.h90; with a value > 1
+!              the dumps hold the interior points 1, 1+nskip, ... of every direction, read strided from the device (cales_out3d)
 program cales
   use, intrinsic :: iso_c_binding
   use, intrinsic :: iso_fortran_env, only: int64
@@ -62,6 +64,8 @@ program cales
   character(len=512) :: iomsg,arg
   character(len=16) :: f2d,ave
   integer :: f2dlen,f2dstat,avelen,avestat
+  character(len=64) :: skp
+  integer :: skplen,skpstat,nskip3d(3)
   character(len=100) :: filename
   character(len=7) :: fldnum
   character(len=4) :: chkptnum
@@ -150,6 +154,18 @@ program cales
     if(myid == 0) print*, 'ERROR: unknown SGS model'
     call die
   end select
+  nskip3d(:) = 1
+  call get_environment_variable('CALES_OUT3D_NSKIP',skp,skplen,skpstat)           ! nskip of out3d.h90, a run-time choice here
+  if(skpstat == 0 .and. skplen > 0) then
+    read(skp,*,iostat=ierr) nskip3d
+    if(ierr /= 0 .or. any(nskip3d < 1)) then
+      if(myid == 0) print*, 'ERROR: CALES_OUT3D_NSKIP must be three integers >= 1, e.g. 2,2,2'
+      call die
+    end if
+  else if(skpstat < 0) then
+    if(myid == 0) print*, 'ERROR: CALES_OUT3D_NSKIP is too long'
+    call die
+  end if
   cs%lwm = reshape(lwm,[6]); cs%hwm = hwm; cs%impdiff = impdiff; cs%nranks = nranks; cs%rank = myid
   !
   ! a-priori input checks (src/sanity.f90:33-67)
@@ -352,18 +368,20 @@ contains
     ! something for a channel (walls in z, periodic x and y): other cases get no velstats files here
     if(do1d.and.is_chan) call out1d_chan_stats('velstats_fld_'//fldnum)
     if(do1d.and.is_duct) call out2d_duct_stats('velstats_fld_'//fldnum//'.out')
-    if(do2d.or.do3d) then     ! main.f90:580-589
+    if(do2d) then     ! main.f90:580-584, out2d.h90: the plane j = ng(2)/2 of the five fields, each read from the device as a plane
+      call visu_2d('vex_slice_fld_'//fldnum//'.bin','Velocity_X',CALES_U); call visu_2d('vey_slice_fld_'//fldnum//'.bin','Velocity_Y',CALES_V)
+      call visu_2d('vez_slice_fld_'//fldnum//'.bin','Velocity_Z',CALES_W); call visu_2d('pre_slice_fld_'//fldnum//'.bin','Pressure_P',CALES_P)
+      call visu_2d('visct_slice_fld_'//fldnum//'.bin','Viscosity',CALES_VISCT)
+    end if
+    if(do3d.and.all(nskip3d == 1)) then     ! main.f90:585-589, out3d.h90: the five fields without halos
       call chk(cales_download_state(ctx,u,v,w,p,visct))
-      if(do2d) then     ! out2d.h90: the plane j = ng(2)/2 of the five fields
-        call visu_2d('vex_slice_fld_'//fldnum//'.bin','Velocity_X',u); call visu_2d('vey_slice_fld_'//fldnum//'.bin','Velocity_Y',v)
-        call visu_2d('vez_slice_fld_'//fldnum//'.bin','Velocity_Z',w); call visu_2d('pre_slice_fld_'//fldnum//'.bin','Pressure_P',p)
-        call visu_2d('visct_slice_fld_'//fldnum//'.bin','Viscosity',visct)
-      end if
-      if(do3d) then     ! out3d.h90: the five fields without halos
-        call visu_3d('vex_fld_'//fldnum//'.bin','Velocity_X',u); call visu_3d('vey_fld_'//fldnum//'.bin','Velocity_Y',v)
-        call visu_3d('vez_fld_'//fldnum//'.bin','Velocity_Z',w); call visu_3d('pre_fld_'//fldnum//'.bin','Pressure',p)
-        call visu_3d('visct_fld_'//fldnum//'.bin','Viscosity',visct)
-      end if
+      call visu_3d('vex_fld_'//fldnum//'.bin','Velocity_X',u); call visu_3d('vey_fld_'//fldnum//'.bin','Velocity_Y',v)
+      call visu_3d('vez_fld_'//fldnum//'.bin','Velocity_Z',w); call visu_3d('pre_fld_'//fldnum//'.bin','Pressure',p)
+      call visu_3d('visct_fld_'//fldnum//'.bin','Viscosity',visct)
+    else if(do3d) then     ! ... every nskip-th point of them (CALES_OUT3D_NSKIP), read strided from the device
+      call visu_3d_every('vex_fld_'//fldnum//'.bin','Velocity_X',CALES_U); call visu_3d_every('vey_fld_'//fldnum//'.bin','Velocity_Y',CALES_V)
+      call visu_3d_every('vez_fld_'//fldnum//'.bin','Velocity_Z',CALES_W); call visu_3d_every('pre_fld_'//fldnum//'.bin','Pressure',CALES_P)
+      call visu_3d_every('visct_fld_'//fldnum//'.bin','Viscosity',CALES_VISCT)
     end if
   end subroutine write_outputs
   subroutine chk(ist)
@@ -404,24 +422,28 @@ contains
     call MPI_ALLREDUCE(t,a,n,MPI_REAL_RP,MPI_SUM,MPI_COMM_WORLD,ie)
 #endif
   end subroutine allsum
-  subroutine visu_log(flog,fbin,varname,nmin,nmax)    ! write_log_output, src/output.f90:244-272
+  subroutine visu_log(flog,fbin,varname,nmin,nmax,nskip)    ! write_log_output, src/output.f90:244-272
     character(len=*), intent(in) :: flog,fbin,varname
-    integer, intent(in) :: nmin(3),nmax(3)
+    integer, intent(in) :: nmin(3),nmax(3),nskip(3)
     integer :: iu
     if(myid /= 0) return
     open(newunit=iu,file=flog,position='append')
-    write(iu,'(A30,A15,9I5,E16.7E3,I7)') fbin,varname,nmin,nmax,[1,1,1],time,istep
+    write(iu,'(A30,A15,9I5,E16.7E3,I7)') fbin,varname,nmin,nmax,nskip,time,istep
     close(iu)
   end subroutine visu_log
-  subroutine visu_2d(fbin,varname,q)    ! write_visu_2d with inorm = 2, islice = ng(2)/2, src/output.f90:289-315
+  subroutine visu_2d(fbin,varname,ifld)    ! write_visu_2d with inorm = 2, islice = ng(2)/2, src/output.f90:289-315
     character(len=*), intent(in) :: fbin,varname
-    real(rp), intent(in) :: q(0:,0:,0:)
+    integer(c_int), intent(in) :: ifld
+    real(rp), allocatable :: plane(:,:)
+    integer(c_int32_t) :: cnt(3)
     integer :: iu,js
     js = ng(2)/2
-    if(js > jlo .and. js <= jlo+n2l) then      ! the rank that owns the row writes the plane
-      open(newunit=iu,file=fbin,access='stream',status='replace'); write(iu) q(1:ng(1),js-jlo,1:ng(3)); close(iu)
+    allocate(plane(ng(1),ng(3)))
+    call chk(cales_out2d(ctx,ifld,2,js,plane,cnt))      ! (every rank asks; the share is empty on all but the one that owns the row)
+    if(cnt(2) > 0) then      ! the rank that owns the row writes the plane
+      open(newunit=iu,file=fbin,access='stream',status='replace'); write(iu) plane; close(iu)
     end if
-    call visu_log('log_visu_2d_slice_1.out',fbin,varname,[1,js,1],[ng(1),js,ng(3)])
+    call visu_log('log_visu_2d_slice_1.out',fbin,varname,[1,js,1],[ng(1),js,ng(3)],[1,1,1])
   end subroutine visu_2d
   subroutine visu_3d(fbin,varname,q)    ! write_visu_3d with nskip = 1, src/output.f90:274-287
     character(len=*), intent(in) :: fbin,varname
@@ -430,8 +452,30 @@ contains
     call open_shared(fbin,iu)
     call write_slab(iu,0_int64,q)
     close(iu)
-    call visu_log('log_visu_3d.out',fbin,varname,[1,1,1],ng)
+    call visu_log('log_visu_3d.out',fbin,varname,[1,1,1],ng,[1,1,1])
   end subroutine visu_3d
+  subroutine visu_3d_every(fbin,varname,ifld)    ! write_visu_3d with nskip > 1 somewhere: decomp_2d_write_every(...,.true.) of out3d, src/output.f90:191-242
+    character(len=*), intent(in) :: fbin,varname
+    integer(c_int), intent(in) :: ifld
+    real(rp), allocatable :: buf(:,:,:)
+    integer(c_int32_t) :: one(3),skp3(3),top(3),first(3),cnt(3)
+    integer(int64) :: pos
+    integer :: iu,kk,n2every
+    one(:) = 1; skp3(:) = nskip3d(:); top(:) = ng(:)
+    call chk(cales_box_share(cs,one,top,skp3,first,cnt))      ! this rank's points: how many, and where they start
+    allocate(buf(cnt(1),max(cnt(2),1),cnt(3)))
+    call chk(cales_out3d(ctx,ifld,skp3,buf,cnt))
+    n2every = (ng(2)-1)/nskip3d(2) + 1                        ! rows of the file; this rank's start at row (first(2)-1)/nskip
+    call open_shared(fbin,iu)
+    if(cnt(2) > 0) then
+      do kk=1,cnt(3)
+        pos = 1 + rsz*((int(kk-1,int64)*n2every + (first(2)-1)/nskip3d(2))*int(cnt(1),int64))
+        write(iu,pos=pos) buf(:,1:cnt(2),kk)
+      end do
+    end if
+    close(iu)
+    call visu_log('log_visu_3d.out',fbin,varname,[1,1,1],ng,nskip3d)
+  end subroutine visu_3d_every
   subroutine out1d_chan_stats(fname)    ! the velstats_fld_*.out/.bin pair of out1d_single_point_chan, src/output.f90:683-699
     character(len=*), intent(in) :: fname
     real(rp), allocatable :: buf(:,:),leak(:,:)

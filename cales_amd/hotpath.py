@@ -79,6 +79,27 @@ def memory_in_use(handle=None) -> Tuple[int, int]:
     return int(b.value), int(n.value)
 
 
+def _i3(v):
+    v = [int(x) for x in v]
+    if len(v) != 3:
+        raise ValueError("three indices, one per direction")
+    return (C.c_int32 * 3)(*v)
+
+
+def _box_share(cs, lo, hi, nskip) -> Tuple[Tuple[int, ...], Tuple[int, ...]]:
+    first, count = (C.c_int32 * 3)(), (C.c_int32 * 3)()
+    L = capi.lib()
+    if L.cales_box_share(C.byref(cs), _i3(lo), _i3(hi), _i3(nskip), first, count):
+        raise CalesError(L.cales_last_error(None).decode())
+    return tuple(first), tuple(count)
+
+
+def box_share(case: Case, lo, hi, nskip=(1, 1, 1), nranks: int = 1, rank: int = 0) -> Tuple[Tuple[int, ...], Tuple[int, ...]]:
+    """cales_box_share (include/cales_post.h; host only): (first, count) of the share of `rank` in the box of the points lo + m nskip <= hi, GLOBAL
+    haloed indices 0 ... ng+1. x and z: every point; y: the points in the rows the rank owns (row 0 with the first rank, ng2+1 with the last)."""
+    return _box_share(capi.make_case(case, nranks, rank), lo, hi, nskip)
+
+
 class HotPath:
     def __init__(self, case: Case, nranks: int = 1, rank: int = 0, stream: int | None = None):
         self.case = case
@@ -120,6 +141,31 @@ class HotPath:
     def get(self, name: str) -> np.ndarray:
         a = self.zeros()
         self._chk(self.L.cales_get_field(self.h, capi.FIELDS[name], _p(a)))
+        return a
+
+    # -- parts of a field (include/cales_post.h): this rank's share, Fortran-ordered, without a copy of the whole field
+    def read_box(self, name: str, lo, hi, nskip=(1, 1, 1)) -> np.ndarray:
+        """cales_read_box: the points lo + m nskip <= hi of field `name`, GLOBAL haloed indices 0 ... ng+1 (box_share tells where a rank's share starts)."""
+        a = np.zeros(_box_share(self.cs, lo, hi, nskip)[1], order="F", dtype=REAL)
+        self._chk(self.L.cales_read_box(self.h, capi.FIELDS[name], _i3(lo), _i3(hi), _i3(nskip), _p(a), None))
+        return a
+
+    def out2d(self, name: str, inorm: int, islice: int) -> np.ndarray:
+        """out2d (src/output.f90:164-189): the interior plane of global index `islice` normal to direction `inorm` (1, 2, 3), shape 1 in that direction."""
+        ng = [int(x) for x in self.case.ng]
+        lo, hi = [1, 1, 1], list(ng)
+        if 1 <= int(inorm) <= 3 and 1 <= int(islice) <= ng[int(inorm) - 1]:      # (anything else: the library refuses it below, nothing is read)
+            lo[int(inorm) - 1] = hi[int(inorm) - 1] = int(islice)
+            a = np.zeros(_box_share(self.cs, lo, hi, (1, 1, 1))[1], order="F", dtype=REAL)
+        else:
+            a = np.zeros((1, 1, 1), order="F", dtype=REAL)
+        self._chk(self.L.cales_out2d(self.h, capi.FIELDS[name], int(inorm), int(islice), _p(a), None))
+        return a
+
+    def out3d(self, name: str, nskip) -> np.ndarray:
+        """out3d (src/output.f90:191-242): the interior points 1, 1 + nskip, 1 + 2 nskip ... of every direction."""
+        a = np.zeros(_box_share(self.cs, (1, 1, 1), [int(x) for x in self.case.ng], nskip)[1], order="F", dtype=REAL)
+        self._chk(self.L.cales_out3d(self.h, capi.FIELDS[name], _i3(nskip), _p(a), None))
         return a
 
     def upload(self, u, v, w, p):
