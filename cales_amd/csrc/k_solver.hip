@@ -1857,6 +1857,34 @@ enum class XKernel { fft_x8, fft_x4, dst1, fft_x };                             
 enum class YKernel { fft_y16, fft_y8, fft_y8r, fft_y4, dst1, fft_y };          // radix-8 (16 | 8 per thread | register ends) | DCT-IV | face-centred | mixed radix
 enum class ZKernel { herm, tile, ri, periodic_real, periodic_cpx };            // k_gaussel_herm | launch_tile | k_gaussel_ri | k_gaussel<real, 1> | k_gaussel<real2, 1>
 static bool radix8_y(YKernel k) { return k == YKernel::fft_y16 || k == YKernel::fft_y8 || k == YKernel::fft_y8r; }
+// A transform pass of a path: its family, the instantiations of that family it launches ([0] forward, [1] inverse; k_fft_x8: [2] the forward one that forms
+// pp = div(u*)/dtrk itself, fillps), the geometry of a block and what the kernels read -- filled once by x_pass / y_pass, read by fft_x / fft_y, solve_sched
+// and path_name. One pointer type per family; only the family's member of `fn` is set.
+typedef void (*FftX8)(Geom, int, int, const cpx *, const cpx *, const cpx *, real *, real, Spec, real2 *, FillArgs, long, long);
+typedef void (*FftX4)(Geom, FftPlan, int, const cpx *, const cpx *, real *, real, Spec, real2 *);
+typedef void (*FftX)(Geom, FftPlan, int, int, const cpx *, const cpx *, const cpx *, real *, real, Spec, real2 *);
+typedef void (*Dst1)(Geom, FftPlan, int, const cpx *, real *, real, Spec, real2 *, int, int);
+typedef void (*FftY16)(Geom, int, int, const cpx *, const cpx *, Spec, real2 *, int, int);
+typedef void (*FftY8)(Geom, int, int, int, const cpx *, const cpx *, Spec, real2 *, int, int);
+typedef void (*FftY8r)(Geom, int, int, int, const cpx *, Spec, real2 *, int, int);
+typedef void (*FftY4)(Geom, FftPlan, int, int, const cpx *, const cpx *, Spec, real2 *);
+typedef void (*FftY)(Geom, FftPlan, int, int, int, const cpx *, const cpx *, Spec, real2 *);
+struct XPass {
+  XKernel k = XKernel::fft_x;
+  union { FftX8 x8[3]; FftX4 x4[2]; FftX x[2]; Dst1 dst1[2]; } fn = {{nullptr, nullptr, nullptr}};
+  int threads = 256, rows = 1; size_t lds = 0;      // of a block: threads, rows, dynamic LDS bytes
+  int odd = 0;                   // fft_x8 on rows of r 2^p points: r = 3, 5, 9 (the ODD = 1 instantiations); 0: a power of two
+  FftPlan plan;                  // fft_x4, fft_x: ng(1)/2 points; dst1: the symmetric extension
+  const cpx *tw = nullptr, *twp = nullptr, *twd = nullptr;      // twiddles | fft_x8, fft_x: of the post / pre step; fft_x4: DCT-IV weights | fft_x8, fft_x: DCT weights
+};
+struct YPass {
+  YKernel k = YKernel::fft_y;
+  union { FftY16 y16[2]; FftY8 y8[2]; FftY8r y8r[2]; FftY4 y4[2]; FftY y[2]; Dst1 dst1[2]; } fn = {{nullptr, nullptr}};
+  int threads = 256, cols = 1; size_t lds = 0;      // of a block: threads, complex columns, dynamic LDS bytes
+  int odd = 0;                   // fft_y8 on lines of r 2^p points (XPass::odd)
+  FftPlan plan;                  // fft_y: ng(2) points; fft_y4: ng(2)/2; dst1: the symmetric extension
+  const cpx *tw = nullptr, *twd = nullptr;      // twiddles | DCT weights; fft_y4: DCT-IV weights
+};
 // planes per lane of the LDS tile that solves nz planes: asked by the tile, the packed column of the modes 0 and n1/2 (it reads the tile's table) and the z-only sweeps
 constexpr int tile_m(int nz) { return nz <= 128 ? 2 : nz <= 256 ? 4 : nz <= 512 ? 8 : 16; }
 // whether the LDS tile solves nz planes (periodic: the cyclic closure inside the tile)
@@ -1867,7 +1895,7 @@ constexpr int TILE_TAB = 3 * 64 * 16;      // reals of a table (k_abc_chunked), 
 struct ZTile { int M = 0, NV = 0, PER = 0, DUD = 0, ndbl = 0, nrow = 0; bool persistent = false; real *tab = nullptr; };
 struct SolvePath {
   int xkind = 0, ykind = 0;      // 0 PP, 1 NN, 2 DD, 3 ND, 4 DN (cell-centred); 5..7 the face-centred kinds of a velocity component (velocity_path)
-  XKernel xk = XKernel::fft_x; YKernel yk = YKernel::fft_y; ZKernel zk = ZKernel::ri;
+  XPass xp; YPass yp; ZKernel zk = ZKernel::ri;
   int nz = 0; bool periodic_z = false, poisson = false;
   ZTile zt;                      // ZKernel::tile: its instantiation and table (tile_setup)
   int fixnull = 0;               // pressure without a Dirichlet condition in z: the zero-eigenvalue mode (if x and y have one) is singular
@@ -1875,10 +1903,7 @@ struct SolvePath {
   bool null_switch = false;      // ... the switch as given (solver_path_name prints it whether or not the problem is singular)
   bool nyq = false;              // the modes 0 and n1/2 share mode column 0 (Spec::nyq): k_gaussel_nyq solves it after the tile
   int cw = 0;                    // complex mode columns per rank
-  int xrows = 1, ycols = 1;      // rows per block of k_fft_x8, columns per block of the radix-8 y kernels
-  int xodd = 0, yodd = 0;        // fft_x8 / fft_y8 on a line of r 2^p points: r = 3, 5, 9 (the ODD = 1 instantiations); 0: a power of two
   real *lamx = nullptr, *lamy = nullptr; real normfft = 1.;      // eigenvalues per stored spectral index; scale of the inverse transforms
-  FftPlan p1x, p1y; real *tw1x = nullptr, *tw1y = nullptr;      // k_dst1 (face-centred kinds)
 };
 // How a path is launched: the chunks of its exchange and the geometry of every pass, made by solve_sched with the path and again when the communication hooks
 // change (solver_comm_changed); solve_field only reads it. Chunk ch is the rows [ch rows, (ch + 1) rows) of the (j,k) row list, the planes ch kpc + 1 .. (ch + 1) kpc.
@@ -1898,13 +1923,10 @@ struct HzPath {
   // the chunked tables of the alphas this component has seen -- three per step, the same every step while dt stays (four slots, round robin, in Solver::tab_hz)
   real alpha[4] = {0., 0., 0., 0.}; bool ok[4] = {false, false, false, false}; int next = 0;
 };
-// the solver state a context owns (cales_ctx::solver): line plans and launch geometry of the transforms, their tables, the paths, the memory of the z solves
+// the solver state a context owns (cales_ctx::solver): the tables of the transforms, the paths, the memory of the z solves
 struct Solver {
-  FftPlan px, py, py4; int Rx, CBy, CBy4 = 0; size_t shx, shy, shy4 = 0;
-  bool x8, y8, y16 = false; int x8_threads, y8_threads; size_t shx8, shy8, shy8r, shy16 = 0;
-  int xodd = 0, yodd = 0;        // the odd factor of an x / y line the radix-8 kernels take (SolvePath::xodd, yodd)
   real *twx = nullptr, *twx_post = nullptr, *twy = nullptr, *twy_post = nullptr, *twyd = nullptr;      // twiddle tables; twy_post, twyd: DCT weights of x, of y
-  real *tw4x = nullptr, *tw4y = nullptr, *twy4 = nullptr;         // DCT-IV weights of x and y, twiddles of the N/2-point y lines
+  real *tw4x = nullptr, *tw4y = nullptr, *twy4 = nullptr;         // DCT-IV weights of x and y, twiddles of the N/2-point y lines: made by the first path that needs them (x_pass, y_pass)
   SolvePath pres, vel[3]; SolveSched sched_pres, sched_vel[3];
   real *d_mpart = nullptr;       // 3 npart partial sums of the bulk means the pressure's forward x transform forms (FusedFill::mean_mask; solver_comm_changed)
   int vel_state[3] = {0, 0, 0}; std::string vel_err[3];      // a component's path: 0 not built yet, 1 built, 2 refused with vel_err (velocity_path_ready)
@@ -1991,7 +2013,7 @@ static void launch_z(cales_ctx *c, const SolvePath &P, const SolveSched &D, real
   if (refnull) LAUNCH(c, k_null_column, dim3(1), dim3(64), 0, c->stream, c->g, D.S, nz, P.periodic_z ? 1 : 0, da, db, dc, P.lamx, P.lamy, mode_spec, c->solver->d_nullw, 1);
 }
 
-bool solver_can_fuse_fillps(cales_ctx *c) { return c->solver && c->solver->x8; }
+bool solver_can_fuse_fillps(cales_ctx *c) { return c->solver && c->solver->pres.xp.k == XKernel::fft_x8; }
 int solver_mode_columns(cales_ctx *c) { return c->solver ? c->solver->pres.cw : c->cw; }
 
 // twiddles exp(-2 pi i q/N), q < cnt
@@ -2008,36 +2030,132 @@ static int upload_dct4_weights(cales_ctx *c, int n, real **dev) {
                                  t[2 * q] = std::cos(a1); t[2 * q + 1] = std::sin(a1); t[2 * (nh + q)] = std::cos(a2); t[2 * (nh + q) + 1] = std::sin(a2); }
   return ctx_upload(c, dev, t);
 }
-// DCT-IV / DST-IV in y (k_fft_y4): N/2-point lines, two per complex column -- plans and tables made by the first path that needs them
-static int dct4_y_setup(cales_ctx *c, Solver &s, const char *who) {
-  const int n2g = c->C.ng[1];
-  if (s.tw4y) return 0;
-  if (!make_plan(n2g / 2, s.py4)) { c->err = std::string(who) + ": ng(2)/2 must factor into primes <= 127"; return 1; }
-  s.CBy4 = 4; s.shy4 = (size_t)2 * s.CBy4 * 2 * (n2g / 2 + 1) * sizeof(cpx);
-  while (s.shy4 > 60 * 1024 && s.CBy4 > 1) { s.CBy4 /= 2; s.shy4 = (size_t)2 * s.CBy4 * 2 * (n2g / 2 + 1) * sizeof(cpx); }
-  if (s.shy4 > 64 * 1024) { c->err = std::string(who) + ": y line too long for the LDS-resident DCT-IV"; return 1; }
-  if (upload_dct4_weights(c, n2g, &s.tw4y)) return 1;
-  return s.twy4 ? 0 : upload_twiddles(c, n2g / 2, n2g / 2, &s.twy4);
+
+// ---- what the pressure (solver_setup) and a velocity component (velocity_path) set up alike, per direction d (0 x, 1 y) with the BC pair bc[0..1]
+// The transform kind of the pair (fft.f90:192-245), -1: unknown. own: along a velocity component, whose points lie on the faces.
+//   'c':  PP 0 (R2HC/HC2R) | NN 1 (REDFT10/01) | DD 2 (RODFT10/01) | ND 3 (REDFT11) | DN 4 (RODFT11)
+//   'f':  PP 0 | NN 6 (REDFT00) | DD 5 (RODFT00, one unknown less) | ND 1 (REDFT10/01) | DN 7 (RODFT01 / RODFT10)
+static int line_kind(const char *bc, bool own) { const std::string b(bc, 2);
+  return b == "PP" ? 0 : b == "NN" ? (own ? 6 : 1) : b == "DD" ? (own ? 5 : 2) : b == "ND" ? (own ? 1 : 3) : b == "DN" ? (own ? 7 : 4) : -1;
+}
+// The eigenvalues of that kind (initsolver.f90:66-98) per stored spectral index, scaled, on the device -- x: modes 0..n1/2 (half-complex symmetry), y: modes
+// 0..n2-1, Dirichlet-Dirichlet reversed: row r of the transformed field holds coefficient N-1-r (see k_fft_y) -- and the direction's factor of 1 / normfft
+// (fft.f90:99,136,142: norm(1) (n + norm(2) - ix): n (PP), 2 n ('c' pairs, 'f' ND/DN), 2 (n + 1 - 1) ('f' DD), 2 (n - 1) ('f' NN))
+static int line_spectrum(cales_ctx *c, int d, const char *bc, bool own, int kind, real **lam, double *norm) {
+  const int n = c->C.ng[d]; std::vector<real> l(d == 0 ? n + 2 : n, 0.);
+  hs_eigenvalues(n, std::string(bc, 2).c_str(), own ? 'f' : 'c', l.data());
+  for (auto &v : l) v = v * (c->dli[d] * c->dli[d]);
+  if (d == 1 && kind == 2) std::reverse(l.begin(), l.end());
+  *norm = kind == 0 ? (double)n : kind == 6 ? 2. * (n - 1) : 2. * n;
+  return ctx_upload(c, lam, l);
 }
 
-// the kernels of a path whose kinds, nz, z condition and equation are set
-static void choose_kernels(cales_ctx *c, const Solver &s, SolvePath &P) {
-  const int nh = c->C.ng[0] / 2, n2g = c->C.ng[1];
-  // the radix-8 kernels know the periodic and the Neumann-Neumann transform; a velocity component of the 3-D implicit step may need others
-  const bool use8x = s.x8 && P.xkind <= 1, use8y = s.y8 && P.ykind <= 1;
-  P.xk = use8x ? XKernel::fft_x8 : P.xkind >= 5 ? XKernel::dst1 : P.xkind >= 3 ? XKernel::fft_x4 : XKernel::fft_x;
-  P.yk = P.ykind >= 5 ? YKernel::dst1 : P.ykind >= 3 ? YKernel::fft_y4 : !use8y ? YKernel::fft_y : s.y16 ? YKernel::fft_y16 : P.ykind ? YKernel::fft_y8 : YKernel::fft_y8r;
-  P.xodd = use8x ? s.xodd : 0; P.yodd = use8y ? s.yodd : 0;
-  if (P.yodd) P.yk = YKernel::fft_y8;      // the staged kernel knows both kinds at these lengths
-  P.xrows = use8x ? s.x8_threads / (nh / 8) : 1;
-  P.ycols = P.yk == YKernel::fft_y16 ? 8 : use8y ? s.y8_threads / (n2g / 8) : 1;
+// ---- the transform passes: every instantiation named once (x8_kernels, y16_kernels, x_pass, y_pass), its LDS attribute set there (lds_attr), launched from one place (fft_x, fft_y)
+// Whether the radix-8 register kernels take the v-point lines of a path of transform kind `kind`: periodic and Neumann-Neumann lines of a power of two from
+// 16 to 1024 points, or of 3, 5, 9 times 2^p, p >= 3, from 48 points on (*odd: that factor; CALES_FFT_NO_ODD_RADIX: those stay with the Stockham kernels);
+// none with CALES_FFT_GENERIC. A velocity component of the 3-D implicit step takes them only in a direction in which the pressure (pres_kind) does.
+static bool radix8_takes(const cales_ctx *c, int v, int kind, int pres_kind, int *odd) {
+  int r = v, p = 0; while (r % 2 == 0) { r /= 2; ++p; }
+  const bool pow2 = v >= 16 && (v & (v - 1)) == 0 && v <= 1024, odd3 = !c->fl.fft_no_odd_radix && (r == 3 || r == 5 || r == 9) && p >= 3 && v >= 48 && v <= 1024;
+  const bool takes = kind <= 1 && pres_kind <= 1 && !c->fl.fft_generic && (pow2 || odd3);
+  *odd = (takes && odd3) ? r : 0; return takes;
+}
+// set-up: kernels launched with more than 64 KB of dynamic LDS are allowed the 150 KB every family is capped at (the contexts of a process share a function's
+// attribute: the need of one must not undercut another's) -- per context, which may sit on another device than the one before it
+template <typename K> static void lds_attr(cales_ctx *c, K *fn, int nfn, size_t lds) {
+  if (lds > 64 * 1024) for (int q = 0; q < nfn; ++q) HIPSOFT(c, hipFuncSetAttribute((const void *)fn[q], hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
+}
+#define X8(KIND, ODD) case 2 * KIND + ODD: k[0] = k_fft_x8<0, KIND, 0, ODD>; k[1] = k_fft_x8<1, KIND, 0, ODD>; k[2] = k_fft_x8<0, KIND, 1, ODD>; break
+static void x8_kernels(int kind, int odd, FftX8 *k) { switch (2 * kind + (odd ? 1 : 0)) { X8(0, 0); X8(0, 1); X8(1, 0); X8(1, 1); } }      // forward | inverse | forward with fillps
+#define Y16(N, KIND) case N + KIND: k[0] = k_fft_y16<N, 0, KIND>; k[1] = k_fft_y16<N, 1, KIND>; break
+static void y16_kernels(int N, int kind, FftY16 *k) { switch (N + kind) { Y16(1024, 0); Y16(1024, 1); Y16(512, 0); Y16(512, 1); Y16(256, 0); Y16(256, 1); } }
+#undef X8
+#undef Y16
+static int dst1_points(int kind, int n) { return kind == 5 ? 2 * n : kind == 6 ? 2 * (n - 1) : 4 * n; }      // points of the symmetric extension (k_dst1)
+// rows (columns) per block of the Stockham kernels, each `line` bytes of LDS: halved from `most` until a block has 60 KB or less
+static size_t stockham_block(int most, size_t line, int *per_block) {
+  for (*per_block = most; (size_t)*per_block * line > 60 * 1024 && *per_block > 1;) *per_block /= 2;
+  return (size_t)*per_block * line; }
+// the x pass of a path whose kinds are set (the twiddles of the context are solver_setup's)
+static int x_pass(cales_ctx *c, Solver &s, SolvePath &P) {
+  XPass &X = P.xp; const int n1 = c->C.ng[0], nh = n1 / 2; X.tw = (const cpx *)s.twx; X.twp = (const cpx *)s.twx_post; X.twd = (const cpx *)s.twy_post;
+  if (radix8_takes(c, nh, P.xkind, s.pres.xkind, &X.odd)) {
+    X.k = XKernel::fft_x8; const int T = nh / 8; X.threads = T >= 256 ? T : (256 / T) * T; X.rows = X.threads / T;
+    X.lds = ((size_t)X.rows * (nh + n1 / 16 + 2) + (n1 + 1) + (P.xkind ? nh + 1 : 0)) * sizeof(cpx);      // (above 64 KB: 768-point rows, 1024-point ones)
+    x8_kernels(P.xkind, X.odd, X.fn.x8); lds_attr(c, X.fn.x8, 3, X.lds); return 0; }
+  if (P.xkind >= 5) {      // along the component: the symmetric extension of a row in one block
+    X.k = XKernel::dst1; const int N = dst1_points(P.xkind, n1); real *tw = nullptr;
+    if (N < 2 || !make_plan(N, X.plan) || (size_t)2 * (N + 1) * sizeof(cpx) > 150 * 1024) { c->err = "helmholtz: x line not supported by the face-centred transform kernel"; return 1; }
+    if (upload_twiddles(c, N, N, &tw)) return 1;
+    X.tw = (const cpx *)tw; X.lds = (size_t)2 * (N + 1) * sizeof(cpx); X.fn.dst1[0] = k_dst1<0>; X.fn.dst1[1] = k_dst1<2>; lds_attr(c, X.fn.dst1, 2, X.lds); return 0; }
+  X.k = P.xkind >= 3 ? XKernel::fft_x4 : XKernel::fft_x;
+  if (!make_plan(nh, X.plan)) { c->err = "solver: ng(1)/2 and ng(2) must factor into primes <= 127"; return 1; }
+  // rows per block in x: aim at ~nh/4 threads per row, 256 threads per block
+  int T = 1; while (T * 2 <= std::max(1, std::min(256, nh / 4))) T *= 2;
+  X.lds = stockham_block(256 / T, (size_t)2 * (nh + 1) * sizeof(cpx), &X.rows);
+  if (X.lds > 64 * 1024) { c->err = "solver: line too long for the LDS-resident transform"; return 1; }
+  if (X.k == XKernel::fft_x) { X.fn.x[0] = k_fft_x<0>; X.fn.x[1] = k_fft_x<1>; return 0; }
+  if (!s.tw4x && upload_dct4_weights(c, n1, &s.tw4x)) return 1; X.twp = (const cpx *)s.tw4x;      // DCT-IV weights: made by the first path that needs them
+  if (P.xkind == 3) { X.fn.x4[0] = k_fft_x4<0, 0>; X.fn.x4[1] = k_fft_x4<1, 0>; } else { X.fn.x4[0] = k_fft_x4<0, 1>; X.fn.x4[1] = k_fft_x4<1, 1>; }
+  return 0;
+}
+// ... and its y pass
+static int y_pass(cales_ctx *c, Solver &s, SolvePath &P, const char *who) {
+  YPass &Y = P.yp; const int n2g = c->C.ng[1]; Y.tw = (const cpx *)s.twy; Y.twd = (const cpx *)s.twyd;
+  if (radix8_takes(c, n2g, P.ykind, s.pres.ykind, &Y.odd)) {
+    // Eight columns per block, sixteen elements per thread (k_fft_y16): 1024-point lines of either kind, 256- and 512-point Neumann lines (where the
+    // alternative is the staged k_fft_y8: 512 x 256 x 256 duct 0.39 / 0.42 -> 0.30 / 0.31 ms per step). Periodic 512-point lines stay with k_fft_y8r:
+    // measured 1.49 / 1.55 against 1.45 / 1.52 ms per step at 512^3 -- both sit at the copy rate of that access pattern (128-B segments at a pitch of 4224 B).
+    // "Neumann" is the PRESSURE's kind, and the velocity components inherit the choice: beside a pressure that is periodic in y, a component with Neumann y
+    // on 256- or 512-point lines takes k_fft_y8<., 1> (82 KB of LDS at 512 points), not k_fft_y16.
+    if (n2g == 1024 || (s.pres.ykind == 1 && (n2g == 512 || n2g == 256))) {
+      Y.k = YKernel::fft_y16; Y.threads = n2g / 2; Y.cols = 8;
+      Y.lds = ((size_t)n2g + 8 * ((size_t)n2g + 1)) * sizeof(cpx) + (size_t)n2g * sizeof(unsigned);
+      y16_kernels(n2g, P.ykind, Y.fn.y16); lds_attr(c, Y.fn.y16, 2, Y.lds); return 0; }
+    const int T = n2g / 8; int CB = std::max(1, std::min(std::max(8, 256 / T), 512 / T));
+    if (Y.odd) CB = CB >= 8 ? CB / 8 * 8 : 4;      // whole 128-B row segments; the longest lines (576, 640, 768 points) half ones, like 1024
+    while (CB > 1 && ((size_t)CB * (n2g + n2g / 8 + 1) + n2g) * sizeof(cpx) > 150 * 1024) CB /= 2;
+    Y.threads = CB * T; Y.cols = CB;
+    if (Y.odd || P.ykind) {      // the staged kernel: Neumann lines, and both kinds at the odd lengths (768-point lines: 4 columns need 66 KB)
+      Y.k = YKernel::fft_y8; Y.lds = ((size_t)CB * (n2g + n2g / 8 + 1) + n2g) * sizeof(cpx);
+      if (!Y.odd) { Y.fn.y8[0] = k_fft_y8<0, 1>; Y.fn.y8[1] = k_fft_y8<1, 1>; }
+      else if (P.ykind) { Y.fn.y8[0] = k_fft_y8<0, 1, 1>; Y.fn.y8[1] = k_fft_y8<1, 1, 1>; }
+      else { Y.fn.y8[0] = k_fft_y8<0, 0, 1>; Y.fn.y8[1] = k_fft_y8<1, 0, 1>; }
+      lds_attr(c, Y.fn.y8, 2, Y.lds);
+    } else {      // periodic lines: register ends, line pitch = 4 (mod 16) slots (512 points: 82 KB)
+      Y.k = YKernel::fft_y8r; Y.lds = ((size_t)CB * ((((n2g + n2g / 8) + 15) & ~15) + 4) + n2g) * sizeof(cpx);
+      Y.fn.y8r[0] = k_fft_y8r<0>; Y.fn.y8r[1] = k_fft_y8r<1>; lds_attr(c, Y.fn.y8r, 2, Y.lds);
+    }
+    return 0;
+  }
+  if (P.ykind >= 5) {      // along the component
+    Y.k = YKernel::dst1; const int N = dst1_points(P.ykind, n2g); real *tw = nullptr;
+    if (N < 2 || !make_plan(N, Y.plan) || (size_t)2 * (N + 1) * sizeof(cpx) > 150 * 1024) { c->err = "helmholtz: y line not supported by the face-centred transform kernel"; return 1; }
+    if (upload_twiddles(c, N, N, &tw)) return 1;
+    Y.tw = (const cpx *)tw; Y.lds = (size_t)2 * (N + 1) * sizeof(cpx); Y.fn.dst1[0] = Y.fn.dst1[1] = k_dst1<1>; lds_attr(c, Y.fn.dst1, 1, Y.lds); return 0; }
+  if (P.ykind >= 3) {      // DCT-IV / DST-IV (k_fft_y4): N/2-point lines, two per complex column -- the tables made by the first path that needs them
+    Y.k = YKernel::fft_y4; if (!make_plan(n2g / 2, Y.plan)) { c->err = std::string(who) + ": ng(2)/2 must factor into primes <= 127"; return 1; }
+    Y.lds = stockham_block(4, (size_t)2 * 2 * (n2g / 2 + 1) * sizeof(cpx), &Y.cols);
+    if (Y.lds > 64 * 1024) { c->err = std::string(who) + ": y line too long for the LDS-resident DCT-IV"; return 1; }
+    if (!s.tw4y && upload_dct4_weights(c, n2g, &s.tw4y)) return 1;
+    if (!s.twy4 && upload_twiddles(c, n2g / 2, n2g / 2, &s.twy4)) return 1;
+    Y.tw = (const cpx *)s.twy4; Y.twd = (const cpx *)s.tw4y; Y.fn.y4[0] = Y.fn.y4[1] = P.ykind == 3 ? k_fft_y4<0> : k_fft_y4<1>; return 0; }
+  Y.k = YKernel::fft_y;      // (the sign changes of the Dirichlet-Dirichlet transform live in this kernel only)
+  if (!make_plan(n2g, Y.plan)) { c->err = "solver: ng(1)/2 and ng(2) must factor into primes <= 127"; return 1; }
+  Y.lds = stockham_block(8, (size_t)2 * (n2g + 1) * sizeof(cpx), &Y.cols);
+  if (Y.lds > 64 * 1024) { c->err = "solver: line too long for the LDS-resident transform"; return 1; }
+  Y.fn.y[0] = k_fft_y<0>; Y.fn.y[1] = k_fft_y<1>; return 0;
+}
+// the kernels of a path whose kinds, nz, z condition and equation are set: the transform passes, then the z solve
+static int choose_kernels(cales_ctx *c, Solver &s, SolvePath &P, const char *who) {
+  if (x_pass(c, s, P) || y_pass(c, s, P, who)) return 1;
   const bool hasd = CBP(c, 0, 3) == 'D' || CBP(c, 1, 3) == 'D';
-  P.fixnull = (P.poisson && !hasd && !c->fl.keep_null_mode) ? 1 : 0;
-  P.refnull = P.poisson && !hasd && c->fl.keep_null_mode; P.null_switch = c->fl.keep_null_mode;
+  P.fixnull = (P.poisson && !hasd && !c->fl.keep_null_mode) ? 1 : 0; P.refnull = P.poisson && !hasd && c->fl.keep_null_mode; P.null_switch = c->fl.keep_null_mode;
   if (P.xkind && !P.ykind) P.zk = ZKernel::herm;      // real x modes paired into complex columns + periodic y: Hermitian separation of rows ky and N-ky
   else if ((P.periodic_z || P.fixnull || !P.poisson || hasd) && tile_takes(c, P.nz, P.periodic_z)) P.zk = ZKernel::tile;
   else if (P.xkind) P.zk = P.periodic_z ? ZKernel::periodic_real : ZKernel::ri;
   else P.zk = P.periodic_z ? ZKernel::periodic_cpx : ZKernel::ri;
+  return 0;
 }
 // ... and its tile, for a path whose kernels, nyq and cw are set: the instantiation, its extent, its LDS attribute, the table it reads
 static void tile_setup(cales_ctx *c, SolvePath &P, real *tab) {
@@ -2051,8 +2169,9 @@ static void tile_setup(cales_ctx *c, SolvePath &P, real *tab) {
 // peer blocks of the path's all-to-all would not fit what the staging buffers were sized for (StageLayout::a2a)
 static int solve_sched(cales_ctx *c, const SolvePath &P, SolveSched &D) {
   D = SolveSched();
-  const int *n = c->n, mh = n[0] / 2 + 1, n2g = c->C.ng[1], nh = c->C.ng[0] / 2, cw = P.cw, Rx8 = P.xrows, CB8 = P.ycols;
-  const bool dist = c->P > 1, use8x = P.xk == XKernel::fft_x8, use8y = radix8_y(P.yk), use16y = P.yk == YKernel::fft_y16;
+  const int *n = c->n, mh = n[0] / 2 + 1, n2g = c->C.ng[1], nh = c->C.ng[0] / 2, cw = P.cw;
+  const bool dist = c->P > 1, use8x = P.xp.k == XKernel::fft_x8, use8y = radix8_y(P.yp.k), use16y = P.yp.k == YKernel::fft_y16;
+  const int Rx8 = use8x ? P.xp.rows : 1, CB8 = use8y ? P.yp.cols : 1;      // rows per block of k_fft_x8, columns per block of the radix-8 y kernels
   if (dist) { D.slab_spec = reinterpret_cast<real2 *>(c->comm.A); D.mode_spec = reinterpret_cast<real2 *>(c->comm.B); }
   D.nmodes = P.nyq ? n[0] / 2 : mh; D.ncol = dist ? cw : D.nmodes; D.mofs = dist ? c->rank * cw : 0;
   // real x modes (Neumann in x) fill the complex columns 0 .. n1/2 - 1: the slot of "mode n1/2" is never written by the x pass nor read back by it
@@ -2109,85 +2228,23 @@ int solver_comm_changed(cales_ctx *c) {
   for (int iv = 0; iv < 3; ++iv) if (s->vel_state[iv] == 1 && solve_sched(c, s->vel[iv], s->sched_vel[iv])) return 1;
   ctx_free(c, s->d_mpart); s->d_mpart = nullptr;
   const bool forced = c->C.is_forced[0] || c->C.is_forced[1] || c->C.is_forced[2];
-  return (forced && s->pres.xk == XKernel::fft_x8) ? ctx_alloc(c, &s->d_mpart, 3 * (size_t)s->sched_pres.npart, false) : 0;
+  return (forced && s->pres.xp.k == XKernel::fft_x8) ? ctx_alloc(c, &s->d_mpart, 3 * (size_t)s->sched_pres.npart, false) : 0;
 }
 
 int solver_setup(cales_ctx *c) {
   Solver &s = *(c->solver = new Solver());
   SolvePath &P = s.pres;
   const int *n = c->n; const int n1 = c->C.ng[0], n2g = c->C.ng[1], n3 = n[2];
-  const std::string bx = std::string(1, c->C.cbcpre[0]) + c->C.cbcpre[1], by = std::string(1, c->C.cbcpre[2]) + c->C.cbcpre[3];
-  // transform kinds of the cell-centred pressure (fft.f90:192-245): 0 PP (R2HC/HC2R), 1 NN (REDFT10/01), 2 DD (RODFT10/01), 3 ND (REDFT11), 4 DN (RODFT11)
-  auto kind_of = [](const std::string &b) { return b == "PP" ? 0 : b == "NN" ? 1 : b == "DD" ? 2 : b == "ND" ? 3 : b == "DN" ? 4 : -1; };
-  P.xkind = kind_of(bx); P.ykind = kind_of(by);
+  // transform kinds of the cell-centred pressure
+  P.xkind = line_kind(&c->C.cbcpre[0], false); P.ykind = line_kind(&c->C.cbcpre[2], false);
   if (P.xkind < 0 || P.ykind < 0) { c->err = "solver: unknown pressure BC pair in x or y"; return 1; }
   if (P.ykind >= 3 && (n2g % 2)) { c->err = "solver: ND/DN in y need an even ng(2)"; return 1; }
   if (P.xkind && c->C.cbcpre[4] == 'P' && (!P.ykind || c->P > 1)) { c->err = "solver: a non-periodic x with periodic z needs a non-periodic y and one rank"; return 1; }
-  if (!make_plan(n1 / 2, s.px) || !make_plan(n2g, s.py)) { c->err = "solver: ng(1)/2 and ng(2) must factor into primes <= 127"; return 1; }
-  // rows per block in x: aim at ~nh/4 threads per row, 256 threads per block
-  { int T = std::max(1, std::min(256, (n1 / 2) / 4)); int p2 = 1; while (p2 * 2 <= T) p2 *= 2; T = p2; s.Rx = 256 / T; }
-  s.shx = (size_t)s.Rx * 2 * (n1 / 2 + 1) * sizeof(cpx);
-  while (s.shx > 60 * 1024 && s.Rx > 1) { s.Rx /= 2; s.shx = (size_t)s.Rx * 2 * (n1 / 2 + 1) * sizeof(cpx); }
-  s.CBy = 8;
-  s.shy = (size_t)s.CBy * 2 * (n2g + 1) * sizeof(cpx);
-  while (s.shy > 60 * 1024 && s.CBy > 1) { s.CBy /= 2; s.shy = (size_t)s.CBy * 2 * (n2g + 1) * sizeof(cpx); }
-  if (s.shx > 64 * 1024 || s.shy > 64 * 1024) { c->err = "solver: line too long for the LDS-resident transform"; return 1; }
-  // power-of-two lines take the radix-8 register kernels
-  auto pow2 = [](int v) { return v >= 16 && (v & (v - 1)) == 0; };
-  // ... and so do lines of 3, 5, 9 times 2^p, p >= 3, from 48 points on (CALES_FFT_NO_ODD_RADIX: those stay with the Stockham kernels)
-  auto odd_of = [&](int v) { int r = v, p = 0; while (r % 2 == 0) { r /= 2; ++p; } return (!c->fl.fft_no_odd_radix && (r == 3 || r == 5 || r == 9) && p >= 3 && v >= 48 && v <= 1024) ? r : 0; };
-  s.xodd = P.xkind <= 1 ? odd_of(n1 / 2) : 0; s.yodd = P.ykind <= 1 ? odd_of(n2g) : 0;
-  s.x8 = ((pow2(n1 / 2) && n1 / 2 <= 1024) || s.xodd) && P.xkind <= 1; s.y8 = (pow2(n2g) && n2g <= 1024) || s.yodd;
-  if (s.x8) { const int T = (n1 / 2) / 8; s.x8_threads = T >= 256 ? T : (256 / T) * T;
-              s.shx8 = ((size_t)(s.x8_threads / T) * (n1 / 2 + n1 / 16 + 2) + (n1 + 1) + (P.xkind ? n1 / 2 + 1 : 0)) * sizeof(cpx);
-              if (s.xodd && s.shx8 > 64 * 1024) {      // 768-point Neumann rows
-#define X8_ATTR(...) HIPSOFT(c, hipFuncSetAttribute((const void *)k_fft_x8<__VA_ARGS__>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)s.shx8))
-                X8_ATTR(0, 0, 0, 1); X8_ATTR(1, 0, 0, 1); X8_ATTR(0, 0, 1, 1); X8_ATTR(0, 1, 0, 1); X8_ATTR(1, 1, 0, 1); X8_ATTR(0, 1, 1, 1);
-#undef X8_ATTR
-              } }
-  if (s.y8) { const int T = n2g / 8; int CB = std::max(1, std::min(std::max(8, 256 / T), 512 / T));
-              if (s.yodd) CB = CB >= 8 ? CB / 8 * 8 : 4;      // whole 128-B row segments; the longest lines (576, 640, 768 points) half ones, like 1024
-              while (CB > 1 && ((size_t)CB * (n2g + n2g / 8 + 1) + n2g) * sizeof(cpx) > 150 * 1024) CB /= 2;
-              s.y8_threads = CB * T; s.shy8 = ((size_t)CB * (n2g + n2g / 8 + 1) + n2g) * sizeof(cpx);
-              s.shy8r = ((size_t)CB * ((((n2g + n2g / 8) + 15) & ~15) + 4) + n2g) * sizeof(cpx);      // k_fft_y8r: line pitch = 4 (mod 16) slots
-              if (s.shy8r > 64 * 1024) { HIPSOFT(c, hipFuncSetAttribute((const void *)k_fft_y8r<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)s.shy8r));
-                                         HIPSOFT(c, hipFuncSetAttribute((const void *)k_fft_y8r<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)s.shy8r)); }
-              if (s.yodd && s.shy8 > 64 * 1024) {      // 768-point lines: 4 columns need 66 KB
-                HIPSOFT(c, hipFuncSetAttribute((const void *)k_fft_y8<0, 0, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)s.shy8));
-                HIPSOFT(c, hipFuncSetAttribute((const void *)k_fft_y8<1, 0, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)s.shy8));
-                HIPSOFT(c, hipFuncSetAttribute((const void *)k_fft_y8<0, 1, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)s.shy8));
-                HIPSOFT(c, hipFuncSetAttribute((const void *)k_fft_y8<1, 1, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)s.shy8));
-              } else
-              if (s.shy8 > 64 * 1024) {      // n2 = 1024: 4 columns (64-B row segments) need 90 KB of LDS
-                HIPSOFT(c, hipFuncSetAttribute((const void *)k_fft_y8<0, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)s.shy8));
-                HIPSOFT(c, hipFuncSetAttribute((const void *)k_fft_y8<1, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)s.shy8)); } }
-  // eight columns per block, sixteen elements per thread (k_fft_y16): 1024-point lines of either kind, 256- and 512-point Neumann lines (where the
-  // alternative is the staged k_fft_y8: 512 x 256 x 256 duct 0.39 / 0.42 -> 0.30 / 0.31 ms per step). Periodic 512-point lines stay with k_fft_y8r:
-  // measured 1.49 / 1.55 against 1.45 / 1.52 ms per step at 512^3 -- both sit at the copy rate of that access pattern (128-B segments at a pitch of 4224 B)
-  s.y16 = s.y8 && P.ykind <= 1 && (n2g == 1024 || (P.ykind == 1 && (n2g == 512 || n2g == 256)));
-  if (s.y16) {
-    s.shy16 = ((size_t)n2g + 8 * ((size_t)n2g + 1)) * sizeof(cpx) + (size_t)n2g * sizeof(unsigned);
-    if (s.shy16 > 64 * 1024) {
-#define Y16_ATTR(NN) do { HIPSOFT(c, hipFuncSetAttribute((const void *)k_fft_y16<NN, 0, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)s.shy16)); \
-                          HIPSOFT(c, hipFuncSetAttribute((const void *)k_fft_y16<NN, 1, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)s.shy16)); \
-                          HIPSOFT(c, hipFuncSetAttribute((const void *)k_fft_y16<NN, 0, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)s.shy16)); \
-                          HIPSOFT(c, hipFuncSetAttribute((const void *)k_fft_y16<NN, 1, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)s.shy16)); } while (0)
-      if (n2g == 1024) Y16_ATTR(1024); else Y16_ATTR(512);
-#undef Y16_ATTR
-    }
-  }
-  if (P.ykind >= 3) { if (dct4_y_setup(c, s, "solver")) return 1; s.y8 = false; }
-  if (P.ykind == 2) s.y8 = false;      // the sign changes of the Dirichlet-Dirichlet transform live in the generic y kernel only
-  if (c->fl.fft_generic) s.x8 = s.y8 = false;
-  if (!s.x8) s.xodd = 0;
-  if (!s.y8) s.yodd = 0;
-  if (!s.y8) s.y16 = false;
-  // eigenvalues (initsolver.f90:66-98); x: modes 0..n1/2 (half-complex symmetry), y: modes 0..n2-1
-  std::vector<real> lx(n1 + 2, 0.), ly(n2g);
-  hs_eigenvalues(n1, bx.c_str(), 'c', lx.data()); hs_eigenvalues(n2g, by.c_str(), 'c', ly.data());
-  for (auto &v : lx) v = v * (c->dli[0] * c->dli[0]);
-  for (auto &v : ly) v = v * (c->dli[1] * c->dli[1]);
-  if (P.ykind == 2) std::reverse(ly.begin(), ly.end());      // row r of the transformed field holds coefficient N-1-r (see k_fft_y)
+  if (upload_twiddles(c, n1 / 2, n1 / 2, &s.twx)) return 1;
+  if (upload_twiddles(c, n1, n1 / 2 + 1, &s.twx_post)) return 1;
+  if (upload_twiddles(c, n2g, n2g, &s.twy)) return 1;
+  if (upload_twiddles(c, 4 * n1, n1 / 2 + 1, &s.twy_post)) return 1;      // DCT weights e^{-i pi k/(2 n1)}, k = 0..n1/2 (x)
+  if (upload_twiddles(c, 4 * n2g, n2g, &s.twyd)) return 1;               // e^{-i pi k/(2 n2)}, k = 0..n2-1 (y)
   const int mh = n1 / 2 + 1;
   c->cw = (mh + c->P - 1) / c->P;                            // complex mode columns per rank (last block padded)
   // rows of the mode-block layout in whole 128-B lines (cw a multiple of 8) where the padding columns -- they travel in the all-to-all -- add 6 % or less: the y
@@ -2197,14 +2254,15 @@ int solver_setup(cales_ctx *c) {
   if (c->P > 1) { const int cw8 = (c->cw + 7) / 8 * 8; if (100 * (cw8 - c->cw) <= 6 * c->cw && (size_t)cw8 * n2g * n3 <= c->ntot) c->cw = cw8; }
   if (c->P > 1 && (size_t)c->cw * n2g * n3 > c->ntot) { c->err = "solver: scratch too small for the mode-block layout"; return 1; }
   P.nz = n3; P.periodic_z = CBP(c, 0, 3) == 'P' && CBP(c, 1, 3) == 'P'; P.poisson = true;
-  choose_kernels(c, s, P);
+  if (choose_kernels(c, s, P, "solver")) return 1;
   // Nyquist packing of the pressure solve (k_gaussel_nyq): periodic x, periodic or Neumann y (the pair is separated by the Hermitian pairing of rows / by real and
   // imaginary part), radix-8 passes, the z solve in the LDS tile; n1/2 mode columns instead of n1/2 + 1
   { const bool hasd = CBP(c, 0, 3) == 'D' || CBP(c, 1, 3) == 'D';
-    P.nyq = P.xkind == 0 && P.ykind <= 1 && s.x8 && s.y8 && !P.periodic_z && (hasd || !c->fl.keep_null_mode) && tile_takes(c, n3, false) && !c->fl.no_nyquist_packing;
+    P.nyq = P.xkind == 0 && P.ykind <= 1 && P.xp.k == XKernel::fft_x8 && radix8_y(P.yp.k) && !P.periodic_z && (hasd || !c->fl.keep_null_mode) && tile_takes(c, n3, false) && !c->fl.no_nyquist_packing;
     if (P.nyq && P.zk != ZKernel::tile) { c->err = "solver: the packed mode column needs the z solve in the LDS tile"; return 1; }
     P.cw = P.nyq ? (n1 / 2 + c->P - 1) / c->P : c->cw; }
-  if (ctx_upload(c, &P.lamx, lx) || ctx_upload(c, &P.lamy, ly)) return 1;
+  { double nx, ny;      // find_fft norm = [1,0] (PP) / [2,0] (NN)
+    if (line_spectrum(c, 0, &c->C.cbcpre[0], false, P.xkind, &P.lamx, &nx) || line_spectrum(c, 1, &c->C.cbcpre[2], false, P.ykind, &P.lamy, &ny)) return 1; P.normfft = 1. / (nx * ny); }
   // tridiagonal (initsolver.f90:127-169), pressure: cell-centred
   std::vector<real> abc(3 * (size_t)n3);      // a | b | c
   hs_tridmatrix(&c->C.cbcpre[4], n3, c->dzci.data(), c->dzfi.data(), 'c', abc.data(), abc.data() + n3, abc.data() + 2 * n3);
@@ -2216,13 +2274,6 @@ int solver_setup(cales_ctx *c) {
     tile_table(c, P.zt.M, P.zt.PER ? n3 - 1 : n3, s.d_a, s.d_b, s.d_c, s.tab_pres);
   }
   if (P.refnull && ctx_alloc(c, &s.d_nullw, (size_t)5 * (n3 + 2), false)) return 1;
-  P.normfft = 1. / ((P.xkind ? 2. : 1.) * (real)n1 * (P.ykind ? 2. : 1.) * (real)n2g);   // fft.f90:99,136,142; find_fft norm = [1,0] (PP) / [2,0] (NN)
-  if (upload_twiddles(c, n1 / 2, n1 / 2, &s.twx)) return 1;
-  if (upload_twiddles(c, n1, n1 / 2 + 1, &s.twx_post)) return 1;
-  if (upload_twiddles(c, n2g, n2g, &s.twy)) return 1;
-  if (upload_twiddles(c, 4 * n1, n1 / 2 + 1, &s.twy_post)) return 1;      // DCT weights e^{-i pi k/(2 n1)}, k = 0..n1/2 (x)
-  if (upload_twiddles(c, 4 * n2g, n2g, &s.twyd)) return 1;               // e^{-i pi k/(2 n2)}, k = 0..n2-1 (y)
-  if (P.xkind >= 3 && upload_dct4_weights(c, n1, &s.tw4x)) return 1;    // DCT-IV weights (k_fft_x4)
   if (!c->C.impdiff) return 0;      // (the schedules: solver_comm_changed, once cales_create has laid the staging buffers out)
   for (int iv = 0; iv < 3; ++iv) {
     hs_tridmatrix(&c->cbcvel[6 * iv + 4], n3, c->dzci.data(), c->dzfi.data(), iv == 2 ? 'f' : 'c', abc.data(), abc.data() + n3, abc.data() + 2 * n3);
@@ -2306,59 +2357,33 @@ __global__ void k_null_column(Geom g, Spec S, int nz, int periodic, const real *
 // The transform passes of a path over chunk ch of its schedule. x: the chunk's rows, the radix-8 kernel in the schedule's blocks and row groups per block;
 // F (forward only): the pass forms pp = div(u*)/dtrk itself (fillps). y: the chunk's planes, the radix-8 kernels D.ykc planes per block.
 // The other kernels take the whole field in a geometry of their own (their schedules have one chunk).
-template <int INV, int KIND, int FILL>
-static void launch_x8(cales_ctx *c, const Solver &s, bool odd, unsigned blocks, int iters, real *pp, real scale, const Spec &S, real2 *spec, const FillArgs &F, long rb, long re) {
-  if (odd) LAUNCH(c, (k_fft_x8<INV, KIND, FILL, 1>), dim3(blocks), dim3(s.x8_threads), s.shx8, c->stream, c->g, c->C.ng[0] / 2, iters, (const cpx *)s.twx, (const cpx *)s.twx_post,
-         (const cpx *)s.twy_post, pp, scale, S, spec, F, rb, re);
-  else LAUNCH(c, (k_fft_x8<INV, KIND, FILL>), dim3(blocks), dim3(s.x8_threads), s.shx8, c->stream, c->g, c->C.ng[0] / 2, iters, (const cpx *)s.twx, (const cpx *)s.twx_post,
-         (const cpx *)s.twy_post, pp, scale, S, spec, F, rb, re);
-}
 template <int INV>
 static void fft_x(cales_ctx *c, const SolvePath &P, const SolveSched &D, int ch, real *pp, const FillArgs *F = nullptr) {
-  const Solver &s = *c->solver;
+  const XPass &X = P.xp;
   const real scale = INV ? P.normfft : (real)1.;
   const long nrows = (long)c->n[1] * c->n[2], rb = D.rows * ch, re = rb + D.rows; const unsigned blocks = INV ? D.xblk_b : D.xblk_f; const int iters = INV ? D.xit_b : D.xit_f;
-  const dim3 gx((unsigned)((nrows + s.Rx - 1) / s.Rx));
+  const dim3 gx((unsigned)((nrows + X.rows - 1) / X.rows));
   const Spec &S = D.S; real2 *spec = spec_of(D.slab_spec, pp);
-  if (P.xk == XKernel::fft_x8) {
-    if constexpr (INV == 0) if (F) { if (P.xkind) launch_x8<0, 1, 1>(c, s, P.xodd != 0, blocks, iters, pp, scale, S, spec, *F, rb, re); else launch_x8<0, 0, 1>(c, s, P.xodd != 0, blocks, iters, pp, scale, S, spec, *F, rb, re); return; }
-    if (P.xkind) launch_x8<INV, 1, 0>(c, s, P.xodd != 0, blocks, iters, pp, scale, S, spec, FillArgs{}, rb, re); else launch_x8<INV, 0, 0>(c, s, P.xodd != 0, blocks, iters, pp, scale, S, spec, FillArgs{}, rb, re);
-  } else if (P.xk == XKernel::dst1)
-    LAUNCH(c, k_dst1<2 * INV>, dim3((unsigned)nrows), dim3(256), (size_t)2 * (P.p1x.N + 1) * sizeof(cpx), c->stream, c->g, P.p1x, 0, (const cpx *)P.tw1x, pp, scale, S, spec, P.xkind, INV);
-  else if (P.xk == XKernel::fft_x4 && P.xkind == 3) LAUNCH(c, (k_fft_x4<INV, 0>), gx, dim3(256), s.shx, c->stream, c->g, s.px, s.Rx, (const cpx *)s.twx, (const cpx *)s.tw4x, pp, scale, S, spec);
-  else if (P.xk == XKernel::fft_x4) LAUNCH(c, (k_fft_x4<INV, 1>), gx, dim3(256), s.shx, c->stream, c->g, s.px, s.Rx, (const cpx *)s.twx, (const cpx *)s.tw4x, pp, scale, S, spec);
-  else LAUNCH(c, k_fft_x<INV>, gx, dim3(256), s.shx, c->stream, c->g, s.px, s.Rx, P.xkind, (const cpx *)s.twx, (const cpx *)s.twx_post, (const cpx *)s.twy_post, pp, scale, S, spec);
-}
-template <int INV, int KIND, int N = 1024>      // N: the line length, 1024, 512 or 256 points
-static void fft_y16(cales_ctx *c, const Solver &s, dim3 gy, int ncols, int kchunk, const Spec &S, real2 *spec, int k0, int k1) {
-  if constexpr (N > 256) if (c->C.ng[1] < N) return fft_y16<INV, KIND, N / 2>(c, s, gy, ncols, kchunk, S, spec, k0, k1);
-  LAUNCH(c, (k_fft_y16<N, INV, KIND>), gy, dim3(N / 2), s.shy16, c->stream, c->g, ncols, kchunk, (const cpx *)s.twy, (const cpx *)s.twyd, S, spec, k0, k1);
+  switch (X.k) {
+  case XKernel::fft_x8: { const FftX8 k_fft_x8_form = X.fn.x8[(F && !INV) ? 2 : INV]; LAUNCH(c, k_fft_x8_form, dim3(blocks), dim3(X.threads), X.lds, c->stream, c->g, c->C.ng[0] / 2, iters, X.tw, X.twp, X.twd, pp, scale, S, spec, (F && !INV) ? *F : FillArgs{}, rb, re); break; }
+  case XKernel::dst1: { const Dst1 k_dst1_form = X.fn.dst1[INV]; LAUNCH(c, k_dst1_form, dim3((unsigned)nrows), dim3(X.threads), X.lds, c->stream, c->g, X.plan, 0, X.tw, pp, scale, S, spec, P.xkind, INV); break; }
+  case XKernel::fft_x4: { const FftX4 k_fft_x4_form = X.fn.x4[INV]; LAUNCH(c, k_fft_x4_form, gx, dim3(X.threads), X.lds, c->stream, c->g, X.plan, X.rows, X.tw, X.twp, pp, scale, S, spec); break; }
+  case XKernel::fft_x: { const FftX k_fft_x_form = X.fn.x[INV]; LAUNCH(c, k_fft_x_form, gx, dim3(X.threads), X.lds, c->stream, c->g, X.plan, X.rows, P.xkind, X.tw, X.twp, X.twd, pp, scale, S, spec); break; }
+  }
 }
 template <int INV>
 static void fft_y(cales_ctx *c, const SolvePath &P, const SolveSched &D, int ch, real *pp) {
-  const Solver &s = *c->solver;
+  const YPass &Y = P.yp;
   const int n2g = c->C.ng[1], n3 = c->n[2], ncol = D.ncol, ncol_y = D.ncol_y, kchunk = D.ykc, k0 = D.kpc * ch, k1 = k0 + D.kpc;
-  const dim3 gy((ncol_y + P.ycols - 1) / P.ycols, (D.kpc + kchunk - 1) / kchunk);
+  const unsigned gk = (D.kpc + kchunk - 1) / kchunk; const dim3 gw((ncol + Y.cols - 1) / Y.cols, n3);      // blocks over the chunk's planes | the whole field
   const Spec &S = D.S; real2 *spec = spec_of(D.mode_spec, pp);
-  switch (P.yk) {
-  case YKernel::dst1:
-    LAUNCH(c, k_dst1<1>, dim3(ncol, n3), dim3(256), (size_t)2 * (P.p1y.N + 1) * sizeof(cpx), c->stream, c->g, P.p1y, ncol, (const cpx *)P.tw1y, pp, 1., S, spec, P.ykind, INV); break;
-  case YKernel::fft_y4:
-    if (P.ykind == 3) LAUNCH(c, k_fft_y4<0>, dim3((ncol + s.CBy4 - 1) / s.CBy4, n3), dim3(256), s.shy4, c->stream, c->g, s.py4, s.CBy4, ncol, (const cpx *)s.twy4, (const cpx *)s.tw4y, S, spec);
-    else LAUNCH(c, k_fft_y4<1>, dim3((ncol + s.CBy4 - 1) / s.CBy4, n3), dim3(256), s.shy4, c->stream, c->g, s.py4, s.CBy4, ncol, (const cpx *)s.twy4, (const cpx *)s.tw4y, S, spec);
-    break;
-  case YKernel::fft_y16:
-    if (P.ykind) fft_y16<INV, 1>(c, s, gy, ncol_y, kchunk, S, spec, k0, k1); else fft_y16<INV, 0>(c, s, gy, ncol_y, kchunk, S, spec, k0, k1);
-    break;
-  case YKernel::fft_y8:
-    if (P.yodd && P.ykind) LAUNCH(c, (k_fft_y8<INV, 1, 1>), gy, dim3(s.y8_threads), s.shy8, c->stream, c->g, n2g, ncol_y, kchunk, (const cpx *)s.twy, (const cpx *)s.twyd, S, spec, k0, k1);
-    else if (P.yodd) LAUNCH(c, (k_fft_y8<INV, 0, 1>), gy, dim3(s.y8_threads), s.shy8, c->stream, c->g, n2g, ncol_y, kchunk, (const cpx *)s.twy, (const cpx *)s.twyd, S, spec, k0, k1);
-    else
-    LAUNCH(c, (k_fft_y8<INV, 1>), gy, dim3(s.y8_threads), s.shy8, c->stream, c->g, n2g, ncol_y, kchunk, (const cpx *)s.twy, (const cpx *)s.twyd, S, spec, k0, k1); break;
-  case YKernel::fft_y8r:
-    LAUNCH(c, (k_fft_y8r<INV>), dim3((ncol + P.ycols - 1) / P.ycols, gy.y), dim3(s.y8_threads), s.shy8r, c->stream, c->g, n2g, ncol, kchunk, (const cpx *)s.twy, S, spec, k0, k1); break;
-  case YKernel::fft_y:
-    LAUNCH(c, k_fft_y<INV>, dim3((ncol + s.CBy - 1) / s.CBy, n3), dim3(256), s.shy, c->stream, c->g, s.py, s.CBy, ncol, P.ykind, (const cpx *)s.twy, (const cpx *)s.twyd, S, spec); break;
+  switch (Y.k) {
+  case YKernel::dst1: { const Dst1 k_dst1_form = Y.fn.dst1[INV]; LAUNCH(c, k_dst1_form, gw, dim3(Y.threads), Y.lds, c->stream, c->g, Y.plan, ncol, Y.tw, pp, (real)1., S, spec, P.ykind, INV); break; }
+  case YKernel::fft_y4: { const FftY4 k_fft_y4_form = Y.fn.y4[INV]; LAUNCH(c, k_fft_y4_form, gw, dim3(Y.threads), Y.lds, c->stream, c->g, Y.plan, Y.cols, ncol, Y.tw, Y.twd, S, spec); break; }
+  case YKernel::fft_y16: { const FftY16 k_fft_y16_form = Y.fn.y16[INV]; LAUNCH(c, k_fft_y16_form, dim3((ncol_y + Y.cols - 1) / Y.cols, gk), dim3(Y.threads), Y.lds, c->stream, c->g, ncol_y, kchunk, Y.tw, Y.twd, S, spec, k0, k1); break; }
+  case YKernel::fft_y8: { const FftY8 k_fft_y8_form = Y.fn.y8[INV]; LAUNCH(c, k_fft_y8_form, dim3((ncol_y + Y.cols - 1) / Y.cols, gk), dim3(Y.threads), Y.lds, c->stream, c->g, n2g, ncol_y, kchunk, Y.tw, Y.twd, S, spec, k0, k1); break; }
+  case YKernel::fft_y8r: { const FftY8r k_fft_y8r_form = Y.fn.y8r[INV]; LAUNCH(c, k_fft_y8r_form, dim3((ncol + Y.cols - 1) / Y.cols, gk), dim3(Y.threads), Y.lds, c->stream, c->g, n2g, ncol, kchunk, Y.tw, S, spec, k0, k1); break; }
+  case YKernel::fft_y: { const FftY k_fft_y_form = Y.fn.y[INV]; LAUNCH(c, k_fft_y_form, gw, dim3(Y.threads), Y.lds, c->stream, c->g, Y.plan, Y.cols, ncol, P.ykind, Y.tw, Y.twd, S, spec); break; }
   }
 }
 
@@ -2379,7 +2404,7 @@ static int solve_field(cales_ctx *c, const SolvePath &P, const SolveSched &D, re
   auto wait_for = [&](int ch) -> int { if (arrived[ch]) HIPCHK(c, hipStreamWaitEvent(c->stream, arrived[ch], 0)); return 0; };
   // fillps inside the forward x transform; the bulk means it sums: several ranks all-reduce them on the context's stream, and RCCL orders the operations of
   // one communicator across streams -- issued between the chunk exchanges it would hold the y transforms back, so the pipelined solve reduces them after the z sweep
-  const bool fill = P.poisson && ff.dtrki != 0. && P.xk == XKernel::fft_x8; FillArgs F{};
+  const bool fill = P.poisson && ff.dtrki != 0. && P.xp.k == XKernel::fft_x8; FillArgs F{};
   if (fill) {
     F = FillArgs{c->f[CALES_U], c->f[CALES_V], c->f[CALES_W], c->d_dzfi, ff.dtrki, ff.dtrki * c->dli[0], ff.dtrki * c->dli[1], ff.mean_mask, c->d_gvr_f, c->d_gvr_c, c->solver->d_mpart};
     F.xwrap = c->step_xskip ? c->n[0] : 0; F.pstride = D.npart;
@@ -2414,13 +2439,13 @@ static int solve_field(cales_ctx *c, const SolvePath &P, const SolveSched &D, re
 // face-centred kinds, for the planes per lane of its tile and for the persistent tile.
 static std::string path_name(const SolvePath &P, bool every) {
   static const char *kinds[] = {"PP", "NN", "DD", "ND", "DN", "DDf", "NNf", "DNf"};      // 5..7: along the component (RODFT00 | REDFT00 | RODFT01/10)
-  std::string s = std::string("x:") + kinds[P.xkind] + (P.xk == XKernel::fft_x8 ? "/radix8" : P.xk == XKernel::fft_x4 ? "/dct4" : (every && P.xk == XKernel::dst1) ? "/face_centred" : "/mixed_radix");
-  if (P.xodd) s += "x" + std::to_string(P.xodd);
+  std::string s = std::string("x:") + kinds[P.xkind] + (P.xp.k == XKernel::fft_x8 ? "/radix8" : P.xp.k == XKernel::fft_x4 ? "/dct4" : (every && P.xp.k == XKernel::dst1) ? "/face_centred" : "/mixed_radix");
+  if (P.xp.odd) s += "x" + std::to_string(P.xp.odd);
   s += std::string(",y:") + kinds[P.ykind];
-  if (every && P.yk == YKernel::fft_y16) s += "/radix8_16_per_thread";
-  else if (every && P.yk == YKernel::dst1) s += "/face_centred";
-  else if (every && radix8_y(P.yk)) s += P.yodd ? "/radix8x" + std::to_string(P.yodd) : P.yk == YKernel::fft_y8 ? "/radix8" : "/radix8_register_ends";
-  else s += radix8_y(P.yk) ? (P.yodd ? "/radix8x" + std::to_string(P.yodd) : P.ykind ? "/radix8" : "/radix8_register_ends") : P.yk == YKernel::fft_y4 ? "/dct4" : "/mixed_radix";
+  if (every && P.yp.k == YKernel::fft_y16) s += "/radix8_16_per_thread";
+  else if (every && P.yp.k == YKernel::dst1) s += "/face_centred";
+  else if (every && radix8_y(P.yp.k)) s += P.yp.odd ? "/radix8x" + std::to_string(P.yp.odd) : P.yp.k == YKernel::fft_y8 ? "/radix8" : "/radix8_register_ends";
+  else s += radix8_y(P.yp.k) ? (P.yp.odd ? "/radix8x" + std::to_string(P.yp.odd) : P.ykind ? "/radix8" : "/radix8_register_ends") : P.yp.k == YKernel::fft_y4 ? "/dct4" : "/mixed_radix";
   s += std::string(",z:") + (P.zk == ZKernel::herm ? "thomas_hermitian" : P.zk == ZKernel::tile ? (P.zt.PER ? "lds_tile_periodic" : "lds_tile")
                              : (every && P.zk == ZKernel::periodic_real) ? "thomas_periodic_real" : (every && P.zk == ZKernel::periodic_cpx) ? "thomas_periodic_complex" : "thomas_march");
   if (every && P.zk == ZKernel::tile) s += P.zt.persistent ? "_persistent" : "_m" + std::to_string(P.zt.M);
@@ -2533,53 +2558,21 @@ int op_helmholtz_z(cales_ctx *c, int ivel, real alpha, bool fused, real hf12) {
 
 // 3-D implicit diffusion (_IMPDIFF without _IMPDIFF_1D, main.f90:423-491): (1 + alpha L) q = q* by the same transforms as the
 // pressure solve, with the transform set of the velocity component: kinds, eigenvalues and normalisation follow its BC pairs and its
-// staggering (initsolver.f90:66-98, find_fft with c_or_f, fft.f90:192-245):
-//   across the component ('c'):  PP 0 | NN 1 (REDFT10/01) | DD 2 (RODFT10/01) | ND 3 (REDFT11) | DN 4 (RODFT11)      -- the pressure's kernels
-//   along it ('f'):              PP 0 | NN 6 (REDFT00) | DD 5 (RODFT00, one unknown less) | ND 1 (REDFT10/01) | DN 7 (RODFT01 / RODFT10)
+// staggering (initsolver.f90:66-98, find_fft with c_or_f; line_kind: across the component the pressure's kinds and kernels, along it the face-centred ones).
 // Built on first use. (As in the reference, the face-centred NN and ND sets are not exact inverses of the discrete operator -- REDFT00 of n
 // points goes with eigenvalues of period n, REDFT10 with half-integer ones; measured on the oracle: residual of (1 + alpha L) x = r of a
 // few per cent -- while PP, DD and DN are exact to round-off. They are provided because the reference provides them.)
 static int velocity_path(cales_ctx *c, Solver &s, int iv, SolvePath &V) {
-  const int n1 = c->C.ng[0], n2g = c->C.ng[1];
-  const char *bc = &c->cbcvel[6 * iv];
-  auto kind = [&](int d) -> int {
-    const std::string b = std::string(1, bc[2 * d]) + bc[2 * d + 1];
-    const bool own = d == iv;
-    if (b == "PP") return 0;
-    if (b == "NN") return own ? 6 : 1;
-    if (b == "DD") return own ? 5 : 2;
-    if (b == "ND") return own ? 1 : 3;
-    if (b == "DN") return own ? 7 : 4;
-    return -1;
-  };
-  V.xkind = kind(0); V.ykind = kind(1);
+  const int n2g = c->C.ng[1]; const char *bc = &c->cbcvel[6 * iv], *bcz = bc + 4;
+  V.xkind = line_kind(bc, iv == 0); V.ykind = line_kind(bc + 2, iv == 1);
   if (V.xkind < 0 || V.ykind < 0) { c->err = "helmholtz: unknown velocity BC pair in x or y"; return 1; }
-  if (V.xkind && !V.ykind && c->cbcvel[6 * iv + 4] == 'P') { c->err = "helmholtz: non-periodic x with periodic y and z is not provided"; return 1; }
-  if (V.xkind && c->cbcvel[6 * iv + 4] == 'P' && c->P > 1) { c->err = "helmholtz: a non-periodic x with periodic z needs one rank"; return 1; }
+  if (V.xkind && !V.ykind && bcz[0] == 'P') { c->err = "helmholtz: non-periodic x with periodic y and z is not provided"; return 1; }
+  if (V.xkind && bcz[0] == 'P' && c->P > 1) { c->err = "helmholtz: a non-periodic x with periodic z needs one rank"; return 1; }
   if ((V.ykind == 3 || V.ykind == 4) && (n2g % 2)) { c->err = "helmholtz: ND/DN in y need an even ng(2)"; return 1; }
-  std::vector<real> lx(n1 + 2, 0.), ly(n2g);
-  const std::string bx = std::string(1, bc[0]) + bc[1], by = std::string(1, bc[2]) + bc[3];
-  hs_eigenvalues(n1, bx.c_str(), iv == 0 ? 'f' : 'c', lx.data()); hs_eigenvalues(n2g, by.c_str(), iv == 1 ? 'f' : 'c', ly.data());
-  for (auto &v : lx) v = v * (c->dli[0] * c->dli[0]);
-  for (auto &v : ly) v = v * (c->dli[1] * c->dli[1]);
-  if (V.ykind == 2) std::reverse(ly.begin(), ly.end());      // see solver_setup
-  if (ctx_upload(c, &V.lamx, lx) || ctx_upload(c, &V.lamy, ly)) return 1;
-  // fft.f90:99,136,142: normfft = prod norm(1) (n + norm(2) - ix): 1 n (PP), 2 n ('c' pairs, 'f' ND/DN), 2 (n + 1 - 1) ('f' DD), 2 (n - 1) ('f' NN)
-  auto nrm = [](int kd, int nn) -> real { return kd == 0 ? (real)nn : kd == 6 ? 2. * (nn - 1) : 2. * nn; };
-  V.normfft = 1. / (nrm(V.xkind, n1) * nrm(V.ykind, n2g));
-  auto next = [](int kd, int nn) { return kd == 5 ? 2 * nn : kd == 6 ? 2 * (nn - 1) : 4 * nn; };      // points of the symmetric extension (k_dst1)
-  if (V.xkind >= 5) { const int N = next(V.xkind, n1);
-    if (N < 2 || !make_plan(N, V.p1x) || (size_t)2 * (N + 1) * sizeof(cpx) > 150 * 1024) { c->err = "helmholtz: x line not supported by the face-centred transform kernel"; return 1; } if (upload_twiddles(c, N, N, &V.tw1x)) return 1; }
-  if (V.ykind >= 5) { const int N = next(V.ykind, n2g);
-    if (N < 2 || !make_plan(N, V.p1y) || (size_t)2 * (N + 1) * sizeof(cpx) > 150 * 1024) { c->err = "helmholtz: y line not supported by the face-centred transform kernel"; return 1; } if (upload_twiddles(c, N, N, &V.tw1y)) return 1; }
-  if (V.xkind >= 5 || V.ykind >= 5) { HIPSOFT(c, hipFuncSetAttribute((const void *)k_dst1<0>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024)); HIPSOFT(c, hipFuncSetAttribute((const void *)k_dst1<1>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024)); HIPSOFT(c, hipFuncSetAttribute((const void *)k_dst1<2>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024)); }
-  // the DCT-IV / DST-IV kernels (kinds 3, 4) read tables that solver_setup makes only when the pressure needs them
-  if ((V.xkind == 3 || V.xkind == 4) && !s.tw4x && upload_dct4_weights(c, n1, &s.tw4x)) return 1;
-  if ((V.ykind == 3 || V.ykind == 4) && dct4_y_setup(c, s, "helmholtz")) return 1;
-  const char *bcz = &c->cbcvel[6 * iv + 4];
-  V.nz = c->n[2] - ((iv == 2 && bcz[1] == 'D') ? 1 : 0); V.periodic_z = bcz[0] == 'P' && bcz[1] == 'P'; V.poisson = false;
-  V.cw = c->cw;
-  choose_kernels(c, s, V);
+  double nx, ny; if (line_spectrum(c, 0, bc, iv == 0, V.xkind, &V.lamx, &nx) || line_spectrum(c, 1, bc + 2, iv == 1, V.ykind, &V.lamy, &ny)) return 1;
+  V.normfft = 1. / (nx * ny);
+  V.nz = c->n[2] - ((iv == 2 && bcz[1] == 'D') ? 1 : 0); V.periodic_z = bcz[0] == 'P' && bcz[1] == 'P'; V.poisson = false; V.cw = c->cw;
+  if (choose_kernels(c, s, V, "helmholtz")) return 1;      // (k_dst1's plans and twiddles, the DCT-IV tables the pressure did not need: x_pass, y_pass)
   tile_setup(c, V, s.tab_imp3d);
   return solve_sched(c, V, s.sched_vel[iv]);
 }
