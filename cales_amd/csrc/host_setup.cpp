@@ -262,6 +262,9 @@ int hs_check_case(const cales_case *cs, std::string &msg) {
     if (!((bv == "PP" && bs == "PP") || (bv != "PP" && bs == "DD"))) { msg = "velocity and sgs BCs not compatible (sanity.f90:191-203)"; return 1; }
     if (d < 2 && (cs->bcpre[0 + 2 * d] != 0. || cs->bcpre[1 + 2 * d] != 0.)) { msg = "pressure BCs in x and y must be homogeneous"; return 1; }
     if (cs->is_forced[d] && bp != "PP") { msg = "flow cannot be forced in a non-periodic direction"; return 1; }
+    // (the reference's `select case(mtype)` has no default: any other value leaves the wall stress undefined there)
+    for (int s = 0; s < 2; ++s) if (cs->lwm[s + 2 * d] < -1 || cs->lwm[s + 2 * d] > 1) {
+      msg = "lwm must be 0 (no wall model), 1 (log law) or -1 (laminar law) (wmodel.f90:303-304)"; return 1; }
     for (int s = 0; s < 2; ++s) if (cs->lwm[s + 2 * d] != 0)
       for (int ivel = 0; ivel < 3; ++ivel) if (cs->cbcvel[s + 2 * d + 6 * ivel] != 'D') { msg = "wall-model faces must have Dirichlet velocity BCs (sanity.f90:209-221)"; return 1; }
   }

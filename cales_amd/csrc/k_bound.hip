@@ -479,7 +479,7 @@ __device__ inline real vel_relative(real v1, real v2, real coef, real mag) {
 }
 __device__ inline void wallmodel(int mtype, real uh, real vh, real h, real l1d, real visc, real &t1, real &t2) {
   const real kap = 0.41, blog = 5.20;
-  real upar = sqrt(uh * uh + vh * vh), tauw_tot;
+  real upar = sqrt(uh * uh + vh * vh), tauw_tot = 0.;      // (mtype: 1 or -1, hs_check_case; the reference's select has no other branch)
   if (mtype == 1) {
     real conv = 1., utau = fmax(sqrt(upar / h * visc), visc / h * exp(-kap * blog));
     while (conv > 0.5e-4) {
@@ -490,7 +490,7 @@ __device__ inline void wallmodel(int mtype, real uh, real vh, real h, real l1d, 
       conv = fabs(utau / utau_old - 1.);
     }
     tauw_tot = utau * utau;
-  } else {
+  } else if (mtype == -1) {      // WM_LAM, wmodel.f90:303
     const real del = 0.5 * l1d, umax = upar / (h / del * (2. - h / del));
     tauw_tot = 2. / del * umax * visc;
   }

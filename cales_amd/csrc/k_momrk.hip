@@ -243,7 +243,8 @@ __global__ __launch_bounds__(64 * (TYM + 2), (TYM <= 6 ? 4 : 3)) void k_momrk(Ge
 
 // The reference updates u,v,w in place, so their ghost cells keep the values of the last bounduvw until the next one -- and the wall model
 // reads them when its sampling height lies between the wall and the first cell centre (index_wm = 1 or n: wmodel.f90:120-131 with i1 = 0 /
-// n+1). The fused kernel writes the new velocities to a second set of buffers: with a wall model the ghost layers travel along.
+// n+1), and in the 2- and 4-point averages along an edge it shares with another wall-model face (wmodel.f90:143-163). The fused kernel writes the new
+// velocities to a second set of buffers: with a wall model the ghost layers travel along.
 struct GhostCopy { const real *src[3]; real *dst[3]; };
 __global__ __launch_bounds__(256) void k_copy_ghosts(Geom g, GhostCopy G) {      // blockIdx.z = 6 (idir - 1) + 2 field + side; the grid spans the largest face
   const int idir = blockIdx.z / 6 + 1, fs = blockIdx.z % 6;
@@ -278,6 +279,11 @@ void mom_setup(cales_ctx *c) {
   M.small = (c->ntot + 16) * sizeof(real) < (1ull << 32) && !c->fl.wide_offsets;
   M.geo = with_bands(tile_geom(c, TYM, 64));
   M.wm = any_wm(c); M.wm_ghosts_in_step = wm_samples_ghost(c) || c->fl.unmerged_bc;
+  // ... and wherever cales_step keeps the first wall-model update of a substep (make_plan, skip_first_wm: wall-model faces in x). The reference's rk writes
+  // interior cells only, so that update's 4- and 2-point averages (wmodel.f90:143-163) read the tangential ghost cells of the NEIGHBOURING wall-model faces as
+  // the substep before left them -- here the new velocity lives in the second set of buffers, whose ghost cells are two substeps old. What the update makes
+  // of them survives the substep along an edge (cavity_dsmag_wm_mixed: w(i1, n2+1, k) -> bcv%x(n2, k) -> v(0, n2, k) -> bcu%z(0, n2) -> u(0, n2, n3+1))
+  for (int sd = 0; sd <= 1; ++sd) if (LWM(c, sd, 1) != 0) M.wm_ghosts_in_step = true;
 }
 // mom_xyz_ad + update of rk (rk.f90:74-94): what is fixed comes from MomPath, what the call decides from its arguments -- o.pending is the projection to apply
 // while loading (cales_step, fold_mom; the caller owns it). Leaves the new velocities in c->f[CALES_U..W] (pointers swapped with c->f2) and, with a pending

@@ -546,7 +546,7 @@ static double vel_relative(double v1, double v2, double coef, double mag) {
   double r = (1. - coef)*v1 + coef*v2; r = r - mag; return r;
 }
 static void wallmodel(int mtype, double uh, double vh, double h, double l1d, double visc, double *tauw) {
-  double upar, utau, f, fp, conv, utau_old, tauw_tot;
+  double upar = 0., utau, f, fp, conv, utau_old, tauw_tot = 0.;     /* (no other mtype: the reference's select case has no default) */
   if (mtype == 1) {
     conv = 1.; upar = sqrt(uh*uh + vh*vh);
     utau = fmax(sqrt(upar/h*visc), visc/h*exp(-KAP_LOG*B_LOG));
@@ -558,7 +558,7 @@ static void wallmodel(int mtype, double uh, double vh, double h, double l1d, dou
       conv = fabs(utau/utau_old - 1.);
     }
     tauw_tot = utau*utau;
-  } else {
+  } else if (mtype == -1) {     /* WM_LAM, wmodel.f90:303 */
     upar = sqrt(uh*uh + vh*vh);
     double del = 0.5*l1d, umax = upar/(h/del*(2. - h/del));
     tauw_tot = 2./del*umax*visc;

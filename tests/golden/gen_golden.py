@@ -72,6 +72,33 @@ CASES = {
                        {r"ng\(1:3\) = .*": "ng(1:3) = 8, 10, 12", r"gr = 0\.": "gr = 2.", r"inivel = .*": "inivel = 'hcp'"}, 2),
     "couette_imp3d_ops": ("dns/couette/input.nml",
                           {r"ng\(1:3\) = .*": "ng(1:3) = 8, 8, 10", r"gr = 0\.": "gr = 1."}, 1),
+    # the wall model where the two shipped wall-model examples never take it (wmodel.f90:65-335): faces in x, the laminar law (lwm = -1, wmodel.f90:303),
+    # moving walls under a model (the *_mag planes of vel_relative), a model on one side of a direction only. hwm per case: profiles/wall_model_cases.md
+    "cavity_smag_wm6": ("dns/lid_driven_cavity/input.nml",
+                        {r"ng\(1:3\) = .*": "ng(1:3) = 10, 8, 12", r"gr = 0\.": "gr = 1.5", r"sgstype = 'none'": "sgstype = 'smag'",
+                         r"lwm\(0:1,1:3\) = .*": "lwm(0:1,1:3) = 1,1, 1,1, 1,1", r"hwm = 0\.": "hwm = 0.17"}, 0),
+    "cavity_dsmag_wm_mixed": ("dns/lid_driven_cavity/input.nml",
+                              {r"ng\(1:3\) = .*": "ng(1:3) = 10, 8, 12", r"gr = 0\.": "gr = 1.5", r"sgstype = 'none'": "sgstype = 'dsmag'",
+                               r"lwm\(0:1,1:3\) = .*": "lwm(0:1,1:3) = 1,0, 0,-1, -1,1", r"hwm = 0\.": "hwm = 0.17",
+                               r"(?m)^bcvel\(0:1,1:3,1\) = .*": "bcvel(0:1,1:3,1) =  0.,0.,   0.,0.25,   0.,1.",
+                               r"(?m)^bcvel\(0:1,1:3,2\) = .*": "bcvel(0:1,1:3,2) =  0.3,0.,   0.,0.,   0.,-0.1",
+                               r"(?m)^bcvel\(0:1,1:3,3\) = .*": "bcvel(0:1,1:3,3) =  -0.2,0.,   0.,0.15,   0.,0."}, 0),
+    # the laminar law on x and y faces of a box with three different edge lengths: its `l1d = l(idir)` (wmodel.f90:150,201,252) is told apart from l(3)
+    # only there -- the two cavities above are cubes and the other laminar faces are z faces
+    "cavity_smag_wm_lam": ("dns/lid_driven_cavity/input.nml",
+                           {r"ng\(1:3\) = .*": "ng(1:3) = 10, 8, 12", r"l\(1:3\) = .*": "l(1:3) = 1.2, 0.8, 1.", r"gr = 0\.": "gr = 1.5", r"sgstype = 'none'": "sgstype = 'smag'",
+                            r"lwm\(0:1,1:3\) = .*": "lwm(0:1,1:3) = -1,-1, -1,-1, 1,1", r"hwm = 0\.": "hwm = 0.17"}, 0),
+    "chan_smag_wm_mov": ("les/_manuscript_turbulent_channel_wall_model/input.nml",
+                         {r"ng\(1:3\) = .*": "ng(1:3) = 12, 8, 10", r"visci = .*": "visci = 5640.", r"lwm\(0:1,1:3\) = .*": "lwm(0:1,1:3) = 0,0, 0,0, -1,1",
+                          r"hwm = 0\.1": "hwm = 0.2",
+                          r"(?m)^bcvel\(0:1,1:3,1\) = .*": "bcvel(0:1,1:3,1) =  0.,0.,   0.,0.,   -0.3,0.4",
+                          r"(?m)^bcvel\(0:1,1:3,2\) = .*": "bcvel(0:1,1:3,2) =  0.,0.,   0.,0.,   0.1,-0.2"}, 0),
+    "halfchan_smag_wm_imp1d": ("dns/half_channel/input.nml",
+                               {r"ng\(1:3\) = .*": "ng(1:3) = 8, 10, 12", r"gr = 0\.": "gr = 2.", r"inivel = .*": "inivel = 'hcp'", r"sgstype = 'none'": "sgstype = 'smag'",
+                                r"lwm\(0:1,1:3\) = .*": "lwm(0:1,1:3) = 0,0, 0,0, 1,0", r"hwm = 0\.": "hwm = 0.03"}, 2),
+    "halfchan_dsmag_wm": ("dns/half_channel/input.nml",
+                          {r"ng\(1:3\) = .*": "ng(1:3) = 8, 10, 12", r"gr = 0\.": "gr = 2.", r"inivel = .*": "inivel = 'hcp'", r"sgstype = 'none'": "sgstype = 'dsmag'",
+                           r"lwm\(0:1,1:3\) = .*": "lwm(0:1,1:3) = 0,0, 0,0, -1,0", r"hwm = 0\.": "hwm = 0.03"}, 0),
 }
 # End-of-step states at POWER-OF-TWO row lengths (only the raw initial fields and the state after one step are kept: the stage-by-stage vectors above
 # would be ~3 MB per case at these sizes): there cales_step takes the radix-8 transforms, forms fillps inside the forward x pass and leaves the x ghost
@@ -135,6 +162,19 @@ END_ONLY = {
                     {r"ng\(1:3\) = .*": "ng(1:3) = 64, 16, 16", r"l\(1:3\) = .*": "l(1:3) = 6.283185307179586, 6.283185307179586, 6.283185307179586",
                      r"visci = .*": "visci = 1600.", r"inivel = .*": "inivel = 'tgv'", r"is_forced\(1:3\) = .*": "is_forced(1:3) = F, T, T",
                      r"velf\(1:3\) = .*": "velf(1:3) = 0., 0.2, -0.15", r"bforce\(1:3\) = .*": "bforce(1:3) = 0.05, 0., 0."}, 0),
+    # three of the wall-model cases above at 64-cell rows: moving z walls with one law per wall, six log-law walls (faces in x: the first wall-model update of a
+    # step is kept), the laminar law on the one wall of a half channel under the dynamic model
+    "chan_smag_wm_mov_x64": ("les/_manuscript_turbulent_channel_wall_model/input.nml",
+                             {r"ng\(1:3\) = .*": "ng(1:3) = 64, 16, 10", r"visci = .*": "visci = 5640.", r"lwm\(0:1,1:3\) = .*": "lwm(0:1,1:3) = 0,0, 0,0, -1,1",
+                              r"hwm = 0\.1": "hwm = 0.2",
+                              r"(?m)^bcvel\(0:1,1:3,1\) = .*": "bcvel(0:1,1:3,1) =  0.,0.,   0.,0.,   -0.3,0.4",
+                              r"(?m)^bcvel\(0:1,1:3,2\) = .*": "bcvel(0:1,1:3,2) =  0.,0.,   0.,0.,   0.1,-0.2"}, 0),
+    "cavity_smag_wm6_x64": ("dns/lid_driven_cavity/input.nml",
+                            {r"ng\(1:3\) = .*": "ng(1:3) = 64, 16, 12", r"gr = 0\.": "gr = 1.5", r"sgstype = 'none'": "sgstype = 'smag'",
+                             r"lwm\(0:1,1:3\) = .*": "lwm(0:1,1:3) = 1,1, 1,1, 1,1", r"hwm = 0\.": "hwm = 0.17"}, 0),
+    "halfchan_dsmag_wm_x64": ("dns/half_channel/input.nml",
+                              {r"ng\(1:3\) = .*": "ng(1:3) = 64, 16, 12", r"gr = 0\.": "gr = 2.", r"inivel = .*": "inivel = 'hcp'", r"sgstype = 'none'": "sgstype = 'dsmag'",
+                               r"lwm\(0:1,1:3\) = .*": "lwm(0:1,1:3) = 0,0, 0,0, -1,0", r"hwm = 0\.": "hwm = 0.03"}, 0),
 }
 END_KEYS = ("input_nml", "impdiff", "dt", "dt_cfl", "dpdl", "r3_div", "s0raw_u", "s0raw_v", "s0raw_w", "s0raw_p", "r3_s7_u", "r3_s7_v", "r3_s7_w", "r3_s8_p", "r3_s9_visct")
 CASES.update(END_ONLY)

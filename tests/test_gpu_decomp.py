@@ -71,7 +71,11 @@ SLAB_CASES = [("chan_smag_wm", (32, 24, 16), 2), ("chan_smag_wm", (32, 24, 16), 
                                        # Neumann 256 / 512 / 1024, periodic 1024), ranks whose mode columns are not a multiple of eight; 1024 planes of real x modes on
                                        # slabs: the persistent z tile (k_gaussel_tile_p) on the blocks of a peer segment
                                        ("cavity_nnn", (32, 1024, 12), 4), ("cavity_nnn", (48, 512, 10), 2), ("cavity_nnn", (64, 256, 12), 8), ("chan_smag", (32, 1024, 8), 2),
-                                       ("cavity_nnn", (32, 16, 1024), 2)]
+                                       ("cavity_nnn", (32, 16, 1024), 2),
+                                       # wall models beyond the shipped examples: six log-law walls (x faces on every slab, y faces on the first and the last), one law
+                                       # or none per face with every wall moving (the one wall-model y face is the last slab's alone), moving z walls with one law each
+                                       ("cavity_smag_wm6", (16, 24, 12), 2), ("cavity_smag_wm6", (16, 24, 12), 3), ("cavity_dsmag_wm_mixed", (16, 24, 12), 2),
+                                       ("chan_smag_wm_mov", (32, 24, 16), 2)]
 
 
 @pytest.mark.parametrize("name,ng,P", SLAB_CASES)
@@ -224,7 +228,8 @@ def test_slab_ranks_batched_scratch_field_exchange(name, ng, P, events, monkeypa
     test_slab_ranks_match_single_rank(name, ng, P)
 
 
-@pytest.mark.parametrize("name,ng,P", [("duct_smag_wm", (16, 32, 24), 4), ("duct_smag_wm_imp1d", (64, 32, 16), 8)])
+@pytest.mark.parametrize("name,ng,P", [("duct_smag_wm", (16, 32, 24), 4), ("duct_smag_wm_imp1d", (64, 32, 16), 8),
+                                       ("cavity_smag_wm6", (16, 24, 12), 2), ("cavity_smag_wm6", (16, 24, 12), 3), ("chan_smag_wm_mov", (32, 24, 16), 2)])
 def test_slab_ranks_smag_reference_sequence(name, ng, P, monkeypatch):
     """The other form of the static-Smagorinsky pass on more than two slabs between y walls: the kernel-per-loop sequence."""
     monkeypatch.setenv("CALES_SMAG_REFERENCE_SEQUENCE", "1")

@@ -14,7 +14,9 @@ pytestmark = pytest.mark.gpu
 TOL = 1e-13
 DEVICE_CASES = ["tgv_ppp", "tgv_dsmag_ppp", "chan_smag_wm", "chan_smag", "chan_dsmag", "chan_dsmag_wm", "halfchan_imp1d",
                 "duct_smag_wm", "duct_smag_wm_imp1d", "cavity_nnn", "devchan_nd",
-                "duct_dsmag_wm", "duct_dsmag", "cavity_dsmag"]    # PP, NN (DCT) and ND (DCT-IV, inflow/outflow) pressure transforms
+                "duct_dsmag_wm", "duct_dsmag", "cavity_dsmag",    # PP, NN (DCT) and ND (DCT-IV, inflow/outflow) pressure transforms
+                # the wall model beyond the shipped examples (wmodel.f90:65-335): faces in x, the laminar law, moving walls, a model on one side of a direction
+                "cavity_smag_wm6", "cavity_dsmag_wm_mixed", "cavity_smag_wm_lam", "chan_smag_wm_mov", "halfchan_smag_wm_imp1d", "halfchan_dsmag_wm"]
 
 
 def _hot(case):
@@ -26,7 +28,7 @@ def _hot(case):
     return HotPath(case)
 
 
-WALLED_DSMAG = ["cavity_dsmag"]    # walls in x: the kernel-per-loop sequence is the only path (ducts, y walls, go through the tile passes)
+WALLED_DSMAG = ["cavity_dsmag", "cavity_dsmag_wm_mixed"]    # walls in x: the kernel-per-loop sequence is the only path (ducts, y walls, go through the tile passes)
 
 
 @pytest.mark.parametrize("name", DEVICE_CASES)
@@ -142,7 +144,8 @@ def test_fused_step_matches_operator_sequence(name):
 @pytest.mark.parametrize("name", ["chan_dsmag_p2", "chan_smag_p2", "duct_dsmag_p2", "tgv_ppp_p2", "chan_dsmag_x64", "chan_dsmag_x128", "tgv_dsmag_ppp_x64",
                                   "chan_smag_wm_x64", "duct_smag_wm_x64", "duct_smag_wm_imp1d_x64",
                                   "chan_nosgs_x64", "cavity_nnn_x64", "halfchan_imp1d_x64", "duct_dsmag_x64", "tgv_ppp_x64",
-                                  "chan_smag_fy_x64", "chan_dsmag_fxy_x64", "tgv_fyz_x64"])      # (forcing in y and z, a body force)
+                                  "chan_smag_fy_x64", "chan_dsmag_fxy_x64", "tgv_fyz_x64",      # (forcing in y and z, a body force)
+                                  "chan_smag_wm_mov_x64", "cavity_smag_wm6_x64", "halfchan_dsmag_wm_x64"])      # (moving walls, wall-model faces in x, the laminar law on one wall)
 def test_fused_step_at_power_of_two_rows(name, keep_x, monkeypatch):
     """Reference-made end-of-step states at power-of-two row lengths: radix-8 transforms, fillps inside the forward x pass, the x ghost columns left
     alone until the step returns (and, with CALES_XGHOSTS_IN_STEP, updated by every ghost-cell operator as at the operator level)."""
@@ -277,16 +280,20 @@ def test_unmerged_bc_operator_level(name, monkeypatch):
     test_startup_and_substeps(name)
 
 
-@pytest.mark.parametrize("name", ["chan_smag", "chan_smag_wm", "duct_smag_wm"])
+@pytest.mark.parametrize("name", ["chan_smag", "chan_smag_wm", "duct_smag_wm", "cavity_smag_wm6", "cavity_smag_wm_lam", "chan_smag_wm_mov", "halfchan_smag_wm_imp1d"])
 def test_smag_reference_sequence(name, monkeypatch):
     """Static Smagorinsky through the kernel-per-loop sequence (the path ducts and cavities take)."""
     monkeypatch.setenv("CALES_SMAG_REFERENCE_SEQUENCE", "1")
     test_startup_and_substeps(name, general_sgs=True)
 
 
-@pytest.mark.parametrize("name", ["chan_dsmag", "chan_dsmag_wm", "tgv_dsmag_ppp", "duct_dsmag_wm", "duct_dsmag"])
+@pytest.mark.parametrize("name", ["chan_dsmag", "chan_dsmag_wm", "tgv_dsmag_ppp", "duct_dsmag_wm", "duct_dsmag", "cavity_dsmag_wm_mixed"])
 def test_dsmag_reference_sequence(name, monkeypatch):
-    """Dynamic Smagorinsky through the kernel-per-loop sequence of sgs.f90:153-380, operator by operator at 1e-13."""
+    """Dynamic Smagorinsky through the kernel-per-loop sequence of sgs.f90:153-380, operator by operator at 1e-13.
+    (Not halfchan_dsmag_wm: the 1e-13 stands for plane sums in another association, and on that case the reference's own algorithm -- the CPU restatement,
+    bit-identical to the golden vectors -- moves the start-up eddy viscosity by 3.8e-12 of its maximum when every input moves by one unit in the last
+    place, against 1e-15 to 6e-14 on the cases listed: a model coefficient that is the quotient of two plane sums that cancel, in plane 12. The sequence gave
+    3.3e-13 there. The case is held at the bars of the tile passes by test_startup_and_substeps and test_unmerged_bc_operator_level.)"""
     monkeypatch.setenv("CALES_DSMAG_REFERENCE_SEQUENCE", "1")
     test_startup_and_substeps(name, general_sgs=True)
 
@@ -652,7 +659,9 @@ def test_every_entry_sees_the_projected_state(name, monkeypatch):
 
 @pytest.mark.parametrize("is_correc", [False, True], ids=["impose", "is_correc"])
 @pytest.mark.parametrize("name,ng", [("duct_smag_wm", (16, 12, 10)), ("duct_dsmag", (24, 10, 12)), ("cavity_nnn", (12, 10, 14)), ("halfchan_imp1d", (16, 12, 10)),
-                                     ("devchan_nd", (14, 8, 10)), ("chan_smag_wm", (16, 8, 12)), ("cavity_dsmag", (10, 12, 8))])
+                                     ("devchan_nd", (14, 8, 10)), ("chan_smag_wm", (16, 8, 12)), ("cavity_dsmag", (10, 12, 8)),
+                                     # wall-model faces in x, on one side of a direction, under moving walls
+                                     ("cavity_smag_wm6", (12, 10, 14)), ("cavity_dsmag_wm_mixed", (10, 12, 8)), ("chan_smag_wm_mov", (16, 8, 12)), ("halfchan_dsmag_wm", (16, 12, 10))])
 def test_all_directions_ghost_cell_kernel_equals_the_sequence(name, ng, is_correc, monkeypatch):
     """k_bc_all (every direction of a bounduvw / boundp in one launch: the closed form Z(Y(X(stored))) of bound.f90:158-199) against the reference's
     order, one launch per direction (CALES_UNMERGED_BC), on RANDOM fields -- ghost cells included, so that every corner and edge cell and every cell a
@@ -689,6 +698,12 @@ def test_all_directions_ghost_cell_kernel_equals_the_sequence(name, ng, is_corre
     ("cavity_nnn_x64", {"CALES_LAZY_PROJECTION": "1"}, {"projection": "in_next_momentum_pass(all_substeps)"}),
     ("cavity_dsmag", {}, {"sgs": "dsmag_reference_sequence", "projection": "own_pass(correc+updatep)"}),
     ("tgv_ppp_x64", {"CALES_UNFOLDED_MOM": "1", "CALES_KEEP_NULL_MODE": "1"}, {"projection": "own_pass(correc+updatep)", "solver": "x:PP/radix8,y:PP/radix8_register_ends,z:lds_tile_periodic,null_mode:reference_order"}),
+    # wall models beyond the shipped examples. Faces in x: the first wall-model update of a substep is kept (make_plan), the sequence is the only form
+    # (sgs_setup: xw); faces in z alone, one law per wall or one wall only: skipped, the row form and the tiles (pair fields: x and y periodic, the normal
+    # velocity prescribed at both z ends -- the free-slip top of the half channel is_wall for the filters as in the reference)
+    ("cavity_smag_wm6_x64", {}, {"first_wall_model_update": "kept", "sgs": "smag_reference_sequence", "bulk_forcing": "none"}),
+    ("chan_smag_wm_mov_x64", {}, {"first_wall_model_update": "skipped", "sgs": "smag_rows"}),
+    ("halfchan_dsmag_wm_x64", {}, {"first_wall_model_update": "skipped", "sgs": "dsmag_tiles(pair_fields)"}),
 ])
 def test_step_plan_is_a_value(name, env, expect, monkeypatch):
     """The path of a step is a VALUE (struct StepPlan, api.hip make_plan): computed from the case, the switches and the context's state, read by step_body,
@@ -703,7 +718,7 @@ def test_step_plan_is_a_value(name, env, expect, monkeypatch):
     for k, v in expect.items():
         assert pl.get(k) == v, (k, pl)
     assert pl["ranks"] == "1"
-    if "first_wall_model_update" in pl and case.impdiff == 0 and not env:      # the deferred forcing needs the first wall-model update to be dead work
+    if "first_wall_model_update" in pl and case.impdiff == 0 and not env and np.any(case.is_forced):      # the deferred forcing needs the first wall-model update to be dead work
         assert pl["bulk_forcing"] == ("in_correction(means_in_x_transform)" if pl["first_wall_model_update"] == "skipped" else "own_pass"), pl
     h.step(float(g["dt"]))
     assert h.describe_plan() == pl

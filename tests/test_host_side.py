@@ -163,6 +163,12 @@ def test_check_case_rules(monkeypatch):
     bad = case.copy(); bad.cbcvel[0, 2, 0] = "N"               # wall-model faces must be all-Dirichlet
     with pytest.raises(CalesError):
         check_case(bad)
+    for val in (2, -2, 3):                                     # lwm: 0, 1 (log law) or -1 (laminar law), nothing else (wmodel.f90:303-304)
+        bad = case.copy(); bad.lwm[1, 2] = val
+        with pytest.raises(CalesError, match=r"wmodel\.f90:303-304"):
+            check_case(bad)
+    ok = case.copy(); ok.lwm[:, 2] = (-1, 1)                   # ... and -1 is the laminar law, on one wall or both
+    check_case(ok)
     bad = case.copy(); bad.bcpre[0, 0] = 1.                    # x,y pressure BC values must be zero
     with pytest.raises(CalesError):
         check_case(bad)

@@ -8,12 +8,12 @@ import numpy as np
 import pytest
 
 from oracle.oracle import Oracle
-from tests.util import FULL_CASES, RK, F, load_golden, relerr
+from tests.util import FULL_CASES, STAGE_CASES, RK, F, load_golden, relerr
 
 TOL = 1e-13
 
 
-@pytest.mark.parametrize("name", FULL_CASES + ["couette_imp3d_ops"])
+@pytest.mark.parametrize("name", STAGE_CASES + ["couette_imp3d_ops"])
 def test_setup_products(name):
     g, case = load_golden(name)
     o = Oracle(case)
@@ -49,7 +49,7 @@ def test_grids():
     assert q == 8
 
 
-@pytest.mark.parametrize("name", FULL_CASES)
+@pytest.mark.parametrize("name", STAGE_CASES)
 def test_initflow(name):
     g, case = load_golden(name)
     o = Oracle(case)
@@ -59,7 +59,7 @@ def test_initflow(name):
         assert np.abs(a - ref).max() <= 2e-15 * max(1., np.abs(ref).max()), k
 
 
-@pytest.mark.parametrize("name", FULL_CASES)
+@pytest.mark.parametrize("name", STAGE_CASES)
 def test_startup_and_substeps(name):
     g, case = load_golden(name)
     o = Oracle(case)
@@ -189,7 +189,7 @@ def test_plane_statistics(name):
         assert (np.abs(got - ref) <= 1e-13 * scale).all(), (nm, np.abs(got - ref).max(axis=1) / scale[:, 0])      # measured: 4e-16, 3e-14, 1e-15
 
 
-@pytest.mark.parametrize("name", FULL_CASES)
+@pytest.mark.parametrize("name", STAGE_CASES)
 def test_solver_operands_and_z_sweep(name):
     """eigenvalues, tridmatrix (initsolver.f90:66-169) and the tridiagonal sweep gaussel / gaussel_periodic / dgtsv_homebrewed with its
     `+eps` pivots (solver.f90:82-179), by the reference's own routines (compiled from their lines by oracle/ref/Makefile): the restatement
@@ -217,7 +217,9 @@ def test_solver_operands_and_z_sweep(name):
 END_CASES = ["chan_dsmag_p2", "chan_smag_p2", "duct_dsmag_p2", "tgv_ppp_p2", "chan_dsmag_x64", "chan_dsmag_x128", "tgv_dsmag_ppp_x64", "chan_smag_wm_x64", "duct_smag_wm_x64", "duct_smag_wm_imp1d_x64",
              "chan_nosgs_x64", "cavity_nnn_x64", "halfchan_imp1d_x64", "duct_dsmag_x64", "tgv_ppp_x64",
              # bulk forcing in y and z, a body force (rk.f90:82-86,209-221): a spanwise bulk velocity with bforce along x and z, x and y forced, the box forced in y and z
-             "chan_smag_fy_x64", "chan_dsmag_fxy_x64", "tgv_fyz_x64"]
+             "chan_smag_fy_x64", "chan_dsmag_fxy_x64", "tgv_fyz_x64",
+             # wall models beyond the shipped examples: moving z walls with one law each, six log-law walls, the laminar law on a half channel's one wall
+             "chan_smag_wm_mov_x64", "cavity_smag_wm6_x64", "halfchan_dsmag_wm_x64"]
 
 
 @pytest.mark.parametrize("name", END_CASES)
