@@ -30,11 +30,11 @@ def filter2d_env() -> bool:
     return os.environ.get("CALES_FILTER_2D", "0") not in ("", "0")
 
 # enum cales_sgs_average of include/cales.h, OR-ed onto the two dynamic values: the directions the Germano identity is averaged over (sgs.f90:359-370)
-SGS_AVE = {"planes": 0, "volume": 4, "xlines": 8}      # the reference's hard-wired _CHANNEL | -D_DIT | _DUCT without _CHANNEL
+SGS_AVE = {"planes": 0, "volume": 4, "xlines": 8, "local": 64}      # the reference's hard-wired _CHANNEL | -D_DIT | _DUCT without _CHANNEL | _CAVITY without it (CALES_SGS_AVE_LOCAL)
 
 
 def dsmag_average_env() -> str:
-    """CALES_DSMAG_AVERAGE, the run-time form of the reference's _DIT / _CHANNEL / _DUCT: planes (also unset or empty), volume or xlines."""
+    """CALES_DSMAG_AVERAGE, the run-time form of the reference's _DIT / _CHANNEL / _DUCT / _CAVITY: planes (also unset or empty), volume, xlines or local."""
     return os.environ.get("CALES_DSMAG_AVERAGE", "") or "planes"
 
 
@@ -94,7 +94,7 @@ def make_case(case, nranks: int = 1, rank: int = 0) -> CalesCase:
         ave = getattr(case, "dsmag_average", None)
         ave = dsmag_average_env() if ave is None else ave
         if ave not in SGS_AVE:
-            raise ValueError(f"ERROR: unknown averaging of the dynamic model {ave!r} (planes, volume or xlines)")
+            raise ValueError(f"ERROR: unknown averaging of the dynamic model {ave!r} (planes, volume, xlines or local)")
         p.sgstype |= SGS_AVE[ave]
     p.lwm[:] = [int(x) for x in case.lwm.ravel(order="F")]
     p.hwm = float(case.hwm)

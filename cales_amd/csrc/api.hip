@@ -230,7 +230,8 @@ int cales_create(const cales_case *cs, void *stream, cales_ctx **out) {
   // ... and so are the directions the Germano identity is averaged over (enum cales_sgs_average; cales_check_case has refused every other combination)
   if (cs->sgstype & CALES_SGS_AVE_VOLUME) c->sgs.ave = SgsAve::volume;
   if (cs->sgstype & CALES_SGS_AVE_XLINES) c->sgs.ave = SgsAve::xlines;
-  c->C.sgstype = cs->sgstype & ~(CALES_SGS_AVE_VOLUME | CALES_SGS_AVE_XLINES);
+  if (cs->sgstype & CALES_SGS_AVE_LOCAL) c->sgs.ave = SgsAve::local;
+  c->C.sgstype = cs->sgstype & ~(CALES_SGS_AVE_VOLUME | CALES_SGS_AVE_XLINES | CALES_SGS_AVE_LOCAL);
   if (c->C.sgstype == CALES_SGS_DSMAG_FILTER2D) { c->C.sgstype = CALES_SGS_DSMAG; c->sgs.filter2d = true; }
   c->fl.read_env();      // the CALES_* switches are fixed for the life of the context
   // (a context is whole at every stage: its members start out null, what it has allocated is in c->mem -- cales_destroy takes it as it is)
@@ -643,7 +644,7 @@ int cales_describe_plan(cales_ctx *c, char *buf, int buflen) {
   s += std::string(";visct_ghost_cells=") + (pl.visct_ghosts ? "updated" : "zero_field");
   s += std::string(";momentum=") + (c->mom.fused ? "fused_mom_rk" : "mom+rk_update");
   s += std::string(";sgs=") + sgs_path_name(c);
-  if (c->sgs.ave != SgsAve::planes) s += std::string(";sgs_average=") + (c->sgs.ave == SgsAve::volume ? "volume" : "x_lines");
+  if (c->sgs.ave != SgsAve::planes) s += std::string(";sgs_average=") + (c->sgs.ave == SgsAve::volume ? "volume" : c->sgs.ave == SgsAve::xlines ? "x_lines" : "local");
   s += std::string(";solver=") + solver_path_name(c);
   if (c->C.impdiff == 1) for (int iv = 0; iv < 3; ++iv) s += std::string(";helmholtz_") + "uvw"[iv] + "=" + helmholtz_path_name(c, iv);
   if (c->P > 1) s += ";mode_columns_per_rank=" + std::to_string(solver_mode_columns(c));      // of the pressure solve (padded to whole 128-B lines where that costs 6 % or less: solver_setup)

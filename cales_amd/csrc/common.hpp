@@ -156,10 +156,10 @@ enum class SgsForm { none, smag_rows, smag_reference, dsmag_tiles, dsmag_referen
 // the instantiation of each launch site (32 / 64: unsigned / size_t byte offsets; yw: walls or wall-model faces in y; ucf: the last pass forms the
 // cell-centred velocity). Pair fields imply x and y periodic, 32-bit offsets and ucf: one instantiation each.
 enum class StrainKernel { corr_rows2, corr, corr5, yw32, yw64, pair, plain32, plain64, f2d32, f2d64 };      // k_corr_strain_tile<unsigned, TYC(, 1: EXT, 2: FIVE)> | k_strain_tile<OFF, TYS, YW(, SSF)>, SSF = 1: pair, 2: f2d (SgsPath::filter2d)
-enum class LmfKernel { pair, pair5, yw_ucf32, yw_ucf64, yw32, yw64, ucf32, ucf64, plain32, plain64, f2d32, f2d64 };      // k_lmf_tile<OFF, YW, UCF(, PAIR)>, PAIR = 1: pair, 2: pair5 (five components) | k_lmf_plane_tile<OFF>: f2d
+enum class LmfKernel { pair, pair5, yw_ucf32, yw_ucf64, yw32, yw64, ucf32, ucf64, plain32, plain64, f2d32, f2d64 };      // k_lmf_tile<OFF, YW, UCF(, PAIR)>, PAIR = 1: pair, 2: pair5 (five components) | k_lmf_plane_tile<OFF>: f2d      // (SgsAve::local: the same names, the LOCAL instantiation of each -- no pair5, no f2d)
 enum class SmagKernel { yw32, yw64, plain32, plain64 };      // k_smag_rows<OFF, YW>
-// the directions <Mij Lij>, <Mij Mij> of the dynamic model are averaged over (sgs.f90:359-370): _CHANNEL (hard-wired there) | -D_DIT | _DUCT
-enum class SgsAve { planes, volume, xlines };
+// the directions <Mij Lij>, <Mij Mij> of the dynamic model are averaged over (sgs.f90:359-370): _CHANNEL (hard-wired there) | -D_DIT | _DUCT | _CAVITY (none)
+enum class SgsAve { planes, volume, xlines, local };
 struct SgsPath {
   SgsForm form = SgsForm::none;
   bool pair = false, lazy = false, ucf = false, small = false, yw = false;      // |S|Sij as pair fields (ss2); lazy: |S| straight into visct (homogeneous sgs BCs)
@@ -168,7 +168,8 @@ struct SgsPath {
   // without the fold (start-up, operator level, CALES_UNFOLDED_CORREC), slabs and every other form keep six (CALES_SGS_SIX_COMPONENTS: everywhere)
   bool five = false;
   bool filter2d = false;    // the reference's -D_FILTER_2D (cales_case.sgstype = CALES_SGS_DSMAG_FILTER2D): test filter in the x-y planes only, alph2 = 2.52 everywhere
-  SgsAve ave = SgsAve::planes;      // cales_case.sgstype & CALES_SGS_AVE_*: volume folds the plane sums into one (k_volume_fold), xlines takes the sequence (k_contract_lines)
+  SgsAve ave = SgsAve::planes;      // cales_case.sgstype & CALES_SGS_AVE_*: volume folds the plane sums into one (k_volume_fold), xlines takes the sequence (k_contract_lines),
+                                    // local (CALES_SGS_AVE_LOCAL) averages nothing: k_lmf_tile<.., LOCAL> / k_contract_local write visct cell by cell -- no lazy form, six components
   bool wraps_x = true;      // reads wrapped interior columns where x is periodic (cales_step may leave the x ghost columns stale)
   // static kernel arguments (y walls: dsmag those this rank owns, smag_rows those of the case -- global distances, the shear reaches every slab)
   int zlo = 0, zhi = 0, wmlo = 0, wmhi = 0, wylo = 0, wyhi = 0, wmylo = 0, wmyhi = 0; real flo = 0., fhi = 0.;

@@ -287,9 +287,10 @@ int hs_check_case(const cales_case *cs, std::string &msg) {
       if (!ok) { msg = "invalid wall model height (sanity.f90:224-231)"; return 1; }
     } }
   {
-    const int ave = cs->sgstype & (CALES_SGS_AVE_VOLUME | CALES_SGS_AVE_XLINES), model = cs->sgstype & ~ave;
+    const int ave = cs->sgstype & (CALES_SGS_AVE_VOLUME | CALES_SGS_AVE_XLINES | CALES_SGS_AVE_LOCAL), model = cs->sgstype & ~ave;
     if (cs->sgstype < 0 || model > CALES_SGS_DSMAG_FILTER2D) { msg = "unknown SGS model"; return 1; }
     if (ave == (CALES_SGS_AVE_VOLUME | CALES_SGS_AVE_XLINES)) { msg = "SGS model: CALES_SGS_AVE_VOLUME and CALES_SGS_AVE_XLINES exclude each other"; return 1; }
+    if ((ave & CALES_SGS_AVE_LOCAL) && ave != CALES_SGS_AVE_LOCAL) { msg = "SGS model: CALES_SGS_AVE_LOCAL and the other averaging flags exclude each other"; return 1; }
     if (ave && model < CALES_SGS_DSMAG) { msg = "SGS model: an averaging flag (CALES_SGS_AVE_*) goes with the dynamic model only"; return 1; }
   }
   // (sanity.f90:98-111 refuses static Smagorinsky with more than two subdomains between two opposite walls because every rank measures the

@@ -1,5 +1,6 @@
 // Eddy-viscosity kernels: cmpt_sgs (reference src/sgs.f90:21-386) for 'smag' (van Driest damped) and
-// 'dsmag' (dynamic, plane-averaged: the reference hard-wires _CHANNEL, sgs.f90:8,362-364), with
+// 'dsmag' (dynamic, plane-averaged: the reference hard-wires _CHANNEL, sgs.f90:8,362-364; averaged over the volume, over x lines or not at all -- _DIT,
+// _DUCT, _CAVITY, sgs.f90:359-370 -- under the flags of cales_case.sgstype, SgsAve), with
 // strain_rate (sgs.f90:1019-1110), extrapolate (682-767), filter3d (616-680), interpolate (850-870),
 // ave1d_channel (433-482) and cmpt_alph2 (769-822).
 #include "common.hpp"
@@ -244,6 +245,25 @@ __global__ __launch_bounds__(BX *BY) void k_contract(Geom g, CP6 mij, CP6 lij, c
   lm[c] = m_[0] * l_[0] + m_[1] * l_[1] + m_[2] * l_[2] + (m_[3] * l_[3] + m_[4] * l_[4] + m_[5] * l_[5]) * 2.;
   mm[c] = m_[0] * m_[0] + m_[1] * m_[1] + m_[2] * m_[2] + (m_[3] * m_[3] + m_[4] * m_[4] + m_[5] * m_[5]) * 2.;
 }
+// The reference's _CAVITY (SgsAve::local, sgs.f90:328-358,368-377): nothing is averaged -- the two contractions of k_contract, its expressions in their
+// order, and visct = max(visct * LM / MM, 0) of the very cell in one pass; the two fields between them are neither stored nor read back, nothing is
+// summed and nothing travels between slabs. 16 words per cell in (visct holds |S|, sgs.f90:184), one out. A cell with MM = 0 (and so LM = 0) gives 0:
+// fmax(NaN, 0) = 0, as in k_dsmag_final; the reference's max(NaN, 0) depends on its compiler, and no cell of the goldens is such a cell.
+__global__ __launch_bounds__(BX *BY) void k_contract_local(Geom g, CP6 mij, CP6 lij, const real *__restrict__ uf, const real *__restrict__ vf,
+                                                            const real *__restrict__ wf, real *visct) {
+  const int i = blockIdx.x * BX + threadIdx.x + 1, j = blockIdx.y * BY + threadIdx.y + 1, k = blockIdx.z + 1;
+  if (i > g.n1 || j > g.n2) return;
+  const size_t c = g.ix(i, j, k);
+  real m_[6], l_[6];
+#pragma unroll
+  for (int m = 0; m < 6; ++m) { m_[m] = mij.p[m][c]; l_[m] = lij.p[m][c]; }
+  const real a = uf[c], b = vf[c], d = wf[c];
+  l_[0] -= a * a; l_[1] -= b * b; l_[2] -= d * d; l_[3] -= a * b; l_[4] -= a * d; l_[5] -= b * d;
+  const real lm = m_[0] * l_[0] + m_[1] * l_[1] + m_[2] * l_[2] + (m_[3] * l_[3] + m_[4] * l_[4] + m_[5] * l_[5]) * 2.;
+  const real mm = m_[0] * m_[0] + m_[1] * m_[1] + m_[2] * m_[2] + (m_[3] * m_[3] + m_[4] * m_[4] + m_[5] * m_[5]) * 2.;
+  real vt = visct[c] * lm / mm;
+  visct[c] = fmax(vt, 0.);
+}
 // ave1d_channel (sgs.f90:462-480): plane sums of two fields -> p1d(2, n3); one block per (k, field)
 __global__ __launch_bounds__(256) void k_plane_sum(Geom g, const real *__restrict__ a, const real *__restrict__ b, real *__restrict__ p1d) {
   __shared__ real sh[4];
@@ -367,8 +387,8 @@ __device__ inline void uiuj(const real *s, real *q) {
   q[6] = s[0] * s[1]; q[7] = s[0] * s[2]; q[8] = s[1] * s[2];
 }
 struct LijMijArgs {
-  const real *uc[3], *uf[3], *mf[6];
-  real *part;
+  const real *uc[3], *uf[3], *mf[6];      // mf[0]: |S| for k_lmf_tile<.., LOCAL> (the layout of this struct is the kernels' argument layout: left as it is)
+  real *part;                             // block sums of the planes; k_lmf_tile<.., LOCAL>: visct
   const real *dzci, *dzfi;
   real dxi, dyi;
   int kchunk, nblk, zlo, zhi;
@@ -415,8 +435,16 @@ constexpr int LMF_KMAX = 256;      // longest k chunk (block sums of a chunk in 
 // solve left (round-off; chkdiv watches it) and |S|S33 = -(|S|S11 + |S|S22). The test filter with its wall rules is linear: the filtered sixth component is
 // the negated sum of the two filtered diagonal ones, formed after the z combination. Fifteen row loads per plane instead of eighteen (six of 16 bytes, three
 // of 8), five rolling values per plane instead of six; 11 compulsory words per cell instead of 12. Only inside cales_step (SgsPath::five).
-template <typename OFF, int YW, int UCF, int PAIR = 0>      // YW = 1: walls or wall-model faces in y (ducts); 0: the channel instantiation carries none of that logic
+// LOCAL = 1 (SgsAve::local, the reference's _CAVITY, sgs.f90:368-377): nothing is averaged. The pass holds LM and MM of its own cell in registers, so it loads
+// |S| of that cell (A.mf[0], one plane ahead, unconditional and clamped like every load of the plane loop) and stores visct = max(|S| LM / MM, 0) of its 62 x TL
+// output cells itself (A.part): the partial sums in fours, psum, fold, bsum and the stores of the block sums drop out, and with them k_plane_fold, the
+// all-reduce and k_dsmag_final. The store is the one conditional vector-memory operation of the plane loop. MM = 0 gives 0 (fmax(NaN, 0), as in k_dsmag_final).
+// Six components only (PAIR = 0 or 1): a cell-wise coefficient has no lazy form, and the plan keeps five components out.
+// (PAIR and LOCAL: one template parameter, SSF = PAIR + 4 LOCAL, as in k_strain_tile -- the instantiations without LOCAL keep their symbols.)
+template <typename OFF, int YW, int UCF, int SSF = 0>      // YW = 1: walls or wall-model faces in y (ducts); 0: the channel instantiation carries none of that logic
 __global__ __launch_bounds__(64 * (LMF_TY(YW) + 2)) void k_lmf_tile(Geom g, LmfArgs B) {
+  static constexpr int PAIR = SSF & 3, LOCAL = SSF >> 2;      // (static: an automatic constant would join the captures of the lambdas below and shuffle their registers)
+  static_assert(PAIR <= 2 && LOCAL <= 1 && (!LOCAL || PAIR != 2), "local averaging keeps six components");
   const LijMijArgs &A = B.L;
   constexpr int TL = LMF_TY(YW);      // tile height
   // FUC (no walls in y): the test-filtered CELL-CENTRED velocity is not filtered here -- the filter is linear and shift-invariant, so F(u_c) =
@@ -433,8 +461,8 @@ __global__ __launch_bounds__(64 * (LMF_TY(YW) + 2)) void k_lmf_tile(Geom g, LmfA
   // plane sums: every working wave adds its lanes in fours (two DPP steps) and leaves sixteen partial sums per quantity; the first halo wave, idle
   // behind the barrier, adds the 128 partials of the previous plane (the full six-step wave sum ran in all ten waves before: 24 vector instructions
   // per plane and wave less in a pass that is bound by them)
-  __shared__ real psum[2][2][TL][16];
-  __shared__ real bsum[2][LMF_KMAX];
+  __shared__ real psum[LOCAL ? 1 : 2][LOCAL ? 1 : 2][LOCAL ? 1 : TL][16];      // (LOCAL: no sums, see above)
+  __shared__ real bsum[LOCAL ? 1 : 2][LOCAL ? 1 : LMF_KMAX];
   const int tx = threadIdx.x, ty = threadIdx.y;
   int bx = blockIdx.x, by = blockIdx.y, bz = blockIdx.z;
   if (B.bm.gx && !band_block(B.bm, bx, by, bz)) return;
@@ -445,6 +473,8 @@ __global__ __launch_bounds__(64 * (LMF_TY(YW) + 2)) void k_lmf_tile(Geom g, LmfA
   const int iw = A.perx ? (i == 0 ? g.n1 : (i == g.n1 + 1 ? 1 : i)) : i;
   const int ic = min(iw, g.n1 + 1), jc = min(j, g.n2 + 1);      // clamped: lanes / rows beyond the field read its last ghost column / row
   const OFF c0 = (OFF)g.ix(ic, jc, 0) * RSZ, sk = (OFF)g.s12 * RSZ, sj = (OFF)g.s1 * RSZ;      // byte offsets
+  real s0n = 0.;      // LOCAL: |S| of this thread's cell, one plane ahead (an output cell has ic = i, jc = j: c0 is its own column)
+  if constexpr (LOCAL) s0n = ldb(A.mf[0], c0 + (OFF)kbeg * sk);
   // rows whose |S|Sij this thread combines: its own and the two beside it; the two halo waves (and rows beyond n2) take a row of the tile
   // interior instead (cache hits, results unused)
   const int jo = max(by * TL + 1, min(min(j, by * TL + TL), g.n2));
@@ -530,13 +560,13 @@ __global__ __launch_bounds__(64 * (LMF_TY(YW) + 2)) void k_lmf_tile(Geom g, LmfA
   ssload(kbeg + 1, rw);
   const int blk = by * B.gx + bx;
   auto fold = [&](int k, int b) {      // block sums of plane k by ONE whole wave, fixed order
-    const real *p0 = &psum[b][0][0][0], *p1 = &psum[b][1][0][0];
+    const real *p0 = &psum[b][0][0][0], *p1 = &psum[b][LOCAL ? 0 : 1][0][0];      // (LOCAL: never called; the arrays have one element per dimension)
     static_assert(TL * 16 >= 128 && TL * 16 <= 192, "two or three partials per lane");
     constexpr int NP3 = TL * 16 - 128;      // partials beyond the first 128
     const int t3 = min(tx, NP3 > 0 ? NP3 - 1 : 0) + 128; const real w3 = (NP3 > 0 && tx < NP3) ? 1. : 0.;
     const real a = wave_sum_lane63(NP3 > 0 ? p0[tx] + p0[tx + 64] + w3 * p0[t3] : p0[tx] + p0[tx + 64]),
                bs = wave_sum_lane63(NP3 > 0 ? p1[tx] + p1[tx + 64] + w3 * p1[t3] : p1[tx] + p1[tx + 64]);
-    if (tx == 63) { bsum[0][k - kbeg] = a; bsum[1][k - kbeg] = bs; }
+    if (tx == 63) { bsum[0][k - kbeg] = a; bsum[LOCAL ? 0 : 1][k - kbeg] = bs; }
   };
   // grid coefficients of the plane, one plane ahead through the scalar cache (uniform: scalar registers)
   real zcm = ldc(A.dzci, kbeg - 1), zcc = ldc(A.dzci, kbeg), zfc = ldc(A.dzfi, kbeg);
@@ -562,7 +592,7 @@ __global__ __launch_bounds__(64 * (LMF_TY(YW) + 2)) void k_lmf_tile(Geom g, LmfA
     }
     if (FUC && (LO || HI)) { const real G = 4. * qc[2]; r[2] = lane_prev(G) + 2. * G + lane_next(G); shw[ty][tx] = r[2]; }      // w_c next to a z wall
     __syncthreads();
-    if (k > kbeg && ty == 0) fold(k - 1, buf ^ 1);
+    if constexpr (!LOCAL) { if (k > kbeg && ty == 0) fold(k - 1, buf ^ 1); }
     // plane k+1 of |S|Sij: its 18 loads were issued at the end of the previous plane and are folded into six values here, before
     // the register-hungry part; the next 18 are issued after it (keeps the kernel under the 168 VGPRs that ten waves per block need)
     sscomb(rw, xp);
@@ -619,10 +649,14 @@ __global__ __launch_bounds__(64 * (LMF_TY(YW) + 2)) void k_lmf_tile(Geom g, LmfA
       }
       lm = m[0] * l0 + m[1] * l1 + m[2] * l2 + (m[3] * l3 + m[4] * l4 + m[5] * l5) * 2.;       // sgs.f90:344-349
       mm = m[0] * m[0] + m[1] * m[1] + m[2] * m[2] + (m[3] * m[3] + m[4] * m[4] + m[5] * m[5]) * 2.;       // sgs.f90:350-355
+      if constexpr (LOCAL) { real vt = s0n * lm / mm; stb(A.part, c0 + (OFF)k * sk, fmax(vt, 0.)); }      // sgs.f90:376-377 (the operations of k_dsmag_final in their order)
     }
     ssload(min(k + 2, g.n3 + 1), rw);
+    if constexpr (LOCAL) s0n = ldb(A.mf[0], c0 + (OFF)min(k + 1, g.n3 + 1) * sk);      // |S| of plane k+1 (clamped: the ghost plane's value is never used)
+    if constexpr (!LOCAL) {
     lm += dpp_f64<0x111>(lm); lm += dpp_f64<0x112>(lm); mm += dpp_f64<0x111>(mm); mm += dpp_f64<0x112>(mm);      // row_shr 1, 2: lanes 3, 7, 11, ... hold four lanes' sum
     if ((tx & 3) == 3 && ty >= 1 && ty <= TL) { psum[buf][0][ty - 1][tx >> 2] = lm; psum[buf][1][ty - 1][tx >> 2] = mm; }
+    }
 #pragma unroll
     for (int q = 0; q < 3; ++q) { sm[q] = sc[q]; sc[q] = sp[q]; sp[q] = sn[q]; }
 #pragma unroll
@@ -637,6 +671,7 @@ __global__ __launch_bounds__(64 * (LMF_TY(YW) + 2)) void k_lmf_tile(Geom g, LmfA
     for (; k <= klast; ++k) plane(k, F_, F_);
     if (k <= kend) plane(k, F_, T);
   }
+  if constexpr (LOCAL) return;      // (every cell's visct left in the plane loop)
   __syncthreads();
   if (ty == 0 && kend >= kbeg) fold(kend, kend & 1);
   __syncthreads();
@@ -1414,6 +1449,12 @@ void sgs_setup(cales_ctx *c) {
   if (c->C.sgstype == 1) P.form = !xw && n[2] >= 3 && n[1] >= 2 && !fl.smag_reference_sequence ? SgsForm::smag_rows : SgsForm::smag_reference;
   // (ducts: the fused last pass knows the wall rule along y from three rows on)
   else if (P.ave == SgsAve::xlines) P.form = SgsForm::dsmag_reference;      // (no tile form yet: k_lmf_tile hands out plane partials, not rows')
+  else if (P.ave == SgsAve::local && P.filter2d) P.form = SgsForm::dsmag_reference;      // (k_lmf_plane_tile has no local form)
+  // local: the tile form for the classes k_lmf_tile forms the cell-centred velocity for (ucf below) -- x periodic, z between two walls or periodic -- with
+  // 32-bit byte offsets (small below): the two LOCAL instantiations with 64-bit offsets spill (profiles/dsmag_local_kernel_resources.md) and are not
+  // built, a field beyond 4 GB takes the sequence
+  else if (P.ave == SgsAve::local && !(CBP(c, 0, 1) == 'P' && CBP(c, 1, 1) == 'P' && !fl.dsmag_xghosts && (c->ntot + 16) * sizeof(real) < (1ull << 32) && !fl.wide_offsets &&
+                                       ((c->is_wall[4] != 0. && c->is_wall[5] != 0.) || (CBP(c, 0, 3) == 'P' && CBP(c, 1, 3) == 'P')))) P.form = SgsForm::dsmag_reference;
   else if (!P.filter2d) P.form = !xw && !(yw && n[1] < 3) && n[2] >= 3 && !fl.dsmag_reference_sequence ? SgsForm::dsmag_tiles : SgsForm::dsmag_reference;
   else {
     // the plane filter (-D_FILTER_2D): tiles for the channel class -- x periodic (the kernels wrap around), nothing at the y faces, z between two walls (no-slip
@@ -1437,7 +1478,8 @@ void sgs_setup(cales_ctx *c) {
   P.yw = P.wylo || P.wyhi || P.wmylo || P.wmyhi;
   P.small = (c->ntot + 16) * sizeof(real) < (1ull << 32) && !fl.wide_offsets;      // 32-bit byte offsets (ldb/stb)
   if (smag) { P.smag = P.yw ? (P.small ? SmagKernel::yw32 : SmagKernel::yw64) : (P.small ? SmagKernel::plain32 : SmagKernel::plain64); return; }
-  P.lazy = true; for (int q = 0; q < 6; ++q) P.lazy = P.lazy && c->C.bcsgs[q] == 0.;
+  const bool local = P.ave == SgsAve::local;      // a coefficient per cell: no cs(k) for the momentum pass to apply (lazy), and six components (five)
+  P.lazy = !local; for (int q = 0; q < 6; ++q) P.lazy = P.lazy && c->C.bcsgs[q] == 0.;
   P.perz = CBP(c, 0, 3) == 'P' && CBP(c, 1, 3) == 'P';
   P.perx = CBP(c, 0, 1) == 'P' && CBP(c, 1, 1) == 'P' && !fl.dsmag_xghosts;
   P.skipz = (P.zlo && P.zhi) ? 4 : 0;
@@ -1448,7 +1490,7 @@ void sgs_setup(cales_ctx *c) {
   P.pair = !P.filter2d && P.ucf && CBP(c, 0, 2) == 'P' && CBP(c, 1, 2) == 'P' && !fl.wide_offsets && !fl.unmerged_bc && (2 * c->ntot + 64) * sizeof(real) < (1ull << 32);
   // five |S|Sij instead of six wherever the strain-rate pass projects the velocity itself (make_plan: fold_correc needs pair fields) on one rank -- on slabs the
   // scratch rows travel in counted planes and keep six
-  P.five = P.pair && c->P == 1 && !fl.sgs_six_components;
+  P.five = P.pair && c->P == 1 && !fl.sgs_six_components && !local;
   P.lmf_ty = P.yw ? TYL : TYLF;
   P.strain = P.pair ? StrainKernel::pair : P.yw ? (P.small ? StrainKernel::yw32 : StrainKernel::yw64) : (P.small ? StrainKernel::plain32 : StrainKernel::plain64);
   static const LmfKernel lmf[2][2][2] = {{{LmfKernel::plain64, LmfKernel::plain32}, {LmfKernel::ucf64, LmfKernel::ucf32}},
@@ -1579,6 +1621,8 @@ static int dsmag_fast(cales_ctx *c, const SgsFold *fold, bool *visct_ghosts_done
   L.part = c->wk[0]; L.dzci = c->d_dzci; L.dzfi = c->d_dzfi; L.dxi = c->dli[0]; L.dyi = c->dli[1];
   L.zlo = P.zlo; L.zhi = P.zhi; L.wmlo = P.wmlo; L.wmhi = P.wmhi; L.flo = P.flo; L.fhi = P.fhi; L.perx = P.perx;
   L.wylo = P.wylo; L.wyhi = P.wyhi; L.wmylo = P.wmylo; L.wmyhi = P.wmyhi;
+  const bool local = P.ave == SgsAve::local;      // the last pass writes visct itself, from |S| (never lazy: K_AC left it in c->s0)
+  if (local) { L.mf[0] = c->s0; L.part = visct; }
   {
     // K_B + K_DF in one pass: filter(|S|Sij) on the fly, strain rate of the filtered velocity, Mij, Lij, contractions, plane partial sums
     ProfScope ps(c, "lij_mij_filter_contract");
@@ -1592,6 +1636,12 @@ static int dsmag_fast(cales_ctx *c, const SgsFold *fold, bool *visct_ghosts_done
       if (nby <= 0) return;
       TileGeom s = t; s.grid.y = nby; s = with_bands(s);
       B.by0 = by0; B.bm = s.bm;
+      if (local) switch (P.lmf) {      // (sgs_setup: ucf, 32-bit offsets, six components, the 3-D filter)
+      case LmfKernel::pair: LAUNCH(c, (k_lmf_tile<unsigned, 0, 1, 5>), s.grid, s.block, 0, c->stream, c->g, B); return;
+      case LmfKernel::yw_ucf32: LAUNCH(c, (k_lmf_tile<unsigned, 1, 1, 4>), s.grid, s.block, 0, c->stream, c->g, B); return;
+      case LmfKernel::ucf32: LAUNCH(c, (k_lmf_tile<unsigned, 0, 1, 4>), s.grid, s.block, 0, c->stream, c->g, B); return;
+      default: c->launch_err = "dsmag: no local form of this last pass"; return;      // (a missing kernel is an error, never another path)
+      }
       switch (five ? LmfKernel::pair5 : P.lmf) {
       case LmfKernel::pair5: LAUNCH(c, (k_lmf_tile<unsigned, 0, 1, 2>), s.grid, s.block, 0, c->stream, c->g, B); break;
       case LmfKernel::pair: LAUNCH(c, (k_lmf_tile<unsigned, 0, 1, 1>), s.grid, s.block, 0, c->stream, c->g, B); break;
@@ -1614,6 +1664,7 @@ static int dsmag_fast(cales_ctx *c, const SgsFold *fold, bool *visct_ghosts_done
       if (int e = stream_after(c, c->stream, c->comm_stream)) return e;
       launch(0, 1); launch(hi0, (int)t.grid.y - hi0);
     } else launch(0, (int)t.grid.y);
+    if (local) { LAUNCHCHK(c); return 0; }      // sgs.f90:368-377: visct is written -- no fold, no all-reduce, no final kernel
     LAUNCH(c, k_plane_fold, dim3(2 * n[2]), dim3(256), 0, c->stream, n[2], L.nblk, c->wk[0], c->d_p1d);
   }
   if (c->P > 1) { if (int e = allreduce_dev(c, c->d_p1d, 2 * n[2], 0)) return e; }   // sgs.f90:475
@@ -1786,6 +1837,11 @@ int op_cmpt_sgs(cales_ctx *c, const SgsFold *fold, bool *visct_ghosts_done) {
   if (c->sgs.ave == SgsAve::xlines) {      // sgs.f90:366-367: x is local to a y slab -- nothing to communicate
     LAUNCH(c, k_contract_lines, dim3((n[1] * n[2] + 3) / 4), dim3(256), 0, c->stream, c->g, cmij, clij, c->uf, c->vf, c->wf, wk[0]);
     LAUNCH(c, k_dsmag_final_lines, gr, b, 0, c->stream, c->g, c->dl[0] / c->C.l[0], wk[0], visct, visct);
+    LAUNCHCHK(c);
+    return 0;
+  }
+  if (c->sgs.ave == SgsAve::local) {      // sgs.f90:368-377: no average, no reduction, no collective -- one kernel in place of k_contract + k_plane_sum + k_dsmag_final
+    LAUNCH(c, k_contract_local, gr, b, 0, c->stream, c->g, cmij, clij, c->uf, c->vf, c->wf, visct);
     LAUNCHCHK(c);
     return 0;
   }

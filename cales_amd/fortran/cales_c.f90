@@ -14,6 +14,8 @@ module cales_c
   integer(c_int), parameter :: CALES_U = 0, CALES_V = 1, CALES_W = 2, CALES_P = 3, CALES_PP = 4, CALES_VISCT = 5
   ! enum cales_sgs_average of include/cales.h: one flag OR-ed onto cales_case%sgstype = 2 or 3 ('dsmag'), the averaging of the Germano identity
   integer(c_int32_t), parameter :: CALES_SGS_AVE_VOLUME = 4, CALES_SGS_AVE_XLINES = 8
+  ! ... and the flag for no averaging at all (the reference's _CAVITY), declared on its own in include/cales.h as well
+  integer(c_int32_t), parameter :: CALES_SGS_AVE_LOCAL = 64
   type, bind(C) :: cales_case
     integer(c_int32_t) :: ng(3)
     real(c_rp)     :: l(3)

@@ -17,7 +17,7 @@
 !                              _IMPDIFF/_IMPDIFF_1D are run-time here); reads ./input.nml
 ! environment: CALES_FILTER_2D (set to anything but 0) = the reference's build switch _FILTER_2D: sgstype = 'dsmag' test-filters in the x-y planes
 !              only and uses alph2 = 2.52 everywhere (src/sgs.f90:236-247,316-327,817-821); no effect on 'none' and 'smag'
-!              CALES_DSMAG_AVERAGE = planes (also unset or empty) | volume | xlines: the reference's _CHANNEL (hard-wired there) | -D_DIT | _DUCT -- the
+!              CALES_DSMAG_AVERAGE = planes (also unset or empty) | volume | xlines | local: the reference's _CHANNEL (hard-wired there) | -D_DIT | _DUCT | _CAVITY -- the
 !              directions sgstype = 'dsmag' averages the Germano identity over (src/sgs.f90:359-370); no effect on 'none' and 'smag'
 !              CALES_OUT3D_NSKIP = "a,b,c": the nskip of the volume dumps, which the reference hard-codes as [1,1,1] in its out3d.h90; with a value > 1
 !              the dumps hold the interior points 1, 1+nskip, ... of every direction, read strided from the device (cales_out3d)
@@ -133,18 +133,19 @@ program cales
     cs%sgstype = 2
     call get_environment_variable('CALES_FILTER_2D',f2d,f2dlen,f2dstat)           ! the run-time form of -D_FILTER_2D
     if(f2dstat <= 0 .and. f2dlen > 0 .and. trim(f2d) /= '0') cs%sgstype = 3       ! CALES_SGS_DSMAG_FILTER2D (include/cales.h)
-    call get_environment_variable('CALES_DSMAG_AVERAGE',ave,avelen,avestat)       ! the run-time form of _DIT / _CHANNEL / _DUCT
+    call get_environment_variable('CALES_DSMAG_AVERAGE',ave,avelen,avestat)       ! the run-time form of _DIT / _CHANNEL / _DUCT / _CAVITY
     if(avestat == 0 .and. avelen > 0) then
       select case(trim(ave))
       case('planes')
       case('volume'); cs%sgstype = ior(cs%sgstype,CALES_SGS_AVE_VOLUME)
       case('xlines'); cs%sgstype = ior(cs%sgstype,CALES_SGS_AVE_XLINES)
+      case('local');  cs%sgstype = ior(cs%sgstype,CALES_SGS_AVE_LOCAL)
       case default
-        if(myid == 0) print*, 'ERROR: unknown CALES_DSMAG_AVERAGE (planes, volume or xlines)'
+        if(myid == 0) print*, 'ERROR: unknown CALES_DSMAG_AVERAGE (planes, volume, xlines or local)'
         call die
       end select
-    else if(avestat < 0) then                                                     ! (longer than any of the three words)
-      if(myid == 0) print*, 'ERROR: unknown CALES_DSMAG_AVERAGE (planes, volume or xlines)'
+    else if(avestat < 0) then                                                     ! (longer than any of the four words)
+      if(myid == 0) print*, 'ERROR: unknown CALES_DSMAG_AVERAGE (planes, volume, xlines or local)'
       call die
     end if
   case('amd')                                                                  ! src/sgs.f90:381-382

@@ -163,8 +163,8 @@ class Case:
     # _FILTER_2D: 'dsmag' test-filters in the x-y planes only (sgs.f90:236-247,316-327,817-821); no effect on 'none' and 'smag'.
     # None: taken from the environment variable CALES_FILTER_2D when the case goes to the library (capi.make_case)
     filter2d: Optional[bool] = None
-    # _DIT / _CHANNEL / _DUCT: the directions 'dsmag' averages the Germano identity over (sgs.f90:359-370): 'planes' (the reference's hard-wired _CHANNEL),
-    # 'volume' (-D_DIT, ave0d_dit) or 'xlines' (_DUCT without _CHANNEL, ave2d_duct along x); no effect on 'none' and 'smag'.
+    # _DIT / _CHANNEL / _DUCT / _CAVITY: the directions 'dsmag' averages the Germano identity over (sgs.f90:359-370): 'planes' (the reference's hard-wired _CHANNEL),
+    # 'volume' (-D_DIT, ave0d_dit), 'xlines' (_DUCT without _CHANNEL, ave2d_duct along x) or 'local' (_CAVITY without _CHANNEL: cell by cell); no effect on 'none' and 'smag'.
     # None: taken from the environment variable CALES_DSMAG_AVERAGE when the case goes to the library (unset or empty: planes)
     dsmag_average: Optional[str] = None
 

@@ -40,7 +40,7 @@ typedef struct cales_case {
   cales_real  bcvel[18], bcpre[6], bcsgs[6];
   cales_real  bforce[3]; int32_t is_forced[3]; cales_real velf[3];
   int32_t sgstype;        /* 0 'none', 1 'smag', 2 'dsmag', 3 'dsmag' of a -D_FILTER_2D build (src/sgs.f90:61-153; enum cales_sgstype below),
-                           * 2 and 3 optionally OR-ed with one flag of enum cales_sgs_average */
+                           * 2 and 3 optionally OR-ed with one flag of enum cales_sgs_average or with CALES_SGS_AVE_LOCAL */
   int32_t lwm[6]; cales_real hwm;
   int32_t impdiff;        /* 0 explicit; 2 = _IMPDIFF + _IMPDIFF_1D (z-implicit); 1 = _IMPDIFF (3-D implicit; periodic or no-slip wall pairs in x and y) */
   int32_t nranks, rank;   /* y-slab decomposition: rank owns rows rank*ng2/nranks+1 ... */
@@ -55,6 +55,13 @@ enum cales_sgstype { CALES_SGS_NONE = 0, CALES_SGS_SMAG = 1, CALES_SGS_DSMAG = 2
  * CALES_SGS_AVE_XLINES: a _DUCT build without _CHANNEL, one coefficient per x line (j, k) (ave2d_duct(...,1,...), sgs.f90:585-612).
  * cales_check_case refuses both flags together and a flag on 'none' or 'smag'. */
 enum cales_sgs_average { CALES_SGS_AVE_VOLUME = 4, CALES_SGS_AVE_XLINES = 8 };
+/* CALES_SGS_AVE_LOCAL: a -D_CAVITY build without _CHANNEL, no averaging at all -- visct = max(|S| MijLij / MijMij, 0) cell by cell (sgs.f90:368-377): the
+ * only choice that makes sense where no direction is homogeneous (cavities, walls in x). A third flag of the same kind, OR-ed onto CALES_SGS_DSMAG or
+ * CALES_SGS_DSMAG_FILTER2D (sgstype 66, 67), declared on its own because the enum above is a closed list that hosts and checks already rely on. The value
+ * is 64, not the next bit: cales_check_case has always refused 16 and 32 on sgstype (18 and 34 as "unknown SGS model") and keeps refusing them.
+ * A cell with MijMij = 0 (then MijLij = 0 too) gets visct = 0 where the reference's max(NaN, 0) depends on its compiler. cales_check_case refuses the flag
+ * together with either flag above and on 'none' or 'smag'. */
+enum { CALES_SGS_AVE_LOCAL = 64 };
 
 typedef struct cales_ctx cales_ctx;
 

@@ -6,8 +6,8 @@
 An entry is CASE:GRID[:key=value,...]. CASE ending in .nml is a file of cales_amd/cases, anything else a key of tests/golden/examples.json (the
 namelists of the examples the reference ships, kept as data); GRID is n1xn2xn3 or `own`; keys: sgs (none | smag | dsmag), impdiff (0 | 1 | 2),
 filter (2d | 3d: the test filter of the dynamic model, Case.filter2d -- the reference's -D_FILTER_2D; without the key CALES_FILTER_2D decides),
-average (planes | volume | xlines: what the dynamic model averages the Germano identity over, Case.dsmag_average -- the reference's _CHANNEL / -D_DIT /
-_DUCT; without the key CALES_DSMAG_AVERAGE decides).
+average (planes | volume | xlines | local: what the dynamic model averages the Germano identity over, Case.dsmag_average -- the reference's _CHANNEL / -D_DIT /
+_DUCT / _CAVITY; without the key CALES_DSMAG_AVERAGE decides).
 Per entry: create the context, warm up, time K steps of cales_step between device synchronisations (K from a pilot so that the window is at
 least --window seconds), repeat them with per-kernel events, print ONE JSON line: ms_per_step, the plan string and, per scope of the solve, the ms
 per call and the fraction of the 8 TB/s peak at 2 compulsory words per cell and pass (4 with fillps inside the forward x pass, 9 for the correction
@@ -47,8 +47,8 @@ def load(entry):
             raise SystemExit(f"{entry}: filter is 2d or 3d")
         case.filter2d = opts["filter"] == "2d"
     if "average" in opts:
-        if opts["average"] not in ("planes", "volume", "xlines"):
-            raise SystemExit(f"{entry}: average is planes, volume or xlines")
+        if opts["average"] not in ("planes", "volume", "xlines", "local"):
+            raise SystemExit(f"{entry}: average is planes, volume, xlines or local")
         case.dsmag_average = opts["average"]
     return case
 
