@@ -1,4 +1,4 @@
-"""ctypes binding of libcales_hip.so (C-ABI declared in include/cales.h and include/cales_post.h).
+"""ctypes binding of libcales_hip.so (C-ABI declared in include/cales.h, include/cales_post.h and include/cales_pdf.h).
 
 There is no CPU fallback: if the HIP library has not been built, importing the symbols raises.
 """
@@ -55,6 +55,11 @@ SYMBOLS = ["cales_real_size", "cales_initgrid", "cales_initflow", "cales_check_c
 # every symbol include/cales_post.h declares, the output side of the C-ABI (planes, boxes and strided samples of a field read from the device); a list of
 # its own, as the header is a header of its own (tests/test_box_reads_host.py checks it against that header)
 POST_SYMBOLS = ["cales_box_share", "cales_read_box", "cales_out2d", "cales_out3d"]
+
+# every symbol include/cales_pdf.h declares: per-plane histograms of a field and joint histograms of two fields, binned on the device; again a list of
+# its own beside a header of its own (tests/test_pdf_host.py checks it against that header)
+PDF_SYMBOLS = ["cales_pdf_planes", "cales_jpdf_planes"]
+PDF_MAX_BINS, JPDF_MAX_BINS = 4096, 128      # CALES_PDF_MAX_BINS, CALES_JPDF_MAX_BINS
 
 
 class CalesCase(C.Structure):
@@ -165,6 +170,13 @@ def lib() -> C.CDLL:
             "cales_read_box": [C.c_void_p, C.c_int, dp, dp, dp, dp, dp],
             "cales_out2d": [C.c_void_p, C.c_int, C.c_int, C.c_int, dp, dp],
             "cales_out3d": [C.c_void_p, C.c_int, dp, dp, dp],
+        }.items():
+            fn = getattr(L, name)
+            fn.argtypes = args
+            fn.restype = C.c_int
+        for name, args in {      # include/cales_pdf.h (PDF_SYMBOLS)
+            "cales_pdf_planes": [C.c_void_p, C.c_int, C.c_int, c_real, c_real, dp, dp],
+            "cales_jpdf_planes": [C.c_void_p, C.c_int, C.c_int, C.c_int, c_real, c_real, c_real, c_real, C.c_int, dp, dp, dp],
         }.items():
             fn = getattr(L, name)
             fn.argtypes = args

@@ -3,6 +3,7 @@
 // HIP-event kernel timers used by bench.py's roofline line.
 #include "common.hpp"
 #include "../../include/cales_post.h"
+#include "../../include/cales_pdf.h"
 #include <algorithm>
 #include <atomic>
 
@@ -482,6 +483,16 @@ int cales_out1d_chan_budgets(cales_ctx *c, real *budget, real *leakage) { if (!c
 int cales_out1d(cales_ctx *c, int field, int idir, int use_dzc, real *buf) { if (!c || !buf) return 1; ENTRY(c, op_out1d(c, field, idir, use_dzc, buf)); }
 int cales_out1d_chan(cales_ctx *c, real *buf) { if (!c || !buf) return 1; ENTRY(c, op_out1d_chan(c, buf)); }
 int cales_out2d_duct(cales_ctx *c, real *buf) { if (!c || !buf) return 1; ENTRY(c, op_out2d_duct(c, buf)); }
+// include/cales_pdf.h (k_pdf.hip)
+int cales_pdf_planes(cales_ctx *c, int field, int nbins, real lo, real hi, int64_t *counts, int64_t *outside) {
+  if (!c) return 1;
+  ENTRY(c, op_pdf_planes(c, field, nbins, lo, hi, counts, outside));
+}
+int cales_jpdf_planes(cales_ctx *c, int field_a, int field_b, int nbins, real lo_a, real hi_a, real lo_b, real hi_b, int nplanes, const int32_t *kplanes,
+                      int64_t *counts, int64_t *outside) {
+  if (!c) return 1;
+  ENTRY(c, op_jpdf_planes(c, field_a, field_b, nbins, lo_a, hi_a, lo_b, hi_b, nplanes, kplanes, counts, outside));
+}
 
 // ------------------------------------------------------------------------------------------ time step (main.f90:412-508)
 __global__ __launch_bounds__(256) void k_row2_to_companion(Geom g, const real *__restrict__ pp, real *__restrict__ comp) {

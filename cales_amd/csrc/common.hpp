@@ -482,6 +482,10 @@ int op_stats_chan_budget(cales_ctx *c, real *budget, real *leak);
 int op_out1d(cales_ctx *c, int field, int idir, int use_dzc, real *buf);
 int op_out1d_chan(cales_ctx *c, real *buf);
 int op_out2d_duct(cales_ctx *c, real *buf);
+// include/cales_pdf.h (k_pdf.hip): per-plane histograms of a field, joint histograms of two fields on chosen planes; synchronous
+int op_pdf_planes(cales_ctx *c, int field, int nbins, real lo, real hi, int64_t *counts, int64_t *outside);
+int op_jpdf_planes(cales_ctx *c, int field_a, int field_b, int nbins, real lo_a, real hi_a, real lo_b, real hi_b, int nplanes, const int32_t *kplanes,
+                   int64_t *counts, int64_t *outside);
 bool solver_can_fuse_fillps(cales_ctx *c);
 int solver_mode_columns(cales_ctx *c);      // complex mode columns per rank of the pressure solve
 std::string solver_path_name(cales_ctx *c);      // which transform / tridiagonal kernels the pressure solve of this context takes (cales_describe_plan)

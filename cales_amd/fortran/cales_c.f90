@@ -1,4 +1,4 @@
-! ISO_C_BINDING view of include/cales.h and include/cales_post.h -- what a Fortran host (the reference's own language) binds to.
+! ISO_C_BINDING view of include/cales.h, include/cales_post.h and include/cales_pdf.h -- what a Fortran host (the reference's own language) binds to.
 ! `type(cales_case)` mirrors `struct cales_case`; character and multi-dimensional members keep the
 ! storage order of the reference's namelist variables (src/param.f90:37-76), so they are copied unchanged.
 module cales_c
@@ -178,6 +178,16 @@ module cales_c
     integer(c_int) function cales_out3d(ctx,field,nskip,buf,count) bind(C,name='cales_out3d')
       import; type(c_ptr), value :: ctx; integer(c_int), value :: field; integer(c_int32_t), intent(in) :: nskip(3)
       real(c_rp) :: buf(*); integer(c_int32_t) :: count(3)
+    end function
+    ! ---- include/cales_pdf.h: histograms binned on the device, this rank's counts. Bin rule: s = nbins/(hi-lo), t = (x-lo)*s, bin int(t) for 0 <= t < nbins.
+    ! counts(nbins,n3), outside(2,n3): below, above | counts(nbins,nbins,nplanes), first axis field_a, outside(nplanes): either variable outside; kplanes: global k
+    integer(c_int) function cales_pdf_planes(ctx,field,nbins,lo,hi,counts,outside) bind(C,name='cales_pdf_planes')
+      import; type(c_ptr), value :: ctx; integer(c_int), value :: field,nbins; real(c_rp), value :: lo,hi
+      integer(c_int64_t) :: counts(*),outside(*)
+    end function
+    integer(c_int) function cales_jpdf_planes(ctx,field_a,field_b,nbins,lo_a,hi_a,lo_b,hi_b,nplanes,kplanes,counts,outside) bind(C,name='cales_jpdf_planes')
+      import; type(c_ptr), value :: ctx; integer(c_int), value :: field_a,field_b,nbins,nplanes; real(c_rp), value :: lo_a,hi_a,lo_b,hi_b
+      integer(c_int32_t), intent(in) :: kplanes(*); integer(c_int64_t) :: counts(*),outside(*)
     end function
   end interface
 end module cales_c

@@ -168,6 +168,29 @@ class HotPath:
         self._chk(self.L.cales_out3d(self.h, capi.FIELDS[name], _i3(nskip), _p(a), None))
         return a
 
+    # -- histograms (include/cales_pdf.h): this rank's counts, int64 and Fortran-ordered; the caller adds the ranks
+    def pdf_planes(self, name: str, nbins: int, lo: float, hi: float) -> Tuple[np.ndarray, np.ndarray]:
+        """cales_pdf_planes: (counts (nbins, n3), outside (2, n3): below, above) of the interior samples of field `name` on every plane, by the bin rule
+        of the header: s = nbins / (hi - lo), t = (x - lo) * s, bin int(t) for 0 <= t < nbins."""
+        nbins = int(nbins)
+        ok = 1 <= nbins <= capi.PDF_MAX_BINS      # (anything else: the library refuses it below, nothing is written)
+        counts = np.zeros((nbins if ok else 1, self.n[2]), order="F", dtype=np.int64)
+        outside = np.zeros((2, self.n[2]), order="F", dtype=np.int64)
+        self._chk(self.L.cales_pdf_planes(self.h, capi.FIELDS[name], nbins, float(lo), float(hi), counts.ctypes.data_as(C.c_void_p), outside.ctypes.data_as(C.c_void_p)))
+        return counts, outside
+
+    def jpdf_planes(self, name_a: str, name_b: str, nbins: int, range_a, range_b, kplanes) -> Tuple[np.ndarray, np.ndarray]:
+        """cales_jpdf_planes: (counts (nbins, nbins, nplanes), first axis `name_a`; outside (nplanes): either variable outside its range) of the sample
+        pairs at the same index on the planes `kplanes` (global k, 1 ... ng(3); any order, repeats allowed)."""
+        nbins = int(nbins)
+        kp = np.ascontiguousarray([int(k) for k in kplanes], dtype=np.int32)
+        ok = 1 <= nbins <= capi.JPDF_MAX_BINS
+        counts = np.zeros((nbins, nbins, kp.size) if ok else (1, 1, max(kp.size, 1)), order="F", dtype=np.int64)
+        outside = np.zeros(max(kp.size, 1), dtype=np.int64)
+        self._chk(self.L.cales_jpdf_planes(self.h, capi.FIELDS[name_a], capi.FIELDS[name_b], nbins, float(range_a[0]), float(range_a[1]), float(range_b[0]), float(range_b[1]),
+                                           int(kp.size), kp.ctypes.data_as(C.c_void_p), counts.ctypes.data_as(C.c_void_p), outside.ctypes.data_as(C.c_void_p)))
+        return counts, outside[:kp.size]
+
     def upload(self, u, v, w, p):
         a = [_In(x) for x in (u, v, w, p)]
         self._chk(self.L.cales_upload_state(self.h, *[x.p for x in a]))
