@@ -9,6 +9,7 @@
 #include <string>
 #include <vector>
 #include "../../include/cales.h"
+#include "lmf_pack.hpp"
 
 // The working precision rp of the reference (src/precision.f90:11-20): FP64, or FP32 when the library is built with -DCALES_SINGLE
 // (the reference's -D_SINGLE_PRECISION; libcales_hip_sp.so). `real` is cales_real of include/cales.h.
@@ -86,7 +87,7 @@ struct Spec {
 
 // Run-time switches: read from the environment ONCE, by cales_create; the launch path only looks at these fields.
 struct Flags {
-  bool unfolded_correc = false, unfolded_mom = false, eager_projection = false, lazy_projection = false, helmholtz_z_per_column = false, unfused_imp_rhs = false, unfused_correc = false, unfused_forcing = false, unfused_fillps = false, unfused_mean = false, keep_last_rhs = false, wide_offsets = false, dsmag_reference_sequence = false, dsmag_xghosts = false, smag_reference_sequence = false, gaussel_march = false, fft_generic = false, fft_no_odd_radix = false, keep_null_mode = false, unfused_rk = false, overlap = false, xghosts_in_step = false, unmerged_bc = false, no_nyquist_packing = false, sgs_six_components = false;
+  bool unfolded_correc = false, unfolded_mom = false, eager_projection = false, lazy_projection = false, helmholtz_z_per_column = false, unfused_imp_rhs = false, unfused_correc = false, unfused_forcing = false, unfused_fillps = false, unfused_mean = false, keep_last_rhs = false, wide_offsets = false, dsmag_reference_sequence = false, dsmag_xghosts = false, smag_reference_sequence = false, gaussel_march = false, fft_generic = false, fft_no_odd_radix = false, keep_null_mode = false, unfused_rk = false, overlap = false, xghosts_in_step = false, unmerged_bc = false, no_nyquist_packing = false, sgs_six_components = false, lmf_unpacked_remainder = false, lmf_main_bands = false;
   int kchunk = 0; long tile_min_blocks = 2048;
   std::string test_bad_launch;      // CALES_TEST_BAD_LAUNCH: test hook of the launch check (LAUNCH below)
   void read_env() {
@@ -106,6 +107,8 @@ struct Flags {
     dsmag_reference_sequence = getenv("CALES_DSMAG_REFERENCE_SEQUENCE") != nullptr;
     dsmag_xghosts = getenv("CALES_DSMAG_XGHOSTS") != nullptr;
     sgs_six_components = getenv("CALES_SGS_SIX_COMPONENTS") != nullptr;      // dynamic model in cales_step on one rank: all six |S|Sij travel between the strain-rate pass and the last pass (default: five, the third from the trace -- SgsPath::five)
+    lmf_unpacked_remainder = getenv("CALES_LMF_UNPACKED_REMAINDER") != nullptr;      // dynamic model's last pass on one rank, pair fields: the remainder x tile as one more tile column of the one launch (default: packed into full waves, a launch of its own -- SgsPath::lmf_packed)
+    lmf_main_bands = getenv("CALES_LMF_MAIN_BANDS") != nullptr;      // ... packed: the launch of the full tiles through the band map even where band_wanted says no (experiments)
     smag_reference_sequence = getenv("CALES_SMAG_REFERENCE_SEQUENCE") != nullptr;
     gaussel_march = getenv("CALES_GAUSSEL_MARCH") != nullptr;
     no_nyquist_packing = getenv("CALES_NO_NYQUIST_PACKING") != nullptr;      // periodic x, periodic or Neumann y: the real modes 0 and n1/2 in columns of their own (n1/2 + 1 mode columns) instead of sharing column 0
@@ -176,6 +179,10 @@ struct SgsPath {
   int perz = 0, perx = 0, skipz = 0, lmf_ty = 0;
   StrainKernel strain = StrainKernel::plain64; LmfKernel lmf = LmfKernel::plain64; SmagKernel smag = SmagKernel::plain64;
   TileGeom strain_geo, corr_geo, corr_rows2_geo, lmf_geo, smag_geo;      // (lmf_geo unbanded: the overlap of cmpt_sgs splits it per call)
+  // lmf_packed (pair fields on one rank, lmf_pack(n1).on, not CALES_LMF_UNPACKED_REMAINDER): lmf_geo covers the full x tiles only and lmf_rem_geo, a launch of
+  // the packed instantiation with a chunk length of its own, the remainder tile of every row (lmf_pack.hpp); lmf_gx: x tiles of a row, the remainder one
+  // included -- the block sums of a plane keep the slots of the one launch
+  bool lmf_packed = false; TileGeom lmf_rem_geo; int lmf_gx = 0;
 };
 // op_cmpt_sgs inside cales_step: the projection folded into the strain-rate pass (StepPlan::fold_correc; rows2: fold_rows2; fmask: deferred forcing)
 struct SgsFold { real dtrk; bool rows2; int fmask; };
@@ -620,9 +627,8 @@ static inline int balanced_kchunk(const cales_ctx *c, long nxy_blocks, int n3, i
 }
 // Geometry of a marching tile kernel (plain 3-D grid): blocks of 64 x (ty + 2), tiles ty x wx over n2 + rows_more rows, k chunks halved until the grid has
 // tile_min_blocks blocks, on small grids one per CU (SMALL_KCH), then balanced over the rounds (balanced_kchunk); CALES_KCHUNK overrides.
-static inline TileGeom tile_geom(const cales_ctx *c, int ty, int wx, int rows_more = 0, int kmax = 1 << 30) {
+static inline void tile_chunks(const cales_ctx *c, TileGeom &t, int kmax = 1 << 30) {      // the k chunks of t.grid.x x t.grid.y tiles: t.kchunk, t.grid.z
   const int *n = c->n;
-  TileGeom t; t.block = dim3(64, ty + 2, 1); t.grid = dim3((n[0] + wx - 1) / wx, (n[1] + rows_more + ty - 1) / ty, 1);
   const long nxy = (long)t.grid.x * t.grid.y;
   int kch = n[2];
   while (nxy * ((n[2] + kch - 1) / kch) < c->fl.tile_min_blocks && kch > 32) kch = (kch + 1) / 2;
@@ -630,6 +636,11 @@ static inline TileGeom tile_geom(const cales_ctx *c, int ty, int wx, int rows_mo
   kch = balanced_kchunk(c, nxy, n[2], kch, kmax);
   if (c->fl.kchunk > 0) kch = c->fl.kchunk < n[2] ? c->fl.kchunk : n[2];      // (experiments)
   t.kchunk = kch; t.grid.z = (n[2] + kch - 1) / kch;
+}
+static inline TileGeom tile_geom(const cales_ctx *c, int ty, int wx, int rows_more = 0, int kmax = 1 << 30) {
+  const int *n = c->n;
+  TileGeom t; t.block = dim3(64, ty + 2, 1); t.grid = dim3((n[0] + wx - 1) / wx, (n[1] + rows_more + ty - 1) / ty, 1);
+  tile_chunks(c, t, kmax);
   return t;
 }
 static inline bool any_wm(const cales_ctx *c) { for (int q = 0; q < 6; ++q) if (c->C.lwm[q] != 0) return true; return false; }      // some face of the CASE has a wall model (a face owned by another slab counts)

@@ -440,11 +440,21 @@ constexpr int LMF_KMAX = 256;      // longest k chunk (block sums of a chunk in 
 // output cells itself (A.part): the partial sums in fours, psum, fold, bsum and the stores of the block sums drop out, and with them k_plane_fold, the
 // all-reduce and k_dsmag_final. The store is the one conditional vector-memory operation of the plane loop. MM = 0 gives 0 (fmax(NaN, 0), as in k_dsmag_final).
 // Six components only (PAIR = 0 or 1): a cell-wise coefficient has no lazy form, and the plan keeps five components out.
-// (PAIR and LOCAL: one template parameter, SSF = PAIR + 4 LOCAL, as in k_strain_tile -- the instantiations without LOCAL keep their symbols.)
+// PACK = 1 (SgsPath::lmf_packed; pair fields on one rank): the REMAINDER x tile of every row -- rem = n1 mod 62 live columns, 16 of 64 lanes at 512 cells, on
+// which the unpacked form runs the whole plane loop with 46 lanes clamped onto cells nobody uses. S stretches of rem + 2 lanes, each with its own two halo lanes
+// and on a y tile of its own, share a wave, one every P lanes (P = rem + 2 rounded up to a multiple of four, S = 64 / P; lmf_pack.hpp: the map, checked on the
+// CPU); the full tiles go in a launch of the unpacked form with grid.x = n1 / 62. The plane loop is the same -- column, row, |S|Sij row and outok per lane come
+// from the prologue: lane_prev / lane_next across a stretch's border feed halo lanes only, the LDS neighbours [ty +- 1][tx], [ty][tx - 1] of an output lane stay
+// in its stretch, dead stretches (y tiles beyond the last) and dead lanes sit on the last tile's rows and add zero to psum. Block sums: ONE PER STRETCH, formed by
+// the operations the unpacked tile's sum takes (stretches start on a multiple of four, so the partials of four are the same; fold adds each stretch's from the
+// places they have in the unpacked tile) and stored in the slot the one launch gives that y tile's remainder tile: the plane sums are the one launch's to the bit.
+// PAIR = 1 and 2, YW = 0, UCF = 1, 32-bit offsets.
+// (PAIR, LOCAL and PACK: one template parameter, SSF = PAIR + 4 LOCAL + 8 PACK, as in k_strain_tile -- the instantiations without LOCAL / PACK keep their symbols.)
 template <typename OFF, int YW, int UCF, int SSF = 0>      // YW = 1: walls or wall-model faces in y (ducts); 0: the channel instantiation carries none of that logic
 __global__ __launch_bounds__(64 * (LMF_TY(YW) + 2)) void k_lmf_tile(Geom g, LmfArgs B) {
-  static constexpr int PAIR = SSF & 3, LOCAL = SSF >> 2;      // (static: an automatic constant would join the captures of the lambdas below and shuffle their registers)
+  static constexpr int PAIR = SSF & 3, LOCAL = (SSF >> 2) & 1, PACK = SSF >> 3;      // (static: an automatic constant would join the captures of the lambdas below and shuffle their registers)
   static_assert(PAIR <= 2 && LOCAL <= 1 && (!LOCAL || PAIR != 2), "local averaging keeps six components");
+  static_assert(PACK <= 1 && (!PACK || (PAIR && !LOCAL && !YW && UCF)), "the packed remainder tile: pair fields on one rank");
   const LijMijArgs &A = B.L;
   constexpr int TL = LMF_TY(YW);      // tile height
   // FUC (no walls in y): the test-filtered CELL-CENTRED velocity is not filtered here -- the filter is linear and shift-invariant, so F(u_c) =
@@ -465,11 +475,15 @@ __global__ __launch_bounds__(64 * (LMF_TY(YW) + 2)) void k_lmf_tile(Geom g, LmfA
   __shared__ real bsum[LOCAL ? 1 : 2][LOCAL ? 1 : LMF_KMAX];
   const int tx = threadIdx.x, ty = threadIdx.y;
   int bx = blockIdx.x, by = blockIdx.y, bz = blockIdx.z;
-  if (B.bm.gx && !band_block(B.bm, bx, by, bz)) return;
+  if (!PACK && B.bm.gx && !band_block(B.bm, bx, by, bz)) return;
   by += B.by0;
-  const int i = bx * 62 + tx, j = by * TL + ty;
+  // PACK: S stretches of rem + 2 lanes per wave, each on a y tile of its own (lmf_pack.hpp) -- column, row and tile per lane; nothing behind this prologue differs
+  const LmfPack pp = PACK ? lmf_pack(g.n1) : LmfPack{};
+  const LmfLane pk = PACK ? lmf_pack_lane(pp, tx, ty, (int)blockIdx.y, B.by0, TL, g.n2) : LmfLane{};
+  const int nlive = PACK ? min(pp.S, (g.n2 + TL - 1) / TL - ((int)blockIdx.y * pp.S + B.by0)) : 0;      // stretches of this block whose y tile exists
+  const int i = PACK ? pk.i : bx * 62 + tx, j = PACK ? pk.j : by * TL + ty;
   const int kbeg = bz * A.kchunk + 1, kend = min(kbeg + A.kchunk - 1, g.n3);
-  const bool outok = tx >= 1 && tx <= 62 && ty >= 1 && ty <= TL && i <= g.n1 && j <= g.n2;
+  const bool outok = PACK ? pk.out : tx >= 1 && tx <= 62 && ty >= 1 && ty <= TL && i <= g.n1 && j <= g.n2;
   const int iw = A.perx ? (i == 0 ? g.n1 : (i == g.n1 + 1 ? 1 : i)) : i;
   const int ic = min(iw, g.n1 + 1), jc = min(j, g.n2 + 1);      // clamped: lanes / rows beyond the field read its last ghost column / row
   const OFF c0 = (OFF)g.ix(ic, jc, 0) * RSZ, sk = (OFF)g.s12 * RSZ, sj = (OFF)g.s1 * RSZ;      // byte offsets
@@ -477,7 +491,7 @@ __global__ __launch_bounds__(64 * (LMF_TY(YW) + 2)) void k_lmf_tile(Geom g, LmfA
   if constexpr (LOCAL) s0n = ldb(A.mf[0], c0 + (OFF)kbeg * sk);
   // rows whose |S|Sij this thread combines: its own and the two beside it; the two halo waves (and rows beyond n2) take a row of the tile
   // interior instead (cache hits, results unused)
-  const int jo = max(by * TL + 1, min(min(j, by * TL + TL), g.n2));
+  const int jo = PACK ? pk.jo : max(by * TL + 1, min(min(j, by * TL + TL), g.n2));
   const OFF c0s = (OFF)g.ix(ic, jo, 0) * RSZ;
   real sm[3], sc[3], sp[3], sn[3], fn[3];
   // ghost rows of u_f and w_f at wall-model y faces: 2 Q(1) - Q(2) along y (extrapolate(...,lwm) after bounduvw, sgs.f90:683-748); v_f keeps its own.
@@ -558,11 +572,23 @@ __global__ __launch_bounds__(64 * (LMF_TY(YW) + 2)) void k_lmf_tile(Geom g, LmfA
   ssload(kbeg - 1, rw); sscomb(rw, xm);
   ssload(kbeg, rw); sscomb(rw, xc);
   ssload(kbeg + 1, rw);
-  const int blk = by * B.gx + bx;
+  const int blk = by * B.gx + bx;      // (PACK: a slot per stretch, see the stores at the end)
   auto fold = [&](int k, int b) {      // block sums of plane k by ONE whole wave, fixed order
     const real *p0 = &psum[b][0][0][0], *p1 = &psum[b][LOCAL ? 0 : 1][0][0];      // (LOCAL: never called; the arrays have one element per dimension)
     static_assert(TL * 16 >= 128 && TL * 16 <= 192, "two or three partials per lane");
     constexpr int NP3 = TL * 16 - 128;      // partials beyond the first 128
+    if constexpr (PACK) {
+      // a sum per stretch, each by the operations the unpacked tile's one sum takes: a stretch starts on a multiple of four lanes, so its partials of four
+      // are the unpacked tile's (psum: P / 4 of the sixteen per row, at s P / 4), and the wave adds them from the places they have there, zeros around them
+      static_assert(NP3 == 0, "eight rows: two partials per lane");
+      const int G = pp.P >> 2, gq = tx & 15;
+      for (int s = 0; s < nlive; ++s) {
+        const int o = (tx & ~15) + min(s * G + gq, 15);
+        const real a = wave_sum_lane63(gq < G ? p0[o] + p0[o + 64] : 0.), bs = wave_sum_lane63(gq < G ? p1[o] + p1[o + 64] : 0.);
+        if (tx == 63) { bsum[0][s * A.kchunk + k - kbeg] = a; bsum[1][s * A.kchunk + k - kbeg] = bs; }      // (sgs_setup_launches: S chunks fit)
+      }
+      return;
+    }
     const int t3 = min(tx, NP3 > 0 ? NP3 - 1 : 0) + 128; const real w3 = (NP3 > 0 && tx < NP3) ? 1. : 0.;
     const real a = wave_sum_lane63(NP3 > 0 ? p0[tx] + p0[tx + 64] + w3 * p0[t3] : p0[tx] + p0[tx + 64]),
                bs = wave_sum_lane63(NP3 > 0 ? p1[tx] + p1[tx + 64] + w3 * p1[t3] : p1[tx] + p1[tx + 64]);
@@ -676,6 +702,14 @@ __global__ __launch_bounds__(64 * (LMF_TY(YW) + 2)) void k_lmf_tile(Geom g, LmfA
   if (ty == 0 && kend >= kbeg) fold(kend, kend & 1);
   __syncthreads();
   // the chunk's block sums leave in one go
+  if constexpr (PACK) {      // every live stretch's into the slot the unpacked launch gives the remainder tile of its y tile (B.gx: x tiles of a row, the remainder one included)
+    const int np = kend - kbeg + 1;
+    for (int q = ty * 64 + tx; q < 2 * np * nlive; q += 64 * (TL + 2)) {
+      const int w = q & 1, kk = (q >> 1) % np, s = (q >> 1) / np, tile = (int)blockIdx.y * pp.S + s + B.by0;
+      A.part[(size_t)(w * g.n3 + kbeg + kk - 1) * A.nblk + tile * B.gx + B.gx - 1] = bsum[w][s * A.kchunk + kk];
+    }
+    return;
+  }
   for (int q = ty * 64 + tx; q < 2 * (kend - kbeg + 1); q += 64 * (TL + 2)) {
     const int w = q & 1, kk = q >> 1;
     A.part[(size_t)(w * g.n3 + kbeg + kk - 1) * A.nblk + blk] = bsum[w][kk];
@@ -1518,8 +1552,24 @@ int sgs_setup_launches(cales_ctx *c) {
   P.strain_geo = with_bands(tile_geom(c, TYS, 64));
   if (P.pair) { P.corr_geo = with_bands(tile_geom(c, TYC, 64)); P.corr_rows2_geo = with_bands(tile_geom(c, TYC, 64, 2)); }
   TileGeom t = tile_geom(c, P.lmf_ty, 62, 0, LMF_KMAX);
+  // The remainder x tile packed into full waves (lmf_pack.hpp; pair fields on one rank): the launch above keeps the full tiles, with the chunk length their
+  // block count gives, and a launch of the packed instantiation takes the remainder tile of S y tiles per block, its chunk length from the same cost model
+  // (few blocks: one round of short chunks). 512^3: 8 x 64 x 4 blocks -- eight full rounds of the 256 CUs instead of nine with every ninth block three
+  // quarters dead lanes -- and 22 x 11 packed blocks of 47 planes. Every y tile's remainder sum keeps the slot it has in the one launch (lmf_gx x tiles per
+  // row), so k_plane_fold adds the same numbers in the same order; a packed block keeps the sums of its S stretches' chunks in the LDS of one chunk of LMF_KMAX.
+  const LmfPack pk = lmf_pack(n[0]);
+  P.lmf_packed = P.pair && P.ave != SgsAve::local && c->P == 1 && pk.on && !c->fl.lmf_unpacked_remainder;      // (local: no block sums, another instantiation)
+  P.lmf_gx = t.grid.x;
   if ((size_t)2 * n[2] * t.grid.x * t.grid.y > c->ntot) { c->err = "dsmag: partial-sum scratch too small"; return 1; }
-  while (t.kchunk > LMF_KMAX) { t.kchunk = (t.kchunk + 1) / 2; t.grid.z = (n[2] + t.kchunk - 1) / t.kchunk; }      // the kernel keeps a chunk's block sums in LDS
+  int kmax_rem = LMF_KMAX;
+  if (P.lmf_packed) {
+    const int gy = t.grid.y;
+    kmax_rem = LMF_KMAX / pk.S;
+    t.grid = dim3(pk.full, gy, 1); tile_chunks(c, t, LMF_KMAX);
+    P.lmf_rem_geo = t; P.lmf_rem_geo.grid = dim3(1, lmf_pack_blocks(pk, gy), 1); tile_chunks(c, P.lmf_rem_geo, kmax_rem);
+  }
+  auto cap = [&](TileGeom &s, int kmax) { while (s.kchunk > kmax) { s.kchunk = (s.kchunk + 1) / 2; s.grid.z = (n[2] + s.kchunk - 1) / s.kchunk; } };      // the kernel keeps a chunk's block sums in LDS
+  cap(t, LMF_KMAX); cap(P.lmf_rem_geo, kmax_rem);
   P.lmf_geo = t;
   return 0;
 }
@@ -1627,14 +1677,15 @@ static int dsmag_fast(cales_ctx *c, const SgsFold *fold, bool *visct_ghosts_done
     // K_B + K_DF in one pass: filter(|S|Sij) on the fly, strain rate of the filtered velocity, Mij, Lij, contractions, plane partial sums
     ProfScope ps(c, "lij_mij_filter_contract");
     const TileGeom &t = P.lmf_geo;
-    L.kchunk = t.kchunk; L.nblk = t.grid.x * t.grid.y;
+    L.kchunk = t.kchunk; L.nblk = P.lmf_gx * t.grid.y;
     LmfArgs B; B.L = L; for (int m = 0; m < 6; ++m) B.ss[m] = ssij[m];
     for (int m = 0; m < 3; ++m) B.ss2[m] = reinterpret_cast<const real2 *>(c->ss2[m]);
     if (five) B.ss2[1] = reinterpret_cast<const real2 *>(s12);
-    B.gx = t.grid.x;
-    auto launch = [&](int by0, int nby) {      // the y tiles by0 .. by0 + nby - 1
+    B.gx = P.lmf_gx;
+    auto launch =[&](int by0, int nby) {      // the y tiles by0 .. by0 + nby - 1
       if (nby <= 0) return;
       TileGeom s = t; s.grid.y = nby; s = with_bands(s);
+      if (P.lmf_packed && c->fl.lmf_main_bands && !s.bm.gx) { s.bm = band_map(s.grid.x, s.grid.y, s.grid.z); s.grid = dim3(band_blocks(s.bm), 1, 1); }      // (experiments)
       B.by0 = by0; B.bm = s.bm;
       if (local) switch (P.lmf) {      // (sgs_setup: ucf, 32-bit offsets, six components, the 3-D filter)
       case LmfKernel::pair: LAUNCH(c, (k_lmf_tile<unsigned, 0, 1, 5>), s.grid, s.block, 0, c->stream, c->g, B); return;
@@ -1657,6 +1708,14 @@ static int dsmag_fast(cales_ctx *c, const SgsFold *fold, bool *visct_ghosts_done
       case LmfKernel::f2d64: LAUNCH(c, (k_lmf_plane_tile<size_t>), s.grid, s.block, 0, c->stream, c->g, B); break;
       }
     };
+    // the remainder x tile of every row, S y tiles per block (SgsPath::lmf_packed: pair fields, one rank): its own chunk length, its block sums behind the others'
+    auto launch_packed = [&]() {
+      if (!P.lmf_packed) return;
+      const TileGeom &s = P.lmf_rem_geo;
+      LmfArgs R = B; R.L.kchunk = s.kchunk; R.by0 = 0; R.bm = BandMap{0, 0, 0, 0};
+      if (five) LAUNCH(c, (k_lmf_tile<unsigned, 0, 1, 10>), s.grid, s.block, 0, c->stream, c->g, R);
+      else LAUNCH(c, (k_lmf_tile<unsigned, 0, 1, 9>), s.grid, s.block, 0, c->stream, c->g, R);
+    };
     if (overlap) {
       // tiles that read the ghost rows j = 0 or j = n2+1 wait for the rows in flight; the others run beside the exchange
       int hi0 = (int)t.grid.y; while (hi0 > 1 && (hi0 - 1) * P.lmf_ty + P.lmf_ty + 1 >= n[1] + 1) --hi0;      // first tile (> 0) that reaches row n2+1
@@ -1664,6 +1723,7 @@ static int dsmag_fast(cales_ctx *c, const SgsFold *fold, bool *visct_ghosts_done
       if (int e = stream_after(c, c->stream, c->comm_stream)) return e;
       launch(0, 1); launch(hi0, (int)t.grid.y - hi0);
     } else launch(0, (int)t.grid.y);
+    launch_packed();
     if (local) { LAUNCHCHK(c); return 0; }      // sgs.f90:368-377: visct is written -- no fold, no all-reduce, no final kernel
     LAUNCH(c, k_plane_fold, dim3(2 * n[2]), dim3(256), 0, c->stream, n[2], L.nblk, c->wk[0], c->d_p1d);
   }
