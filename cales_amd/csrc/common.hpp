@@ -153,19 +153,22 @@ struct StepPlan {
 struct BandMap { int gx, gy, gz, sub; };
 struct TileGeom { dim3 block, grid; int kchunk = 0; BandMap bm{0, 0, 0, 0}; };
 
+// A kernel held by a path record: the instantiation a set-up function chose and its name AS THAT FUNCTION SPELLS IT -- what the launch check reports and the
+// test hook matches (LAUNCH_REC below). KERNEL_REC(k_tile<unsigned, 0, 1>) fills one: variadic, so the commas of a template argument list survive.
+template <typename Fn> struct KernelRec { Fn *fn = nullptr; const char *name = ""; };
+#define KERNEL_REC(...) {__VA_ARGS__, #__VA_ARGS__}
+// a tile pass: the kernel and its launch geometry (k.fn == nullptr: the path has no such pass)
+template <typename Args> struct TilePass { KernelRec<void(Geom, Args)> k; TileGeom geo; };
+
 // The path of cmpt_sgs (k_sgs.hip), decided once by cales_create (sgs_setup; sgs_setup_launches once the CU count is known) and only read after:
 // op_cmpt_sgs launches it, sgs_path_name prints it, cales_create allocates its scratch fields, make_plan folds the projection only into pair fields.
 enum class SgsForm { none, smag_rows, smag_reference, dsmag_tiles, dsmag_reference };
-// the instantiation of each launch site (32 / 64: unsigned / size_t byte offsets; yw: walls or wall-model faces in y; ucf: the last pass forms the
-// cell-centred velocity). Pair fields imply x and y periodic, 32-bit offsets and ucf: one instantiation each.
-enum class StrainKernel { corr_rows2, corr, corr5, yw32, yw64, pair, plain32, plain64, f2d32, f2d64 };      // k_corr_strain_tile<unsigned, TYC(, 1: EXT, 2: FIVE)> | k_strain_tile<OFF, TYS, YW(, SSF)>, SSF = 1: pair, 2: f2d (SgsPath::filter2d)
-enum class LmfKernel { pair, pair5, yw_ucf32, yw_ucf64, yw32, yw64, ucf32, ucf64, plain32, plain64, f2d32, f2d64 };      // k_lmf_tile<OFF, YW, UCF(, PAIR)>, PAIR = 1: pair, 2: pair5 (five components) | k_lmf_plane_tile<OFF>: f2d      // (SgsAve::local: the same names, the LOCAL instantiation of each -- no pair5, no f2d)
-enum class SmagKernel { yw32, yw64, plain32, plain64 };      // k_smag_rows<OFF, YW>
 // the directions <Mij Lij>, <Mij Mij> of the dynamic model are averaged over (sgs.f90:359-370): _CHANNEL (hard-wired there) | -D_DIT | _DUCT | _CAVITY (none)
 enum class SgsAve { planes, volume, xlines, local };
+struct StrainTileArgs; struct LmfArgs;      // the kernels' arguments (k_sgs.hip)
 struct SgsPath {
   SgsForm form = SgsForm::none;
-  bool pair = false, lazy = false, ucf = false, small = false, yw = false;      // |S|Sij as pair fields (ss2); lazy: |S| straight into visct (homogeneous sgs BCs)
+  bool pair = false, lazy = false, ucf = false;      // |S|Sij as pair fields (ss2); lazy: |S| straight into visct (homogeneous sgs BCs); ucf: the last pass forms the cell-centred velocity
   // five: inside cales_step with the projection folded into the strain-rate pass on ONE rank, five |S|Sij travel (two pair fields and S12 plain) and the last
   // pass takes |S|S33 = -(|S|S11 + |S|S22): the trace of the strain rate of a velocity that pass has just projected is the divergence the solve left. Calls
   // without the fold (start-up, operator level, CALES_UNFOLDED_CORREC), slabs and every other form keep six (CALES_SGS_SIX_COMPONENTS: everywhere)
@@ -177,12 +180,17 @@ struct SgsPath {
   // static kernel arguments (y walls: dsmag those this rank owns, smag_rows those of the case -- global distances, the shear reaches every slab)
   int zlo = 0, zhi = 0, wmlo = 0, wmhi = 0, wylo = 0, wyhi = 0, wmylo = 0, wmyhi = 0; real flo = 0., fhi = 0.;
   int perz = 0, perx = 0, skipz = 0, lmf_ty = 0;
-  StrainKernel strain = StrainKernel::plain64; LmfKernel lmf = LmfKernel::plain64; SmagKernel smag = SmagKernel::plain64;
-  TileGeom strain_geo, corr_geo, corr_rows2_geo, lmf_geo, smag_geo;      // (lmf_geo unbanded: the overlap of cmpt_sgs splits it per call)
-  // lmf_packed (pair fields on one rank, lmf_pack(n1).on, not CALES_LMF_UNPACKED_REMAINDER): lmf_geo covers the full x tiles only and lmf_rem_geo, a launch of
-  // the packed instantiation with a chunk length of its own, the remainder tile of every row (lmf_pack.hpp); lmf_gx: x tiles of a row, the remainder one
+  // The passes: kernel records from sgs_setup -- the one place every instantiation is named, from the properties that select it (32- or 64-bit byte offsets,
+  // walls or wall-model faces in y, ucf, pair fields, the plane filter, the averaging) --, geometries from sgs_setup_launches. What a call may choose between is
+  // a separate entry, and the call only indexes: strain without the projection folded in, corr[rows2][five] with it (rows2: SgsFold::rows2, from two ghost rows
+  // of the prediction; five components on one rank only, so corr[1][1] stays empty); lmf[five] the last pass and lmf_rem[five] its packed remainder pass. An
+  // entry the path does not have stays empty (pair fields only: corr, lmf_rem; five only: the [1] entries).
+  TilePass<StrainTileArgs> smag, strain, corr[2][2];
+  TilePass<LmfArgs> lmf[2], lmf_rem[2];      // (lmf's geometry unbanded: the overlap of cmpt_sgs splits it per call)
+  // lmf_packed (pair fields on one rank, lmf_pack(n1).on, not CALES_LMF_UNPACKED_REMAINDER): lmf covers the full x tiles only and lmf_rem, a launch of the
+  // packed instantiation with a chunk length of its own, the remainder tile of every row (lmf_pack.hpp); lmf_gx: x tiles of a row, the remainder one
   // included -- the block sums of a plane keep the slots of the one launch
-  bool lmf_packed = false; TileGeom lmf_rem_geo; int lmf_gx = 0;
+  bool lmf_packed = false; int lmf_gx = 0;
 };
 // op_cmpt_sgs inside cales_step: the projection folded into the strain-rate pass (StepPlan::fold_correc; rows2: fold_rows2; fmask: deferred forcing)
 struct SgsFold { real dtrk; bool rows2; int fmask; };
@@ -401,14 +409,17 @@ struct cales_ctx {
 // never a silently wrong field. Void helpers and lambdas record through the same path (HIPSOFT for other HIP calls whose status must not be lost).
 // Test hook: CALES_TEST_BAD_LAUNCH=<substring of a kernel name> gives the matching launches a block of 4096 threads (invalid on every device).
 void launch_failed(cales_ctx *c, const char *what, hipError_t e);
-#define LAUNCH(c, kernel, grid, block, lds, stream, ...)                                           \
+#define LAUNCH_NAMED(c, kernel, name, grid, block, lds, stream, ...)                               \
   do {                                                                                             \
     dim3 blk_ = (block);                                                                           \
-    if (!(c)->fl.test_bad_launch.empty() && strstr(#kernel, (c)->fl.test_bad_launch.c_str())) blk_ = dim3(4096, 1, 1); \
+    if (!(c)->fl.test_bad_launch.empty() && strstr(name, (c)->fl.test_bad_launch.c_str())) blk_ = dim3(4096, 1, 1); \
     hipLaunchKernelGGL(kernel, grid, blk_, lds, stream, __VA_ARGS__);                              \
     const hipError_t le_ = hipGetLastError();                                                      \
-    if (le_ != hipSuccess) launch_failed(c, #kernel, le_);                                         \
+    if (le_ != hipSuccess) launch_failed(c, name, le_);                                            \
   } while (0)
+#define LAUNCH(c, kernel, ...) LAUNCH_NAMED(c, kernel, #kernel, __VA_ARGS__)
+// ... of a kernel record (KernelRec above): the kernel a set-up function chose, under the name that function spelled
+#define LAUNCH_REC(c, rec, ...) LAUNCH_NAMED(c, (rec).fn, (rec).name, __VA_ARGS__)
 #define LAUNCHCHK(c)                                                                               \
   do {                                                                                             \
     if (!(c)->launch_err.empty()) { (c)->err = (c)->launch_err; return 1; }                        \
@@ -498,7 +509,7 @@ int solver_mode_columns(cales_ctx *c);      // complex mode columns per rank of 
 std::string solver_path_name(cales_ctx *c);      // which transform / tridiagonal kernels the pressure solve of this context takes (cales_describe_plan)
 std::string helmholtz_path_name(cales_ctx *c, int iv);      // ... and the Helmholtz solve of velocity component iv (0..2) of the 3-D implicit step
 const char *sgs_path_name(const cales_ctx *c);      // likewise for cmpt_sgs (SgsPath)
-void sgs_setup(cales_ctx *c);               // SgsPath: form, flags, static kernel arguments and kernels (needs is_wall)
+void sgs_setup(cales_ctx *c);               // SgsPath: form, flags, static kernel arguments and kernel records (needs is_wall)
 int sgs_setup_launches(cales_ctx *c);       // ... and the launch geometry of its tile passes (needs ncu)
 int op_force_from_partials(cales_ctx *c, int mask, const real *part, int nblk);
 int op_correc_updatep(cales_ctx *c, real dtrk, real alpha, int upd, int fmask = 0);      // fmask: the components whose deferred bulk-forcing increment the pass adds (StepPlan::defer_force)

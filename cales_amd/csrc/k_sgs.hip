@@ -450,6 +450,9 @@ constexpr int LMF_KMAX = 256;      // longest k chunk (block sums of a chunk in 
 // places they have in the unpacked tile) and stored in the slot the one launch gives that y tile's remainder tile: the plane sums are the one launch's to the bit.
 // PAIR = 1 and 2, YW = 0, UCF = 1, 32-bit offsets.
 // (PAIR, LOCAL and PACK: one template parameter, SSF = PAIR + 4 LOCAL + 8 PACK, as in k_strain_tile -- the instantiations without LOCAL / PACK keep their symbols.)
+// The values of SSF by name. lmf_kernel (below, the one place the instantiations are named) spells them as the literal numbers -- the launch check reports the
+// spelled name and the tests match it -- and asserts them against these: 1 pair, 2 pair5, 4 / 5 local without / with pair fields, 9 / 10 packed pair / pair5.
+constexpr int LMF_PAIR = 1, LMF_PAIR5 = 2, LMF_LOCAL = 4, LMF_PACK = 8;
 template <typename OFF, int YW, int UCF, int SSF = 0>      // YW = 1: walls or wall-model faces in y (ducts); 0: the channel instantiation carries none of that logic
 __global__ __launch_bounds__(64 * (LMF_TY(YW) + 2)) void k_lmf_tile(Geom g, LmfArgs B) {
   static constexpr int PAIR = SSF & 3, LOCAL = (SSF >> 2) & 1, PACK = SSF >> 3;      // (static: an automatic constant would join the captures of the lambdas below and shuffle their registers)
@@ -927,6 +930,7 @@ __global__ __launch_bounds__(256) void k_wall_shear_y(Geom g, const real *__rest
 // F2D = 1 (the reference's -D_FILTER_2D): the filtered velocity is the in-plane (1,2,1)^2/16 of plane k of the raw u, v, w (filter2d, sgs.f90:244-246,839-847):
 // no z combination, no wall rule; the strain rate and the wall-model ghost planes of the ring are what they were
 // (PAIR and F2D: the values 1 and 2 of one template parameter, as in k_lmf_tile.)
+constexpr int STRAIN_PAIR = 1, STRAIN_F2D = 2;      // the values of SSF by name (strain_kernel below spells them as numbers, as lmf_kernel does)
 template <typename OFF, int TY, int YW, int SSF = 0>      // YW = 1: walls or wall-model faces in y (ducts); the channel instantiations carry none of that logic
 __global__ __launch_bounds__(64 * (TY + 2)) void k_strain_tile(Geom g, StrainTileArgs A) {
   constexpr int PAIR = SSF == 1, F2D = SSF == 2;
@@ -1471,32 +1475,62 @@ __global__ __launch_bounds__(256) void k_fold_ghost_rows(Geom g, const real *__r
   wd[a] = ((fmask & 4) ? ws[a] + f2 : ws[a]) - cdt * dzci[k] * (pz - P0);
   p[a] = p[a] + P0;
 }
-// ---- the path of cmpt_sgs (SgsPath, common.hpp). sgs_setup: the form, its flags, static kernel arguments and kernels -- from the case, the switches
-// and is_wall, before cales_create allocates the scratch fields of the form (pair fields or sij / mij)
+// ---- the path of cmpt_sgs (SgsPath, common.hpp). The kernel records first: one function per kernel family, every instantiation named ONCE, picked by the properties that
+// select it; sgs_setup is their only caller. The launch check reports a record's name as spelled here and tests match it: the numbers stay numbers. Not built: an empty record
+using StrainKernelRec = KernelRec<void(Geom, StrainTileArgs)>; using LmfKernelRec = KernelRec<void(Geom, LmfArgs)>;
+// K_AC. Pair fields and the plane filter imply no y logic, pair fields 32-bit offsets too: one instantiation, two
+static StrainKernelRec strain_kernel(bool pair, bool f2d, bool yw, bool small) {
+  static_assert(STRAIN_PAIR == 1 && STRAIN_F2D == 2, "SSF as spelled below");
+  static const StrainKernelRec plain[2][2] = {{KERNEL_REC(k_strain_tile<size_t, TYS, 0>), KERNEL_REC(k_strain_tile<unsigned, TYS, 0>)}, {KERNEL_REC(k_strain_tile<size_t, TYS, 1>), KERNEL_REC(k_strain_tile<unsigned, TYS, 1>)}};      // [yw][small]
+  static const StrainKernelRec plane[2] = {KERNEL_REC(k_strain_tile<size_t, TYS, 0, 2>), KERNEL_REC(k_strain_tile<unsigned, TYS, 0, 2>)}, pairs = KERNEL_REC(k_strain_tile<unsigned, TYS, 0, 1>);      // [small]
+  return pair ? pairs : f2d ? plane[small] : plain[yw][small];
+}
+// K_AC with the projection folded in (pair fields). rows2: from two ghost rows of the prediction (several slabs); five components: one rank
+static StrainKernelRec corr_strain_kernel(bool rows2, bool five) {
+  static const StrainKernelRec t[2][2] = {{KERNEL_REC(k_corr_strain_tile<unsigned, TYC>), KERNEL_REC(k_corr_strain_tile<unsigned, TYC, 2>)}, {KERNEL_REC(k_corr_strain_tile<unsigned, TYC, 1>), {}}};      // [rows2][five]
+  return t[rows2][five];
+}
+// The last pass. pair: 0 | LMF_PAIR | LMF_PAIR5 (x and y periodic, ucf, 32-bit offsets: one instantiation each, and one more each for the packed remainder tile). local: built for
+// ucf with 32-bit offsets (with 64-bit ones it spills: profiles/dsmag_local_kernel_resources.md), six components, the 3-D filter; every other: empty, sgs_setup takes the sequence
+static LmfKernelRec lmf_kernel(bool f2d, int pair, bool local, bool packed, bool yw, bool ucf, bool small) {
+  static_assert(LMF_PAIR == 1 && LMF_PAIR5 == 2 && LMF_LOCAL == 4 && (LMF_LOCAL | LMF_PAIR) == 5 && (LMF_PACK | LMF_PAIR) == 9 && (LMF_PACK | LMF_PAIR5) == 10, "SSF as spelled below");
+  static const LmfKernelRec six[2][2][2] = {{{KERNEL_REC(k_lmf_tile<size_t, 0, 0>), KERNEL_REC(k_lmf_tile<unsigned, 0, 0>)}, {KERNEL_REC(k_lmf_tile<size_t, 0, 1>), KERNEL_REC(k_lmf_tile<unsigned, 0, 1>)}},
+                                            {{KERNEL_REC(k_lmf_tile<size_t, 1, 0>), KERNEL_REC(k_lmf_tile<unsigned, 1, 0>)}, {KERNEL_REC(k_lmf_tile<size_t, 1, 1>), KERNEL_REC(k_lmf_tile<unsigned, 1, 1>)}}};      // [yw][ucf][small]
+  static const LmfKernelRec plane[2] = {KERNEL_REC(k_lmf_plane_tile<size_t>), KERNEL_REC(k_lmf_plane_tile<unsigned>)};      // [small]
+  static const LmfKernelRec pairs[3] = {{}, KERNEL_REC(k_lmf_tile<unsigned, 0, 1, 1>), KERNEL_REC(k_lmf_tile<unsigned, 0, 1, 2>)};      // [pair]
+  static const LmfKernelRec packs[3] = {{}, KERNEL_REC(k_lmf_tile<unsigned, 0, 1, 9>), KERNEL_REC(k_lmf_tile<unsigned, 0, 1, 10>)};      // [pair]
+  static const LmfKernelRec locals[2] = {KERNEL_REC(k_lmf_tile<unsigned, 0, 1, 4>), KERNEL_REC(k_lmf_tile<unsigned, 1, 1, 4>)}, local_pairs = KERNEL_REC(k_lmf_tile<unsigned, 0, 1, 5>);      // [yw]
+  if (local) return f2d || packed || pair == LMF_PAIR5 || !ucf || !small ? LmfKernelRec{} : pair ? local_pairs : locals[yw];
+  return packed ? packs[pair] : pair ? pairs[pair] : f2d ? plane[small] : six[yw][ucf][small];
+}
+static StrainKernelRec smag_rows_kernel(bool yw, bool small) {
+  static const StrainKernelRec t[2][2] = {{KERNEL_REC(k_smag_rows<size_t, 0>), KERNEL_REC(k_smag_rows<unsigned, 0>)}, {KERNEL_REC(k_smag_rows<size_t, 1>), KERNEL_REC(k_smag_rows<unsigned, 1>)}};      // [yw][small]
+  return t[yw][small];
+}
+// sgs_setup: the form, its flags, static kernel arguments and kernel records -- from the case, the switches and is_wall, before cales_create allocates the
+// scratch fields of the form (pair fields or sij / mij)
 void sgs_setup(cales_ctx *c) {
-  SgsPath &P = c->sgs;
-  const int *n = c->n; const Flags &fl = c->fl;
+  SgsPath &P = c->sgs; const int *n = c->n; const Flags &fl = c->fl;
   if (c->C.sgstype == 0) return;
-  bool xw = false, yw = false;      // walls or wall model in x (the reference sequences only), in y
+  bool xw = false, yw = false;      // the predicates, each computed here and nowhere else. Walls or wall model in x (the reference sequences only), in y
   for (int q = 0; q < 2; ++q) xw = xw || c->is_wall[q] != 0. || c->C.lwm[q] != 0;
   for (int q = 2; q < 4; ++q) yw = yw || c->is_wall[q] != 0. || c->C.lwm[q] != 0;
+  const bool perx = CBP(c, 0, 1) == 'P' && CBP(c, 1, 1) == 'P' && !fl.dsmag_xghosts;      // x periodic and the kernels wrap around
+  const bool perz = CBP(c, 0, 3) == 'P' && CBP(c, 1, 3) == 'P', zwalls = c->is_wall[4] != 0. && c->is_wall[5] != 0.;      // (walls: no-slip or wall-modelled)
+  const bool small = (c->ntot + 16) * sizeof(real) < (1ull << 32) && !fl.wide_offsets;      // 32-bit byte offsets (ldb/stb)
+  // the cell-centred velocity is not stored where the last pass can form it itself (k_lmf_tile<.., UCF = 1>): x periodic, z walls or periodic
+  const bool ucf = perx && (zwalls || perz);
+  const bool local = P.ave == SgsAve::local;      // a coefficient per cell: no cs(k) for the momentum pass to apply (lazy), and six components (five)
   if (c->C.sgstype == 1) P.form = !xw && n[2] >= 3 && n[1] >= 2 && !fl.smag_reference_sequence ? SgsForm::smag_rows : SgsForm::smag_reference;
   // (ducts: the fused last pass knows the wall rule along y from three rows on)
   else if (P.ave == SgsAve::xlines) P.form = SgsForm::dsmag_reference;      // (no tile form yet: k_lmf_tile hands out plane partials, not rows')
-  else if (P.ave == SgsAve::local && P.filter2d) P.form = SgsForm::dsmag_reference;      // (k_lmf_plane_tile has no local form)
-  // local: the tile form for the classes k_lmf_tile forms the cell-centred velocity for (ucf below) -- x periodic, z between two walls or periodic -- with
-  // 32-bit byte offsets (small below): the two LOCAL instantiations with 64-bit offsets spill (profiles/dsmag_local_kernel_resources.md) and are not
-  // built, a field beyond 4 GB takes the sequence
-  else if (P.ave == SgsAve::local && !(CBP(c, 0, 1) == 'P' && CBP(c, 1, 1) == 'P' && !fl.dsmag_xghosts && (c->ntot + 16) * sizeof(real) < (1ull << 32) && !fl.wide_offsets &&
-                                       ((c->is_wall[4] != 0. && c->is_wall[5] != 0.) || (CBP(c, 0, 3) == 'P' && CBP(c, 1, 3) == 'P')))) P.form = SgsForm::dsmag_reference;
+  else if (local && P.filter2d) P.form = SgsForm::dsmag_reference;      // (k_lmf_plane_tile has no local form)
+  // local: the tile form where a LOCAL instantiation is built (lmf_kernel: ucf, 32-bit byte offsets); every other class, and a field beyond 4 GB, takes the sequence
+  else if (local && !(ucf && small)) P.form = SgsForm::dsmag_reference;
   else if (!P.filter2d) P.form = !xw && !(yw && n[1] < 3) && n[2] >= 3 && !fl.dsmag_reference_sequence ? SgsForm::dsmag_tiles : SgsForm::dsmag_reference;
-  else {
-    // the plane filter (-D_FILTER_2D): tiles for the channel class -- x periodic (the kernels wrap around), nothing at the y faces, z between two walls (no-slip
-    // or wall-modelled) or periodic: where the last pass forms the cell-centred velocity itself (ucf below); every other case takes the sequence
-    const bool perx = CBP(c, 0, 1) == 'P' && CBP(c, 1, 1) == 'P' && !fl.dsmag_xghosts, perz = CBP(c, 0, 3) == 'P' && CBP(c, 1, 3) == 'P';
-    const bool zwalls = c->is_wall[4] != 0. && c->is_wall[5] != 0.;
-    P.form = perx && !xw && !yw && (zwalls || perz) && n[2] >= 3 && !fl.dsmag_reference_sequence ? SgsForm::dsmag_tiles : SgsForm::dsmag_reference;
-  }
+  // the plane filter (-D_FILTER_2D): tiles for the channel class -- ucf (the kernels wrap around in x, z between two walls or periodic) and nothing at the y
+  // faces; every other case takes the sequence
+  else P.form = ucf && !xw && !yw && n[2] >= 3 && !fl.dsmag_reference_sequence ? SgsForm::dsmag_tiles : SgsForm::dsmag_reference;
   P.wraps_x = P.form == SgsForm::smag_rows || (P.form == SgsForm::dsmag_tiles && !fl.dsmag_xghosts);
   if (P.form != SgsForm::smag_rows && P.form != SgsForm::dsmag_tiles) return;
   const bool smag = P.form == SgsForm::smag_rows;
@@ -1509,28 +1543,25 @@ void sgs_setup(cales_ctx *c) {
   // rows, the shear of both walls reaches every slab). Wall-model y faces: extrapolated ghost rows for the strain rates
   P.wylo = (smag || ISB(c, 0, 2)) && c->is_wall[2] != 0.; P.wyhi = (smag || ISB(c, 1, 2)) && c->is_wall[3] != 0.;
   P.wmylo = ISB(c, 0, 2) && LWM(c, 0, 2) != 0; P.wmyhi = ISB(c, 1, 2) && LWM(c, 1, 2) != 0;
-  P.yw = P.wylo || P.wyhi || P.wmylo || P.wmyhi;
-  P.small = (c->ntot + 16) * sizeof(real) < (1ull << 32) && !fl.wide_offsets;      // 32-bit byte offsets (ldb/stb)
-  if (smag) { P.smag = P.yw ? (P.small ? SmagKernel::yw32 : SmagKernel::yw64) : (P.small ? SmagKernel::plain32 : SmagKernel::plain64); return; }
-  const bool local = P.ave == SgsAve::local;      // a coefficient per cell: no cs(k) for the momentum pass to apply (lazy), and six components (five)
+  const bool ywk = P.wylo || P.wyhi || P.wmylo || P.wmyhi;      // the y logic of the kernels (YW)
+  if (smag) { P.smag.k = smag_rows_kernel(ywk, small); return; }
   P.lazy = !local; for (int q = 0; q < 6; ++q) P.lazy = P.lazy && c->C.bcsgs[q] == 0.;
-  P.perz = CBP(c, 0, 3) == 'P' && CBP(c, 1, 3) == 'P';
-  P.perx = CBP(c, 0, 1) == 'P' && CBP(c, 1, 1) == 'P' && !fl.dsmag_xghosts;
-  P.skipz = (P.zlo && P.zhi) ? 4 : 0;
-  // the cell-centred velocity is not stored where the last pass can form it itself (k_lmf_tile<.., UCF = 1>): x periodic, z walls or periodic
-  P.ucf = P.perx && ((P.zlo && P.zhi) || P.perz);
+  P.perz = perz; P.perx = perx; P.ucf = ucf; P.skipz = zwalls ? 4 : 0;
   // |S|Sij as three fields of pairs between K_AC and the fused last pass: ucf, and y periodic (the one-launch ghost-cell kernel takes a pair field as a
   // field of twice the width), 32-bit byte offsets still enough for a field twice as long
-  P.pair = !P.filter2d && P.ucf && CBP(c, 0, 2) == 'P' && CBP(c, 1, 2) == 'P' && !fl.wide_offsets && !fl.unmerged_bc && (2 * c->ntot + 64) * sizeof(real) < (1ull << 32);
+  P.pair = !P.filter2d && ucf && CBP(c, 0, 2) == 'P' && CBP(c, 1, 2) == 'P' && !fl.wide_offsets && !fl.unmerged_bc && (2 * c->ntot + 64) * sizeof(real) < (1ull << 32);
   // five |S|Sij instead of six wherever the strain-rate pass projects the velocity itself (make_plan: fold_correc needs pair fields) on one rank -- on slabs the
   // scratch rows travel in counted planes and keep six
   P.five = P.pair && c->P == 1 && !fl.sgs_six_components && !local;
-  P.lmf_ty = P.yw ? TYL : TYLF;
-  P.strain = P.pair ? StrainKernel::pair : P.yw ? (P.small ? StrainKernel::yw32 : StrainKernel::yw64) : (P.small ? StrainKernel::plain32 : StrainKernel::plain64);
-  static const LmfKernel lmf[2][2][2] = {{{LmfKernel::plain64, LmfKernel::plain32}, {LmfKernel::ucf64, LmfKernel::ucf32}},
-                                         {{LmfKernel::yw64, LmfKernel::yw32}, {LmfKernel::yw_ucf64, LmfKernel::yw_ucf32}}};      // [yw][ucf][small]
-  P.lmf = P.pair ? LmfKernel::pair : lmf[P.yw][P.ucf][P.small];
-  if (P.filter2d) { P.strain = P.small ? StrainKernel::f2d32 : StrainKernel::f2d64; P.lmf = P.small ? LmfKernel::f2d32 : LmfKernel::f2d64; }      // (ucf, no yw: the form's condition)
+  // the remainder x tile packed into full waves (sgs_setup_launches): pair fields on one rank (local: no block sums, another instantiation)
+  P.lmf_packed = P.pair && !local && c->P == 1 && lmf_pack(n[0]).on && !fl.lmf_unpacked_remainder;
+  P.lmf_ty = ywk ? TYL : TYLF;
+  // the passes (plane filter: ucf, no yw -- the form's condition)
+  auto lmf = [&](int pair, bool packed) { return lmf_kernel(P.filter2d, pair, local, packed, ywk, ucf, small); };
+  P.strain.k = strain_kernel(P.pair, P.filter2d, ywk, small); P.lmf[0].k = lmf(P.pair ? LMF_PAIR : 0, false);
+  if (P.pair) { P.corr[0][0].k = corr_strain_kernel(false, false); if (c->P > 1) P.corr[1][0].k = corr_strain_kernel(true, false); }
+  if (P.five) { P.corr[0][1].k = corr_strain_kernel(false, true); P.lmf[1].k = lmf(LMF_PAIR5, false); }
+  if (P.lmf_packed) { P.lmf_rem[0].k = lmf(LMF_PAIR, true); if (P.five) P.lmf_rem[1].k = lmf(LMF_PAIR5, true); }
 }
 // sgs_setup_launches: the launch geometry of the tile passes (after cales_create has read the CU count: balanced_kchunk)
 int sgs_setup_launches(cales_ctx *c) {
@@ -1544,60 +1575,58 @@ int sgs_setup_launches(cales_ctx *c) {
     while ((long)rgx * rgy * ((n[2] + kr - 1) / kr) < 8192 && kr > 32) kr = (kr + 1) / 2;
     while ((long)rgx * rgy * ((n[2] + kr - 1) / kr) < 1024 && kr > 8) kr = (kr + 1) / 2;
     if (c->fl.kchunk > 0) kr = c->fl.kchunk < n[2] ? c->fl.kchunk : n[2];
-    P.smag_geo.kchunk = kr; P.smag_geo.bm = band_map(rgx, rgy, (n[2] + kr - 1) / kr);
-    P.smag_geo.block = dim3(64, SROWS, 1); P.smag_geo.grid = dim3(band_blocks(P.smag_geo.bm), 1, 1);
+    TileGeom &s = P.smag.geo; s.kchunk = kr; s.bm = band_map(rgx, rgy, (n[2] + kr - 1) / kr);
+    s.block = dim3(64, SROWS, 1); s.grid = dim3(band_blocks(s.bm), 1, 1);
   }
   if (P.form != SgsForm::dsmag_tiles) return 0;
+  // a missing kernel is an error, never another path: only LOCAL has instantiations that are not built (lmf_kernel), and sgs_setup must not take the tile form there
+  if (!P.lmf[0].k.fn) { c->err = "dsmag: no local form of this last pass"; return 1; }
   // K_AC: tiles of 64 x TYS, folded 64 x TYC (with two ghost rows of the prediction on several slabs: two rows more); the last pass 62 x lmf_ty
-  P.strain_geo = with_bands(tile_geom(c, TYS, 64));
-  if (P.pair) { P.corr_geo = with_bands(tile_geom(c, TYC, 64)); P.corr_rows2_geo = with_bands(tile_geom(c, TYC, 64, 2)); }
-  TileGeom t = tile_geom(c, P.lmf_ty, 62, 0, LMF_KMAX);
+  P.strain.geo = with_bands(tile_geom(c, TYS, 64));
+  if (P.pair) { P.corr[0][0].geo = P.corr[0][1].geo = with_bands(tile_geom(c, TYC, 64)); P.corr[1][0].geo = with_bands(tile_geom(c, TYC, 64, 2)); }
+  TileGeom t = tile_geom(c, P.lmf_ty, 62, 0, LMF_KMAX), rem;
   // The remainder x tile packed into full waves (lmf_pack.hpp; pair fields on one rank): the launch above keeps the full tiles, with the chunk length their
   // block count gives, and a launch of the packed instantiation takes the remainder tile of S y tiles per block, its chunk length from the same cost model
   // (few blocks: one round of short chunks). 512^3: 8 x 64 x 4 blocks -- eight full rounds of the 256 CUs instead of nine with every ninth block three
   // quarters dead lanes -- and 22 x 11 packed blocks of 47 planes. Every y tile's remainder sum keeps the slot it has in the one launch (lmf_gx x tiles per
   // row), so k_plane_fold adds the same numbers in the same order; a packed block keeps the sums of its S stretches' chunks in the LDS of one chunk of LMF_KMAX.
-  const LmfPack pk = lmf_pack(n[0]);
-  P.lmf_packed = P.pair && P.ave != SgsAve::local && c->P == 1 && pk.on && !c->fl.lmf_unpacked_remainder;      // (local: no block sums, another instantiation)
   P.lmf_gx = t.grid.x;
   if ((size_t)2 * n[2] * t.grid.x * t.grid.y > c->ntot) { c->err = "dsmag: partial-sum scratch too small"; return 1; }
-  int kmax_rem = LMF_KMAX;
-  if (P.lmf_packed) {
-    const int gy = t.grid.y;
-    kmax_rem = LMF_KMAX / pk.S;
-    t.grid = dim3(pk.full, gy, 1); tile_chunks(c, t, LMF_KMAX);
-    P.lmf_rem_geo = t; P.lmf_rem_geo.grid = dim3(1, lmf_pack_blocks(pk, gy), 1); tile_chunks(c, P.lmf_rem_geo, kmax_rem);
-  }
   auto cap = [&](TileGeom &s, int kmax) { while (s.kchunk > kmax) { s.kchunk = (s.kchunk + 1) / 2; s.grid.z = (n[2] + s.kchunk - 1) / s.kchunk; } };      // the kernel keeps a chunk's block sums in LDS
-  cap(t, LMF_KMAX); cap(P.lmf_rem_geo, kmax_rem);
-  P.lmf_geo = t;
+  if (P.lmf_packed) {
+    const LmfPack pk = lmf_pack(n[0]); const int gy = t.grid.y, kmax_rem = LMF_KMAX / pk.S;
+    t.grid = dim3(pk.full, gy, 1); tile_chunks(c, t, LMF_KMAX);
+    rem = t; rem.grid = dim3(1, lmf_pack_blocks(pk, gy), 1); tile_chunks(c, rem, kmax_rem); cap(rem, kmax_rem);
+  }
+  cap(t, LMF_KMAX);
+  P.lmf[0].geo = P.lmf[1].geo = t; P.lmf_rem[0].geo = P.lmf_rem[1].geo = rem;
   return 0;
 }
-static int dsmag_fast(cales_ctx *c, const SgsFold *fold, bool *visct_ghosts_done) {
-  const SgsPath &P = c->sgs;
-  const int *n = c->n; real **f = c->f; real *visct = f[CALES_VISCT];
-  dim3 b(BX, BY, 1), gr = grid3(n[0], n[1], n[2], b);
-  real **ssij = c->sij, **mij = c->mij;
-  // K_AC: |S|, |S|Sij, cell-centred and test-filtered velocity in one pass over u,v,w (no wall-model faces -> extrapolate(...,lwm) is a no-op; u,v
-  // are extrapolated through the z walls, w on the faces is not, sgs.f90:705-710); fold (pair fields, make_plan): with the projection folded in, ext:
-  // from two ghost rows of the prediction, forming the ghost rows of its outputs too
+// the static wall arguments of a tile pass: the ten that StrainTileArgs and LijMijArgs both carry
+template <typename A> static void wall_args(const SgsPath &P, A &a) {
+  a.zlo = P.zlo; a.zhi = P.zhi; a.wmlo = P.wmlo; a.wmhi = P.wmhi; a.flo = P.flo; a.fhi = P.fhi;
+  a.wylo = P.wylo; a.wyhi = P.wyhi; a.wmylo = P.wmylo; a.wmyhi = P.wmyhi;
+}
+// ---- the tile form of the dynamic model, in four steps (dsmag_fast below). What a call decides: fold (the projection of this substep is pending), and with it s12 != nullptr:
+// FIVE components -- S12 as a plain field in the buffer of the pair field (S33,S12), placed like every field: cell (1, j, k) at the head of a 128-B line (field_alloc: a pair
+// field starts 2 field_ofs reals into its allocation, a field field_ofs; 8 bytes off, every wave's 512-B store touches a fifth line).
+// 1. K_AC: |S|, |S|Sij, cell-centred and test-filtered velocity in one pass over u,v,w (no wall-model faces -> extrapolate(...,lwm) is a no-op; u,v
+// are extrapolated through the z walls, w on the faces is not, sgs.f90:705-710); fold (pair fields, make_plan): with the projection folded in, rows2:
+// from two ghost rows of the prediction, forming the ghost rows of its outputs too
+static int dsmag_strain_pass(cales_ctx *c, const SgsFold *fold, real *s12) {
+  const SgsPath &P = c->sgs; const int *n = c->n; real **f = c->f;
   const bool ext = fold && fold->rows2;
-  const bool five = fold && !ext && P.five;      // (the identity holds for the velocity this call projects, not for one it is handed)
-  // five components: S12 as a plain field in the buffer of the pair field (S33,S12), placed like every field -- cell (1, j, k) at the head of a 128-B line
-  // (field_alloc: a pair field starts 2 field_ofs reals into its allocation, a field field_ofs; 8 bytes off, every wave's 512-B store touches a fifth line)
-  real *const s12 = five ? c->ss2[1] - c->field_ofs : nullptr;
   { ProfScope ps(c, fold ? "correc_strain_filter_uvw" : "strain_filter_uvw");
-    const TileGeom &t = !fold ? P.strain_geo : ext ? P.corr_rows2_geo : P.corr_geo;
+    const TilePass<StrainTileArgs> &pass = !fold ? P.strain : P.corr[ext][s12 != nullptr]; const TileGeom &t = pass.geo;
     StrainTileArgs S;
-    S.u[0] = f[CALES_U]; S.u[1] = f[CALES_V]; S.u[2] = f[CALES_W]; S.s0 = P.lazy ? visct : c->s0;
-    for (int m = 0; m < 6; ++m) S.ssij[m] = ssij[m];
+    S.u[0] = f[CALES_U]; S.u[1] = f[CALES_V]; S.u[2] = f[CALES_W]; S.s0 = P.lazy ? f[CALES_VISCT] : c->s0;
+    for (int m = 0; m < 6; ++m) S.ssij[m] = c->sij[m];
     for (int m = 0; m < 3; ++m) S.ss2[m] = reinterpret_cast<real2 *>(c->ss2[m]);
-    if (five) S.ss2[1] = reinterpret_cast<real2 *>(s12);
+    if (s12) S.ss2[1] = reinterpret_cast<real2 *>(s12);
     S.uc[0] = P.ucf ? nullptr : c->uc; S.uc[1] = P.ucf ? nullptr : c->vc; S.uc[2] = P.ucf ? nullptr : c->wc; S.uf[0] = c->uf; S.uf[1] = c->vf; S.uf[2] = c->wf;
-    S.dzci = c->d_dzci; S.dzfi = c->d_dzfi; S.dxi = c->dli[0]; S.dyi = c->dli[1]; S.kchunk = t.kchunk; S.zlo = P.zlo; S.zhi = P.zhi; S.wmlo = P.wmlo; S.wmhi = P.wmhi; S.flo = P.flo; S.fhi = P.fhi;
-    S.wylo = P.wylo; S.wyhi = P.wyhi; S.wmylo = P.wmylo; S.wmyhi = P.wmyhi; S.twy = nullptr; S.dl2 = c->dl[1];
-    S.bm = t.bm; S.perx = c->step_xskip ? 1 : 0;
-    if (fold) {      // the projection of this substep is pending (cales_step): corrected velocity on load, u, v, w to the second buffers, p += pp
+    S.dzci = c->d_dzci; S.dzfi = c->d_dzfi; S.dxi = c->dli[0]; S.dyi = c->dli[1]; S.kchunk = t.kchunk;
+    wall_args(P, S); S.twy = nullptr; S.dl2 = c->dl[1]; S.bm = t.bm; S.perx = c->step_xskip ? 1 : 0;
+    if (fold) {      // corrected velocity on load, u, v, w to the second buffers, p += pp
       S.pp = f[CALES_PP]; S.p = f[CALES_P]; for (int q = 0; q < 3; ++q) S.un[q] = c->f2[q];
       S.force = c->d_force; S.fmask = fold->fmask;
       S.cdt = fold->dtrk; S.cfi = fold->dtrk * c->dli[0]; S.cfj = fold->dtrk * c->dli[1]; S.zper = P.perz;
@@ -1606,44 +1635,32 @@ static int dsmag_fast(cales_ctx *c, const SgsFold *fold, bool *visct_ghosts_done
       S.bcz[0][0] = c->bcu.z; S.bcz[0][1] = c->bcu.z + pl; S.bcz[1][0] = c->bcv.z; S.bcz[1][1] = c->bcv.z + pl;
       S.vcg = c->vc;
     }
-    switch (!fold ? P.strain : ext ? StrainKernel::corr_rows2 : five ? StrainKernel::corr5 : StrainKernel::corr) {
-    case StrainKernel::corr_rows2: LAUNCH(c, (k_corr_strain_tile<unsigned, TYC, 1>), t.grid, t.block, 0, c->stream, c->g, S); break;
-    case StrainKernel::corr5: LAUNCH(c, (k_corr_strain_tile<unsigned, TYC, 2>), t.grid, t.block, 0, c->stream, c->g, S); break;
-    case StrainKernel::corr: LAUNCH(c, (k_corr_strain_tile<unsigned, TYC>), t.grid, t.block, 0, c->stream, c->g, S); break;
-    case StrainKernel::yw32: LAUNCH(c, (k_strain_tile<unsigned, TYS, 1>), t.grid, t.block, 0, c->stream, c->g, S); break;
-    case StrainKernel::yw64: LAUNCH(c, (k_strain_tile<size_t, TYS, 1>), t.grid, t.block, 0, c->stream, c->g, S); break;
-    case StrainKernel::pair: LAUNCH(c, (k_strain_tile<unsigned, TYS, 0, 1>), t.grid, t.block, 0, c->stream, c->g, S); break;
-    case StrainKernel::plain32: LAUNCH(c, (k_strain_tile<unsigned, TYS, 0>), t.grid, t.block, 0, c->stream, c->g, S); break;
-    case StrainKernel::plain64: LAUNCH(c, (k_strain_tile<size_t, TYS, 0>), t.grid, t.block, 0, c->stream, c->g, S); break;
-    case StrainKernel::f2d32: LAUNCH(c, (k_strain_tile<unsigned, TYS, 0, 2>), t.grid, t.block, 0, c->stream, c->g, S); break;
-    case StrainKernel::f2d64: LAUNCH(c, (k_strain_tile<size_t, TYS, 0, 2>), t.grid, t.block, 0, c->stream, c->g, S); break;
-    } }
-  if (fold) {
-    // the corrected velocity sits in the second buffers: swap (as the fused momentum pass does), give the normal component its two z faces -- the
-    // reference's correc covers w(:,:,0) (correc.f90:60-66) and leaves w(:,:,n3+1) as it was, and bounduvw with is_correc touches neither -- and
-    // fill the ghost cells of u, v, w and p (the pressure rides along: pair fields come with the one-launch ghost-cell kernel) as main.f90:500-504
-    // does after correc / updatep
-    for (int q = 0; q < 3; ++q) std::swap(c->f[CALES_U + q], c->f2[q]);
-    if (!P.perz)
-      LAUNCH(c, k_wface_fold, dim3((n[0] + 2 + 63) / 64, (n[1] + 2 + 3) / 4), dim3(64, 4), 0, c->stream, c->g, c->f2[2], c->f[CALES_W], f[CALES_PP], fold->dtrk * c->dzci[0]);
-    // several slabs: the ghost rows of u, v, w and p do not travel at all -- k_fold_ghost_rows forms them from the prediction's ghost rows and pp's,
-    // the ghost-cell kernel below gives them their x and z ghost cells (round 5: in the same exchange as the scratch fields', fifteen planes; now eleven)
-    if (c->P > 1 && !ext)      // (ext: the strain-rate pass has formed them itself)
-      LAUNCH(c, k_fold_ghost_rows, dim3((n[0] + 63) / 64, (n[2] + 3) / 4, 2), dim3(64, 4), 0, c->stream, c->g, c->f2[0], c->f2[1], c->f2[2], c->f[CALES_U], c->f[CALES_V],
-             c->f[CALES_W], f[CALES_PP], c->scr2, f[CALES_P], c->d_force, fold->fmask, fold->dtrk * c->dli[0], fold->dtrk * c->dli[1], fold->dtrk, c->d_dzci, c->step_xskip ? 1 : 0);
-    BcCall bc; bc.rows_current = c->P > 1; bc.rider(f[CALES_P], 0);
-    if (int e = op_bounduvw(c, VelSet::state, 1, 1, bc)) return e;
-  }
-  // sgs-type ghost cells: only the periodic exchange matters (products of ghosts = ghosts of products; the wall ghosts are
-  // replaced by the extrapolation rule inside the filters)
-  // These twelve scratch fields are read by the tile kernels only: with periodic x their ghost columns are not filled (perx: the
-  // kernels wrap around instead; an x ghost update touches four cache lines per row for two values), and the z ghost planes
-  // of the quantities the wall rule covers are never read (skipz).
-  // several ranks with the second stream: the y-halo rows of the twelve scratch fields travel while the interior tiles of the last pass run
-  const bool overlap = c->comm.halo_second_stream && !ext;      // (ext: no row of these fields travels)
-  // several ranks: ONE exchange for the y-halo rows of all these fields (six |S|Sij, three filtered velocities, v_c, and |S| itself in the lazy form
-  // inside cales_step) instead of one per ghost-cell call; their ghost-cell kernels run first, the rows that then arrive carry the neighbour's
-  // x/z ghost cells
+    LAUNCH_REC(c, pass.k, t.grid, t.block, 0, c->stream, c->g, S); }
+  if (!fold) return 0;
+  // the corrected velocity sits in the second buffers: swap (as the fused momentum pass does), give the normal component its two z faces -- the
+  // reference's correc covers w(:,:,0) (correc.f90:60-66) and leaves w(:,:,n3+1) as it was, and bounduvw with is_correc touches neither -- and
+  // fill the ghost cells of u, v, w and p (the pressure rides along: pair fields come with the one-launch ghost-cell kernel) as main.f90:500-504
+  // does after correc / updatep
+  for (int q = 0; q < 3; ++q) std::swap(c->f[CALES_U + q], c->f2[q]);
+  if (!P.perz)
+    LAUNCH(c, k_wface_fold, dim3((n[0] + 2 + 63) / 64, (n[1] + 2 + 3) / 4), dim3(64, 4), 0, c->stream, c->g, c->f2[2], c->f[CALES_W], f[CALES_PP], fold->dtrk * c->dzci[0]);
+  // several slabs: the ghost rows of u, v, w and p do not travel at all -- k_fold_ghost_rows forms them from the prediction's ghost rows and pp's,
+  // the ghost-cell kernel below gives them their x and z ghost cells (round 5: in the same exchange as the scratch fields', fifteen planes; now eleven)
+  if (c->P > 1 && !ext)      // (ext: the strain-rate pass has formed them itself)
+    LAUNCH(c, k_fold_ghost_rows, dim3((n[0] + 63) / 64, (n[2] + 3) / 4, 2), dim3(64, 4), 0, c->stream, c->g, c->f2[0], c->f2[1], c->f2[2], c->f[CALES_U], c->f[CALES_V],
+           c->f[CALES_W], f[CALES_PP], c->scr2, f[CALES_P], c->d_force, fold->fmask, fold->dtrk * c->dli[0], fold->dtrk * c->dli[1], fold->dtrk, c->d_dzci, c->step_xskip ? 1 : 0);
+  BcCall bc; bc.rows_current = c->P > 1; bc.rider(f[CALES_P], 0);
+  return op_bounduvw(c, VelSet::state, 1, 1, bc);
+}
+// 2. The ghost cells of the scratch fields, sgs-type: only the periodic exchange matters (products of ghosts = ghosts of products; the wall ghosts are
+// replaced by the extrapolation rule inside the filters). The tile kernels alone read these fields: with periodic x their ghost columns are not filled
+// (perx: the kernels wrap around instead; an x ghost update touches four cache lines per row for two values), and the z ghost planes of the quantities the
+// wall rule covers are never read (skipz). Several ranks: ONE exchange for the y-halo rows of all these fields (six |S|Sij, three filtered velocities, v_c,
+// and |S| itself in the lazy form inside cales_step) instead of one per ghost-cell call; their ghost-cell kernels run first, the rows that then arrive
+// carry the neighbour's x/z ghost cells. overlap: on the second stream, beside the interior tiles of the last pass
+static int dsmag_scratch_ghosts(cales_ctx *c, bool ext, real *s12, bool overlap, bool *visct_ghosts_done) {
+  const SgsPath &P = c->sgs; const int *n = c->n; real **f = c->f;
+  const bool five = s12 != nullptr;
   HaloBatch rows;
   BcCall bc; bc.skip = P.perx | P.skipz;
   if (ext) bc.rows_current = true;      // the ghost rows of every field below were formed by the strain-rate pass: their x and z ghost cells only
@@ -1651,7 +1668,7 @@ static int dsmag_fast(cales_ctx *c, const SgsFold *fold, bool *visct_ghosts_done
   BcCall bz = bc; bz.skip = P.perx;      // (the filtered velocity: its z ghost planes are read)
   // (five components: the pair fields (S11,S22) and (S13,S23); S12, a plain field at the head of ss2[1], goes with v_c below -- no launch more)
   real *ssp[3] = {c->ss2[0], five ? c->ss2[2] : c->ss2[1], c->ss2[2]};
-  if (int e = P.pair ? op_boundp_wide(c, five ? 2 : 3, ssp, 1, bc) : op_boundp_multi(c, 6, ssij, 1, bc)) return e;
+  if (int e = P.pair ? op_boundp_wide(c, five ? 2 : 3, ssp, 1, bc) : op_boundp_multi(c, 6, c->sij, 1, bc)) return e;
   if (int e = op_bounduvw(c, VelSet::filtered, 0, 0, bz)) return e;
   if (!P.ucf) { real *cc[3] = {c->uc, c->vc, c->wc}; if (int e = op_boundp_multi(c, 3, cc, 1, bc)) return e; }
   else if (ext) { if (int e = op_boundp(c, c->vc, 1, bc)) return e; }      // (v_c of the two ghost rows came from the strain-rate pass)
@@ -1661,82 +1678,75 @@ static int dsmag_fast(cales_ctx *c, const SgsFold *fold, bool *visct_ghosts_done
     if (int e = op_boundp_multi(c, five ? 2 : 1, two, 1, bc)) return e; }
   if (P.lazy && visct_ghosts_done && c->P > 1) {      // inside cales_step |S| is final (K_AC wrote it): its rows travel along
     BcCall bv = bc; bv.skip = 0;
-    if (int e = op_boundp(c, visct, 1, bv)) return e;
+    if (int e = op_boundp(c, f[CALES_VISCT], 1, bv)) return e;
     *visct_ghosts_done = true; }
-  if (int e = halo_flush(c, rows, overlap)) return e;
-  LijMijArgs L;
+  return halo_flush(c, rows, overlap);
+}
+// 3. K_B + K_DF in one pass: filter(|S|Sij) on the fly, strain rate of the filtered velocity, Mij, Lij, contractions, plane partial sums (local: visct itself)
+static int dsmag_last_pass(cales_ctx *c, real *s12, bool overlap) {
+  const SgsPath &P = c->sgs; const int *n = c->n; real **f = c->f;
+  const bool five = s12 != nullptr;
+  ProfScope ps(c, "lij_mij_filter_contract");
+  const TilePass<LmfArgs> &pass = P.lmf[five]; const TileGeom &t = pass.geo;
+  LmfArgs B; LijMijArgs &L = B.L;
   L.uc[0] = P.ucf ? f[CALES_U] : c->uc; L.uc[1] = P.ucf ? f[CALES_V] : c->vc; L.uc[2] = P.ucf ? f[CALES_W] : c->wc; L.uf[0] = c->uf; L.uf[1] = c->vf; L.uf[2] = c->wf;
   L.vcg = c->vc; L.perz = P.perz; L.xwrap = c->step_xskip ? 1 : 0;
-  for (int m = 0; m < 6; ++m) L.mf[m] = mij[m];
+  for (int m = 0; m < 6; ++m) L.mf[m] = c->mij[m];
   L.part = c->wk[0]; L.dzci = c->d_dzci; L.dzfi = c->d_dzfi; L.dxi = c->dli[0]; L.dyi = c->dli[1];
-  L.zlo = P.zlo; L.zhi = P.zhi; L.wmlo = P.wmlo; L.wmhi = P.wmhi; L.flo = P.flo; L.fhi = P.fhi; L.perx = P.perx;
-  L.wylo = P.wylo; L.wyhi = P.wyhi; L.wmylo = P.wmylo; L.wmyhi = P.wmyhi;
-  const bool local = P.ave == SgsAve::local;      // the last pass writes visct itself, from |S| (never lazy: K_AC left it in c->s0)
-  if (local) { L.mf[0] = c->s0; L.part = visct; }
-  {
-    // K_B + K_DF in one pass: filter(|S|Sij) on the fly, strain rate of the filtered velocity, Mij, Lij, contractions, plane partial sums
-    ProfScope ps(c, "lij_mij_filter_contract");
-    const TileGeom &t = P.lmf_geo;
-    L.kchunk = t.kchunk; L.nblk = P.lmf_gx * t.grid.y;
-    LmfArgs B; B.L = L; for (int m = 0; m < 6; ++m) B.ss[m] = ssij[m];
-    for (int m = 0; m < 3; ++m) B.ss2[m] = reinterpret_cast<const real2 *>(c->ss2[m]);
-    if (five) B.ss2[1] = reinterpret_cast<const real2 *>(s12);
-    B.gx = P.lmf_gx;
-    auto launch =[&](int by0, int nby) {      // the y tiles by0 .. by0 + nby - 1
-      if (nby <= 0) return;
-      TileGeom s = t; s.grid.y = nby; s = with_bands(s);
-      if (P.lmf_packed && c->fl.lmf_main_bands && !s.bm.gx) { s.bm = band_map(s.grid.x, s.grid.y, s.grid.z); s.grid = dim3(band_blocks(s.bm), 1, 1); }      // (experiments)
-      B.by0 = by0; B.bm = s.bm;
-      if (local) switch (P.lmf) {      // (sgs_setup: ucf, 32-bit offsets, six components, the 3-D filter)
-      case LmfKernel::pair: LAUNCH(c, (k_lmf_tile<unsigned, 0, 1, 5>), s.grid, s.block, 0, c->stream, c->g, B); return;
-      case LmfKernel::yw_ucf32: LAUNCH(c, (k_lmf_tile<unsigned, 1, 1, 4>), s.grid, s.block, 0, c->stream, c->g, B); return;
-      case LmfKernel::ucf32: LAUNCH(c, (k_lmf_tile<unsigned, 0, 1, 4>), s.grid, s.block, 0, c->stream, c->g, B); return;
-      default: c->launch_err = "dsmag: no local form of this last pass"; return;      // (a missing kernel is an error, never another path)
-      }
-      switch (five ? LmfKernel::pair5 : P.lmf) {
-      case LmfKernel::pair5: LAUNCH(c, (k_lmf_tile<unsigned, 0, 1, 2>), s.grid, s.block, 0, c->stream, c->g, B); break;
-      case LmfKernel::pair: LAUNCH(c, (k_lmf_tile<unsigned, 0, 1, 1>), s.grid, s.block, 0, c->stream, c->g, B); break;
-      case LmfKernel::yw_ucf32: LAUNCH(c, (k_lmf_tile<unsigned, 1, 1>), s.grid, s.block, 0, c->stream, c->g, B); break;
-      case LmfKernel::yw_ucf64: LAUNCH(c, (k_lmf_tile<size_t, 1, 1>), s.grid, s.block, 0, c->stream, c->g, B); break;
-      case LmfKernel::yw32: LAUNCH(c, (k_lmf_tile<unsigned, 1, 0>), s.grid, s.block, 0, c->stream, c->g, B); break;
-      case LmfKernel::yw64: LAUNCH(c, (k_lmf_tile<size_t, 1, 0>), s.grid, s.block, 0, c->stream, c->g, B); break;
-      case LmfKernel::ucf32: LAUNCH(c, (k_lmf_tile<unsigned, 0, 1>), s.grid, s.block, 0, c->stream, c->g, B); break;
-      case LmfKernel::ucf64: LAUNCH(c, (k_lmf_tile<size_t, 0, 1>), s.grid, s.block, 0, c->stream, c->g, B); break;
-      case LmfKernel::plain32: LAUNCH(c, (k_lmf_tile<unsigned, 0, 0>), s.grid, s.block, 0, c->stream, c->g, B); break;
-      case LmfKernel::plain64: LAUNCH(c, (k_lmf_tile<size_t, 0, 0>), s.grid, s.block, 0, c->stream, c->g, B); break;
-      case LmfKernel::f2d32: LAUNCH(c, (k_lmf_plane_tile<unsigned>), s.grid, s.block, 0, c->stream, c->g, B); break;
-      case LmfKernel::f2d64: LAUNCH(c, (k_lmf_plane_tile<size_t>), s.grid, s.block, 0, c->stream, c->g, B); break;
-      }
-    };
-    // the remainder x tile of every row, S y tiles per block (SgsPath::lmf_packed: pair fields, one rank): its own chunk length, its block sums behind the others'
-    auto launch_packed = [&]() {
-      if (!P.lmf_packed) return;
-      const TileGeom &s = P.lmf_rem_geo;
-      LmfArgs R = B; R.L.kchunk = s.kchunk; R.by0 = 0; R.bm = BandMap{0, 0, 0, 0};
-      if (five) LAUNCH(c, (k_lmf_tile<unsigned, 0, 1, 10>), s.grid, s.block, 0, c->stream, c->g, R);
-      else LAUNCH(c, (k_lmf_tile<unsigned, 0, 1, 9>), s.grid, s.block, 0, c->stream, c->g, R);
-    };
-    if (overlap) {
-      // tiles that read the ghost rows j = 0 or j = n2+1 wait for the rows in flight; the others run beside the exchange
-      int hi0 = (int)t.grid.y; while (hi0 > 1 && (hi0 - 1) * P.lmf_ty + P.lmf_ty + 1 >= n[1] + 1) --hi0;      // first tile (> 0) that reaches row n2+1
-      launch(1, hi0 - 1);
-      if (int e = stream_after(c, c->stream, c->comm_stream)) return e;
-      launch(0, 1); launch(hi0, (int)t.grid.y - hi0);
-    } else launch(0, (int)t.grid.y);
-    launch_packed();
-    if (local) { LAUNCHCHK(c); return 0; }      // sgs.f90:368-377: visct is written -- no fold, no all-reduce, no final kernel
-    LAUNCH(c, k_plane_fold, dim3(2 * n[2]), dim3(256), 0, c->stream, n[2], L.nblk, c->wk[0], c->d_p1d);
+  wall_args(P, L); L.perx = P.perx;
+  if (P.ave == SgsAve::local) { L.mf[0] = c->s0; L.part = f[CALES_VISCT]; }      // the pass writes visct itself, from |S| (never lazy: K_AC left it in c->s0)
+  L.kchunk = t.kchunk; L.nblk = P.lmf_gx * t.grid.y; B.gx = P.lmf_gx;
+  for (int m = 0; m < 6; ++m) B.ss[m] = c->sij[m];
+  for (int m = 0; m < 3; ++m) B.ss2[m] = reinterpret_cast<const real2 *>(c->ss2[m]);
+  if (five) B.ss2[1] = reinterpret_cast<const real2 *>(s12);
+  auto launch = [&](int by0, int nby) {      // the y tiles by0 .. by0 + nby - 1
+    if (nby <= 0) return;
+    TileGeom s = t; s.grid.y = nby; s = with_bands(s);
+    if (P.lmf_packed && c->fl.lmf_main_bands && !s.bm.gx) { s.bm = band_map(s.grid.x, s.grid.y, s.grid.z); s.grid = dim3(band_blocks(s.bm), 1, 1); }      // (experiments)
+    B.by0 = by0; B.bm = s.bm;
+    LAUNCH_REC(c, pass.k, s.grid, s.block, 0, c->stream, c->g, B);
+  };
+  if (overlap) {
+    // several ranks with the second stream: tiles that read the ghost rows j = 0 or j = n2+1 wait for the rows in flight; the others run beside the exchange
+    int hi0 = (int)t.grid.y; while (hi0 > 1 && (hi0 - 1) * P.lmf_ty + P.lmf_ty + 1 >= n[1] + 1) --hi0;      // first tile (> 0) that reaches row n2+1
+    launch(1, hi0 - 1);
+    if (int e = stream_after(c, c->stream, c->comm_stream)) return e;
+    launch(0, 1); launch(hi0, (int)t.grid.y - hi0);
+  } else launch(0, (int)t.grid.y);
+  if (P.lmf_packed) {      // the remainder x tile of every row, S y tiles per block: its own chunk length, its block sums behind the others'
+    const TilePass<LmfArgs> &rem = P.lmf_rem[five];
+    LmfArgs R = B; R.L.kchunk = rem.geo.kchunk; R.by0 = 0; R.bm = BandMap{0, 0, 0, 0};
+    LAUNCH_REC(c, rem.k, rem.geo.grid, rem.geo.block, 0, c->stream, c->g, R);
   }
+  return 0;
+}
+// 4. (and the end of the reference sequence) The coefficient from the sums of MijLij and MijMij over the planes, and the eddy viscosity (sgs.f90:359-379). nblk
+// != 0: the sums are still the nblk block sums per plane the last pass left in wk[0] -- folded in a fixed order first. s0: where |S| sits (not lazy)
+static int dsmag_coefficient(cales_ctx *c, int nblk, const real *s0) {
+  const SgsPath &P = c->sgs; const int *n = c->n; real *visct = c->f[CALES_VISCT];
+  if (nblk) LAUNCH(c, k_plane_fold, dim3(2 * n[2]), dim3(256), 0, c->stream, n[2], nblk, c->wk[0], c->d_p1d);
   if (c->P > 1) { if (int e = allreduce_dev(c, c->d_p1d, 2 * n[2], 0)) return e; }   // sgs.f90:475
   if (P.ave == SgsAve::volume) LAUNCH(c, k_volume_fold, dim3(1), dim3(256), 0, c->stream, n[2], c->d_dzf, c->d_p1d);      // sgs.f90:360-361
   const real gar = c->dl[0] * c->dl[1] / (c->C.l[0] * c->C.l[1]);
-  if (P.lazy) {
+  if (P.lazy) {      // |S| is in visct already: cs(k) alone, the momentum pass applies it
     if (!c->d_cs && ctx_alloc(c, &c->d_cs, n[2] + 2, false)) return 1;
     LAUNCH(c, k_dsmag_coef, dim3(1), dim3(256), 0, c->stream, n[2], gar, c->d_p1d, c->d_cs, P.perz);
     c->visct_lazy = true;
-  } else LAUNCH(c, k_dsmag_final, gr, b, 0, c->stream, c->g, gar, c->d_p1d, c->s0, visct);
+  } else { const dim3 b(BX, BY, 1); LAUNCH(c, k_dsmag_final, grid3(n[0], n[1], n[2], b), b, 0, c->stream, c->g, gar, c->d_p1d, s0, visct); }
   LAUNCHCHK(c);
   return 0;
+}
+static int dsmag_fast(cales_ctx *c, const SgsFold *fold, bool *visct_ghosts_done) {
+  const SgsPath &P = c->sgs;
+  const bool ext = fold && fold->rows2;
+  const bool five = fold && !ext && P.five;      // (the identity holds for the velocity this call projects, not for one it is handed)
+  real *const s12 = five ? c->ss2[1] - c->field_ofs : nullptr;
+  const bool overlap = c->comm.halo_second_stream && !ext;      // (ext: no row of the scratch fields travels)
+  if (int e = dsmag_strain_pass(c, fold, s12)) return e;
+  if (int e = dsmag_scratch_ghosts(c, ext, s12, overlap, visct_ghosts_done)) return e;
+  if (int e = dsmag_last_pass(c, s12, overlap)) return e;
+  if (P.ave == SgsAve::local) { LAUNCHCHK(c); return 0; }      // sgs.f90:368-377: visct is written -- no fold, no all-reduce, no final kernel
+  return dsmag_coefficient(c, P.lmf_gx * (int)P.lmf[0].geo.grid.y, c->s0);
 }
 
 static inline dim3 lin_grid(size_t n) { size_t b = (n + 255) / 256; if (b > 4096) b = 4096; return dim3((unsigned)b); }
@@ -1781,74 +1791,46 @@ static int smag_fast(cales_ctx *c) {
   StrainTileArgs S = {};
   S.u[0] = f[CALES_U]; S.u[1] = f[CALES_V]; S.u[2] = f[CALES_W]; S.visct = f[CALES_VISCT];
   S.dzci = c->d_dzci; S.dzfi = c->d_dzfi; S.dxi = c->dli[0]; S.dyi = c->dli[1];
-  S.zlo = P.zlo; S.zhi = P.zhi; S.wmlo = P.wmlo; S.wmhi = P.wmhi; S.flo = P.flo; S.fhi = P.fhi;
+  wall_args(P, S); S.dl2 = c->dl[1]; S.twy = nullptr;
   S.zc = c->d_zc; S.del = c->d_del; S.l3 = c->C.l[2]; S.visc = c->visc; S.perx = c->step_xskip ? 1 : 0;
-  S.wylo = P.wylo; S.wyhi = P.wyhi; S.dl2 = c->dl[1]; S.wmylo = P.wmylo; S.wmyhi = P.wmyhi;
-  S.twy = nullptr;
   if (S.wylo || S.wyhi) { if (int e = wall_shear_y_planes(c, S.wylo, S.wyhi, &S.twy)) return e; }
-  const TileGeom &t = P.smag_geo;
+  const TileGeom &t = P.smag.geo;
   S.kchunk = t.kchunk; S.bm = t.bm;
-  switch (P.smag) {
-  case SmagKernel::yw32: LAUNCH(c, (k_smag_rows<unsigned, 1>), t.grid, t.block, 0, c->stream, c->g, S); break;
-  case SmagKernel::yw64: LAUNCH(c, (k_smag_rows<size_t, 1>), t.grid, t.block, 0, c->stream, c->g, S); break;
-  case SmagKernel::plain32: LAUNCH(c, (k_smag_rows<unsigned, 0>), t.grid, t.block, 0, c->stream, c->g, S); break;
-  case SmagKernel::plain64: LAUNCH(c, (k_smag_rows<size_t, 0>), t.grid, t.block, 0, c->stream, c->g, S); break;
-  }
+  LAUNCH_REC(c, P.smag.k, t.grid, t.block, 0, c->stream, c->g, S);
   LAUNCHCHK(c);
   return 0;
 }
-
-// the form of cmpt_sgs this context takes (cales_describe_plan): the record op_cmpt_sgs launches
-const char *sgs_path_name(const cales_ctx *c) {
-  static const char *names[] = {"none", "smag_rows", "smag_reference_sequence", "dsmag_tiles", "dsmag_reference_sequence"};      // (SgsForm order)
-  if (c->sgs.filter2d) return c->sgs.form == SgsForm::dsmag_tiles ? "dsmag_tiles(filter2d)" : "dsmag_reference_sequence(filter2d)";
-  return c->sgs.pair ? "dsmag_tiles(pair_fields)" : names[(int)c->sgs.form];
+// The reference's sequence of the static model, kernel per loop (walls or wall model in x, degenerate grids, CALES_SMAG_REFERENCE_SEQUENCE)
+static int smag_sequence(cales_ctx *c) {
+  const int *n = c->n, if123[3] = {1, 2, 3}; const size_t nt = c->ntot; real **f = c->f, **wk = c->wk;
+  const dim3 b(BX, BY, 1), gr = grid3(n[0], n[1], n[2], b);
+  // wk(1:3) = u,v,w ; extrapolate at wall-model faces ; strain rate (sgs.f90:84-92) -- without the copies: the ghost cells of
+  // u,v,w at the wall-model faces are replaced in place, kept in wk(1), and given back before anything else reads them
+  real *uvw[3] = {f[CALES_U], f[CALES_V], f[CALES_W]};
+  const size_t need = 6 * ((size_t)(n[1] + 2) * (n[2] + 2) + (size_t)(n[0] + 2) * (n[2] + 2) + (size_t)(n[0] + 2) * (n[1] + 2));
+  if (need <= c->ntot) {
+    if (int e = extrapolate(c, 3, uvw, if123, 0, wk[0], 0)) return e;
+    if (int e = strain_rate(c, uvw[0], uvw[1], uvw[2], c->s0, nullptr)) return e;
+    if (int e = extrapolate(c, 3, uvw, if123, 0, wk[0], 1)) return e;
+  } else {            // degenerate grids: the copies of the reference
+    LAUNCH(c, k_copy3, lin_grid(nt), dim3(256), 0, c->stream, nt, f[CALES_U], f[CALES_V], f[CALES_W], wk[0], wk[1], wk[2]);
+    if (int e = extrapolate(c, 3, wk, if123, 0)) return e;
+    if (int e = strain_rate(c, wk[0], wk[1], wk[2], c->s0, nullptr)) return e;
+  }
+  SmagArgs A; A.w0 = c->is_wall[0]; A.w1 = c->is_wall[1]; A.w2 = c->is_wall[2]; A.w3 = c->is_wall[3]; A.w4 = c->is_wall[4]; A.w5 = c->is_wall[5];
+  A.dl1 = c->dl[0]; A.dl2 = c->dl[1]; A.l3 = c->C.l[2]; A.dxi = c->dli[0]; A.dyi = c->dli[1]; A.visc = c->visc;
+  A.sumw = 0.; for (int q = 0; q < 6; ++q) A.sumw += c->is_wall[q];
+  if (int e = smag_del(c)) return e;
+  const real *twy = nullptr;      // several slabs: the shear of the y walls comes from the slabs that own them
+  if (c->P > 1 && (c->is_wall[2] != 0. || c->is_wall[3] != 0.)) { if (int e = wall_shear_y_planes(c, c->is_wall[2] != 0., c->is_wall[3] != 0., &twy)) return e; }
+  LAUNCH(c, k_smag, gr, b, 0, c->stream, c->g, A, c->d_zc, c->d_dzci, c->d_del, f[CALES_U], f[CALES_V], f[CALES_W], c->s0, f[CALES_VISCT], twy);
+  LAUNCHCHK(c);
+  return 0;
 }
-int op_cmpt_sgs(cales_ctx *c, const SgsFold *fold, bool *visct_ghosts_done) {
-  const int *n = c->n; const size_t nt = c->ntot;
-  real **f = c->f; real *visct = f[CALES_VISCT];
-  if (c->C.sgstype == 0) {           // 'none': visct = 0 once (sgs.f90:62-68)
-    if (c->sgs_first) { c->sgs_first = false; HIPCHK(c, hipMemsetAsync(visct, 0, nt * sizeof(real), c->stream)); c->visct_zero = true; }
-    return 0;
-  }
-  c->visct_lazy = false;      // the field is rewritten from scratch
-  ProfScope ps(c, c->C.sgstype == 1 ? "cmpt_sgs_smag" : "cmpt_sgs_dsmag");
-  dim3 b(BX, BY, 1), gr = grid3(n[0], n[1], n[2], b);
-  if (c->sgs_first) {
-    c->sgs_first = false;
-    if (c->C.sgstype == 2 && !c->sgs.filter2d)      // (the plane filter: 2.52 everywhere, sgs.f90:817-821 -- no field)
-      LAUNCH(c, k_alph2, grid3(n[0] + 2, n[1] + 2, n[2] + 2, dim3(64, 4, 1)), dim3(64, 4, 1), 0, c->stream, c->g, c->is_wall[0], c->is_wall[1],
-                         c->is_wall[2], c->is_wall[3], c->is_wall[4], c->is_wall[5], c->alph2);
-  }
-  if (c->sgs.form == SgsForm::dsmag_tiles) return dsmag_fast(c, fold, visct_ghosts_done);
-  if (c->sgs.form == SgsForm::smag_rows) return smag_fast(c);
-  real **wk = c->wk;
-  const int if123[3] = {1, 2, 3};
-  if (c->C.sgstype == 1) {
-    // wk(1:3) = u,v,w ; extrapolate at wall-model faces ; strain rate (sgs.f90:84-92) -- without the copies: the ghost cells of
-    // u,v,w at the wall-model faces are replaced in place, kept in wk(1), and given back before anything else reads them
-    real *uvw[3] = {f[CALES_U], f[CALES_V], f[CALES_W]};
-    const size_t need = 6 * ((size_t)(n[1] + 2) * (n[2] + 2) + (size_t)(n[0] + 2) * (n[2] + 2) + (size_t)(n[0] + 2) * (n[1] + 2));
-    if (need <= c->ntot) {
-      if (int e = extrapolate(c, 3, uvw, if123, 0, wk[0], 0)) return e;
-      if (int e = strain_rate(c, uvw[0], uvw[1], uvw[2], c->s0, nullptr)) return e;
-      if (int e = extrapolate(c, 3, uvw, if123, 0, wk[0], 1)) return e;
-    } else {            // degenerate grids: the copies of the reference
-      LAUNCH(c, k_copy3, lin_grid(nt), dim3(256), 0, c->stream, nt, f[CALES_U], f[CALES_V], f[CALES_W], wk[0], wk[1], wk[2]);
-      if (int e = extrapolate(c, 3, wk, if123, 0)) return e;
-      if (int e = strain_rate(c, wk[0], wk[1], wk[2], c->s0, nullptr)) return e;
-    }
-    SmagArgs A; A.w0 = c->is_wall[0]; A.w1 = c->is_wall[1]; A.w2 = c->is_wall[2]; A.w3 = c->is_wall[3]; A.w4 = c->is_wall[4]; A.w5 = c->is_wall[5];
-    A.dl1 = c->dl[0]; A.dl2 = c->dl[1]; A.l3 = c->C.l[2]; A.dxi = c->dli[0]; A.dyi = c->dli[1]; A.visc = c->visc;
-    A.sumw = 0.; for (int q = 0; q < 6; ++q) A.sumw += c->is_wall[q];
-    if (int e = smag_del(c)) return e;
-    const real *twy = nullptr;      // several slabs: the shear of the y walls comes from the slabs that own them
-    if (c->P > 1 && (c->is_wall[2] != 0. || c->is_wall[3] != 0.)) { if (int e = wall_shear_y_planes(c, c->is_wall[2] != 0., c->is_wall[3] != 0., &twy)) return e; }
-    LAUNCH(c, k_smag, gr, b, 0, c->stream, c->g, A, c->d_zc, c->d_dzci, c->d_del, f[CALES_U], f[CALES_V], f[CALES_W], c->s0, visct, twy);
-    LAUNCHCHK(c);
-    return 0;
-  }
-  // ---- dynamic model (sgs.f90:153-380): wk(1:3) = u,v,w ; extrapolate at wall-model faces ; strain rate (sgs.f90:173-181)
+// The reference's sequence of the dynamic model, kernel per loop (sgs.f90:153-380): wk(1:3) = u,v,w ; extrapolate at wall-model faces ; strain rate (sgs.f90:173-181) ...
+static int dsmag_sequence(cales_ctx *c) {
+  const int *n = c->n, if123[3] = {1, 2, 3}; const size_t nt = c->ntot; real **f = c->f, **wk = c->wk; real *visct = f[CALES_VISCT];
+  const dim3 b(BX, BY, 1), gr = grid3(n[0], n[1], n[2], b);
   LAUNCH(c, k_copy3, lin_grid(nt), dim3(256), 0, c->stream, nt, f[CALES_U], f[CALES_V], f[CALES_W], wk[0], wk[1], wk[2]);
   if (int e = extrapolate(c, 3, wk, if123, 0)) return e;
   real **sij = c->sij, **mij = c->mij, **lij = c->sij;
@@ -1897,20 +1879,39 @@ int op_cmpt_sgs(cales_ctx *c, const SgsFold *fold, bool *visct_ghosts_done) {
   if (c->sgs.ave == SgsAve::xlines) {      // sgs.f90:366-367: x is local to a y slab -- nothing to communicate
     LAUNCH(c, k_contract_lines, dim3((n[1] * n[2] + 3) / 4), dim3(256), 0, c->stream, c->g, cmij, clij, c->uf, c->vf, c->wf, wk[0]);
     LAUNCH(c, k_dsmag_final_lines, gr, b, 0, c->stream, c->g, c->dl[0] / c->C.l[0], wk[0], visct, visct);
-    LAUNCHCHK(c);
-    return 0;
+    LAUNCHCHK(c); return 0;
   }
   if (c->sgs.ave == SgsAve::local) {      // sgs.f90:368-377: no average, no reduction, no collective -- one kernel in place of k_contract + k_plane_sum + k_dsmag_final
     LAUNCH(c, k_contract_local, gr, b, 0, c->stream, c->g, cmij, clij, c->uf, c->vf, c->wf, visct);
-    LAUNCHCHK(c);
-    return 0;
+    LAUNCHCHK(c); return 0;
   }
   LAUNCH(c, k_contract, gr, b, 0, c->stream, c->g, cmij, clij, c->uf, c->vf, c->wf, wk[0], wk[1]);
   LAUNCH(c, k_plane_sum, dim3(n[2], 2), dim3(256), 0, c->stream, c->g, wk[0], wk[1], c->d_p1d);
-  if (c->P > 1) { if (int e = allreduce_dev(c, c->d_p1d, 2 * n[2], 0)) return e; }   // sgs.f90:475
-  if (c->sgs.ave == SgsAve::volume) LAUNCH(c, k_volume_fold, dim3(1), dim3(256), 0, c->stream, n[2], c->d_dzf, c->d_p1d);      // sgs.f90:360-361
-  const real gar = c->dl[0] * c->dl[1] / (c->C.l[0] * c->C.l[1]);
-  LAUNCH(c, k_dsmag_final, gr, b, 0, c->stream, c->g, gar, c->d_p1d, visct, visct);
-  LAUNCHCHK(c);
-  return 0;
+  return dsmag_coefficient(c, 0, visct);      // (|S| sits in visct: k_copy1 above)
+}
+
+// the form of cmpt_sgs this context takes (cales_describe_plan): the record op_cmpt_sgs launches
+const char *sgs_path_name(const cales_ctx *c) {
+  static const char *names[] = {"none", "smag_rows", "smag_reference_sequence", "dsmag_tiles", "dsmag_reference_sequence"};      // (SgsForm order)
+  if (c->sgs.filter2d) return c->sgs.form == SgsForm::dsmag_tiles ? "dsmag_tiles(filter2d)" : "dsmag_reference_sequence(filter2d)";
+  return c->sgs.pair ? "dsmag_tiles(pair_fields)" : names[(int)c->sgs.form];
+}
+// cmpt_sgs: the first call's work, then the form sgs_setup chose
+int op_cmpt_sgs(cales_ctx *c, const SgsFold *fold, bool *visct_ghosts_done) {
+  const int *n = c->n;
+  if (c->C.sgstype == 0) {           // 'none': visct = 0 once (sgs.f90:62-68)
+    if (c->sgs_first) { c->sgs_first = false; HIPCHK(c, hipMemsetAsync(c->f[CALES_VISCT], 0, c->ntot * sizeof(real), c->stream)); c->visct_zero = true; }
+    return 0;
+  }
+  c->visct_lazy = false;      // the field is rewritten from scratch
+  ProfScope ps(c, c->C.sgstype == 1 ? "cmpt_sgs_smag" : "cmpt_sgs_dsmag");
+  if (c->sgs_first) {
+    c->sgs_first = false;
+    if (c->C.sgstype == 2 && !c->sgs.filter2d)      // (the plane filter: 2.52 everywhere, sgs.f90:817-821 -- no field)
+      LAUNCH(c, k_alph2, grid3(n[0] + 2, n[1] + 2, n[2] + 2, dim3(64, 4, 1)), dim3(64, 4, 1), 0, c->stream, c->g, c->is_wall[0], c->is_wall[1],
+                         c->is_wall[2], c->is_wall[3], c->is_wall[4], c->is_wall[5], c->alph2);
+  }
+  if (c->sgs.form == SgsForm::dsmag_tiles) return dsmag_fast(c, fold, visct_ghosts_done);
+  if (c->sgs.form == SgsForm::smag_rows) return smag_fast(c);
+  return c->sgs.form == SgsForm::smag_reference ? smag_sequence(c) : dsmag_sequence(c);
 }
