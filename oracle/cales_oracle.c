@@ -48,6 +48,7 @@ struct ostate {
   int sgs_first;
   int nthreads;
   int team_sums;                    /* o_set_team_sums: sums over all cells by planes (timing runs); 0 = the reference's cell-by-cell order */
+  int dsmag_local;                  /* o_set_dsmag_local: the dynamic coefficient without averaging (sgs.f90:368-370) */
 };
 
 #define IX(i,j,k) ((size_t)(i) + s1*((size_t)(j) + s2*(size_t)(k)))
@@ -446,6 +447,7 @@ void o_destroy(ostate *s) {
 /* first touch of a haloed field by the threads that will work on its planes (timing aid of bench.py's cpu_baseline: a field allocated by the
    caller and first written by one thread lives on that thread's NUMA node; the loops below are split over (k, j) like this one). No arithmetic. */
 void o_set_team_sums(ostate *s, int on) { s->team_sums = on != 0; }
+void o_set_dsmag_local(ostate *s, int on) { s->dsmag_local = on != 0; }
 void o_first_touch(const ostate *s, double *a) {
   const int *n = s->n; const size_t s1 = s->s1, s2 = s->s2;
   #pragma omp parallel for collapse(2) schedule(static) num_threads(s->nthreads)
@@ -1301,7 +1303,7 @@ void o_cmpt_sgs(ostate *s, const double *u, const double *v, const double *w, do
     l_[0] = l_[0] - uf*uf; l_[1] = l_[1] - vf*vf; l_[2] = l_[2] - wf*wf; l_[3] = l_[3] - uf*vf; l_[4] = l_[4] - uf*wf; l_[5] = l_[5] - vf*wf;
     wk[0][c] = m_[0]*l_[0] + m_[1]*l_[1] + m_[2]*l_[2] + (m_[3]*l_[3] + m_[4]*l_[4] + m_[5]*l_[5])*2.;
     wk[1][c] = m_[0]*m_[0] + m_[1]*m_[1] + m_[2]*m_[2] + (m_[3]*m_[3] + m_[4]*m_[4] + m_[5]*m_[5])*2.; }
-  ave1d_channel_z(s, wk[0]); ave1d_channel_z(s, wk[1]);
+  if (!s->dsmag_local) { ave1d_channel_z(s, wk[0]); ave1d_channel_z(s, wk[1]); }
   #pragma omp parallel for collapse(2) schedule(static) num_threads(s->nthreads)
   for (int k = 1; k <= n[2]; k++) for (int j = 1; j <= n[1]; j++) for (int i = 1; i <= n[0]; i++) { size_t c = IX(i,j,k);
     visct[c] = visct[c]*wk[0][c]/wk[1][c]; visct[c] = fmax(visct[c], 0.); }

@@ -71,6 +71,8 @@ class Oracle:
         self.h = C.c_void_p(L.o_create(C.byref(p)))
         if team_sums:      # timing runs: sums over all cells by planes over the team instead of cell by cell on one thread (cales_oracle.h)
             L.o_set_team_sums(self.h, 1)
+        if getattr(case, "dsmag_average", None) == "local":      # Case.dsmag_average = 'local': no averaging of the Germano identity (the reference's _CAVITY)
+            L.o_set_dsmag_local(self.h, 1)
         self.n = tuple(int(x) for x in case.ng)
         self.shape = tuple(x + 2 for x in self.n)
 

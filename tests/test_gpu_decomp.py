@@ -28,14 +28,14 @@ def _case(name, ng):
     return case
 
 
-def _single(case, nsteps):
+def _single(case, nsteps, factors=None):
     from cales_amd.hotpath import HotPath, initflow
     h = HotPath(case)
     u, v, w, p = initflow(case)
     h.upload(u, v, w, p); h.startup()
     dt = 0.5 * h.chkdt()
-    for _ in range(nsteps):
-        h.step(dt)
+    for n in range(nsteps):
+        h.step(dt if factors is None else factors[n] * dt)
     out = h.download() + [dt, h.chkdiv(), h.dpdl()]
     h.close()
     return out
@@ -107,16 +107,17 @@ def test_slab_ranks_forced_in_y_and_z(name, ng, P, fset):
     _slabs_against_single_rank(case, P, 2)
 
 
-def _slabs_against_single_rank(case, P, nsteps):
+def _slabs_against_single_rank(case, P, nsteps, factors=None):
+    """`factors`: step n is made with factors[n] * dt on both sides (dpdl then is that of the LAST step, with its own dt)"""
     from cales_amd.decomp import run_loopback
-    u, v, w, p, visct, dt, div, dpdl = _single(case, nsteps)
+    u, v, w, p, visct, dt, div, dpdl = _single(case, nsteps, factors)
 
     def body(h, r):
         h.upload_initial(); h.startup()
         dtr = 0.5 * h.chkdt()
         assert abs(dtr / dt - 1) < 1e-12
-        for _ in range(nsteps):
-            h.step(dtr)
+        for n in range(nsteps):
+            h.step(dtr if factors is None else factors[n] * dtr)
         return h.download() + [h.chkdiv(), h.dpdl(), h.lo, h.n]
 
     res = run_loopback(case, P, body)
@@ -131,6 +132,25 @@ def _slabs_against_single_rank(case, P, nsteps):
     pg = np.concatenate([res[r][3][:, 1:-1, :] for r in range(P)], axis=1)
     pref = p[:, 1:-1, :]
     assert relerr(pg[1:-1, :, 1:-1] - pg[1:-1, :, 1:-1].mean(), pref[1:-1, :, 1:-1] - pref[1:-1, :, 1:-1].mean()) < 1e-9
+
+
+@pytest.mark.parametrize("name,ng,P,fset", [("chan_dsmag", (64, 32, 24), 4, None), ("chan_nosgs", (64, 24, 16), 2, None), ("chan_smag_wm", (32, 24, 16), 2, None),
+                                            ("tgv_dsmag_ppp", (64, 24, 16), 3, None), ("couette_imp3d_ops", (32, 24, 16), 2, None), ("chan_dsmag", (64, 32, 24), 4, "B")])
+def test_slab_ranks_with_a_changing_time_step(name, ng, P, fset):
+    """Five steps with four different time steps (the first five of DT_FACTORS, tests/util.py) on several slabs against the one-rank run, which
+    tests/test_gpu_variable_dt.py holds to the oracle under the same schedule: the ghost rows the folded projection scales with dtrk itself (fold_rows2, the
+    companion-field form), the momentum pass that applies the projection of the substep before on every slab, the deferred forcing with and without a wall
+    model, the Helmholtz solves of 3-D implicit diffusion with a new alpha every step, and dpdl of the last step on every rank. The bars of
+    _slabs_against_single_rank, unchanged."""
+    from tests.util import DT_FACTORS, forced_case
+    if fset is not None:
+        case = forced_case(name, ng, fset)
+    elif name == "chan_nosgs":
+        from tests.test_gpu_golden import _nosgs_case
+        case = _nosgs_case(name, ng)
+    else:
+        case = _case(name, ng)
+    _slabs_against_single_rank(case, P, 5, DT_FACTORS[:5])
 
 
 @pytest.mark.parametrize("lazy", [False, True], ids=["eager", "lazy-ignored"])

@@ -5,7 +5,7 @@ import numpy as np
 import pytest
 
 from oracle.oracle import Oracle
-from tests.util import OPEN_SETS, F, load_golden, relerr
+from tests.util import DT_FACTORS, OPEN_SETS, F, load_golden, relerr
 from tests.util import open_case as _open_case      # (tests/test_helmholtz_reference.py runs the same cases on the CPU)
 
 pytestmark = pytest.mark.gpu
@@ -121,8 +121,9 @@ def test_nyquist_packing_agrees(name, ng, monkeypatch):
                                             ("duct_smag", (64, 16, 20), 3), ("duct_smag", (128, 12, 16), 2), ("duct_smag", (24, 18, 12), 3),
                                             # BASELINE configs[0] at its own size in FP64
                                             ("tgv_ppp", (64, 64, 64), 3)])
-def test_time_steps(name, ng, nsteps):
-    """u,v,w <= 1e-9, p (mean removed) <= 1e-8 after the steps; divmax same order of magnitude"""
+def test_time_steps(name, ng, nsteps, factors=None):
+    """u,v,w <= 1e-9, p (mean removed) <= 1e-8 after the steps; divmax same order of magnitude. `factors` (not parametrized: for callers
+    such as tests/test_gpu_variable_dt.py): step n is made with factors[n] * dt instead of dt"""
     from cales_amd.hotpath import initflow
     g, case = load_golden(name)
     case.ng[:] = ng
@@ -136,8 +137,9 @@ def test_time_steps(name, ng, nsteps):
     o.bounduvw(u, v, w, True, False); o.boundp(p, 0); o.cmpt_sgs(u, v, w, visct); o.boundp(visct, 1)
     dt = 0.5 * o.chkdt(visct, u, v, w)
     assert abs(h.chkdt() / (2 * dt) - 1) < 1e-12
-    for _ in range(nsteps):
-        h.step(dt); o.step(dt, u, v, w, p, pp, visct)
+    for n in range(nsteps):
+        dtn = dt if factors is None else factors[n] * dt
+        h.step(dtn); o.step(dtn, u, v, w, p, pp, visct)
     gu, gv, gw, gp, gvis = h.download()
     for a, b, nm in ((gu, u, "u"), (gv, v, "v"), (gw, w, "w")):
         assert relerr(a, b) < 1e-9, nm
@@ -175,7 +177,7 @@ def test_z_implicit_steps_with_a_changing_time_step(name, ng):
     visct, pp = o.zeros(), o.zeros()
     o.bounduvw(u, v, w, True, False); o.boundp(p, 0); o.cmpt_sgs(u, v, w, visct); o.boundp(visct, 1)
     dt = 0.5 * o.chkdt(visct, u, v, w)
-    for fac in (1., 0.7, 1., 0.5, 0.9, 0.7, 0.6):
+    for fac in DT_FACTORS:
         h.step(fac * dt); o.step(fac * dt, u, v, w, p, pp, visct)
     gu, gv, gw, gp, gvis = h.download()
     for a, b, nm in ((gu, u, "u"), (gv, v, "v"), (gw, w, "w")):

@@ -387,12 +387,16 @@ def perturbed_start(case, o, seed=1):
     return (u, v, w, p, visct, pp, dt), raw
 
 
-def oracle_forcing_of_substeps(o, case, dt, u, v, w, p, pp, visct):
-    """One step of the oracle operator by operator (the sequence of o_step, main.f90:417-508), on the caller's arrays; returns the forcing f of every substep"""
+def oracle_forcing_of_substeps(o, case, dt, u, v, w, p, pp, visct, stale=None, dt_stale=None):
+    """One step of the oracle operator by operator (the sequence of o_step, main.f90:417-508), on the caller's arrays; returns the forcing f of every substep.
+    `stale` names ONE factor that is taken from the time step `dt_stale` instead (STALE_FACTORS: the mistakes a step that carries dt-dependent state over
+    a step boundary can make; tests/test_variable_dt_oracle.py measures what each costs)."""
+    assert stale is None or (stale in STALE_FACTORS and dt_stale is not None)
     fs = []
     for irk in (1, 2, 3):
         dtrk = (RK[irk - 1][0] + RK[irk - 1][1]) * dt; alpha = 0.
-        f = o.rk(irk, dt, p, visct, u, v, w); fs.append(f.copy())
+        dtrk_stale = (RK[irk - 1][0] + RK[irk - 1][1]) * dt_stale if stale else None
+        f = o.rk(irk, dt_stale if (stale == "dt_of_rk_1" and irk == 1) else dt, p, visct, u, v, w); fs.append(f.copy())
         o.bulk_forcing(f, u, v, w)
         if case.impdiff:
             alpha = -.5 * case.visc * dtrk
@@ -402,8 +406,118 @@ def oracle_forcing_of_substeps(o, case, dt, u, v, w, p, pp, visct):
                 else:
                     o.updt_rhs_b_vel(iv, alpha, q); o.solver_helmholtz(iv, alpha, q)
         o.bounduvw(u, v, w, True, False)
-        o.fillps(1. / dtrk, u, v, w, pp); o.updt_rhs_b_p(pp); o.solver(pp); o.boundp(pp, 0)
-        o.correc(dtrk, pp, u, v, w); o.bounduvw(u, v, w, True, True)
+        o.fillps(1. / (dtrk_stale if (stale == "dtrki_of_fillps_1" and irk == 1) else dtrk), u, v, w, pp); o.updt_rhs_b_p(pp); o.solver(pp); o.boundp(pp, 0)
+        o.correc(dtrk_stale if (stale == "dtrk_of_correc_3" and irk == 3) else dtrk, pp, u, v, w); o.bounduvw(u, v, w, True, True)
         o.updatep(alpha, pp, p); o.boundp(p, 0)
         o.cmpt_sgs(u, v, w, visct); o.boundp(visct, 1)
     return fs
+
+
+# ------------------------------------------------------------------ whole steps under a time step that changes at every step (main.f90:395-416: dt = min(cfl dtmax, dt_f) anew per icheck block)
+# the factors on dt0 = half the bound of chkdt at the start: five different steps in seven, none above dt0
+DT_FACTORS = (1., 0.7, 1., 0.5, 0.9, 0.7, 0.6)
+STALE_FACTORS = ("dtrk_of_correc_3", "dt_of_rk_1", "dtrki_of_fillps_1")
+
+_LAZY = {"CALES_LAZY_PROJECTION": "1"}
+_MOM12, _MOM123, _STRAIN = "in_next_momentum_pass(substeps_1_2)", "in_next_momentum_pass(all_substeps)", "in_strain_rate_pass"
+_OWN = "own_pass(correc+updatep)"
+# case, grid, forcing set of FORCING_SETS (None: the case's own), edits of the Case, what cales_describe_plan must say (the path the row is there for; "*": any
+# value that starts so), switches, the values of `reads` (both wherever the projection of a substep is applied by a later pass)
+VARIABLE_DT_ROWS = [
+    ("chan_nosgs_x64", (64, 24, 16), "B", {}, {"projection": _MOM12}, {}, (False, True)),
+    ("chan_nosgs_x64", (64, 24, 16), "B", {}, {"projection": _MOM123}, _LAZY, (False, True)),
+    ("chan_nosgs_x64", (64, 24, 16), "A", {}, {"projection": _MOM123}, _LAZY, (False, True)),      # the body force
+    ("tgv_ppp", (32, 24, 16), "D", {}, {"projection": _MOM12}, {}, (False, True)),
+    ("tgv_ppp", (32, 24, 16), "D", {}, {"projection": _MOM123}, _LAZY, (False, True)),
+    ("tgv_ppp", (64, 16, 16), "D", {}, {"projection": _MOM12}, {}, (False, True)),
+    ("tgv_ppp", (64, 16, 16), "D", {}, {"projection": _MOM123}, _LAZY, (False, True)),
+    ("cavity_nnn", (16, 16, 16), None, {}, {"projection": _MOM12, "x_ghost_columns": "maintained"}, {}, (False, True)),      # walls in x
+    ("cavity_nnn", (16, 16, 16), None, {}, {"projection": _MOM123, "x_ghost_columns": "maintained"}, _LAZY, (False, True)),
+    # the projection inside the strain-rate pass: five |S|Sij fields (the default), six, two x tiles, periodic z, the local coefficient
+    ("chan_dsmag", (64, 20, 12), "B", {}, {"projection": _STRAIN, "sgs": "dsmag_tiles(pair_fields)"}, {}, (False, True)),
+    ("chan_dsmag", (64, 20, 12), "B", {}, {"projection": _STRAIN, "sgs": "dsmag_tiles(pair_fields)"}, {"CALES_SGS_SIX_COMPONENTS": "1"}, (False, True)),
+    ("chan_dsmag", (128, 12, 20), "B", {}, {"projection": _STRAIN, "sgs": "dsmag_tiles(pair_fields)"}, {}, (False, True)),
+    ("tgv_dsmag_ppp", (64, 16, 24), "D", {}, {"projection": _STRAIN}, {}, (False, True)),
+    ("chan_dsmag", (64, 20, 12), "B", {"dsmag_average": "local"}, {"projection": _STRAIN, "sgs_average": "local"}, {}, (False, True)),
+    # tiles without the fold
+    ("chan_dsmag", (32, 16, 16), "B", {}, {"projection": _OWN, "sgs": "dsmag_tiles*"}, {}, (True,)),
+    ("chan_dsmag", (80, 20, 12), "B", {}, {"projection": _OWN, "sgs": "dsmag_tiles*"}, {}, (True,)),
+    # fillps as a pass of its own / inside the x transform
+    ("chan_smag", (24, 20, 12), "B", {}, {"fillps": "own_pass", "projection": _OWN}, {}, (True,)),
+    ("chan_smag", (64, 18, 12), "B", {}, {"fillps": "in_x_transform", "projection": _OWN}, {}, (True,)),
+    ("chan_smag_wm", (32, 16, 16), "B", {}, {"first_wall_model_update": "skipped", "bulk_forcing": "in_correction(means_in_x_transform)"}, {}, (True,)),
+    # further classes (wall model with the dynamic model, ducts, a cavity with the model, inflow / outflow): the plan as it stands
+    ("chan_dsmag_wm", (64, 16, 12), "B", {}, {"projection": _OWN, "x_ghost_columns": "maintained", "first_wall_model_update": "skipped", "bulk_forcing": "in_correction(means_in_x_transform)",
+                                              "sgs": "dsmag_tiles(pair_fields)"}, {}, (True,)),
+    ("duct_dsmag", (64, 18, 20), None, {}, {"projection": _OWN, "x_ghost_columns": "wrapped", "bulk_forcing": "in_correction(means_in_x_transform)", "sgs": "dsmag_tiles"}, {}, (True,)),
+    ("duct_smag_wm", (16, 24, 24), None, {}, {"projection": _OWN, "fillps": "own_pass", "first_wall_model_update": "skipped", "bulk_forcing": "in_correction(means_own_pass)", "sgs": "smag_rows"}, {}, (True,)),
+    ("cavity_dsmag", (16, 16, 12), None, {}, {"projection": _OWN, "fillps": "own_pass", "bulk_forcing": "none", "sgs": "dsmag_reference_sequence"}, {}, (True,)),
+    ("devchan_nd", (32, 16, 16), None, {}, {"projection": _OWN, "x_ghost_columns": "maintained", "fillps": "own_pass", "bulk_forcing": "none", "sgs": "none"}, {}, (True,)),
+    ("couette_imp3d_ops", (16, 16, 16), None, {}, {"projection": "own_passes", "helmholtz_u": "*", "helmholtz_v": "*", "helmholtz_w": "*"}, {}, (True,)),      # 3-D implicit diffusion: a new alpha every step
+] + [
+    # the forms behind the switches, one at a time
+    (name, ng, "B", {}, expect, {env: "1"}, (False, True))
+    for name, ng in (("chan_smag", (64, 18, 12)), ("chan_dsmag", (64, 20, 12)))
+    for env, expect in (("CALES_UNFUSED_CORREC", {"projection": "own_passes", "bulk_forcing": "own_pass"}), ("CALES_UNFOLDED_CORREC", {"projection": _OWN}),
+                        ("CALES_UNFOLDED_MOM", {"projection": _OWN if name == "chan_smag" else _STRAIN}), ("CALES_UNFUSED_FORCING", {"bulk_forcing": "own_pass"}),
+                        ("CALES_XGHOSTS_IN_STEP", {"x_ghost_columns": "maintained"}), ("CALES_EAGER_PROJECTION", {"projection": _OWN if name == "chan_smag" else _STRAIN}))]
+VARIABLE_DT_PARAMS = [(name, ng, fset, edits, expect, env, r) for name, ng, fset, edits, expect, env, reads in VARIABLE_DT_ROWS for r in reads]
+VARIABLE_DT_IDS = ["-".join([name, forcing_id(ng), str(fset)] + list(edits.values()) + [k[6:] for k in env] + ["reads" if r else "no_reads"])
+                   for name, ng, fset, edits, expect, env, r in VARIABLE_DT_PARAMS]
+# the grids of the switch combinations (tests/test_gpu_variable_dt.py, through test_time_steps: the case's own forcing)
+VARIABLE_DT_COMBINATION_GRIDS = [("chan_dsmag", (32, 16, 16)), ("chan_smag_wm", (32, 16, 12)), ("chan_smag", (64, 12, 10))]
+
+
+def variable_dt_case(name, ng, fset, edits):
+    if fset is not None:
+        case = forced_case(name, ng, fset)
+    else:
+        g, case = load_golden(name); case.ng[:] = ng
+    for k, v in edits.items():
+        setattr(case, k, v)
+    return case
+
+
+def last_forcing(h):
+    """f(1:3) of the last substep on the device (cales_get_forcing)"""
+    import ctypes as C
+    f = np.zeros(3)
+    h._chk(h.L.cales_get_forcing(h.h, f.ctypes.data_as(C.c_void_p)))
+    return f
+
+
+def steps_under_schedule(case, o, h, reads, factors=DT_FACTORS, hook=None, tag=""):
+    """Oracle `o` and device `h` together through the steps dt_n = factors[n] * dt0 from perturbed_start, dt0 from the ORACLE (the device's chkdt is a
+    quantity under test). Between two steps: nothing (`reads` False: whatever the step left to its successor crosses the boundary to a step with another
+    dt) or the block of the production loop (main.f90:395-416 with the outputs of its 0-D file): chkdt, chkdiv, dpdl and the forcing of the last substep,
+    each held to the oracle's value for THAT step -- chkdt 1e-7 relative (the loosest bar among its inputs, visct), divmax < 20 x oracle + 1e-14, dpdl and
+    the forcing 1e-9 max(1, |.|). After the last step the block runs either way. `hook(n, 'started' | 'stepped' | 'read')` is called after the start-up (n = -1: the plan of the steps
+    is known from here on), after step n and after its block.
+    The oracle steps operator by operator (oracle_forcing_of_substeps; tests/test_variable_dt_oracle.py: bit for bit o.step, whose dpdl is -sum(f) / dt_n).
+    Returns the oracle's (u, v, w, p, visct), dt0 and the largest measured error of every read, each in units of its bar's scale."""
+    (u, v, w, p, visct, pp, dt0), raw = perturbed_start(case, o)
+    h.upload(*raw); h.startup()
+    if hook: hook(-1, "started")
+    worst = {"chkdt": abs(h.chkdt() / (2. * dt0) - 1.), "dpdl": 0., "forcing": 0., "div": None}
+    assert worst["chkdt"] < 1e-7, (tag, "chkdt at the start", worst["chkdt"])
+    for n, fac in enumerate(factors):
+        dtn = fac * dt0
+        h.step(dtn)
+        fs = oracle_forcing_of_substeps(o, case, dtn, u, v, w, p, pp, visct)
+        if hook: hook(n, "stepped")
+        if not (reads or n == len(factors) - 1):
+            continue
+        e = abs(h.chkdt() / o.chkdt(visct, u, v, w) - 1.)
+        dg, do = h.chkdiv()[1], o.chkdiv(u, v, w)[1]
+        dpdl = -sum(fs) / dtn
+        hd, hf = h.dpdl(), last_forcing(h)
+        ed = np.abs(hd - dpdl).max() / max(1., np.abs(dpdl).max()); ef = np.abs(hf - fs[2]).max() / max(1., np.abs(fs[2]).max())
+        print(tag, "step", n, "dt/dt0", fac, "chkdt", e, "divmax", dg, do, "dpdl", hd, dpdl, ed, "f", hf, fs[2], ef)
+        assert e < 1e-7, (tag, n, "chkdt", e)
+        assert dg < 20. * do + 1e-14, (tag, n, "divmax", dg, do)
+        assert ed < 1e-9, (tag, n, "dpdl", hd, dpdl)
+        assert ef < 1e-9, (tag, n, "forcing", hf, fs[2])
+        worst["chkdt"] = max(worst["chkdt"], e); worst["dpdl"] = max(worst["dpdl"], ed); worst["forcing"] = max(worst["forcing"], ef)
+        if worst["div"] is None or dg / (20. * do + 1e-14) > worst["div"][0] / (20. * worst["div"][1] + 1e-14): worst["div"] = (dg, do)
+        if hook: hook(n, "read")
+    return (u, v, w, p, visct), dt0, worst
