@@ -1,4 +1,4 @@
-"""ctypes binding of libcales_hip.so (C-ABI declared in include/cales.h, include/cales_post.h and include/cales_pdf.h).
+"""ctypes binding of libcales_hip.so (C-ABI declared in include/cales.h, include/cales_post.h, include/cales_pdf.h and include/cales_spectra.h).
 
 There is no CPU fallback: if the HIP library has not been built, importing the symbols raises.
 """
@@ -60,6 +60,11 @@ POST_SYMBOLS = ["cales_box_share", "cales_read_box", "cales_out2d", "cales_out3d
 # its own beside a header of its own (tests/test_pdf_host.py checks it against that header)
 PDF_SYMBOLS = ["cales_pdf_planes", "cales_jpdf_planes"]
 PDF_MAX_BINS, JPDF_MAX_BINS = 4096, 128      # CALES_PDF_MAX_BINS, CALES_JPDF_MAX_BINS
+
+# every symbol include/cales_spectra.h declares: power spectra of a field along x, along y and in x-y planes, transformed on the device; once more a
+# list of its own beside a header of its own (tests/test_spectra_host.py checks it against that header)
+SPECTRA_SYMBOLS = ["cales_spectra_lines", "cales_spectra_planes"]
+SPECTRA_MAX_LINE = 2048      # CALES_SPECTRA_MAX_LINE
 
 
 class CalesCase(C.Structure):
@@ -177,6 +182,13 @@ def lib() -> C.CDLL:
         for name, args in {      # include/cales_pdf.h (PDF_SYMBOLS)
             "cales_pdf_planes": [C.c_void_p, C.c_int, C.c_int, c_real, c_real, dp, dp],
             "cales_jpdf_planes": [C.c_void_p, C.c_int, C.c_int, C.c_int, c_real, c_real, c_real, c_real, C.c_int, dp, dp, dp],
+        }.items():
+            fn = getattr(L, name)
+            fn.argtypes = args
+            fn.restype = C.c_int
+        for name, args in {      # include/cales_spectra.h (SPECTRA_SYMBOLS)
+            "cales_spectra_lines": [C.c_void_p, C.c_int, C.c_int, dp, dp],
+            "cales_spectra_planes": [C.c_void_p, C.c_int, C.c_int, dp, dp],
         }.items():
             fn = getattr(L, name)
             fn.argtypes = args

@@ -4,6 +4,7 @@
 #include "common.hpp"
 #include "../../include/cales_post.h"
 #include "../../include/cales_pdf.h"
+#include "../../include/cales_spectra.h"
 #include <algorithm>
 #include <atomic>
 
@@ -492,6 +493,15 @@ int cales_jpdf_planes(cales_ctx *c, int field_a, int field_b, int nbins, real lo
                       int64_t *counts, int64_t *outside) {
   if (!c) return 1;
   ENTRY(c, op_jpdf_planes(c, field_a, field_b, nbins, lo_a, hi_a, lo_b, hi_b, nplanes, kplanes, counts, outside));
+}
+// include/cales_spectra.h (k_spectra.hip)
+int cales_spectra_lines(cales_ctx *c, int field, int idir, real *power, real *lsum) {
+  if (!c) return 1;
+  ENTRY(c, op_spectra_lines(c, field, idir, power, lsum));
+}
+int cales_spectra_planes(cales_ctx *c, int field, int nplanes, const int32_t *kplanes, real *power2) {
+  if (!c) return 1;
+  ENTRY(c, op_spectra_planes(c, field, nplanes, kplanes, power2));
 }
 
 // ------------------------------------------------------------------------------------------ time step (main.f90:412-508)

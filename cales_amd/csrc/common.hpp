@@ -504,6 +504,9 @@ int op_out2d_duct(cales_ctx *c, real *buf);
 int op_pdf_planes(cales_ctx *c, int field, int nbins, real lo, real hi, int64_t *counts, int64_t *outside);
 int op_jpdf_planes(cales_ctx *c, int field_a, int field_b, int nbins, real lo_a, real hi_a, real lo_b, real hi_b, int nplanes, const int32_t *kplanes,
                    int64_t *counts, int64_t *outside);
+// include/cales_spectra.h (k_spectra.hip): power spectra of a field along x or y on every plane, and in chosen x-y planes; synchronous
+int op_spectra_lines(cales_ctx *c, int field, int idir, real *power, real *lsum);
+int op_spectra_planes(cales_ctx *c, int field, int nplanes, const int32_t *kplanes, real *power2);
 bool solver_can_fuse_fillps(cales_ctx *c);
 int solver_mode_columns(cales_ctx *c);      // complex mode columns per rank of the pressure solve
 std::string solver_path_name(cales_ctx *c);      // which transform / tridiagonal kernels the pressure solve of this context takes (cales_describe_plan)

@@ -1,0 +1,389 @@
+// Power spectra of a field along x, along y and in x-y planes (include/cales_spectra.h): the kernels and their host side. A translation unit of its own
+// with a line transform of its own -- the transforms of the pressure solve (k_solver.hip) are neither called nor touched.
+//
+// The line lives in LDS: up to `nl` complex lines of N points in buffer A, a second buffer B of the same size, and a complex Stockham transform that
+// goes back and forth between the two, one stage per factor 4, 2, 3 or 5 of N (spec_stage). Twiddles exp(-2 pi I t / N), t = 0 ... N-1, come from a
+// table in global memory that a small kernel fills once per call (evaluated in double, rounded once). A line whose length has another prime factor
+// takes the plain sum over its points (spec_direct): correct, O(N^2), the profile scope then carries the suffix _direct. Two REAL lines ride in one
+// complex transform as real and imaginary part and are told apart by the Hermitian symmetry (spec_pair); an odd last line rides alone.
+//
+// LDS per block = 2 buffers x nl lines x N x sizeof(real2), nl = 8 halved until that fits 64 KB, but not below 2 (spec_nl):
+//   double: N <= 256: nl = 8, at most 64 KB | N <= 512: nl = 4, 64 KB | N <= 1024: nl = 2, 64 KB | N <= 2048 (the cap): nl = 2, 128 KB
+//   float:  N <= 512: nl = 8, at most 64 KB | N <= 1024: nl = 4, 64 KB | N <= 2048: nl = 2, 64 KB
+//   the smallest lines (N = 1, 2): nl = 8, 256 B / 512 B.
+// Sums over lines are formed in a fixed order and without atomics: a thread owns its modes, adds the lines of its block in line order and writes ONE
+// partial per block; k_spec_fold adds the blocks of a plane in block order. The same bits from run to run.
+#include "common.hpp"
+#include "../../include/cales_spectra.h"
+#include <algorithm>
+
+#ifdef CALES_SINGLE
+typedef float4 realv;      // 16 bytes per lane
+#else
+typedef double2 realv;
+#endif
+constexpr int SPEC_VEC = 16 / RSZ;
+constexpr int SPEC_MAX_STAGES = 12;                                     // 2048 = 4^5 2: 6 stages; 2 3^6 = 1458: 7
+constexpr int SPEC_MPT = (CALES_SPECTRA_MAX_LINE / 2 + 1 + 255) / 256;  // modes a thread of a block of 256 owns at the cap: 5
+constexpr size_t SPEC_LDS_SOFT = 64 * 1024, SPEC_LDS_MAX = 128 * 1024;
+
+// n = radix(0) ... radix(nst-1), or direct. The radices are packed four bits each: a kernel argument indexed by the stage would be copied to scratch
+struct SpecPlan {
+  int n, nst, direct; unsigned long long radices;
+  __host__ __device__ inline int radix(int st) const { return (int)((radices >> (4 * st)) & 15ull); }
+};
+// rows: rows of a plane per block (x) | chunks: 16-byte chunks per row (x) or per tile row (y) | nl: complex lines in LDS | nh: n/2+1 | nb: blocks per plane
+struct SpecGeom { int rows, chunks, nl, nh, nb; };
+
+__host__ __device__ inline real2 cadd(real2 a, real2 b) { return make_real2(a.x + b.x, a.y + b.y); }
+__host__ __device__ inline real2 csub(real2 a, real2 b) { return make_real2(a.x - b.x, a.y - b.y); }
+__host__ __device__ inline real2 cmul(real2 a, real2 b) { return make_real2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x); }
+__host__ __device__ inline real cabs2(real2 a) { return a.x * a.x + a.y * a.y; }
+
+// One butterfly of a Stockham stage of radix R on one line: x -> y, N points, s = the product of the radices of the stages before, M = N / R butterflies
+// numbered item = q + s p (q < s, p < N / (R s)). With n' = N / s the length of the sub-transforms of this stage:
+//   y[q + s (R p + u)] = w^(p u) sum_t x[q + s (p + t n'/R)] W_R^(t u),   w = exp(-2 pi I / n') = tw[s],   u = 0 ... R-1
+// and s (p + t n'/R) + q = item + t M. The last stage leaves the transform in natural order.
+template <int R>
+__host__ __device__ inline void spec_bfly(const real2 *__restrict__ x, real2 *__restrict__ y, const real2 *__restrict__ tw, int N, int s, int item) {
+  const int M = N / R, p = item / s, q = item - p * s;
+  real2 a[R], b[R];
+#pragma unroll
+  for (int t = 0; t < R; ++t) a[t] = x[item + t * M];
+  if constexpr (R == 2) { b[0] = cadd(a[0], a[1]); b[1] = csub(a[0], a[1]); }
+  else if constexpr (R == 4) {
+    const real2 e0 = cadd(a[0], a[2]), e1 = csub(a[0], a[2]), o0 = cadd(a[1], a[3]), o1 = csub(a[1], a[3]);
+    b[0] = cadd(e0, o0); b[2] = csub(e0, o0);
+    b[1] = make_real2(e1.x + o1.y, e1.y - o1.x);      // e1 - I o1
+    b[3] = make_real2(e1.x - o1.y, e1.y + o1.x);      // e1 + I o1
+  } else if constexpr (R == 3) {      // W_3 = -1/2 - I sin(2 pi / 3)
+    const real s3 = (real)0.86602540378443864676;
+    const real2 t1 = cadd(a[1], a[2]), t3 = csub(a[1], a[2]);
+    const real2 m = make_real2(a[0].x - (real)0.5 * t1.x, a[0].y - (real)0.5 * t1.y), n = make_real2(s3 * t3.x, s3 * t3.y);
+    b[0] = cadd(a[0], t1);
+    b[1] = make_real2(m.x + n.y, m.y - n.x);      // m - I n
+    b[2] = make_real2(m.x - n.y, m.y + n.x);      // m + I n
+  } else {                  // R == 5: W_5^t = c_t - I s_t, c = cos, s = sin of 2 pi / 5 and 4 pi / 5
+    const real c1 = (real)0.30901699437494742410, c2 = (real)-0.80901699437494742410, s1 = (real)0.95105651629515357212, s2 = (real)0.58778525229247312917;
+    const real2 t1 = cadd(a[1], a[4]), t2 = cadd(a[2], a[3]), t3 = csub(a[1], a[4]), t4 = csub(a[2], a[3]);
+    const real2 m1 = make_real2(a[0].x + c1 * t1.x + c2 * t2.x, a[0].y + c1 * t1.y + c2 * t2.y), m2 = make_real2(a[0].x + c2 * t1.x + c1 * t2.x, a[0].y + c2 * t1.y + c1 * t2.y);
+    const real2 n1 = make_real2(s1 * t3.x + s2 * t4.x, s1 * t3.y + s2 * t4.y), n2 = make_real2(s2 * t3.x - s1 * t4.x, s2 * t3.y - s1 * t4.y);
+    b[0] = cadd(a[0], cadd(t1, t2));
+    b[1] = make_real2(m1.x + n1.y, m1.y - n1.x); b[4] = make_real2(m1.x - n1.y, m1.y + n1.x);      // m1 -/+ I n1
+    b[2] = make_real2(m2.x + n2.y, m2.y - n2.x); b[3] = make_real2(m2.x - n2.y, m2.y + n2.x);      // m2 -/+ I n2
+  }
+  real2 *out = y + q + s * R * p;
+  out[0] = b[0];
+#pragma unroll
+  for (int u = 1; u < R; ++u) out[s * u] = cmul(b[u], tw[p * u * s]);      // p u s < N
+}
+// stage `st` of the plan on `nl` lines of N points, x -> y: the work of thread tid of nthr
+__host__ __device__ inline void spec_stage(const SpecPlan &pl, int st, int s, const real2 *__restrict__ tw, int nl, const real2 *__restrict__ x, real2 *__restrict__ y, int tid, int nthr) {
+  const int N = pl.n, r = pl.radix(st), M = N / r;
+  for (int w = tid; w < nl * M; w += nthr) {
+    const int line = w / M, item = w - line * M;
+    const real2 *xi = x + line * N; real2 *yo = y + line * N;
+    if (r == 4) spec_bfly<4>(xi, yo, tw, N, s, item);
+    else if (r == 2) spec_bfly<2>(xi, yo, tw, N, s, item);
+    else if (r == 3) spec_bfly<3>(xi, yo, tw, N, s, item);
+    else spec_bfly<5>(xi, yo, tw, N, s, item);
+  }
+}
+// the plain sum, one output point per item: y[m] = sum_i x[i] tw[i m mod N], added in the order of i. The sum is compensated (Kahan): the rounding error
+// of a plain running sum grows with N -- on a constant line of 2046 points it was measured at 200 eps |F|, past what a staged transform of that
+// length is held to (16 log2 N eps) -- and the compensated one does not
+__host__ __device__ inline void spec_direct(int N, const real2 *__restrict__ tw, int nl, const real2 *__restrict__ x, real2 *__restrict__ y, int tid, int nthr) {
+  for (int w = tid; w < nl * N; w += nthr) {
+    const int line = w / N, m = w - line * N;
+    const real2 *xi = x + line * N;
+    real2 acc = make_real2((real)0., (real)0.), lost = acc;
+    for (int i = 0, e = 0; i < N; ++i) {
+      const real2 term = csub(cmul(xi[i], tw[e]), lost), t = cadd(acc, term);
+      lost = csub(csub(t, acc), term); acc = t;
+      e += m; if (e >= N) e -= N;
+    }
+    y[w] = acc;
+  }
+}
+// Z = DFT(a + I b) of two real lines a, b: F_a(m) and F_b(m), m = 0 ... N/2, from Z(m) and Z(N - m)
+__host__ __device__ inline void spec_pair(const real2 *__restrict__ Z, int N, int m, real2 *fa, real2 *fb) {
+  const real2 zm = Z[m], zn = Z[m ? N - m : 0];
+  *fa = make_real2((real)0.5 * (zm.x + zn.x), (real)0.5 * (zm.y - zn.y));
+  *fb = make_real2((real)0.5 * (zm.y + zn.y), (real)0.5 * (zn.x - zm.x));
+}
+// The block transforms the `nl` lines it has put into A (every thread past the barrier that ends the loading); returns the buffer that holds the
+// result, behind a barrier
+__device__ inline real2 *spec_transform(const SpecPlan &pl, const real2 *__restrict__ tw, int nl, real2 *A, real2 *B) {
+  if (pl.direct) { spec_direct(pl.n, tw, nl, A, B, threadIdx.x, 256); __syncthreads(); return B; }
+  int s = 1;
+  for (int st = 0; st < pl.nst; ++st) {
+    spec_stage(pl, st, s, tw, nl, A, B, threadIdx.x, 256);
+    __syncthreads();
+    real2 *t = A; A = B; B = t;
+    s *= pl.radix(st);
+  }
+  return A;
+}
+
+__global__ __launch_bounds__(256) void k_spec_twiddle(int N, real2 *__restrict__ tw) {
+  const int t = blockIdx.x * 256 + threadIdx.x;
+  if (t >= N) return;
+  const double a = 2. * (double)t / (double)N;
+  tw[t] = make_real2((real)cospi(a), (real)(-sinpi(a)));
+}
+
+// a thread's sums over the lines of its block: the modes m = threadIdx.x + 256 u
+struct SpecAcc {
+  real pw[SPEC_MPT], sr[SPEC_MPT], si[SPEC_MPT];
+  __device__ inline void clear() {
+#pragma unroll
+    for (int u = 0; u < SPEC_MPT; ++u) pw[u] = sr[u] = si[u] = (real)0.;
+  }
+  // the real lines 2c and 2c+1 of the transformed complex lines c = 0 ... (nreal+1)/2 - 1, in that order
+  __device__ inline void add(const real2 *__restrict__ Z, int N, int nh, int nreal) {
+#pragma unroll
+    for (int u = 0; u < SPEC_MPT; ++u) {
+      const int m = threadIdx.x + 256 * u;
+      if (m >= nh) continue;
+      for (int c = 0; 2 * c < nreal; ++c) {
+        real2 fa, fb; spec_pair(Z + c * N, N, m, &fa, &fb);
+        pw[u] += cabs2(fa); sr[u] += fa.x; si[u] += fa.y;
+        if (2 * c + 1 < nreal) { pw[u] += cabs2(fb); sr[u] += fb.x; si[u] += fb.y; }
+      }
+    }
+  }
+  // one partial per block: power(nh) | real part (nh) | imaginary part (nh)
+  __device__ inline void store(real *__restrict__ dst, int nh) const {
+#pragma unroll
+    for (int u = 0; u < SPEC_MPT; ++u) {
+      const int m = threadIdx.x + 256 * u;
+      if (m < nh) { dst[m] = pw[u]; dst[nh + m] = sr[u]; dst[2 * nh + m] = si[u]; }
+    }
+  }
+};
+
+// x lines. blockIdx.y: the plane (k = blockIdx.y + 1, or the entry of kplanes), blockIdx.x: a run of sg.rows consecutive rows of it (the last run may be
+// shorter), taken 2 nl rows at a time: rows r and r+1 of a batch are real and imaginary part of complex line r/2. A row is read in 16-byte chunks from
+// element 1, which sits on a 128-B boundary in every row (Geom); the last chunk of a row may reach past n1 into the pitch padding or the next row's first
+// element -- inside the field's allocation, and masked out (k_pdf.hip reads the same way).
+// PLANES = false: |F|^2 and F summed over the rows of the block in row order, one partial per block (SpecAcc::store) at part[(blockIdx.y nb + blockIdx.x) 3 nh]
+// PLANES = true:  the rows' transforms F(0 ... n1/2) go to rows_out[(blockIdx.y n2 + j - 1) nh + m]
+template <bool PLANES>
+__global__ __launch_bounds__(256) void k_spec_x(Geom g, SpecGeom sg, SpecPlan pl, const real2 *__restrict__ tw, const int32_t *__restrict__ kplanes,
+                                                const real *__restrict__ f, real *__restrict__ part, real2 *__restrict__ rows_out) {
+  extern __shared__ real2 spec_lds[];      // 2 nl N
+  const int N = pl.n, nh = sg.nh;
+  real2 *A = spec_lds, *B = spec_lds + sg.nl * N;
+  const int k = kplanes ? kplanes[blockIdx.y] : (int)blockIdx.y + 1, j0 = blockIdx.x * sg.rows + 1, nrows = min(sg.rows, g.n2 - j0 + 1);
+  SpecAcc acc; acc.clear();
+  for (int r0 = 0; r0 < nrows; r0 += 2 * sg.nl) {
+    const int nr = min(2 * sg.nl, nrows - r0), nc = (nr + 1) / 2;
+    for (int q = threadIdx.x; q < nr * sg.chunks; q += 256) {
+      const int r = q / sg.chunks, i = 1 + SPEC_VEC * (q - r * sg.chunks);
+      const realv v = *(const realv *)(f + g.ix(i, j0 + r0 + r, k));
+      real *dst = (real *)(A + (r >> 1) * N + (i - 1)) + (r & 1);
+      dst[0] = v.x;
+      if (i + 1 <= g.n1) dst[2] = v.y;
+#ifdef CALES_SINGLE
+      if (i + 2 <= g.n1) dst[4] = v.z;
+      if (i + 3 <= g.n1) dst[6] = v.w;
+#endif
+    }
+    if (nr & 1) for (int i = threadIdx.x; i < N; i += 256) A[(nc - 1) * N + i].y = (real)0.;      // the odd last row rides alone
+    __syncthreads();
+    const real2 *Z = spec_transform(pl, tw, nc, A, B);
+    if (PLANES) {
+      for (int w = threadIdx.x; w < nr * nh; w += 256) {
+        const int r = w / nh, m = w - r * nh;
+        real2 fa, fb; spec_pair(Z + (r >> 1) * N, N, m, &fa, &fb);
+        const bool odd = r & 1;
+        rows_out[((size_t)blockIdx.y * g.n2 + (size_t)(j0 - 1 + r0 + r)) * nh + m] = make_real2(odd ? fb.x : fa.x, odd ? fb.y : fa.y);
+      }
+    } else acc.add(Z, N, nh, nr);
+    __syncthreads();      // the next batch overwrites both buffers
+  }
+  if (!PLANES) acc.store(part + ((size_t)blockIdx.y * sg.nb + blockIdx.x) * 3 * (size_t)nh, nh);
+}
+
+// y lines of plane k = blockIdx.y + 1. blockIdx.x: a tile of 2 nl adjacent columns from i0 = 1 + 2 nl blockIdx.x (the last tile may hold fewer), columns
+// c and c+1 of the tile real and imaginary part of complex line c/2. Every row of the tile is sg.chunks 16-byte chunks (with nl = 8 in double one whole
+// 128-B segment); a chunk that starts past n1 is not read, one that reaches past n1 is masked as above. |G|^2 and G summed over the columns of the tile
+// in column order, one partial per tile at part[(blockIdx.y nb + blockIdx.x) 3 nh]
+__global__ __launch_bounds__(256) void k_spec_y(Geom g, SpecGeom sg, SpecPlan pl, const real2 *__restrict__ tw, const real *__restrict__ f, real *__restrict__ part) {
+  extern __shared__ real2 spec_lds[];
+  const int N = pl.n, nh = sg.nh;      // N = n2
+  real2 *A = spec_lds, *B = spec_lds + sg.nl * N;
+  const int k = blockIdx.y + 1, i0 = 1 + 2 * sg.nl * blockIdx.x, ncols = min(2 * sg.nl, g.n1 - i0 + 1), nc = (ncols + 1) / 2;
+  for (int q = threadIdx.x; q < N * sg.chunks; q += 256) {
+    const int j = q / sg.chunks, col = SPEC_VEC * (q - j * sg.chunks), i = i0 + col;
+    if (i > g.n1) continue;
+    const realv v = *(const realv *)(f + g.ix(i, j + 1, k));
+    const real e[SPEC_VEC] = {v.x, v.y,
+#ifdef CALES_SINGLE
+                              v.z, v.w
+#endif
+    };
+#pragma unroll
+    for (int t = 0; t < SPEC_VEC; ++t) if (i + t <= g.n1) ((real *)(A + ((col + t) >> 1) * N + j))[(col + t) & 1] = e[t];
+  }
+  if (ncols & 1) for (int j = threadIdx.x; j < N; j += 256) A[(nc - 1) * N + j].y = (real)0.;      // the odd last column rides alone
+  __syncthreads();
+  const real2 *Z = spec_transform(pl, tw, nc, A, B);
+  SpecAcc acc; acc.clear();
+  acc.add(Z, N, nh, ncols);
+  acc.store(part + ((size_t)blockIdx.y * sg.nb + blockIdx.x) * 3 * (size_t)nh, nh);
+}
+
+// the y pass of the plane spectra: blockIdx.y a plane of the chunk, blockIdx.x a tile of nl adjacent columns m of its complex rows (nhx = n1/2+1 per row,
+// what k_spec_x<true> wrote). Transforms every column along y (N = n2 points), forms |H(m, ky)|^2, adds ky and n2 - ky where the two differ and writes
+// power2(m, q, plane), q = 0 ... n2/2: no sum across blocks
+__global__ __launch_bounds__(256) void k_spec_y2(int nhx, SpecGeom sg, SpecPlan pl, const real2 *__restrict__ tw, const real2 *__restrict__ rows, real *__restrict__ power2) {
+  extern __shared__ real2 spec_lds[];
+  const int N = pl.n, nhy = sg.nh;
+  real2 *A = spec_lds, *B = spec_lds + sg.nl * N;
+  const int m0 = sg.nl * blockIdx.x, ncol = min(sg.nl, nhx - m0);
+  const real2 *src = rows + (size_t)blockIdx.y * N * nhx + m0;
+  for (int q = threadIdx.x; q < N * ncol; q += 256) {
+    const int j = q / ncol, c = q - j * ncol;
+    A[c * N + j] = src[(size_t)j * nhx + c];
+  }
+  __syncthreads();
+  const real2 *Z = spec_transform(pl, tw, ncol, A, B);
+  real *dst = power2 + (size_t)blockIdx.y * nhx * nhy + m0;
+  for (int w = threadIdx.x; w < ncol * nhy; w += 256) {
+    const int q = w / ncol, c = w - q * ncol, ky2 = q ? N - q : 0;
+    real v = cabs2(Z[c * N + q]);
+    if (ky2 != q) v += cabs2(Z[c * N + ky2]);
+    dst[(size_t)q * nhx + c] = v;
+  }
+}
+
+// the partials of the nb blocks of every plane, added in block order: power(nh, nplanes), lsum(2, nh, nplanes)
+__global__ __launch_bounds__(256) void k_spec_fold(int nh, int nb, int nplanes, const real *__restrict__ part, real *__restrict__ power, real *__restrict__ lsum) {
+  const int t = blockIdx.x * 256 + threadIdx.x;
+  if (t >= nh * nplanes) return;
+  const int k = t / nh, m = t - k * nh;
+  const real *p = part + (size_t)k * nb * 3 * nh + m;
+  real pw = 0., sr = 0., si = 0.;
+  for (int b = 0; b < nb; ++b, p += 3 * nh) { pw += p[0]; sr += p[nh]; si += p[2 * nh]; }
+  power[t] = pw; lsum[2 * (size_t)t] = sr; lsum[2 * (size_t)t + 1] = si;
+}
+
+// ------------------------------------------------------------------------------------------ host side
+// N as factors 4 (first), 2, 3, 5; anything else: the direct sum
+static SpecPlan spec_plan(int n) {
+  SpecPlan pl; pl.n = n; pl.nst = 0; pl.direct = 0; pl.radices = 0ull;
+  int m = n;
+  const int rs[4] = {4, 2, 3, 5};
+  for (int r : rs) while (m % r == 0 && pl.nst < SPEC_MAX_STAGES) { pl.radices |= (unsigned long long)r << (4 * pl.nst++); m /= r; }
+  if (m != 1) { pl.nst = 0; pl.direct = 1; pl.radices = 0ull; }
+  return pl;
+}
+// complex lines of N points a block keeps in LDS (see the head of the file)
+static int spec_nl(int N) {
+  int nl = 8;
+  while (nl > 2 && 2 * (size_t)nl * N * sizeof(real2) > SPEC_LDS_SOFT) nl /= 2;
+  return nl;
+}
+static size_t spec_lds_bytes(int nl, int N) { return 2 * (size_t)nl * N * sizeof(real2); }
+// a kernel that asks for more than 64 KB of dynamic LDS has to say so once
+template <class K> static int spec_lds_attr(cales_ctx *c, K kernel, size_t lds) {
+  if (lds > SPEC_LDS_MAX) { c->err = "spectra: the line does not fit the LDS budget"; return 1; }
+  if (lds > SPEC_LDS_SOFT) HIPCHK(c, hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SPEC_LDS_MAX));
+  return 0;
+}
+// runs of rows per block of the x kernel: about 2048 blocks over the planes, whole batches of 2 nl rows
+static void spec_x_geom(const cales_ctx *c, int nplanes, SpecGeom *sg) {
+  const int n1 = c->n[0], n2 = c->n[1];
+  sg->nl = spec_nl(n1); sg->nh = n1 / 2 + 1; sg->chunks = (n1 + SPEC_VEC - 1) / SPEC_VEC;
+  const int want = (2048 + nplanes - 1) / nplanes, batch = 2 * sg->nl;
+  int rows = (n2 + want - 1) / want;
+  rows = (rows + batch - 1) / batch * batch;
+  sg->rows = rows; sg->nb = (n2 + rows - 1) / rows;
+}
+static int spec_field(cales_ctx *c, int field, const char *who) {
+  if (field < 0 || field >= CALES_NFIELDS || !c->f[field]) { c->err = std::string(who) + ": bad field id"; return 1; }
+  // the kernels load 16 bytes per lane from element 1 of a row, which every field of a context has on a 128-B boundary (field_alloc, api.hip)
+  if (((uintptr_t)(c->f[field] + 1) & 15u) != 0) { c->err = std::string(who) + ": the field's rows are not 16-byte aligned"; return 1; }
+  return 0;
+}
+static int spec_line_ok(cales_ctx *c, int n, const char *who) {
+  if (n > CALES_SPECTRA_MAX_LINE) { c->err = std::string(who) + ": a line of " + std::to_string(n) + " points is longer than CALES_SPECTRA_MAX_LINE = " + std::to_string(CALES_SPECTRA_MAX_LINE); return 1; }
+  return 0;
+}
+static size_t even(size_t n) { return (n + 1) & ~(size_t)1; }      // (what follows in a temporary stays 16-byte aligned)
+
+int op_spectra_lines(cales_ctx *c, int field, int idir, real *power, real *lsum) {
+  const char *who = "cales_spectra_lines";
+  if (spec_field(c, field, who)) return 1;
+  if (idir != 1 && idir != 2) { c->err = std::string(who) + ": idir must be 1 or 2"; return 1; }
+  if (idir == 2 && c->P > 1) { c->err = std::string(who) + ": idir = 2 on one rank only (a slab holds no whole y line)"; return 1; }
+  const int n1 = c->n[0], n2 = c->n[1], n3 = c->n[2], N = idir == 1 ? n1 : n2;
+  if (spec_line_ok(c, N, who)) return 1;
+  if (!power) { c->err = std::string(who) + ": power is NULL"; return 1; }
+  if (field == CALES_VISCT) if (int e = materialize_visct(c)) return e;
+  const SpecPlan pl = spec_plan(N);
+  SpecGeom sg;
+  if (idir == 1) spec_x_geom(c, n3, &sg);
+  else { sg.nl = spec_nl(N); sg.nh = N / 2 + 1; sg.rows = 0; sg.chunks = 2 * sg.nl / SPEC_VEC; sg.nb = (n1 + 2 * sg.nl - 1) / (2 * sg.nl); }
+  const int nh = sg.nh;
+  const size_t lds = spec_lds_bytes(sg.nl, N);
+  if (idir == 1 ? spec_lds_attr(c, k_spec_x<false>, lds) : spec_lds_attr(c, k_spec_y, lds)) return 1;
+  // twiddles | partials | power | lsum
+  const size_t n_tw = 2 * (size_t)N, n_part = even((size_t)n3 * sg.nb * 3 * nh), n_pow = even((size_t)nh * n3), n_ls = 2 * (size_t)nh * n3;
+  CtxTemp tmp(c, n_tw + n_part + n_pow + n_ls); if (!tmp.p) return 1;
+  real2 *d_tw = (real2 *)tmp.p; real *d_part = tmp.p + n_tw, *d_pow = d_part + n_part, *d_ls = d_pow + n_pow;
+  { ProfScope ps(c, pl.direct ? "spectra_lines_direct" : "spectra_lines");
+    LAUNCH(c, k_spec_twiddle, dim3((N + 255) / 256), dim3(256), 0, c->stream, N, d_tw);
+    const dim3 grid(sg.nb, n3), block(256);
+    if (idir == 1) LAUNCH(c, k_spec_x<false>, grid, block, lds, c->stream, c->g, sg, pl, d_tw, (const int32_t *)nullptr, c->f[field], d_part, (real2 *)nullptr);
+    else LAUNCH(c, k_spec_y, grid, block, lds, c->stream, c->g, sg, pl, d_tw, c->f[field], d_part);
+    LAUNCH(c, k_spec_fold, dim3((nh * n3 + 255) / 256), block, 0, c->stream, nh, sg.nb, n3, d_part, d_pow, d_ls); }
+  LAUNCHCHK(c);
+  HIPCHK(c, hipMemcpyAsync(power, d_pow, (size_t)nh * n3 * sizeof(real), hipMemcpyDeviceToHost, c->stream));
+  if (lsum) HIPCHK(c, hipMemcpyAsync(lsum, d_ls, n_ls * sizeof(real), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+int op_spectra_planes(cales_ctx *c, int field, int nplanes, const int32_t *kplanes, real *power2) {
+  const char *who = "cales_spectra_planes";
+  if (spec_field(c, field, who)) return 1;
+  if (c->P > 1) { c->err = std::string(who) + ": one rank only (a slab holds no whole y line)"; return 1; }
+  const int n1 = c->n[0], n2 = c->n[1];
+  if (spec_line_ok(c, n1, who) || spec_line_ok(c, n2, who)) return 1;
+  if (!power2) { c->err = std::string(who) + ": power2 is NULL"; return 1; }
+  if (nplanes < 1) { c->err = std::string(who) + ": nplanes < 1"; return 1; }
+  if (!kplanes) { c->err = std::string(who) + ": kplanes is NULL"; return 1; }
+  for (int p = 0; p < nplanes; ++p) if (kplanes[p] < 1 || kplanes[p] > c->C.ng[2]) { c->err = std::string(who) + ": plane outside 1 ... ng(3)"; return 1; }
+  if (field == CALES_VISCT) if (int e = materialize_visct(c)) return e;
+  const SpecPlan plx = spec_plan(n1), ply = spec_plan(n2);
+  const int nhx = n1 / 2 + 1, nhy = n2 / 2 + 1;
+  // the complex rows of a plane take about as much as a plane of the field: as many planes at a time as 32 MB of scratch hold, one at least
+  const size_t plane_rows = (size_t)nhx * n2, plane_out = (size_t)nhx * nhy;
+  const int chunk = (int)std::min<size_t>((size_t)nplanes, std::max<size_t>(1, ((size_t)32 << 20) / (plane_rows * sizeof(real2))));
+  SpecGeom sx; spec_x_geom(c, chunk, &sx);
+  SpecGeom sy; sy.nl = spec_nl(n2); sy.nh = nhy; sy.rows = 0; sy.chunks = 0; sy.nb = (nhx + sy.nl - 1) / sy.nl;
+  const size_t ldsx = spec_lds_bytes(sx.nl, n1), ldsy = spec_lds_bytes(sy.nl, n2);
+  if (spec_lds_attr(c, k_spec_x<true>, ldsx) || spec_lds_attr(c, k_spec_y2, ldsy)) return 1;
+  // twiddles of x | of y | the complex rows of a chunk | its power2 | the planes (32-bit)
+  const size_t n_twx = 2 * (size_t)n1, n_twy = 2 * (size_t)n2, n_rows = 2 * plane_rows * chunk, n_out = even(plane_out * chunk);
+  const size_t n_k = even(((size_t)nplanes * sizeof(int32_t) + sizeof(real) - 1) / sizeof(real));
+  CtxTemp tmp(c, n_twx + n_twy + n_rows + n_out + n_k); if (!tmp.p) return 1;
+  real2 *d_twx = (real2 *)tmp.p, *d_twy = d_twx + n1, *d_rows = d_twy + n2;
+  real *d_out = tmp.p + n_twx + n_twy + n_rows; int32_t *d_k = (int32_t *)(d_out + n_out);
+  HIPCHK(c, hipMemcpyAsync(d_k, kplanes, (size_t)nplanes * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+  { ProfScope ps(c, (plx.direct || ply.direct) ? "spectra_planes_direct" : "spectra_planes");
+    const dim3 block(256);
+    LAUNCH(c, k_spec_twiddle, dim3((n1 + 255) / 256), block, 0, c->stream, n1, d_twx);
+    LAUNCH(c, k_spec_twiddle, dim3((n2 + 255) / 256), block, 0, c->stream, n2, d_twy);
+    for (int p0 = 0; p0 < nplanes; p0 += chunk) {
+      const int np = std::min(chunk, nplanes - p0);
+      LAUNCH(c, k_spec_x<true>, dim3(sx.nb, np), block, ldsx, c->stream, c->g, sx, plx, d_twx, (const int32_t *)(d_k + p0), c->f[field], (real *)nullptr, d_rows);
+      LAUNCH(c, k_spec_y2, dim3(sy.nb, np), block, ldsy, c->stream, nhx, sy, ply, d_twy, d_rows, d_out);
+      HIPCHK(c, hipMemcpyAsync(power2 + plane_out * p0, d_out, plane_out * np * sizeof(real), hipMemcpyDeviceToHost, c->stream));
+    } }
+  LAUNCHCHK(c);
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return 0;
+}

@@ -1,4 +1,4 @@
-! ISO_C_BINDING view of include/cales.h, include/cales_post.h and include/cales_pdf.h -- what a Fortran host (the reference's own language) binds to.
+! ISO_C_BINDING view of include/cales.h, include/cales_post.h, include/cales_pdf.h and include/cales_spectra.h -- what a Fortran host (the reference's own language) binds to.
 ! `type(cales_case)` mirrors `struct cales_case`; character and multi-dimensional members keep the
 ! storage order of the reference's namelist variables (src/param.f90:37-76), so they are copied unchanged.
 module cales_c
@@ -188,6 +188,17 @@ module cales_c
     integer(c_int) function cales_jpdf_planes(ctx,field_a,field_b,nbins,lo_a,hi_a,lo_b,hi_b,nplanes,kplanes,counts,outside) bind(C,name='cales_jpdf_planes')
       import; type(c_ptr), value :: ctx; integer(c_int), value :: field_a,field_b,nbins,nplanes; real(c_rp), value :: lo_a,hi_a,lo_b,hi_b
       integer(c_int32_t), intent(in) :: kplanes(*); integer(c_int64_t) :: counts(*),outside(*)
+    end function
+    ! ---- include/cales_spectra.h: sums of unnormalised forward DFTs of the interior samples, transformed on the device, this rank's sums.
+    ! idir = 1 | 2: power(n/2+1,n3) = sum over the lines of |F|^2, lsum(2,n/2+1,n3) = sum of F, real and imaginary part (always written through this interface);
+    ! power2(n1/2+1,n2/2+1,nplanes): |2-D DFT|^2 with ky and n2-ky added; kplanes: global k. idir = 2 and the planes: one rank only
+    integer(c_int) function cales_spectra_lines(ctx,field,idir,power,lsum) bind(C,name='cales_spectra_lines')
+      import; type(c_ptr), value :: ctx; integer(c_int), value :: field,idir
+      real(c_rp) :: power(*),lsum(*)
+    end function
+    integer(c_int) function cales_spectra_planes(ctx,field,nplanes,kplanes,power2) bind(C,name='cales_spectra_planes')
+      import; type(c_ptr), value :: ctx; integer(c_int), value :: field,nplanes
+      integer(c_int32_t), intent(in) :: kplanes(*); real(c_rp) :: power2(*)
     end function
   end interface
 end module cales_c

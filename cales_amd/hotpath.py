@@ -191,6 +191,30 @@ class HotPath:
                                            int(kp.size), kp.ctypes.data_as(C.c_void_p), counts.ctypes.data_as(C.c_void_p), outside.ctypes.data_as(C.c_void_p)))
         return counts, outside[:kp.size]
 
+    # -- spectra (include/cales_spectra.h): this rank's sums, Fortran-ordered; normalisation is the caller's (cales_amd/spectra.py)
+    def spectra_lines(self, name: str, idir: int, lsum: bool = True):
+        """cales_spectra_lines: power (nh, n3) = the sum over the lines of plane k of |DFT of the line|^2, nh = n/2 + 1 modes of the lines along x
+        (idir = 1, this rank's rows; the caller adds the ranks) or y (idir = 2, one rank only); with lsum also the complex sum of the lines' DFTs,
+        (nh, n3) complex. Unnormalised forward transforms of the interior samples (numpy.fft.rfft)."""
+        idir = int(idir)
+        n = self.n[idir - 1] if idir in (1, 2) else 1      # (anything else: the library refuses it below, nothing is written)
+        nh = (n if n <= capi.SPECTRA_MAX_LINE else 0) // 2 + 1
+        power = np.zeros((nh, self.n[2]), order="F", dtype=REAL)
+        ls = np.zeros((2, nh, self.n[2]), order="F", dtype=REAL) if lsum else None
+        self._chk(self.L.cales_spectra_lines(self.h, capi.FIELDS[name], idir, _p(power), _p(ls) if lsum else None))
+        if not lsum:
+            return power
+        return power, np.asfortranarray(ls[0] + 1j * ls[1])
+
+    def spectra_planes(self, name: str, kplanes) -> np.ndarray:
+        """cales_spectra_planes (one rank only): power2 (n1/2+1, n2/2+1, nplanes) = |2-D DFT|^2 of the planes `kplanes` (global k, 1 ... ng(3); any
+        order, repeats allowed), mode m along x, and along y the two modes ky = q and n2 - q added where they differ."""
+        kp = np.ascontiguousarray([int(k) for k in kplanes], dtype=np.int32)
+        ok = self.n[0] <= capi.SPECTRA_MAX_LINE and self.n[1] <= capi.SPECTRA_MAX_LINE
+        power2 = np.zeros((self.n[0] // 2 + 1, self.n[1] // 2 + 1, max(kp.size, 1)) if ok else (1, 1, 1), order="F", dtype=REAL)
+        self._chk(self.L.cales_spectra_planes(self.h, capi.FIELDS[name], int(kp.size), kp.ctypes.data_as(C.c_void_p), _p(power2)))
+        return power2
+
     def upload(self, u, v, w, p):
         a = [_In(x) for x in (u, v, w, p)]
         self._chk(self.L.cales_upload_state(self.h, *[x.p for x in a]))

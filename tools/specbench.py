@@ -1,0 +1,98 @@
+#!/usr/bin/env python3
+"""Times the spectra of include/cales_spectra.h against the route they replace -- the full download of the field (cales_get_field) and numpy.fft on the
+host --, in one process, at 512^3 and at 192 x 128 x 128.
+
+  python tools/specbench.py [--grids 512x512x512,192x128x128] [--calls 10] [--warmup 2]
+
+An explicit channel without subgrid model per grid, u a random field. Per case ONE JSON line: spectra_lines along x and along y on every plane and
+spectra_planes on 8 planes -- the wall-clock time of a call as the host sees it (median of --calls calls after --warmup, ms), the device time of its
+profile scope (twiddle table, transform and fold kernels), that device time's read rate of the samples it transforms as a fraction of the same run's
+read-only calibration (cales_calibrate), the wall-clock time relative to the download of the field measured in the same run, and the largest error
+against numpy relative to the largest value. The download is timed alone and, once each, with the numpy transforms of the field on top. CALES_LIB
+picks the library."""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--grids", default="512x512x512,192x128x128")
+    ap.add_argument("--calls", type=int, default=10)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--tag", default="", help="copied into every line")
+    a = ap.parse_args()
+    import numpy as np
+    from cales_amd import capi
+    from cales_amd.hotpath import HotPath
+    from cales_amd.nml import parse_text
+    R = capi.np_real
+
+    def emit(r):
+        if a.tag:
+            r["tag"] = a.tag
+        print(json.dumps(r), flush=True)
+
+    for grid in a.grids.split(","):
+        case = parse_text(open(os.path.join(ROOT, "cales_amd", "cases", "turbulent_channel.nml")).read())
+        case.ng[:] = [int(x) for x in grid.split("x")]
+        case.sgstype = "none"; case.impdiff = 0
+        ng = [int(x) for x in case.ng]
+        shape = tuple(n + 2 for n in ng)
+        plane_bytes = ng[0] * ng[1] * np.dtype(R).itemsize
+        h = HotPath(case)
+        try:
+            def timed(call, scope=None, calls=a.calls, warmup=a.warmup):
+                for _ in range(warmup):
+                    out = call()
+                h.profile_reset(); h.profile(True)
+                ts = []
+                for _ in range(calls):
+                    h.sync(); t0 = time.perf_counter()
+                    out = call()
+                    ts.append(1e3 * (time.perf_counter() - t0))
+                h.profile(False)
+                st = [v for k, v in h.profile_stats().items() if scope and k.startswith(scope)]
+                st = st[0] if st else (0, 0.)
+                return out, statistics.median(ts), min(ts), max(ts), (st[1] / st[0] if st[0] else None)
+            cal = h.calibrate(3)
+            base = {"ng": ng, "lib": os.path.basename(capi.LIB_PATH)}
+            rng = np.random.RandomState(1)
+            x = np.zeros(shape, order="F", dtype=R); x[...] = rng.standard_normal(shape).astype(R)
+            h.set("u", x)
+            _, get_ms, get_min, get_max, _ = timed(lambda: h.get("u"), calls=max(3, a.calls // 2), warmup=1)
+            emit(dict(base, case="get_field(u)", ms=round(get_ms, 3), ms_min=round(get_min, 3), ms_max=round(get_max, 3), bytes=int(np.prod(shape)) * np.dtype(R).itemsize))
+            kp = [1 + (q * ng[2]) // 8 for q in range(8)]
+            # the route this replaces, and what the device results are compared with
+            host = {}
+            for what, fn in (("x", lambda f: (np.abs(np.fft.rfft(f, axis=0)) ** 2).sum(1)), ("y", lambda f: (np.abs(np.fft.rfft(f, axis=1)) ** 2).sum(0)),
+                             ("planes", lambda f: np.abs(np.fft.fft(np.fft.rfft(f[:, :, [k - 1 for k in kp]], axis=0), axis=1)) ** 2)):
+                t0 = time.perf_counter()
+                host[what] = fn(h.get("u")[1:-1, 1:-1, 1:-1].astype(np.float64))
+                emit(dict(base, case=f"get_field(u) + numpy.fft, {what}", ms=round(1e3 * (time.perf_counter() - t0), 1), calls=1))
+            n2 = ng[1]
+            fold = host["planes"][:, :n2 // 2 + 1, :].copy()
+            fold[:, 1:(n2 + 1) // 2, :] += host["planes"][:, :n2 // 2:-1, :]
+            host["planes"] = fold
+            for what, call, scope, nplanes in (("x", lambda: h.spectra_lines("u", 1, lsum=False), "spectra_lines", ng[2]), ("y", lambda: h.spectra_lines("u", 2, lsum=False), "spectra_lines", ng[2]),
+                                               ("planes", lambda: h.spectra_planes("u", kp), "spectra_planes", 8)):
+                got, ms, ms_min, ms_max, dev_ms = timed(call, scope)
+                nbytes = plane_bytes * nplanes
+                emit(dict(base, case=f"spectra_lines(u, {1 if what == 'x' else 2})" if what != "planes" else "spectra_planes(u, 8 planes)", ms=round(ms, 4), ms_min=round(ms_min, 4),
+                          ms_max=round(ms_max, 4), device_ms=round(dev_ms, 4), read_GBps=round(nbytes / dev_ms * 1e-6, 1),
+                          fraction_of_read_calibration=round(nbytes / dev_ms * 1e-6 / cal["read_GBps"], 3), ms_over_get_field=round(ms / get_ms, 5),
+                          faster_than_get_field=bool(ms < get_ms), max_error_over_max_value=float(np.abs(got - host[what]).max() / host[what].max())))
+            emit({"calibration": {k: (round(v, 1) if isinstance(v, float) else v) for k, v in cal.items()}, "ng": ng, "device": h.device_info()[0]})
+        finally:
+            h.close()
+        del x
+
+
+if __name__ == "__main__":
+    main()
