@@ -168,6 +168,13 @@ real *stage_borrow(cales_ctx *c, int64_t n) {
   if (c->comm_stream && stream_after(c, c->stream, c->comm_stream)) return nullptr;
   return c->comm.A;
 }
+real *field_ptr(cales_ctx *c, int id, const char *who, int use) {
+  if (id < 0 || id >= CALES_NFIELDS || !c->f[id]) { c->err = std::string(who) + ": bad field id"; return nullptr; }
+  // (element 1 of a row: every field of a context has it on a 128-B boundary, field_alloc above)
+  if ((use & FIELD_ROWS16) && ((uintptr_t)(c->f[id] + 1) & 15u) != 0) { c->err = std::string(who) + ": the field's rows are not 16-byte aligned"; return nullptr; }
+  if ((use & FIELD_READ) && id == CALES_VISCT && materialize_visct(c)) return nullptr;
+  return c->f[id];
+}
 static int upload_bound(cales_ctx *c, DBound &b, std::vector<real> h[3]) {
   return ctx_upload(c, &b.x, h[0]) || ctx_upload(c, &b.y, h[1]) || ctx_upload(c, &b.z, h[2]);
 }
@@ -340,23 +347,22 @@ int cales_local_size(const cales_ctx *c, int32_t n[3], int32_t lo[3]) { for (int
 // ------------------------------------------------------------------------------------------ copies
 int cales_set_field(cales_ctx *c, int field, const real *host) {
   ENTER(c);
-  if (field < 0 || field >= CALES_NFIELDS || !c->f[field]) { c->err = "bad field id"; return 1; }
+  real *f = field_ptr(c, field, "cales_set_field", FIELD_WRITE); if (!f) return 1;
   if (field == CALES_VISCT) { c->visct_zero = false; c->visct_lazy = false; }
   const size_t nh = (size_t)(c->n[0] + 2) * (c->n[1] + 2) * (c->n[2] + 2);
   const dim3 b(64, 4, 1), gr((c->n[0] + 2 + 63) / 64, (c->n[1] + 2 + 3) / 4, c->n[2] + 2);
   HIPCHK(c, hipMemcpyAsync(c->scr1, host, nh * sizeof(real), hipMemcpyHostToDevice, c->stream));     // scr1: scratch between operators
-  LAUNCH(c, k_repack, gr, b, 0, c->stream, c->g, 1, c->f[field], c->scr1);
+  LAUNCH(c, k_repack, gr, b, 0, c->stream, c->g, 1, f, c->scr1);
   LAUNCHCHK(c);
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return 0;
 }
 int cales_get_field(cales_ctx *c, int field, real *host) {
   ENTER(c);
-  if (field < 0 || field >= CALES_NFIELDS || !c->f[field]) { c->err = "bad field id"; return 1; }
-  if (field == CALES_VISCT) if (int e = materialize_visct(c)) return e;
+  real *f = field_ptr(c, field, "cales_get_field", FIELD_READ); if (!f) return 1;
   const size_t nh = (size_t)(c->n[0] + 2) * (c->n[1] + 2) * (c->n[2] + 2);
   const dim3 b(64, 4, 1), gr((c->n[0] + 2 + 63) / 64, (c->n[1] + 2 + 3) / 4, c->n[2] + 2);
-  LAUNCH(c, k_repack, gr, b, 0, c->stream, c->g, 0, c->f[field], c->scr1);
+  LAUNCH(c, k_repack, gr, b, 0, c->stream, c->g, 0, f, c->scr1);
   LAUNCHCHK(c);
   return read_back(c, host, c->scr1, nh);
 }
@@ -406,19 +412,20 @@ int cales_box_share(const cales_case *cs, const int32_t lo[3], const int32_t hi[
 }
 int cales_read_box(cales_ctx *c, int field, const int32_t lo[3], const int32_t hi[3], const int32_t nskip[3], real *buf, int32_t count[3]) {
   ENTER(c);
-  if (field < 0 || field >= CALES_NFIELDS || !c->f[field]) { c->err = "bad field id"; return 1; }
+  const char *who = "cales_read_box";
+  if (!field_ptr(c, field, who, FIELD_WRITE)) return 1;      // (the id first; nothing is read yet)
   int32_t first[3], cnt[3];
   if (int e = box_share(&c->C, lo, hi, nskip, first, cnt, c->err)) return e;
   if (count) for (int d = 0; d < 3; ++d) count[d] = cnt[d];
   const size_t total = (size_t)cnt[0] * (size_t)cnt[1] * (size_t)cnt[2];      // (never more than a field: the points of a share are distinct cells of the slab)
   if (total == 0) return 0;
   if (!buf) { c->err = "box: buf is NULL"; return 1; }
-  if (field == CALES_VISCT) if (int e = materialize_visct(c)) return e;
+  const real *f = field_ptr(c, field, who, FIELD_READ); if (!f) return 1;
   BoxRead b;
   for (int d = 0; d < 3; ++d) { b.first[d] = first[d]; b.skip[d] = nskip[d]; b.count[d] = cnt[d]; }
   b.first[1] -= c->g.jlo;      // global row -> row of the slab
   { ProfScope ps(c, "box_read");
-    LAUNCH(c, k_box_read, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, c->stream, c->g, b, total, c->f[field], c->scr1); }     // scr1: scratch between operators
+    LAUNCH(c, k_box_read, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, c->stream, c->g, b, total, f, c->scr1); }     // scr1: scratch between operators
   LAUNCHCHK(c);
   return read_back(c, buf, c->scr1, total);
 }
@@ -441,7 +448,7 @@ int cales_bounduvw(cales_ctx *c, int is_updt_wm, int is_correc) {
   ENTRY(c, op_bounduvw(c, VelSet::state, is_updt_wm, is_correc));
 }
 int cales_boundp(cales_ctx *c, int field, int which) {
-  if (field < 0 || field >= CALES_NFIELDS || !c->f[field]) { c->err = "bad field id"; return 1; }
+  if (!field_ptr(c, field, "cales_boundp", FIELD_WRITE)) return 1;
   ENTRY(c, op_boundp(c, c->f[field], which));
 }
 int cales_get_forcing(cales_ctx *c, real f[3]);
@@ -461,7 +468,7 @@ int cales_get_forcing(cales_ctx *c, real f[3]) {
   return 0;
 }
 int cales_bulk_mean(cales_ctx *c, int field, int c_or_f, real *mean) {
-  if (field < 0 || field >= CALES_NFIELDS || !c->f[field]) { c->err = "bad field id"; return 1; }
+  if (!field_ptr(c, field, "cales_bulk_mean", FIELD_WRITE)) return 1;      // (the mean of the field as it is stored: nothing is materialized)
   ENTER(c);
   if (int e = op_bulk_mean_dev(c, c->f[field], c_or_f)) return e;
   LAUNCHCHK(c);

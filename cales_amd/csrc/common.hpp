@@ -486,6 +486,11 @@ real *red_partials(cales_ctx *c, size_t need);      // room for `need` partial s
 int allreduce_dev(cales_ctx *c, real *p, int64_t count, int op);      // [p, p + count) over the slabs, in place (op: 0 sum, 1 max): nothing on one rank; the range must lie in the tail of staging buffer A or in its borrowed head
 real *stage_borrow(cales_ctx *c, int64_t n);      // n reals at the head of staging buffer A, free of every exchange queued so far (StageLayout::borrow); nullptr and c->err otherwise
 int read_back(cales_ctx *c, real *host, const real *dev, size_t n);      // n reals to the host on the context's stream, complete on return
+// ... n elements of any type, queued on the context's stream and NOT waited for: the caller syncs once behind its last copy
+template <class T> int read_back_queued(cales_ctx *c, T *host, const void *dev, size_t n) {
+  HIPCHK(c, hipMemcpyAsync(host, dev, n * sizeof(T), hipMemcpyDeviceToHost, c->stream));
+  return 0;
+}
 int op_zero_force(cales_ctx *c, int first, int last);      // d_force[first, last) = 0 (f(3), dpdl(3))
 int op_fillps(cales_ctx *c, real dtrki);
 int op_updt_rhs_b(cales_ctx *c);
@@ -495,6 +500,12 @@ extern "C" void cales_comm_release_native(cales_ctx *c);
 int op_helmholtz(cales_ctx *c, int ivel, real alpha);
 int op_correc(cales_ctx *c, real dtrk, int fmask = 0);      // fmask: see op_correc_updatep
 int materialize_visct(cales_ctx *c);
+// THE check of a field id of the C-ABI (api.hip): the device pointer of field `id` (enum cales_field), or nullptr and c->err = "<who>: bad field id" for an
+// id out of range or a field this context did not allocate. `use`: FIELD_READ -- the caller reads the field: a lazy eddy viscosity is materialized first |
+// FIELD_ROWS16 -- its kernels load 16 bytes per lane from element 1 of a row (readout.hpp): refused unless that is a 16-byte boundary. An entry that refuses
+// other arguments checks the id first WITHOUT FIELD_READ and asks again with it last: nothing is materialized or launched for a call that is refused
+enum FieldUse { FIELD_WRITE = 0, FIELD_READ = 1, FIELD_ROWS16 = 2 };
+real *field_ptr(cales_ctx *c, int id, const char *who, int use);
 int op_stats_chan(cales_ctx *c, real *buf);
 int op_stats_chan_budget(cales_ctx *c, real *budget, real *leak);
 int op_out1d(cales_ctx *c, int field, int idir, int use_dzc, real *buf);

@@ -2,17 +2,10 @@
 // library that scatter: every block counts its samples into 32-bit counters in LDS (atomicAdd on __shared__ memory), keeps the samples that fall
 // outside the range in registers, and adds its non-zero counters to the 64-bit counts in global memory with one atomicAdd each. The sums are integers:
 // exact, independent of the order in which the blocks arrive, the same bits from run to run.
-#include "common.hpp"
+#include "readout.hpp"
 #include "../../include/cales_pdf.h"
-#include <algorithm>
 
 typedef unsigned long long u64;
-#ifdef CALES_SINGLE
-typedef float4 realv;      // 16 bytes per lane
-#else
-typedef double2 realv;
-#endif
-constexpr int PDF_VEC = 16 / RSZ;
 
 // The bin rule of include/cales_pdf.h to the letter: t = (x - lo) * s, that subtraction then that multiplication (no contraction: there is no sum
 // after the product, and the pragma says so); -1: below, nb: above (x >= hi, +inf, NaN, a t rounded up to nb), otherwise the bin
@@ -31,8 +24,7 @@ __device__ inline unsigned wave_sum_u32(unsigned v) {
   return v;
 }
 // What a launch of either kernel walks: blocks of 256 threads, blockIdx.y the plane, blockIdx.x a run of `rows` rows of it (the last run of a plane
-// may be shorter). A row is read in chunks of PDF_VEC elements from element 1, which sits on a 128-B boundary in every row (Geom); the last chunk of
-// a row may reach past n1 into the pitch padding or the next row's first element -- inside the field's allocation, and masked out.
+// may be shorter), read in `chunks` 16-byte chunks per row (read_rows16, readout.hpp)
 struct PdfGeom { int rows, chunks; };
 
 __global__ __launch_bounds__(256) void k_pdf_planes(Geom g, PdfGeom pg, int nb, real lo, real s, const real *__restrict__ f, u64 *__restrict__ counts, u64 *__restrict__ outside) {
@@ -41,21 +33,10 @@ __global__ __launch_bounds__(256) void k_pdf_planes(Geom g, PdfGeom pg, int nb, 
   for (int b = threadIdx.x; b < nb; b += 256) cnt[b] = 0u;
   __syncthreads();
   unsigned below = 0u, above = 0u;
-  auto tally = [&](real x) {
+  read_rows16<1>(g, pg.chunks, j0, nrows, k, f, nullptr, [&](int, int, real x) {
     const int b = pdf_bin(x, lo, s, nb);
     if (b < 0) ++below; else if (b >= nb) ++above; else atomicAdd(&cnt[b], 1u);
-  };
-  const int nq = nrows * pg.chunks;
-  for (int q = threadIdx.x; q < nq; q += 256) {
-    const int r = q / pg.chunks, i = 1 + PDF_VEC * (q - r * pg.chunks);
-    const realv v = *(const realv *)(f + g.ix(i, j0 + r, k));
-    tally(v.x);
-    if (i + 1 <= g.n1) tally(v.y);
-#ifdef CALES_SINGLE
-    if (i + 2 <= g.n1) tally(v.z);
-    if (i + 3 <= g.n1) tally(v.w);
-#endif
-  }
+  });
   __syncthreads();
   u64 *out = counts + (size_t)nb * (size_t)(k - 1);
   for (int b = threadIdx.x; b < nb; b += 256) { const unsigned v = cnt[b]; if (v) atomicAdd(&out[b], (u64)v); }
@@ -73,22 +54,10 @@ __global__ __launch_bounds__(256) void k_jpdf_planes(Geom g, PdfGeom pg, int nb,
   for (int b = threadIdx.x; b < nc; b += 256) cnt[b] = 0u;
   __syncthreads();
   unsigned out = 0u;
-  auto tally = [&](real xa, real xb) {
+  read_rows16<2>(g, pg.chunks, j0, nrows, k, fa, fb, [&](int, int, real xa, real xb) {
     const int a = pdf_bin(xa, lo_a, s_a, nb), b = pdf_bin(xb, lo_b, s_b, nb);
     if (a < 0 || a >= nb || b < 0 || b >= nb) ++out; else atomicAdd(&cnt[a + nb * b], 1u);
-  };
-  const int nq = nrows * pg.chunks;
-  for (int q = threadIdx.x; q < nq; q += 256) {
-    const int r = q / pg.chunks, i = 1 + PDF_VEC * (q - r * pg.chunks);
-    const size_t c = g.ix(i, j0 + r, k);
-    const realv va = *(const realv *)(fa + c), vb = *(const realv *)(fb + c);
-    tally(va.x, vb.x);
-    if (i + 1 <= g.n1) tally(va.y, vb.y);
-#ifdef CALES_SINGLE
-    if (i + 2 <= g.n1) tally(va.z, vb.z);
-    if (i + 3 <= g.n1) tally(va.w, vb.w);
-#endif
-  }
+  });
   __syncthreads();
   u64 *dst = counts + (size_t)nc * (size_t)blockIdx.y;
   for (int b = threadIdx.x; b < nc; b += 256) { const unsigned v = cnt[b]; if (v) atomicAdd(&dst[b], (u64)v); }
@@ -97,21 +66,12 @@ __global__ __launch_bounds__(256) void k_jpdf_planes(Geom g, PdfGeom pg, int nb,
 }
 
 // ------------------------------------------------------------------------------------------ host side
-// Rows per block: enough blocks to fill the device (about 2048 over the planes), but no block with fewer samples than it has counters to clear and
-// flush, or fewer than 4096; *nbx: the blocks of a plane
+// Rows per block (row_runs, readout.hpp): no block with fewer samples than it has counters to clear and flush, or fewer than 4096; *nbx: the blocks of a plane
 static PdfGeom pdf_geom(const cales_ctx *c, int nplanes, int ncounters, unsigned *nbx) {
-  const int n1 = c->n[0], n2 = c->n[1];
-  const int want = (2048 + nplanes - 1) / nplanes, least = std::max(4096, ncounters);
-  int rows = std::max((n2 + want - 1) / want, (least + n1 - 1) / n1);
-  rows = std::min(std::max(rows, 1), n2);
-  *nbx = (unsigned)((n2 + rows - 1) / rows);
-  return PdfGeom{rows, (n1 + PDF_VEC - 1) / PDF_VEC};
-}
-static int pdf_field(cales_ctx *c, int field, const char *who) {
-  if (field < 0 || field >= CALES_NFIELDS || !c->f[field]) { c->err = std::string(who) + ": bad field id"; return 1; }
-  // the kernels load 16 bytes per lane from element 1 of a row, which every field of a context has on a 128-B boundary (field_alloc, api.hip)
-  if (((uintptr_t)(c->f[field] + 1) & 15u) != 0) { c->err = std::string(who) + ": the field's rows are not 16-byte aligned"; return 1; }
-  return 0;
+  const int n1 = c->n[0], least = std::max(4096, ncounters);
+  const RowRuns rr = row_runs(c->n[1], nplanes, (least + n1 - 1) / n1, 1);
+  *nbx = (unsigned)rr.per_plane;
+  return PdfGeom{rr.rows, (n1 + REALV - 1) / REALV};
 }
 // s of the bin rule; refuses a range that is not one
 static int pdf_scale(cales_ctx *c, int nbins, real lo, real hi, const char *who, real *s) {
@@ -120,33 +80,28 @@ static int pdf_scale(cales_ctx *c, int nbins, real lo, real hi, const char *who,
   *s = (real)nbins / (hi - lo);
   return 0;
 }
-// n 64-bit integers in a temporary of reals
-static size_t reals_for_i64(size_t n) { return (n * sizeof(int64_t) + sizeof(real) - 1) / sizeof(real); }
-static int read_back_i64(cales_ctx *c, int64_t *host, const u64 *dev, size_t n) {
-  HIPCHK(c, hipMemcpyAsync(host, dev, n * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
-  return 0;
-}
 
 int op_pdf_planes(cales_ctx *c, int field, int nbins, real lo, real hi, int64_t *counts, int64_t *outside) {
   const char *who = "cales_pdf_planes";
-  if (pdf_field(c, field, who)) return 1;
+  if (!field_ptr(c, field, who, FIELD_ROWS16)) return 1;
   if (nbins < 1 || nbins > CALES_PDF_MAX_BINS) { c->err = std::string(who) + ": nbins must be 1 ... " + std::to_string(CALES_PDF_MAX_BINS); return 1; }
   real s;
   if (pdf_scale(c, nbins, lo, hi, who, &s)) return 1;
   if (!counts) { c->err = std::string(who) + ": counts is NULL"; return 1; }
-  if (field == CALES_VISCT) if (int e = materialize_visct(c)) return e;
+  const real *f = field_ptr(c, field, who, FIELD_READ); if (!f) return 1;
   const int n3 = c->n[2];
-  const size_t ncnt = (size_t)nbins * n3, nall = ncnt + 2 * (size_t)n3;
-  CtxTemp tmp(c, reals_for_i64(nall)); if (!tmp.p) return 1;
-  u64 *d_counts = (u64 *)tmp.p, *d_out = d_counts + ncnt;
+  const size_t ncnt = (size_t)nbins * n3;
+  TempCarver tc; const auto p_counts = tc.part<u64>(ncnt), p_out = tc.part<u64>(2 * (size_t)n3);
+  CtxTemp tmp(c, tc.reals(sizeof(real))); if (!tmp.p) return 1;
+  u64 *d_counts = p_counts.in(tmp.p), *d_out = p_out.in(tmp.p);
   unsigned nbx; const PdfGeom pg = pdf_geom(c, n3, nbins, &nbx);
   { ProfScope ps(c, "pdf_planes");
-    HIPCHK(c, hipMemsetAsync(d_counts, 0, nall * sizeof(u64), c->stream));
+    HIPCHK(c, hipMemsetAsync(tmp.p, 0, tc.bytes, c->stream));
     const dim3 grid(nbx, n3), block(256); const size_t lds = (size_t)nbins * sizeof(unsigned);
-    LAUNCH(c, k_pdf_planes, grid, block, lds, c->stream, c->g, pg, nbins, lo, s, c->f[field], d_counts, d_out); }
+    LAUNCH(c, k_pdf_planes, grid, block, lds, c->stream, c->g, pg, nbins, lo, s, f, d_counts, d_out); }
   LAUNCHCHK(c);
-  if (int e = read_back_i64(c, counts, d_counts, ncnt)) return e;
-  if (outside) if (int e = read_back_i64(c, outside, d_out, 2 * (size_t)n3)) return e;
+  if (int e = read_back_queued(c, counts, d_counts, ncnt)) return e;
+  if (outside) if (int e = read_back_queued(c, outside, d_out, 2 * (size_t)n3)) return e;
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return 0;
 }
@@ -154,28 +109,26 @@ int op_pdf_planes(cales_ctx *c, int field, int nbins, real lo, real hi, int64_t 
 int op_jpdf_planes(cales_ctx *c, int field_a, int field_b, int nbins, real lo_a, real hi_a, real lo_b, real hi_b, int nplanes, const int32_t *kplanes,
                    int64_t *counts, int64_t *outside) {
   const char *who = "cales_jpdf_planes";
-  if (pdf_field(c, field_a, who) || pdf_field(c, field_b, who)) return 1;
+  if (!field_ptr(c, field_a, who, FIELD_ROWS16) || !field_ptr(c, field_b, who, FIELD_ROWS16)) return 1;
   if (nbins < 1 || nbins > CALES_JPDF_MAX_BINS) { c->err = std::string(who) + ": nbins must be 1 ... " + std::to_string(CALES_JPDF_MAX_BINS); return 1; }
   real s_a, s_b;
   if (pdf_scale(c, nbins, lo_a, hi_a, who, &s_a) || pdf_scale(c, nbins, lo_b, hi_b, who, &s_b)) return 1;
   if (!counts) { c->err = std::string(who) + ": counts is NULL"; return 1; }
-  if (nplanes < 1) { c->err = std::string(who) + ": nplanes < 1"; return 1; }
-  if (!kplanes) { c->err = std::string(who) + ": kplanes is NULL"; return 1; }
-  for (int p = 0; p < nplanes; ++p) if (kplanes[p] < 1 || kplanes[p] > c->C.ng[2]) { c->err = std::string(who) + ": plane outside 1 ... ng(3)"; return 1; }
-  if (field_a == CALES_VISCT || field_b == CALES_VISCT) if (int e = materialize_visct(c)) return e;
-  const size_t nc = (size_t)nbins * nbins, ncnt = nc * (size_t)nplanes, nall = ncnt + (size_t)nplanes;
-  // counts | outside | the planes (32-bit, behind the 64-bit integers)
-  CtxTemp tmp(c, reals_for_i64(nall + ((size_t)nplanes + 1) / 2)); if (!tmp.p) return 1;
-  u64 *d_counts = (u64 *)tmp.p, *d_out = d_counts + ncnt; int32_t *d_k = (int32_t *)(d_out + nplanes);
+  if (plane_list_check(who, nplanes, kplanes, c->C.ng[2], c->err)) return 1;
+  const real *fa = field_ptr(c, field_a, who, FIELD_READ), *fb = field_ptr(c, field_b, who, FIELD_READ); if (!fa || !fb) return 1;
+  const size_t nc = (size_t)nbins * nbins, ncnt = nc * (size_t)nplanes;
+  TempCarver tc; const auto p_counts = tc.part<u64>(ncnt), p_out = tc.part<u64>(nplanes); const auto p_k = tc.part<int32_t>(nplanes);
+  CtxTemp tmp(c, tc.reals(sizeof(real))); if (!tmp.p) return 1;
+  u64 *d_counts = p_counts.in(tmp.p), *d_out = p_out.in(tmp.p); int32_t *d_k = p_k.in(tmp.p);
   unsigned nbx; const PdfGeom pg = pdf_geom(c, nplanes, (int)nc, &nbx);
-  HIPCHK(c, hipMemcpyAsync(d_k, kplanes, (size_t)nplanes * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+  if (int e = plane_list_upload(c, d_k, kplanes, nplanes)) return e;
   { ProfScope ps(c, "jpdf_planes");
-    HIPCHK(c, hipMemsetAsync(d_counts, 0, nall * sizeof(u64), c->stream));
+    HIPCHK(c, hipMemsetAsync(tmp.p, 0, p_k.at, c->stream));      // the counters: everything in front of the planes
     const dim3 grid(nbx, nplanes), block(256); const size_t lds = nc * sizeof(unsigned);
-    LAUNCH(c, k_jpdf_planes, grid, block, lds, c->stream, c->g, pg, nbins, lo_a, s_a, lo_b, s_b, d_k, c->f[field_a], c->f[field_b], d_counts, d_out); }
+    LAUNCH(c, k_jpdf_planes, grid, block, lds, c->stream, c->g, pg, nbins, lo_a, s_a, lo_b, s_b, d_k, fa, fb, d_counts, d_out); }
   LAUNCHCHK(c);
-  if (int e = read_back_i64(c, counts, d_counts, ncnt)) return e;
-  if (outside) if (int e = read_back_i64(c, outside, d_out, (size_t)nplanes)) return e;
+  if (int e = read_back_queued(c, counts, d_counts, ncnt)) return e;
+  if (outside) if (int e = read_back_queued(c, outside, d_out, (size_t)nplanes)) return e;
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return 0;
 }

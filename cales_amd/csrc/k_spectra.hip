@@ -13,16 +13,9 @@
 //   the smallest lines (N = 1, 2): nl = 8, 256 B / 512 B.
 // Sums over lines are formed in a fixed order and without atomics: a thread owns its modes, adds the lines of its block in line order and writes ONE
 // partial per block; k_spec_fold adds the blocks of a plane in block order. The same bits from run to run.
-#include "common.hpp"
+#include "readout.hpp"
 #include "../../include/cales_spectra.h"
-#include <algorithm>
 
-#ifdef CALES_SINGLE
-typedef float4 realv;      // 16 bytes per lane
-#else
-typedef double2 realv;
-#endif
-constexpr int SPEC_VEC = 16 / RSZ;
 constexpr int SPEC_MAX_STAGES = 12;                                     // 2048 = 4^5 2: 6 stages; 2 3^6 = 1458: 7
 constexpr int SPEC_MPT = (CALES_SPECTRA_MAX_LINE / 2 + 1 + 255) / 256;  // modes a thread of a block of 256 owns at the cap: 5
 constexpr size_t SPEC_LDS_SOFT = 64 * 1024, SPEC_LDS_MAX = 128 * 1024;
@@ -163,9 +156,8 @@ struct SpecAcc {
 };
 
 // x lines. blockIdx.y: the plane (k = blockIdx.y + 1, or the entry of kplanes), blockIdx.x: a run of sg.rows consecutive rows of it (the last run may be
-// shorter), taken 2 nl rows at a time: rows r and r+1 of a batch are real and imaginary part of complex line r/2. A row is read in 16-byte chunks from
-// element 1, which sits on a 128-B boundary in every row (Geom); the last chunk of a row may reach past n1 into the pitch padding or the next row's first
-// element -- inside the field's allocation, and masked out (k_pdf.hip reads the same way).
+// shorter), taken 2 nl rows at a time: rows r and r+1 of a batch are real and imaginary part of complex line r/2, read in sg.chunks 16-byte chunks per row
+// (read_rows16, readout.hpp).
 // PLANES = false: |F|^2 and F summed over the rows of the block in row order, one partial per block (SpecAcc::store) at part[(blockIdx.y nb + blockIdx.x) 3 nh]
 // PLANES = true:  the rows' transforms F(0 ... n1/2) go to rows_out[(blockIdx.y n2 + j - 1) nh + m]
 template <bool PLANES>
@@ -178,17 +170,7 @@ __global__ __launch_bounds__(256) void k_spec_x(Geom g, SpecGeom sg, SpecPlan pl
   SpecAcc acc; acc.clear();
   for (int r0 = 0; r0 < nrows; r0 += 2 * sg.nl) {
     const int nr = min(2 * sg.nl, nrows - r0), nc = (nr + 1) / 2;
-    for (int q = threadIdx.x; q < nr * sg.chunks; q += 256) {
-      const int r = q / sg.chunks, i = 1 + SPEC_VEC * (q - r * sg.chunks);
-      const realv v = *(const realv *)(f + g.ix(i, j0 + r0 + r, k));
-      real *dst = (real *)(A + (r >> 1) * N + (i - 1)) + (r & 1);
-      dst[0] = v.x;
-      if (i + 1 <= g.n1) dst[2] = v.y;
-#ifdef CALES_SINGLE
-      if (i + 2 <= g.n1) dst[4] = v.z;
-      if (i + 3 <= g.n1) dst[6] = v.w;
-#endif
-    }
+    read_rows16<1>(g, sg.chunks, j0 + r0, nr, k, f, nullptr, [&](int r, int i, real x) { ((real *)(A + (r >> 1) * N + (i - 1)))[r & 1] = x; });
     if (nr & 1) for (int i = threadIdx.x; i < N; i += 256) A[(nc - 1) * N + i].y = (real)0.;      // the odd last row rides alone
     __syncthreads();
     const real2 *Z = spec_transform(pl, tw, nc, A, B);
@@ -207,7 +189,7 @@ __global__ __launch_bounds__(256) void k_spec_x(Geom g, SpecGeom sg, SpecPlan pl
 
 // y lines of plane k = blockIdx.y + 1. blockIdx.x: a tile of 2 nl adjacent columns from i0 = 1 + 2 nl blockIdx.x (the last tile may hold fewer), columns
 // c and c+1 of the tile real and imaginary part of complex line c/2. Every row of the tile is sg.chunks 16-byte chunks (with nl = 8 in double one whole
-// 128-B segment); a chunk that starts past n1 is not read, one that reaches past n1 is masked as above. |G|^2 and G summed over the columns of the tile
+// 128-B segment); a chunk that starts past n1 is not read, one that reaches past n1 is masked as read_rows16 masks it. |G|^2 and G summed over the columns of the tile
 // in column order, one partial per tile at part[(blockIdx.y nb + blockIdx.x) 3 nh]
 __global__ __launch_bounds__(256) void k_spec_y(Geom g, SpecGeom sg, SpecPlan pl, const real2 *__restrict__ tw, const real *__restrict__ f, real *__restrict__ part) {
   extern __shared__ real2 spec_lds[];
@@ -215,16 +197,11 @@ __global__ __launch_bounds__(256) void k_spec_y(Geom g, SpecGeom sg, SpecPlan pl
   real2 *A = spec_lds, *B = spec_lds + sg.nl * N;
   const int k = blockIdx.y + 1, i0 = 1 + 2 * sg.nl * blockIdx.x, ncols = min(2 * sg.nl, g.n1 - i0 + 1), nc = (ncols + 1) / 2;
   for (int q = threadIdx.x; q < N * sg.chunks; q += 256) {
-    const int j = q / sg.chunks, col = SPEC_VEC * (q - j * sg.chunks), i = i0 + col;
+    const int j = q / sg.chunks, col = REALV * (q - j * sg.chunks), i = i0 + col;
     if (i > g.n1) continue;
-    const realv v = *(const realv *)(f + g.ix(i, j + 1, k));
-    const real e[SPEC_VEC] = {v.x, v.y,
-#ifdef CALES_SINGLE
-                              v.z, v.w
-#endif
-    };
+    real e[REALV]; realv_unpack(*(const realv *)(f + g.ix(i, j + 1, k)), e);
 #pragma unroll
-    for (int t = 0; t < SPEC_VEC; ++t) if (i + t <= g.n1) ((real *)(A + ((col + t) >> 1) * N + j))[(col + t) & 1] = e[t];
+    for (int t = 0; t < REALV; ++t) if (i + t <= g.n1) ((real *)(A + ((col + t) >> 1) * N + j))[(col + t) & 1] = e[t];
   }
   if (ncols & 1) for (int j = threadIdx.x; j < N; j += 256) A[(nc - 1) * N + j].y = (real)0.;      // the odd last column rides alone
   __syncthreads();
@@ -292,71 +269,60 @@ template <class K> static int spec_lds_attr(cales_ctx *c, K kernel, size_t lds) 
   if (lds > SPEC_LDS_SOFT) HIPCHK(c, hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SPEC_LDS_MAX));
   return 0;
 }
-// runs of rows per block of the x kernel: about 2048 blocks over the planes, whole batches of 2 nl rows
+// runs of rows per block of the x kernel (row_runs, readout.hpp): whole batches of 2 nl rows
 static void spec_x_geom(const cales_ctx *c, int nplanes, SpecGeom *sg) {
-  const int n1 = c->n[0], n2 = c->n[1];
-  sg->nl = spec_nl(n1); sg->nh = n1 / 2 + 1; sg->chunks = (n1 + SPEC_VEC - 1) / SPEC_VEC;
-  const int want = (2048 + nplanes - 1) / nplanes, batch = 2 * sg->nl;
-  int rows = (n2 + want - 1) / want;
-  rows = (rows + batch - 1) / batch * batch;
-  sg->rows = rows; sg->nb = (n2 + rows - 1) / rows;
-}
-static int spec_field(cales_ctx *c, int field, const char *who) {
-  if (field < 0 || field >= CALES_NFIELDS || !c->f[field]) { c->err = std::string(who) + ": bad field id"; return 1; }
-  // the kernels load 16 bytes per lane from element 1 of a row, which every field of a context has on a 128-B boundary (field_alloc, api.hip)
-  if (((uintptr_t)(c->f[field] + 1) & 15u) != 0) { c->err = std::string(who) + ": the field's rows are not 16-byte aligned"; return 1; }
-  return 0;
+  const int n1 = c->n[0];
+  sg->nl = spec_nl(n1); sg->nh = n1 / 2 + 1; sg->chunks = (n1 + REALV - 1) / REALV;
+  const RowRuns rr = row_runs(c->n[1], nplanes, 1, 2 * sg->nl);
+  sg->rows = rr.rows; sg->nb = rr.per_plane;
 }
 static int spec_line_ok(cales_ctx *c, int n, const char *who) {
   if (n > CALES_SPECTRA_MAX_LINE) { c->err = std::string(who) + ": a line of " + std::to_string(n) + " points is longer than CALES_SPECTRA_MAX_LINE = " + std::to_string(CALES_SPECTRA_MAX_LINE); return 1; }
   return 0;
 }
-static size_t even(size_t n) { return (n + 1) & ~(size_t)1; }      // (what follows in a temporary stays 16-byte aligned)
 
 int op_spectra_lines(cales_ctx *c, int field, int idir, real *power, real *lsum) {
   const char *who = "cales_spectra_lines";
-  if (spec_field(c, field, who)) return 1;
+  if (!field_ptr(c, field, who, FIELD_ROWS16)) return 1;
   if (idir != 1 && idir != 2) { c->err = std::string(who) + ": idir must be 1 or 2"; return 1; }
   if (idir == 2 && c->P > 1) { c->err = std::string(who) + ": idir = 2 on one rank only (a slab holds no whole y line)"; return 1; }
   const int n1 = c->n[0], n2 = c->n[1], n3 = c->n[2], N = idir == 1 ? n1 : n2;
   if (spec_line_ok(c, N, who)) return 1;
   if (!power) { c->err = std::string(who) + ": power is NULL"; return 1; }
-  if (field == CALES_VISCT) if (int e = materialize_visct(c)) return e;
+  const real *f = field_ptr(c, field, who, FIELD_READ); if (!f) return 1;
   const SpecPlan pl = spec_plan(N);
   SpecGeom sg;
   if (idir == 1) spec_x_geom(c, n3, &sg);
-  else { sg.nl = spec_nl(N); sg.nh = N / 2 + 1; sg.rows = 0; sg.chunks = 2 * sg.nl / SPEC_VEC; sg.nb = (n1 + 2 * sg.nl - 1) / (2 * sg.nl); }
+  else { sg.nl = spec_nl(N); sg.nh = N / 2 + 1; sg.rows = 0; sg.chunks = 2 * sg.nl / REALV; sg.nb = (n1 + 2 * sg.nl - 1) / (2 * sg.nl); }
   const int nh = sg.nh;
   const size_t lds = spec_lds_bytes(sg.nl, N);
   if (idir == 1 ? spec_lds_attr(c, k_spec_x<false>, lds) : spec_lds_attr(c, k_spec_y, lds)) return 1;
-  // twiddles | partials | power | lsum
-  const size_t n_tw = 2 * (size_t)N, n_part = even((size_t)n3 * sg.nb * 3 * nh), n_pow = even((size_t)nh * n3), n_ls = 2 * (size_t)nh * n3;
-  CtxTemp tmp(c, n_tw + n_part + n_pow + n_ls); if (!tmp.p) return 1;
-  real2 *d_tw = (real2 *)tmp.p; real *d_part = tmp.p + n_tw, *d_pow = d_part + n_part, *d_ls = d_pow + n_pow;
+  const size_t n_pow = (size_t)nh * n3, n_ls = 2 * n_pow;
+  TempCarver tc; const auto p_tw = tc.part<real2>(N); const auto p_part = tc.part<real>((size_t)n3 * sg.nb * 3 * nh), p_pow = tc.part<real>(n_pow), p_ls = tc.part<real>(n_ls);
+  CtxTemp tmp(c, tc.reals(sizeof(real))); if (!tmp.p) return 1;
+  real2 *d_tw = p_tw.in(tmp.p); real *d_part = p_part.in(tmp.p), *d_pow = p_pow.in(tmp.p), *d_ls = p_ls.in(tmp.p);
   { ProfScope ps(c, pl.direct ? "spectra_lines_direct" : "spectra_lines");
     LAUNCH(c, k_spec_twiddle, dim3((N + 255) / 256), dim3(256), 0, c->stream, N, d_tw);
     const dim3 grid(sg.nb, n3), block(256);
-    if (idir == 1) LAUNCH(c, k_spec_x<false>, grid, block, lds, c->stream, c->g, sg, pl, d_tw, (const int32_t *)nullptr, c->f[field], d_part, (real2 *)nullptr);
-    else LAUNCH(c, k_spec_y, grid, block, lds, c->stream, c->g, sg, pl, d_tw, c->f[field], d_part);
+    if (idir == 1) LAUNCH(c, k_spec_x<false>, grid, block, lds, c->stream, c->g, sg, pl, d_tw, (const int32_t *)nullptr, f, d_part, (real2 *)nullptr);
+    else LAUNCH(c, k_spec_y, grid, block, lds, c->stream, c->g, sg, pl, d_tw, f, d_part);
     LAUNCH(c, k_spec_fold, dim3((nh * n3 + 255) / 256), block, 0, c->stream, nh, sg.nb, n3, d_part, d_pow, d_ls); }
   LAUNCHCHK(c);
-  HIPCHK(c, hipMemcpyAsync(power, d_pow, (size_t)nh * n3 * sizeof(real), hipMemcpyDeviceToHost, c->stream));
-  if (lsum) HIPCHK(c, hipMemcpyAsync(lsum, d_ls, n_ls * sizeof(real), hipMemcpyDeviceToHost, c->stream));
+  if (int e = read_back_queued(c, power, d_pow, n_pow)) return e;
+  if (lsum) if (int e = read_back_queued(c, lsum, d_ls, n_ls)) return e;
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return 0;
 }
 
 int op_spectra_planes(cales_ctx *c, int field, int nplanes, const int32_t *kplanes, real *power2) {
   const char *who = "cales_spectra_planes";
-  if (spec_field(c, field, who)) return 1;
+  if (!field_ptr(c, field, who, FIELD_ROWS16)) return 1;
   if (c->P > 1) { c->err = std::string(who) + ": one rank only (a slab holds no whole y line)"; return 1; }
   const int n1 = c->n[0], n2 = c->n[1];
   if (spec_line_ok(c, n1, who) || spec_line_ok(c, n2, who)) return 1;
   if (!power2) { c->err = std::string(who) + ": power2 is NULL"; return 1; }
-  if (nplanes < 1) { c->err = std::string(who) + ": nplanes < 1"; return 1; }
-  if (!kplanes) { c->err = std::string(who) + ": kplanes is NULL"; return 1; }
-  for (int p = 0; p < nplanes; ++p) if (kplanes[p] < 1 || kplanes[p] > c->C.ng[2]) { c->err = std::string(who) + ": plane outside 1 ... ng(3)"; return 1; }
-  if (field == CALES_VISCT) if (int e = materialize_visct(c)) return e;
+  if (plane_list_check(who, nplanes, kplanes, c->C.ng[2], c->err)) return 1;
+  const real *f = field_ptr(c, field, who, FIELD_READ); if (!f) return 1;
   const SpecPlan plx = spec_plan(n1), ply = spec_plan(n2);
   const int nhx = n1 / 2 + 1, nhy = n2 / 2 + 1;
   // the complex rows of a plane take about as much as a plane of the field: as many planes at a time as 32 MB of scratch hold, one at least
@@ -366,22 +332,22 @@ int op_spectra_planes(cales_ctx *c, int field, int nplanes, const int32_t *kplan
   SpecGeom sy; sy.nl = spec_nl(n2); sy.nh = nhy; sy.rows = 0; sy.chunks = 0; sy.nb = (nhx + sy.nl - 1) / sy.nl;
   const size_t ldsx = spec_lds_bytes(sx.nl, n1), ldsy = spec_lds_bytes(sy.nl, n2);
   if (spec_lds_attr(c, k_spec_x<true>, ldsx) || spec_lds_attr(c, k_spec_y2, ldsy)) return 1;
-  // twiddles of x | of y | the complex rows of a chunk | its power2 | the planes (32-bit)
-  const size_t n_twx = 2 * (size_t)n1, n_twy = 2 * (size_t)n2, n_rows = 2 * plane_rows * chunk, n_out = even(plane_out * chunk);
-  const size_t n_k = even(((size_t)nplanes * sizeof(int32_t) + sizeof(real) - 1) / sizeof(real));
-  CtxTemp tmp(c, n_twx + n_twy + n_rows + n_out + n_k); if (!tmp.p) return 1;
-  real2 *d_twx = (real2 *)tmp.p, *d_twy = d_twx + n1, *d_rows = d_twy + n2;
-  real *d_out = tmp.p + n_twx + n_twy + n_rows; int32_t *d_k = (int32_t *)(d_out + n_out);
-  HIPCHK(c, hipMemcpyAsync(d_k, kplanes, (size_t)nplanes * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+  // twiddles of x | of y | the complex rows of a chunk | its power2 | the planes
+  TempCarver tc; const auto p_twx = tc.part<real2>(n1), p_twy = tc.part<real2>(n2), p_rows = tc.part<real2>(plane_rows * chunk);
+  const auto p_out = tc.part<real>(plane_out * chunk); const auto p_k = tc.part<int32_t>(nplanes);
+  CtxTemp tmp(c, tc.reals(sizeof(real))); if (!tmp.p) return 1;
+  real2 *d_twx = p_twx.in(tmp.p), *d_twy = p_twy.in(tmp.p), *d_rows = p_rows.in(tmp.p);
+  real *d_out = p_out.in(tmp.p); int32_t *d_k = p_k.in(tmp.p);
+  if (int e = plane_list_upload(c, d_k, kplanes, nplanes)) return e;
   { ProfScope ps(c, (plx.direct || ply.direct) ? "spectra_planes_direct" : "spectra_planes");
     const dim3 block(256);
     LAUNCH(c, k_spec_twiddle, dim3((n1 + 255) / 256), block, 0, c->stream, n1, d_twx);
     LAUNCH(c, k_spec_twiddle, dim3((n2 + 255) / 256), block, 0, c->stream, n2, d_twy);
     for (int p0 = 0; p0 < nplanes; p0 += chunk) {
       const int np = std::min(chunk, nplanes - p0);
-      LAUNCH(c, k_spec_x<true>, dim3(sx.nb, np), block, ldsx, c->stream, c->g, sx, plx, d_twx, (const int32_t *)(d_k + p0), c->f[field], (real *)nullptr, d_rows);
+      LAUNCH(c, k_spec_x<true>, dim3(sx.nb, np), block, ldsx, c->stream, c->g, sx, plx, d_twx, (const int32_t *)(d_k + p0), f, (real *)nullptr, d_rows);
       LAUNCH(c, k_spec_y2, dim3(sy.nb, np), block, ldsy, c->stream, nhx, sy, ply, d_twy, d_rows, d_out);
-      HIPCHK(c, hipMemcpyAsync(power2 + plane_out * p0, d_out, plane_out * np * sizeof(real), hipMemcpyDeviceToHost, c->stream));
+      if (int e = read_back_queued(c, power2 + plane_out * p0, d_out, plane_out * np)) return e;
     } }
   LAUNCHCHK(c);
   HIPCHK(c, hipStreamSynchronize(c->stream));

@@ -647,6 +647,7 @@ int op_stats_chan_budget(cales_ctx *c, real *budget, real *leak) {
     LAUNCH(c, k_stats_budget_partial, dim3(nbx, n3), dim3(256), 0, c->stream, c->g, c->dl[0], c->dl[1], c->d_dzc, c->d_dzf, c->f[CALES_U], c->f[CALES_V],
                        c->f[CALES_W], c->f[CALES_P], part);
     LAUNCH(c, k_stats_fold_n, dim3((NBUDGET * n3 + 255) / 256), dim3(256), 0, c->stream, NBUDGET, n3, nbx, ratio, part, out);
+    LAUNCHCHK(c);
     if (int e = read_back(c, budget, out, (size_t)NBUDGET * n3)) return e;
   }
   if (leak) {
@@ -654,9 +655,9 @@ int op_stats_chan_budget(cales_ctx *c, real *budget, real *leak) {
     real *part = tmp.p, *out = tmp.p + (size_t)3 * nbx * n3;
     LAUNCH(c, k_stats_leak_partial, dim3(nbx, n3), dim3(256), 0, c->stream, c->g, c->dl[0], c->dl[1], c->d_dzf, c->f[CALES_U], c->f[CALES_V], c->f[CALES_W], part);
     LAUNCH(c, k_stats_leak_fold, dim3((n3 + 63) / 64), dim3(64), 0, c->stream, n3, nbx, ratio, c->d_dzf, part, out);
+    LAUNCHCHK(c);
     if (int e = read_back(c, leak, out, (size_t)6 * n3)) return e;
   }
-  LAUNCHCHK(c);
   return 0;
 }
 
@@ -681,13 +682,13 @@ __global__ __launch_bounds__(256) void k_out1d(Geom g, int idir, real ratio, con
   if (threadIdx.x == 0) out[e - 1] = r * ratio;
 }
 int op_out1d(cales_ctx *c, int field, int idir, int use_dzc, real *buf) {
-  if (field < 0 || field >= CALES_NFIELDS || idir < 1 || idir > 3) { c->err = "cales_out1d: bad field or direction"; return 1; }
-  if (field == CALES_VISCT) if (int e = materialize_visct(c)) return e;
+  if (idir < 1 || idir > 3) { c->err = "cales_out1d: idir must be 1..3"; return 1; }
+  const real *f = field_ptr(c, field, "cales_out1d", FIELD_READ); if (!f) return 1;
   const int ne = c->n[idir - 1];
   CtxTemp tmp(c, (size_t)ne); real *out = tmp.p; if (!out) return 1;
   // grid_area_ratio of the reference: dl(1) dl(2) / (l(1) l(2)) along z, dl(1) / (l(1) l(3)) along y, dl(2) / (l(2) l(3)) along x
   const real ratio = idir == 3 ? c->dl[0] * c->dl[1] / (c->C.l[0] * c->C.l[1]) : idir == 2 ? c->dl[0] / (c->C.l[0] * c->C.l[2]) : c->dl[1] / (c->C.l[1] * c->C.l[2]);
-  LAUNCH(c, k_out1d, dim3(ne), dim3(256), 0, c->stream, c->g, idir, ratio, use_dzc ? c->d_dzc : c->d_dzf, c->f[field], out);
+  LAUNCH(c, k_out1d, dim3(ne), dim3(256), 0, c->stream, c->g, idir, ratio, use_dzc ? c->d_dzc : c->d_dzf, f, out);
   LAUNCHCHK(c);
   return read_back(c, buf, out, (size_t)ne);
 }

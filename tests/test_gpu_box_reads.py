@@ -140,6 +140,58 @@ def test_refusals_leave_the_context_usable(loaded):
     same(h.out2d("u", 2, ng[1]), ref["u"][1:-1, ng[1]:ng[1] + 1, 1:-1])
 
 
+def test_every_entry_refuses_a_field_id_the_context_cannot_resolve():
+    """Every entry of the C-ABI that takes a field id -- the four headers' -- resolves it through the one host-side check (field_ptr, api.hip) before
+    it launches anything: an id out of range (-1, CALES_NFIELDS) and dudtd, which a context with explicit diffusion did not allocate, are refused
+    with "<entry>: bad field id", nothing is allocated, no profile scope opens, and the context goes on to give the values numpy gives."""
+    from cales_amd import capi
+    from cales_amd.hotpath import HotPath
+    from tests.test_pdf_host import pdf_ref
+    ng = SLAB_NG      # the smallest explicit case of this file
+    h = HotPath(nosgs_channel(ng))
+    a = coded(ng); h.set("u", a)
+    L, H = h.L, h.h
+    i3 = lambda v: (C.c_int32 * 3)(*v)
+    buf = np.zeros(tuple(n + 2 for n in ng), order="F", dtype=capi.np_real)      # room for the reals of every entry below
+    ints = np.zeros(8 * 8 * 2 + 8 * ng[2] + 2 * ng[2], dtype=np.int64)
+    kp = np.asarray([2, 1], dtype=np.int32)
+    P, PC, PO, K = buf.ctypes.data_as(C.c_void_p), ints.ctypes.data_as(C.c_void_p), ints[128 + 8 * ng[2]:].ctypes.data_as(C.c_void_p), kp.ctypes.data_as(C.c_void_p)
+    U, cnt, mean = capi.FIELDS["u"], i3((0, 0, 0)), capi.c_real(0.)
+    entries = {
+        "cales_get_field": lambda f: L.cales_get_field(H, f, P),
+        "cales_set_field": lambda f: L.cales_set_field(H, f, P),
+        "cales_read_box": lambda f: L.cales_read_box(H, f, i3((1, 1, 1)), i3(ng), i3((1, 1, 1)), P, cnt),
+        "cales_boundp": lambda f: L.cales_boundp(H, f, 0),
+        "cales_bulk_mean": lambda f: L.cales_bulk_mean(H, f, 1, C.byref(mean)),
+        "cales_out1d": lambda f: L.cales_out1d(H, f, 3, 0, P),
+        "cales_pdf_planes": lambda f: L.cales_pdf_planes(H, f, 8, 0., 1., PC, PO),
+        "cales_jpdf_planes": lambda f: L.cales_jpdf_planes(H, f, U, 8, 0., 1., 0., 1., 2, K, PC, PO),
+        "cales_jpdf_planes (second field)": lambda f: L.cales_jpdf_planes(H, U, f, 8, 0., 1., 0., 1., 2, K, PC, PO),
+        "cales_spectra_lines": lambda f: L.cales_spectra_lines(H, f, 1, P, None),
+        "cales_spectra_planes": lambda f: L.cales_spectra_planes(H, f, 2, K, P),
+    }
+    assert capi.FIELDS["dudtd"] < len(capi.FIELDS) == 15
+    before = h.memory_in_use()
+    h.profile_reset(); h.profile(True)
+    for entry, call in entries.items():
+        for f in (capi.FIELDS["dudtd"], -1, len(capi.FIELDS)):
+            assert call(f) != 0, (entry, f)
+            assert L.cales_last_error(H).decode() == entry.split(" ")[0] + ": bad field id", (entry, f, L.cales_last_error(H))
+            assert h.memory_in_use() == before, (entry, f)
+    h.profile(False)
+    assert all(v[0] == 0 for v in h.profile_stats().values()), h.profile_stats()
+    assert not buf.any() and not ints.any()
+    # the context is as usable as before, and set_field has written nothing
+    prof = h.out1d("u", 3)
+    want = a[1:-1, 1:-1, 1:-1].mean(axis=(0, 1))      # (sums of integers: exact; the rounding is that of the grid ratio and the product)
+    assert np.abs(prof - want).max() <= 8 * np.finfo(capi.np_real).eps * np.abs(want).max()
+    counts, outside = h.pdf_planes("u", 64, 3000., 3000. + 64 * 256)
+    wc, wo = pdf_ref(np.asarray(a[1:-1, 1:-1, 1:-1], dtype=capi.np_real), 64, 3000., 3000. + 64 * 256)
+    assert np.array_equal(counts, wc) and np.array_equal(outside, wo) and counts.sum() > 0
+    assert h.memory_in_use() == before
+    h.close()
+
+
 @pytest.mark.parametrize("read_first", [False, True], ids=["get_first", "read_first"])
 def test_visct_is_materialised(read_first):
     """The dynamic model's tile passes leave visct = |S| cs(k) as |S| and the plane coefficients until somebody other than the momentum pass reads it:
