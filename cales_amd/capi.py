@@ -1,4 +1,5 @@
-"""ctypes binding of libcales_hip.so (C-ABI declared in include/cales.h, include/cales_post.h, include/cales_pdf.h and include/cales_spectra.h).
+"""ctypes binding of libcales_hip.so (C-ABI declared in include/cales.h, include/cales_post.h, include/cales_pdf.h, include/cales_spectra.h and
+include/cales_derived.h).
 
 There is no CPU fallback: if the HIP library has not been built, importing the symbols raises.
 """
@@ -65,6 +66,11 @@ PDF_MAX_BINS, JPDF_MAX_BINS = 4096, 128      # CALES_PDF_MAX_BINS, CALES_JPDF_MA
 # list of its own beside a header of its own (tests/test_spectra_host.py checks it against that header)
 SPECTRA_SYMBOLS = ["cales_spectra_lines", "cales_spectra_planes"]
 SPECTRA_MAX_LINE = 2048      # CALES_SPECTRA_MAX_LINE
+
+# every symbol include/cales_derived.h declares: vorticity, SijSij, WijWij and Q of the stored velocity (the reference's src/post.f90), formed on the device;
+# a fifth list beside a fifth header (tests/test_derived_host.py checks it against that header)
+DERIVED_SYMBOLS = ["cales_derived_box", "cales_derived_out2d", "cales_derived_out3d", "cales_derived_to_pp"]
+DERIVED = dict(vox=0, voy=1, voz=2, str=3, ens=4, qcr=5, vox_edge=6, voy_edge=7, voz_edge=8)      # enum cales_derived
 
 
 class CalesCase(C.Structure):
@@ -189,6 +195,15 @@ def lib() -> C.CDLL:
         for name, args in {      # include/cales_spectra.h (SPECTRA_SYMBOLS)
             "cales_spectra_lines": [C.c_void_p, C.c_int, C.c_int, dp, dp],
             "cales_spectra_planes": [C.c_void_p, C.c_int, C.c_int, dp, dp],
+        }.items():
+            fn = getattr(L, name)
+            fn.argtypes = args
+            fn.restype = C.c_int
+        for name, args in {      # include/cales_derived.h (DERIVED_SYMBOLS)
+            "cales_derived_box": [C.c_void_p, C.c_int, dp, dp, dp, dp, dp],
+            "cales_derived_out2d": [C.c_void_p, C.c_int, C.c_int, C.c_int, dp, dp],
+            "cales_derived_out3d": [C.c_void_p, C.c_int, dp, dp, dp],
+            "cales_derived_to_pp": [C.c_void_p, C.c_int],
         }.items():
             fn = getattr(L, name)
             fn.argtypes = args

@@ -5,6 +5,7 @@
 #include "../../include/cales_post.h"
 #include "../../include/cales_pdf.h"
 #include "../../include/cales_spectra.h"
+#include "../../include/cales_derived.h"
 #include <algorithm>
 #include <atomic>
 
@@ -509,6 +510,49 @@ int cales_spectra_lines(cales_ctx *c, int field, int idir, real *power, real *ls
 int cales_spectra_planes(cales_ctx *c, int field, int nplanes, const int32_t *kplanes, real *power2) {
   if (!c) return 1;
   ENTRY(c, op_spectra_planes(c, field, nplanes, kplanes, power2));
+}
+// include/cales_derived.h (k_derived.hip)
+static int derived_quantity_ok(cales_ctx *c, int quantity, const char *who) {
+  if (quantity >= 0 && quantity < CALES_NDERIVED) return 1;
+  c->err = std::string(who) + ": unknown quantity";
+  return 0;
+}
+int cales_derived_box(cales_ctx *c, int quantity, const int32_t lo[3], const int32_t hi[3], const int32_t nskip[3], real *buf, int32_t count[3]) {
+  if (!c) return 1;
+  ENTER(c);
+  if (!derived_quantity_ok(c, quantity, "cales_derived_box")) return 1;
+  int32_t first[3], cnt[3];
+  if (int e = box_share(&c->C, lo, hi, nskip, first, cnt, c->err)) return e;
+  for (int d = 0; d < 3; ++d) if (lo[d] < 1 || hi[d] > c->C.ng[d]) {      // (the quantities are those of interior cells)
+    c->err = std::string("derived box: ") + (lo[d] < 1 ? "lo < 1 in " : "hi > ng in ") + "xyz"[d]; return 1;
+  }
+  if (count) for (int d = 0; d < 3; ++d) count[d] = cnt[d];
+  if ((size_t)cnt[0] * (size_t)cnt[1] * (size_t)cnt[2] == 0) return 0;
+  if (!buf) { c->err = "derived box: buf is NULL"; return 1; }
+  if (int e = op_derived_box(c, quantity, first, cnt, nskip, buf)) return e;
+  LAUNCHCHK(c);
+  return 0;
+}
+int cales_derived_out2d(cales_ctx *c, int quantity, int inorm, int islice, real *buf, int32_t count[3]) {
+  if (!c) return 1;
+  ENTER(c);
+  if (inorm < 1 || inorm > 3) { c->err = "derived out2d: inorm must be 1..3"; return 1; }
+  if (islice < 1 || islice > c->C.ng[inorm - 1]) { c->err = "derived out2d: islice outside 1..ng"; return 1; }
+  int32_t lo[3] = {1, 1, 1}, hi[3] = {c->C.ng[0], c->C.ng[1], c->C.ng[2]};
+  const int32_t one[3] = {1, 1, 1};
+  lo[inorm - 1] = hi[inorm - 1] = islice;
+  return cales_derived_box(c, quantity, lo, hi, one, buf, count);
+}
+int cales_derived_out3d(cales_ctx *c, int quantity, const int32_t nskip[3], real *buf, int32_t count[3]) {
+  if (!c) return 1;
+  const int32_t lo[3] = {1, 1, 1};
+  return cales_derived_box(c, quantity, lo, c->C.ng, nskip, buf, count);
+}
+int cales_derived_to_pp(cales_ctx *c, int quantity) {
+  if (!c) return 1;
+  ENTER(c);
+  if (!derived_quantity_ok(c, quantity, "cales_derived_to_pp")) return 1;
+  ENTRY(c, op_derived_to_pp(c, quantity));
 }
 
 // ------------------------------------------------------------------------------------------ time step (main.f90:412-508)

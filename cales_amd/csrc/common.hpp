@@ -87,7 +87,7 @@ struct Spec {
 
 // Run-time switches: read from the environment ONCE, by cales_create; the launch path only looks at these fields.
 struct Flags {
-  bool unfolded_correc = false, unfolded_mom = false, eager_projection = false, lazy_projection = false, helmholtz_z_per_column = false, unfused_imp_rhs = false, unfused_correc = false, unfused_forcing = false, unfused_fillps = false, unfused_mean = false, keep_last_rhs = false, wide_offsets = false, dsmag_reference_sequence = false, dsmag_xghosts = false, smag_reference_sequence = false, gaussel_march = false, fft_generic = false, fft_no_odd_radix = false, keep_null_mode = false, unfused_rk = false, overlap = false, xghosts_in_step = false, unmerged_bc = false, no_nyquist_packing = false, sgs_six_components = false, lmf_unpacked_remainder = false, lmf_main_bands = false;
+  bool unfolded_correc = false, unfolded_mom = false, eager_projection = false, lazy_projection = false, helmholtz_z_per_column = false, unfused_imp_rhs = false, unfused_correc = false, unfused_forcing = false, unfused_fillps = false, unfused_mean = false, keep_last_rhs = false, wide_offsets = false, dsmag_reference_sequence = false, dsmag_xghosts = false, smag_reference_sequence = false, gaussel_march = false, fft_generic = false, fft_no_odd_radix = false, keep_null_mode = false, unfused_rk = false, overlap = false, xghosts_in_step = false, unmerged_bc = false, no_nyquist_packing = false, sgs_six_components = false, lmf_unpacked_remainder = false, lmf_main_bands = false, derived_points = false;
   int kchunk = 0; long tile_min_blocks = 2048;
   std::string test_bad_launch;      // CALES_TEST_BAD_LAUNCH: test hook of the launch check (LAUNCH below)
   void read_env() {
@@ -121,6 +121,7 @@ struct Flags {
     // ranks of the tests cannot show a gain, and the in-order exchanges are the form with the fewest assumptions (CALES_NO_OVERLAP wins)
     overlap = getenv("CALES_OVERLAP") != nullptr && atoi(getenv("CALES_OVERLAP")) != 0 && getenv("CALES_NO_OVERLAP") == nullptr;
     unmerged_bc = getenv("CALES_UNMERGED_BC") != nullptr;
+    derived_points = getenv("CALES_DERIVED_POINTS") != nullptr && atoi(getenv("CALES_DERIVED_POINTS")) != 0;      // derived fields (include/cales_derived.h): dense boxes too by the one-thread-per-point kernel instead of the LDS-tile form (k_derived.hip)
     kchunk = getenv("CALES_KCHUNK") ? atoi(getenv("CALES_KCHUNK")) : 0;
     tile_min_blocks = getenv("CALES_TILE_MIN_BLOCKS") ? atol(getenv("CALES_TILE_MIN_BLOCKS")) : 2048;
   }
@@ -518,6 +519,10 @@ int op_jpdf_planes(cales_ctx *c, int field_a, int field_b, int nbins, real lo_a,
 // include/cales_spectra.h (k_spectra.hip): power spectra of a field along x or y on every plane, and in chosen x-y planes; synchronous
 int op_spectra_lines(cales_ctx *c, int field, int idir, real *power, real *lsum);
 int op_spectra_planes(cales_ctx *c, int field, int nplanes, const int32_t *kplanes, real *power2);
+// include/cales_derived.h (k_derived.hip): vorticity, SijSij, WijWij and Q of the stored velocity, as a strided box for the host or into the interior of pp; synchronous
+// (first, count: the rank's share of the box as cales_box_share gives it, checked by the entry -- interior cells only, first in GLOBAL indices)
+int op_derived_box(cales_ctx *c, int quantity, const int32_t *first, const int32_t *count, const int32_t *nskip, real *buf);
+int op_derived_to_pp(cales_ctx *c, int quantity);
 bool solver_can_fuse_fillps(cales_ctx *c);
 int solver_mode_columns(cales_ctx *c);      // complex mode columns per rank of the pressure solve
 std::string solver_path_name(cales_ctx *c);      // which transform / tridiagonal kernels the pressure solve of this context takes (cales_describe_plan)

@@ -1,4 +1,4 @@
-! ISO_C_BINDING view of include/cales.h, include/cales_post.h, include/cales_pdf.h and include/cales_spectra.h -- what a Fortran host (the reference's own language) binds to.
+! ISO_C_BINDING view of include/cales.h, include/cales_post.h, include/cales_pdf.h, include/cales_spectra.h and include/cales_derived.h -- what a Fortran host (the reference's own language) binds to.
 ! `type(cales_case)` mirrors `struct cales_case`; character and multi-dimensional members keep the
 ! storage order of the reference's namelist variables (src/param.f90:37-76), so they are copied unchanged.
 module cales_c
@@ -16,6 +16,9 @@ module cales_c
   integer(c_int32_t), parameter :: CALES_SGS_AVE_VOLUME = 4, CALES_SGS_AVE_XLINES = 8
   ! ... and the flag for no averaging at all (the reference's _CAVITY), declared on its own in include/cales.h as well
   integer(c_int32_t), parameter :: CALES_SGS_AVE_LOCAL = 64
+  ! enum cales_derived of include/cales_derived.h
+  integer(c_int), parameter :: CALES_DERIVED_VOX = 0, CALES_DERIVED_VOY = 1, CALES_DERIVED_VOZ = 2, CALES_DERIVED_STR = 3, CALES_DERIVED_ENS = 4, &
+                               CALES_DERIVED_QCR = 5, CALES_DERIVED_VOX_EDGE = 6, CALES_DERIVED_VOY_EDGE = 7, CALES_DERIVED_VOZ_EDGE = 8
   type, bind(C) :: cales_case
     integer(c_int32_t) :: ng(3)
     real(c_rp)     :: l(3)
@@ -199,6 +202,22 @@ module cales_c
     integer(c_int) function cales_spectra_planes(ctx,field,nplanes,kplanes,power2) bind(C,name='cales_spectra_planes')
       import; type(c_ptr), value :: ctx; integer(c_int), value :: field,nplanes
       integer(c_int32_t), intent(in) :: kplanes(*); real(c_rp) :: power2(*)
+    end function
+    ! ---- include/cales_derived.h: vorticity, SijSij, WijWij and Q of the stored velocity (src/post.f90), formed on the device at interior cells; `quantity` one
+    ! of CALES_DERIVED_* above. Boxes, planes and strided samples as cales_read_box / cales_out2d / cales_out3d give them; to_pp overwrites the interior of CALES_PP
+    integer(c_int) function cales_derived_box(ctx,quantity,lo,hi,nskip,buf,count) bind(C,name='cales_derived_box')
+      import; type(c_ptr), value :: ctx; integer(c_int), value :: quantity; integer(c_int32_t), intent(in) :: lo(3),hi(3),nskip(3)
+      real(c_rp) :: buf(*); integer(c_int32_t) :: count(3)
+    end function
+    integer(c_int) function cales_derived_out2d(ctx,quantity,inorm,islice,buf,count) bind(C,name='cales_derived_out2d')
+      import; type(c_ptr), value :: ctx; integer(c_int), value :: quantity,inorm,islice; real(c_rp) :: buf(*); integer(c_int32_t) :: count(3)
+    end function
+    integer(c_int) function cales_derived_out3d(ctx,quantity,nskip,buf,count) bind(C,name='cales_derived_out3d')
+      import; type(c_ptr), value :: ctx; integer(c_int), value :: quantity; integer(c_int32_t), intent(in) :: nskip(3)
+      real(c_rp) :: buf(*); integer(c_int32_t) :: count(3)
+    end function
+    integer(c_int) function cales_derived_to_pp(ctx,quantity) bind(C,name='cales_derived_to_pp')
+      import; type(c_ptr), value :: ctx; integer(c_int), value :: quantity
     end function
   end interface
 end module cales_c

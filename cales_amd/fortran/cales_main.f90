@@ -21,6 +21,9 @@
 !              directions sgstype = 'dsmag' averages the Germano identity over (src/sgs.f90:359-370); no effect on 'none' and 'smag'
 !              CALES_OUT3D_NSKIP = "a,b,c": the nskip of the volume dumps, which the reference hard-codes as [1,1,1] in its out3d.h90; with a value > 1
 !              the dumps hold the interior points 1, 1+nskip, ... of every direction, read strided from the device (cales_out3d)
+!              CALES_OUT3D_DERIVED = "vox,qcr": quantities of src/post.f90 dumped with the volumes every iout3d steps, as a case of the reference does by pasting
+!              utils/useful_fortran_blocks/vorticity-inc.f90 / q-criterion-inc.f90 into its out3d.h90 -- any of vox, voy, voz (Vorticity_X/Y/Z), qcr (Q-criterion),
+!              str (SijSij), ens (WijWij), formed on the device (cales_derived_out3d) and written as <name>_fld_NNNNNNN.bin with CALES_OUT3D_NSKIP honoured
 program cales
   use, intrinsic :: iso_c_binding
   use, intrinsic :: iso_fortran_env, only: int64
@@ -66,6 +69,11 @@ program cales
   integer :: f2dlen,f2dstat,avelen,avestat
   character(len=64) :: skp
   integer :: skplen,skpstat,nskip3d(3)
+  character(len=64) :: dlist                                   ! CALES_OUT3D_DERIVED
+  integer :: dlen,dstat,nderived,dq(6),ia,ib,iq
+  character(len=3),  parameter :: dnames(6) = ['vox','voy','voz','qcr','str','ens']
+  character(len=11), parameter :: dvars(6) = ['Vorticity_X','Vorticity_Y','Vorticity_Z','Q-criterion','SijSij     ','WijWij     ']
+  integer(c_int),    parameter :: dids(6) = [CALES_DERIVED_VOX,CALES_DERIVED_VOY,CALES_DERIVED_VOZ,CALES_DERIVED_QCR,CALES_DERIVED_STR,CALES_DERIVED_ENS]
   character(len=100) :: filename
   character(len=7) :: fldnum
   character(len=4) :: chkptnum
@@ -165,6 +173,28 @@ program cales
     end if
   else if(skpstat < 0) then
     if(myid == 0) print*, 'ERROR: CALES_OUT3D_NSKIP is too long'
+    call die
+  end if
+  nderived = 0
+  call get_environment_variable('CALES_OUT3D_DERIVED',dlist,dlen,dstat)           ! derived quantities dumped with the volumes
+  if(dstat == 0 .and. dlen > 0) then
+    ia = 1
+    do while(ia <= dlen)
+      ib = index(dlist(ia:dlen),',')
+      ib = merge(dlen,ia+ib-2,ib == 0)
+      m = 0
+      do iq=1,size(dnames)
+        if(ib-ia+1 == 3 .and. dlist(ia:ib) == dnames(iq)) m = iq
+      end do
+      if(m == 0 .or. nderived == size(dq)) then
+        if(myid == 0) print*, 'ERROR: CALES_OUT3D_DERIVED must be a comma-separated list of vox, voy, voz, qcr, str, ens'
+        call die
+      end if
+      nderived = nderived + 1; dq(nderived) = m
+      ia = ib + 2
+    end do
+  else if(dstat < 0) then
+    if(myid == 0) print*, 'ERROR: CALES_OUT3D_DERIVED is too long'
     call die
   end if
   cs%lwm = reshape(lwm,[6]); cs%hwm = hwm; cs%impdiff = impdiff; cs%nranks = nranks; cs%rank = myid
@@ -384,6 +414,11 @@ contains
       call visu_3d_every('vez_fld_'//fldnum//'.bin','Velocity_Z',CALES_W); call visu_3d_every('pre_fld_'//fldnum//'.bin','Pressure',CALES_P)
       call visu_3d_every('visct_fld_'//fldnum//'.bin','Viscosity',CALES_VISCT)
     end if
+    if(do3d) then     ! vorticity-inc.f90 / q-criterion-inc.f90 in out3d.h90: the quantities of CALES_OUT3D_DERIVED, formed on the device
+      do m=1,nderived
+        call visu_3d_every(dnames(dq(m))//'_fld_'//fldnum//'.bin',trim(dvars(dq(m))),dids(dq(m)),.true.)
+      end do
+    end if
   end subroutine write_outputs
   subroutine chk(ist)
     integer(c_int), intent(in) :: ist
@@ -455,9 +490,10 @@ contains
     close(iu)
     call visu_log('log_visu_3d.out',fbin,varname,[1,1,1],ng,[1,1,1])
   end subroutine visu_3d
-  subroutine visu_3d_every(fbin,varname,ifld)    ! write_visu_3d with nskip > 1 somewhere: decomp_2d_write_every(...,.true.) of out3d, src/output.f90:191-242
+  subroutine visu_3d_every(fbin,varname,ifld,derived)    ! write_visu_3d with nskip > 1 somewhere: decomp_2d_write_every(...,.true.) of out3d, src/output.f90:191-242
     character(len=*), intent(in) :: fbin,varname
-    integer(c_int), intent(in) :: ifld
+    integer(c_int), intent(in) :: ifld                         ! a field, or with `derived` a quantity of include/cales_derived.h (any nskip)
+    logical, intent(in), optional :: derived
     real(rp), allocatable :: buf(:,:,:)
     integer(c_int32_t) :: one(3),skp3(3),top(3),first(3),cnt(3)
     integer(int64) :: pos
@@ -465,7 +501,11 @@ contains
     one(:) = 1; skp3(:) = nskip3d(:); top(:) = ng(:)
     call chk(cales_box_share(cs,one,top,skp3,first,cnt))      ! this rank's points: how many, and where they start
     allocate(buf(cnt(1),max(cnt(2),1),cnt(3)))
-    call chk(cales_out3d(ctx,ifld,skp3,buf,cnt))
+    if(present(derived)) then
+      call chk(cales_derived_out3d(ctx,ifld,skp3,buf,cnt))
+    else
+      call chk(cales_out3d(ctx,ifld,skp3,buf,cnt))
+    end if
     n2every = (ng(2)-1)/nskip3d(2) + 1                        ! rows of the file; this rank's start at row (first(2)-1)/nskip
     call open_shared(fbin,iu)
     if(cnt(2) > 0) then

@@ -100,6 +100,10 @@ def box_share(case: Case, lo, hi, nskip=(1, 1, 1), nranks: int = 1, rank: int = 
     return _box_share(capi.make_case(case, nranks, rank), lo, hi, nskip)
 
 
+def _derived_id(quantity) -> int:
+    return capi.DERIVED[quantity] if isinstance(quantity, str) else int(quantity)
+
+
 class HotPath:
     def __init__(self, case: Case, nranks: int = 1, rank: int = 0, stream: int | None = None):
         self.case = case
@@ -214,6 +218,36 @@ class HotPath:
         power2 = np.zeros((self.n[0] // 2 + 1, self.n[1] // 2 + 1, max(kp.size, 1)) if ok else (1, 1, 1), order="F", dtype=REAL)
         self._chk(self.L.cales_spectra_planes(self.h, capi.FIELDS[name], int(kp.size), kp.ctypes.data_as(C.c_void_p), _p(power2)))
         return power2
+
+    # -- derived fields (include/cales_derived.h): `quantity` a name of capi.DERIVED (or its number); this rank's share, Fortran-ordered, interior cells only
+    def derived_box(self, quantity, lo, hi, nskip=(1, 1, 1)) -> np.ndarray:
+        """cales_derived_box: the quantity at the points lo + m nskip <= hi, GLOBAL indices 1 ... ng (box_share tells where a rank's share starts)."""
+        a = np.zeros(_box_share(self.cs, lo, hi, nskip)[1], order="F", dtype=REAL)
+        self._chk(self.L.cales_derived_box(self.h, _derived_id(quantity), _i3(lo), _i3(hi), _i3(nskip), _p(a), None))
+        return a
+
+    def derived_out2d(self, quantity, inorm: int, islice: int) -> np.ndarray:
+        """cales_derived_out2d: the quantity on the interior plane of global index `islice` normal to direction `inorm` (1, 2, 3), shape 1 in that direction."""
+        ng = [int(x) for x in self.case.ng]
+        lo, hi = [1, 1, 1], list(ng)
+        if 1 <= int(inorm) <= 3 and 1 <= int(islice) <= ng[int(inorm) - 1]:      # (anything else: the library refuses it below, nothing is read)
+            lo[int(inorm) - 1] = hi[int(inorm) - 1] = int(islice)
+            a = np.zeros(_box_share(self.cs, lo, hi, (1, 1, 1))[1], order="F", dtype=REAL)
+        else:
+            a = np.zeros((1, 1, 1), order="F", dtype=REAL)
+        self._chk(self.L.cales_derived_out2d(self.h, _derived_id(quantity), int(inorm), int(islice), _p(a), None))
+        return a
+
+    def derived_out3d(self, quantity, nskip=(1, 1, 1)) -> np.ndarray:
+        """cales_derived_out3d: the quantity at the interior points 1, 1 + nskip, 1 + 2 nskip ... of every direction."""
+        a = np.zeros(_box_share(self.cs, (1, 1, 1), [int(x) for x in self.case.ng], nskip)[1], order="F", dtype=REAL)
+        self._chk(self.L.cales_derived_out3d(self.h, _derived_id(quantity), _i3(nskip), _p(a), None))
+        return a
+
+    def derived_to_pp(self, quantity):
+        """cales_derived_to_pp: the quantity into the interior of field pp, which it OVERWRITES (ghost cells untouched): read_box, pdf_planes, jpdf_planes,
+        spectra_lines ... on "pp" then work on the derived field."""
+        self._chk(self.L.cales_derived_to_pp(self.h, _derived_id(quantity)))
 
     def upload(self, u, v, w, p):
         a = [_In(x) for x in (u, v, w, p)]
