@@ -258,21 +258,19 @@ __global__ __launch_bounds__(256) void k_copy_ghosts(Geom g, GhostCopy G) {     
 // ---- which k_momrk a call launches. The 64 instantiations: IMP x offset type x NOS x RD x WR without a pending projection (48), and with one
 // the two forms that exist -- explicit with the pressure update inside (IMP = 0, CORR = 1), z-implicit with the velocity only (IMP = 2, CORR = 2), both
 // without subgrid model -- x offset type x RD x WR (16). corr is 0 or the CORR of those two (op_momrk refuses a pending projection on any other form)
-typedef void (*MomRkKernel)(Geom, MomRkArgs);
-template <typename OFF, int RD, int WR> static MomRkKernel momrk_form(int imp, bool nos, int corr) {
-  if (corr) return corr == 2 ? k_momrk<2, OFF, 1, RD, WR, 2> : k_momrk<0, OFF, 1, RD, WR, 1>;
-  if (imp == 2) return nos ? k_momrk<2, OFF, 1, RD, WR> : k_momrk<2, OFF, 0, RD, WR>;
-  if (imp == 1) return nos ? k_momrk<1, OFF, 1, RD, WR> : k_momrk<1, OFF, 0, RD, WR>;
-  return nos ? k_momrk<0, OFF, 1, RD, WR> : k_momrk<0, OFF, 0, RD, WR>;
-}
-template <int RD, int WR> static MomRkKernel momrk_offsets(bool small, int imp, bool nos, int corr) {
-  return small ? momrk_form<unsigned, RD, WR>(imp, nos, corr) : momrk_form<size_t, RD, WR>(imp, nos, corr);
-}
+using MomRkKernelRec = KernelRec<void(Geom, MomRkArgs)>;
+// the eight forms of one (offset type, RD, WR) under the names the launch check reports: 2 imp + nos, then CORR = 1 and CORR = 2
+#define MOMRK_FORMS(OFF, RD, WR) {KERNEL_REC(k_momrk<0, OFF, 0, RD, WR, 0>), KERNEL_REC(k_momrk<0, OFF, 1, RD, WR, 0>), KERNEL_REC(k_momrk<1, OFF, 0, RD, WR, 0>), \
+                                  KERNEL_REC(k_momrk<1, OFF, 1, RD, WR, 0>), KERNEL_REC(k_momrk<2, OFF, 0, RD, WR, 0>), KERNEL_REC(k_momrk<2, OFF, 1, RD, WR, 0>), \
+                                  KERNEL_REC(k_momrk<0, OFF, 1, RD, WR, 1>), KERNEL_REC(k_momrk<2, OFF, 1, RD, WR, 2>)}
+#define MOMRK_RD_WR(OFF) {{MOMRK_FORMS(OFF, 0, 0), MOMRK_FORMS(OFF, 0, 1)}, {MOMRK_FORMS(OFF, 1, 0), MOMRK_FORMS(OFF, 1, 1)}}
 // (read the old r.h.s., store the new one): (0,1) first substep, (1,1) second, (1,0) third inside cales_step; (0,0) a first substep whose r.h.s. nobody keeps
-static MomRkKernel momrk_kernel(const MomPath &M, bool nos, bool rd, bool wr, int corr) {
-  return rd ? (wr ? momrk_offsets<1, 1>(M.small, M.imp, nos, corr) : momrk_offsets<1, 0>(M.small, M.imp, nos, corr))
-            : (wr ? momrk_offsets<0, 1>(M.small, M.imp, nos, corr) : momrk_offsets<0, 0>(M.small, M.imp, nos, corr));
+static MomRkKernelRec momrk_kernel(const MomPath &M, bool nos, bool rd, bool wr, int corr) {
+  static const MomRkKernelRec t[2][2][2][8] = {MOMRK_RD_WR(size_t), MOMRK_RD_WR(unsigned)};      // [small][rd][wr][form]
+  return t[M.small][rd][wr][corr ? 5 + corr : 2 * M.imp + nos];
 }
+#undef MOMRK_RD_WR
+#undef MOMRK_FORMS
 void mom_setup(cales_ctx *c) {
   MomPath &M = c->mom;
   M.fused = !c->fl.unfused_rk; M.imp = c->C.impdiff;
@@ -315,8 +313,8 @@ int op_momrk(cales_ctx *c, real f1, real f2, real f12, const RkOpts &o) {
     // or 3, 5, 9 times one: solver_can_fuse_fillps), hence an even n1, so nothing reaches this today; the kernel's assumption is enforced here rather than left to that coincidence
     if (A.perx && n[0] % 64 == 63) { c->err = "momrk: the folded projection with wrapped x columns needs n1 % 64 != 63"; return 1; }
   }
-  const MomRkKernel k_momrk_form = momrk_kernel(M, nos, A.rd_old, A.wr_new, !pj ? 0 : pdone ? 2 : 1);
-  LAUNCH(c, k_momrk_form, M.geo.grid, M.geo.block, 0, c->stream, c->g, A);
+  const MomRkKernelRec k_momrk_form = momrk_kernel(M, nos, A.rd_old, A.wr_new, !pj ? 0 : pdone ? 2 : 1);
+  LAUNCH_REC(c, k_momrk_form, M.geo.grid, M.geo.block, 0, c->stream, c->g, A);
   LAUNCHCHK(c);
   if (M.wm && (!c->in_step || M.wm_ghosts_in_step)) {
     GhostCopy G; for (int q = 0; q < 3; ++q) { G.src[q] = c->f[CALES_U + q]; G.dst[q] = c->f2[q]; }
