@@ -1,4 +1,4 @@
-"""ctypes binding of libcales_hip.so (C-ABI declared in include/cales.h, include/cales_post.h, include/cales_pdf.h, include/cales_spectra.h and
+"""ctypes binding of libcales_hip.so (C-ABI declared in include/cales.h, include/cales_post.h, include/cales_pdf.h, include/cales_spectra.h, include/cales_cospectra.h and
 include/cales_derived.h).
 
 There is no CPU fallback: if the HIP library has not been built, importing the symbols raises.
@@ -66,6 +66,10 @@ PDF_MAX_BINS, JPDF_MAX_BINS = 4096, 128      # CALES_PDF_MAX_BINS, CALES_JPDF_MA
 # list of its own beside a header of its own (tests/test_spectra_host.py checks it against that header)
 SPECTRA_SYMBOLS = ["cales_spectra_lines", "cales_spectra_planes"]
 SPECTRA_MAX_LINE = 2048      # CALES_SPECTRA_MAX_LINE
+
+# every symbol include/cales_cospectra.h declares: cross-spectra of two fields sampled at the same index, along x, along y and in x-y planes; a sixth
+# list beside a sixth header (tests/test_cospectra_host.py checks it against that header)
+COSPECTRA_SYMBOLS = ["cales_cospectra_lines", "cales_cospectra_planes"]
 
 # every symbol include/cales_derived.h declares: vorticity, SijSij, WijWij and Q of the stored velocity (the reference's src/post.f90), formed on the device;
 # a fifth list beside a fifth header (tests/test_derived_host.py checks it against that header)
@@ -195,6 +199,13 @@ def lib() -> C.CDLL:
         for name, args in {      # include/cales_spectra.h (SPECTRA_SYMBOLS)
             "cales_spectra_lines": [C.c_void_p, C.c_int, C.c_int, dp, dp],
             "cales_spectra_planes": [C.c_void_p, C.c_int, C.c_int, dp, dp],
+        }.items():
+            fn = getattr(L, name)
+            fn.argtypes = args
+            fn.restype = C.c_int
+        for name, args in {      # include/cales_cospectra.h (COSPECTRA_SYMBOLS)
+            "cales_cospectra_lines": [C.c_void_p, C.c_int, C.c_int, C.c_int, dp, dp, dp],
+            "cales_cospectra_planes": [C.c_void_p, C.c_int, C.c_int, C.c_int, dp, dp],
         }.items():
             fn = getattr(L, name)
             fn.argtypes = args

@@ -5,6 +5,7 @@
 #include "../../include/cales_post.h"
 #include "../../include/cales_pdf.h"
 #include "../../include/cales_spectra.h"
+#include "../../include/cales_cospectra.h"
 #include "../../include/cales_derived.h"
 #include <algorithm>
 #include <atomic>
@@ -510,6 +511,15 @@ int cales_spectra_lines(cales_ctx *c, int field, int idir, real *power, real *ls
 int cales_spectra_planes(cales_ctx *c, int field, int nplanes, const int32_t *kplanes, real *power2) {
   if (!c) return 1;
   ENTRY(c, op_spectra_planes(c, field, nplanes, kplanes, power2));
+}
+// include/cales_cospectra.h (k_cospectra.hip)
+int cales_cospectra_lines(cales_ctx *c, int field_a, int field_b, int idir, real *cross, real *lsum_a, real *lsum_b) {
+  if (!c) return 1;
+  ENTRY(c, op_cospectra_lines(c, field_a, field_b, idir, cross, lsum_a, lsum_b));
+}
+int cales_cospectra_planes(cales_ctx *c, int field_a, int field_b, int nplanes, const int32_t *kplanes, real *cross2) {
+  if (!c) return 1;
+  ENTRY(c, op_cospectra_planes(c, field_a, field_b, nplanes, kplanes, cross2));
 }
 // include/cales_derived.h (k_derived.hip)
 static int derived_quantity_ok(cales_ctx *c, int quantity, const char *who) {

@@ -519,6 +519,9 @@ int op_jpdf_planes(cales_ctx *c, int field_a, int field_b, int nbins, real lo_a,
 // include/cales_spectra.h (k_spectra.hip): power spectra of a field along x or y on every plane, and in chosen x-y planes; synchronous
 int op_spectra_lines(cales_ctx *c, int field, int idir, real *power, real *lsum);
 int op_spectra_planes(cales_ctx *c, int field, int nplanes, const int32_t *kplanes, real *power2);
+// include/cales_cospectra.h (k_cospectra.hip): cross-spectra of two fields sampled at the same index, along x or y on every plane and in chosen x-y planes; synchronous
+int op_cospectra_lines(cales_ctx *c, int field_a, int field_b, int idir, real *cross, real *lsum_a, real *lsum_b);
+int op_cospectra_planes(cales_ctx *c, int field_a, int field_b, int nplanes, const int32_t *kplanes, real *cross2);
 // include/cales_derived.h (k_derived.hip): vorticity, SijSij, WijWij and Q of the stored velocity, as a strided box for the host or into the interior of pp; synchronous
 // (first, count: the rank's share of the box as cales_box_share gives it, checked by the entry -- interior cells only, first in GLOBAL indices)
 int op_derived_box(cales_ctx *c, int quantity, const int32_t *first, const int32_t *count, const int32_t *nskip, real *buf);

@@ -1,4 +1,4 @@
-! ISO_C_BINDING view of include/cales.h, include/cales_post.h, include/cales_pdf.h, include/cales_spectra.h and include/cales_derived.h -- what a Fortran host (the reference's own language) binds to.
+! ISO_C_BINDING view of include/cales.h, include/cales_post.h, include/cales_pdf.h, include/cales_spectra.h, include/cales_cospectra.h and include/cales_derived.h -- what a Fortran host (the reference's own language) binds to.
 ! `type(cales_case)` mirrors `struct cales_case`; character and multi-dimensional members keep the
 ! storage order of the reference's namelist variables (src/param.f90:37-76), so they are copied unchanged.
 module cales_c
@@ -202,6 +202,17 @@ module cales_c
     integer(c_int) function cales_spectra_planes(ctx,field,nplanes,kplanes,power2) bind(C,name='cales_spectra_planes')
       import; type(c_ptr), value :: ctx; integer(c_int), value :: field,nplanes
       integer(c_int32_t), intent(in) :: kplanes(*); real(c_rp) :: power2(*)
+    end function
+    ! ---- include/cales_cospectra.h: the same sums for two fields sampled at the same index: cross(2,n/2+1,n3) = sum over the lines of F_a conj(F_b), real
+    ! and imaginary part (co-spectrum and quadrature spectrum), lsum_a, lsum_b(2,n/2+1,n3) the line sums of either field (always written through this
+    ! interface); cross2(2,n1/2+1,n2/2+1,nplanes) with ky and n2-ky added. idir = 2 and the planes: one rank only
+    integer(c_int) function cales_cospectra_lines(ctx,field_a,field_b,idir,cross,lsum_a,lsum_b) bind(C,name='cales_cospectra_lines')
+      import; type(c_ptr), value :: ctx; integer(c_int), value :: field_a,field_b,idir
+      real(c_rp) :: cross(*),lsum_a(*),lsum_b(*)
+    end function
+    integer(c_int) function cales_cospectra_planes(ctx,field_a,field_b,nplanes,kplanes,cross2) bind(C,name='cales_cospectra_planes')
+      import; type(c_ptr), value :: ctx; integer(c_int), value :: field_a,field_b,nplanes
+      integer(c_int32_t), intent(in) :: kplanes(*); real(c_rp) :: cross2(*)
     end function
     ! ---- include/cales_derived.h: vorticity, SijSij, WijWij and Q of the stored velocity (src/post.f90), formed on the device at interior cells; `quantity` one
     ! of CALES_DERIVED_* above. Boxes, planes and strided samples as cales_read_box / cales_out2d / cales_out3d give them; to_pp overwrites the interior of CALES_PP

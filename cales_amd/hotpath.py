@@ -24,11 +24,18 @@ class CalesError(RuntimeError):
 
 
 REAL = capi.np_real      # numpy dtype of rp: float64, or float32 with CALES_PRECISION=single (capi.py)
+_COMPLEX = np.result_type(REAL, np.complex64)      # a pair of rp: complex128, or complex64
 
 
 def _p(a: np.ndarray):
     if a.dtype != REAL or not (a.flags.f_contiguous or a.ndim == 1):
         raise ValueError(f"fields must be Fortran-ordered {np.dtype(REAL).name} arrays")
+    return a.ctypes.data_as(C.c_void_p)
+
+
+def _pc(a: np.ndarray):
+    """a Fortran-ordered array of _COMPLEX where the library writes (2, ...) reals"""
+    assert a.dtype == _COMPLEX and (a.flags.f_contiguous or a.ndim == 1)
     return a.ctypes.data_as(C.c_void_p)
 
 
@@ -218,6 +225,31 @@ class HotPath:
         power2 = np.zeros((self.n[0] // 2 + 1, self.n[1] // 2 + 1, max(kp.size, 1)) if ok else (1, 1, 1), order="F", dtype=REAL)
         self._chk(self.L.cales_spectra_planes(self.h, capi.FIELDS[name], int(kp.size), kp.ctypes.data_as(C.c_void_p), _p(power2)))
         return power2
+
+    # -- cross-spectra (include/cales_cospectra.h): this rank's sums, Fortran-ordered and complex; normalisation is the caller's (cales_amd/cospectra.py)
+    def cospectra_lines(self, name_a: str, name_b: str, idir: int, lsum: bool = True):
+        """cales_cospectra_lines: cross (nh, n3) complex = the sum over the lines of plane k of DFT(a) conj(DFT(b)), the two fields sampled at the same
+        index; nh = n/2 + 1 modes of the lines along x (idir = 1, this rank's rows; the caller adds the ranks) or y (idir = 2, one rank only). The real
+        part is the co-spectrum, the imaginary part the quadrature spectrum. With lsum also the complex sums of the lines' DFTs of either field,
+        (cross, lsum_a, lsum_b), what spectra_lines returns as lsum."""
+        idir = int(idir)
+        n = self.n[idir - 1] if idir in (1, 2) else 1      # (anything else: the library refuses it below, nothing is written)
+        nh = (n if n <= capi.SPECTRA_MAX_LINE else 0) // 2 + 1
+        # (a Fortran-ordered complex array IS the (2, ...) array of reals the library writes: real part, imaginary part)
+        cross = np.zeros((nh, self.n[2]), order="F", dtype=_COMPLEX)
+        la, lb = (np.zeros((nh, self.n[2]), order="F", dtype=_COMPLEX) for _ in range(2)) if lsum else (None, None)
+        self._chk(self.L.cales_cospectra_lines(self.h, capi.FIELDS[name_a], capi.FIELDS[name_b], idir, _pc(cross), _pc(la) if lsum else None, _pc(lb) if lsum else None))
+        cplx = lambda a: np.asfortranarray(a, dtype=np.complex128)
+        return (cplx(cross), cplx(la), cplx(lb)) if lsum else cplx(cross)
+
+    def cospectra_planes(self, name_a: str, name_b: str, kplanes) -> np.ndarray:
+        """cales_cospectra_planes (one rank only): cross2 (n1/2+1, n2/2+1, nplanes) complex = 2-D DFT(a) conj(2-D DFT(b)) of the planes `kplanes` (global
+        k, 1 ... ng(3); any order, repeats allowed), mode m along x, and along y the two modes ky = q and n2 - q added where they differ."""
+        kp = np.ascontiguousarray([int(k) for k in kplanes], dtype=np.int32)
+        ok = self.n[0] <= capi.SPECTRA_MAX_LINE and self.n[1] <= capi.SPECTRA_MAX_LINE
+        cross2 = np.zeros((self.n[0] // 2 + 1, self.n[1] // 2 + 1, max(kp.size, 1)) if ok else (1, 1, 1), order="F", dtype=_COMPLEX)
+        self._chk(self.L.cales_cospectra_planes(self.h, capi.FIELDS[name_a], capi.FIELDS[name_b], int(kp.size), kp.ctypes.data_as(C.c_void_p), _pc(cross2)))
+        return np.asfortranarray(cross2, dtype=np.complex128)
 
     # -- derived fields (include/cales_derived.h): `quantity` a name of capi.DERIVED (or its number); this rank's share, Fortran-ordered, interior cells only
     def derived_box(self, quantity, lo, hi, nskip=(1, 1, 1)) -> np.ndarray:

@@ -3,7 +3,8 @@
 Compiles every unit of this tree's cales_amd/csrc and of OTHER_CSRC_DIR (cales_amd/csrc INSIDE a full checkout of the commit to compare with, e.g. a
 git worktree: common.hpp includes ../../include/cales.h) to gfx950 assembly, FP64 and
 -DCALES_SINGLE, and compares per kernel symbol: the same set of symbols, the same instructions between a symbol's label and its .Lfunc_end (comments
-dropped, the function index of local labels removed: a refactor of the host side may change the ORDER in which the kernels are emitted) and the same
+and section directives dropped, the function index of local labels removed: a refactor of the host side may change the ORDER in which the kernels
+are emitted, and a kernel moved into a header as an inline function the SECTION it is emitted into) and the same
 .amdhsa_ resource lines. Exit status 1 when anything differs. No GPU needed."""
 import os, re, subprocess, sys, tempfile
 
@@ -26,6 +27,7 @@ def kernels(path):
         elif hsa is not None: res[hsa].append(t)
         elif m and cur is None: cur = m.group(1); body[cur] = []
         elif cur is not None and t.startswith(".Lfunc_end"): cur = None
+        elif cur is not None and t.startswith((".text", ".section")): pass      # (where the code goes, not what it is: a kernel defined inline in a header sits in a section of its own)
         elif cur is not None and t: body[cur].append(t)
     return {k: (body[k], res.get(k)) for k in body if k in res}      # (kernels only: device functions have no descriptor)
 
