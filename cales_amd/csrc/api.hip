@@ -512,7 +512,7 @@ int cales_spectra_planes(cales_ctx *c, int field, int nplanes, const int32_t *kp
   if (!c) return 1;
   ENTRY(c, op_spectra_planes(c, field, nplanes, kplanes, power2));
 }
-// include/cales_cospectra.h (k_cospectra.hip)
+// include/cales_cospectra.h (k_spectra.hip)
 int cales_cospectra_lines(cales_ctx *c, int field_a, int field_b, int idir, real *cross, real *lsum_a, real *lsum_b) {
   if (!c) return 1;
   ENTRY(c, op_cospectra_lines(c, field_a, field_b, idir, cross, lsum_a, lsum_b));

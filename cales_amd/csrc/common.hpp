@@ -519,7 +519,7 @@ int op_jpdf_planes(cales_ctx *c, int field_a, int field_b, int nbins, real lo_a,
 // include/cales_spectra.h (k_spectra.hip): power spectra of a field along x or y on every plane, and in chosen x-y planes; synchronous
 int op_spectra_lines(cales_ctx *c, int field, int idir, real *power, real *lsum);
 int op_spectra_planes(cales_ctx *c, int field, int nplanes, const int32_t *kplanes, real *power2);
-// include/cales_cospectra.h (k_cospectra.hip): cross-spectra of two fields sampled at the same index, along x or y on every plane and in chosen x-y planes; synchronous
+// include/cales_cospectra.h (k_spectra.hip, the two-field form of the above): cross-spectra of two fields sampled at the same index, along x or y on every plane and in chosen x-y planes; synchronous
 int op_cospectra_lines(cales_ctx *c, int field_a, int field_b, int idir, real *cross, real *lsum_a, real *lsum_b);
 int op_cospectra_planes(cales_ctx *c, int field_a, int field_b, int nplanes, const int32_t *kplanes, real *cross2);
 // include/cales_derived.h (k_derived.hip): vorticity, SijSij, WijWij and Q of the stored velocity, as a strided box for the host or into the interior of pp; synchronous

@@ -1,4 +1,4 @@
-// What the field read-outs share (api.hip: box reads; k_pdf.hip: histograms; k_spectra.hip: spectra): the host side of a call -- its temporary, the plane
+// What the field read-outs share (api.hip: box reads; k_pdf.hip: histograms; k_spectra.hip: spectra and cross-spectra): the host side of a call -- its temporary, the plane
 // list, the rows a block takes -- and, for the kernels, the 16-byte reader of a run of rows. The host part uses no HIP type: a plain host compiler
 // includes it (tests/readout_host.cpp), as it does lmf_pack.hpp. The field id of a call goes through field_ptr (common.hpp).
 #pragma once

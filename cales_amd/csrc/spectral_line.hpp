@@ -1,21 +1,48 @@
-// The line transform the spectra (k_spectra.hip) and the cross-spectra (k_cospectra.hip) share: the plan of a line, the Stockham stages that take it back and
-// forth between two LDS buffers, the compensated plain sum for a length with another prime factor, the Hermitian split of two real lines that rode in one
-// complex transform, the twiddle table, and the host's sizing of LDS and of the runs of rows. k_spectra.hip's head says how the pieces go together.
+// The line transform of the spectra and cross-spectra (k_spectra.hip): the launch geometry of its kernels, the plan of a line, the Stockham stages that take
+// it back and forth between two LDS buffers, the compensated plain sum for a length with another prime factor, the Hermitian split of two real lines that
+// rode in one complex transform, the twiddle table, and the host's sizing of LDS. k_spectra.hip's head says how the pieces go together.
 #pragma once
 #include "readout.hpp"
 #include "../../include/cales_spectra.h"
 
+// ------------------------------------------------------------------------------------------ launch geometry: plain integers, no HIP type -- a plain host
+// compiler includes this part (tests/readout_host.cpp). nf = 1 (power spectra) or 2 (cross-spectra) fields share the nl complex lines of a block;
+// real_size = sizeof(real)
+constexpr size_t SPEC_LDS_SOFT = 64 * 1024, SPEC_LDS_MAX = 128 * 1024;
+// rows: rows of a plane per block (x) | chunks: 16-byte chunks per row (x) or per tile row (y) | nl: complex lines in LDS | nh: n/2+1 | nb: blocks per plane
+struct SpecGeom { int rows, chunks, nl, nh, nb; };
+// complex lines of N points a block keeps in LDS (see the head of k_spectra.hip)
+inline int spec_nl(int N, size_t real_size) {
+  int nl = 8;
+  while (nl > 2 && 2 * (size_t)nl * N * 2 * real_size > SPEC_LDS_SOFT) nl /= 2;
+  return nl;
+}
+// k_spec_x: runs of rows per block (row_runs, readout.hpp) in whole batches of 2 nl / nf rows -- nl / nf complex lines of every field
+inline SpecGeom spec_geom_x(int n1, int n2, int nplanes, int nf, size_t real_size) {
+  const int nl = spec_nl(n1, real_size), realv = 16 / (int)real_size;
+  const RowRuns rr = row_runs(n2, nplanes, 1, 2 * nl / nf);
+  return SpecGeom{rr.rows, (n1 + realv - 1) / realv, nl, n1 / 2 + 1, rr.per_plane};
+}
+// k_spec_y: tiles of 2 nl / nf adjacent columns; a tile narrower than a chunk (nf = 2, nl = 2 in single precision) has none and is read by element
+inline SpecGeom spec_geom_y(int n1, int n2, int nf, size_t real_size) {
+  const int nl = spec_nl(n2, real_size), tile = 2 * nl / nf;
+  return SpecGeom{0, tile / (16 / (int)real_size), nl, n2 / 2 + 1, (n1 + tile - 1) / tile};
+}
+// k_spec_y2: nl / nf of the n1/2+1 mode columns per block
+inline SpecGeom spec_geom_y2(int n1, int n2, int nf, size_t real_size) {
+  const int nl = spec_nl(n2, real_size), cols = nl / nf;
+  return SpecGeom{0, 0, nl, n2 / 2 + 1, (n1 / 2 + 1 + cols - 1) / cols};
+}
+
+#ifdef __HIPCC__
 constexpr int SPEC_MAX_STAGES = 12;                                     // 2048 = 4^5 2: 6 stages; 2 3^6 = 1458: 7
 constexpr int SPEC_MPT = (CALES_SPECTRA_MAX_LINE / 2 + 1 + 255) / 256;  // modes a thread of a block of 256 owns at the cap: 5
-constexpr size_t SPEC_LDS_SOFT = 64 * 1024, SPEC_LDS_MAX = 128 * 1024;
 
 // n = radix(0) ... radix(nst-1), or direct. The radices are packed four bits each: a kernel argument indexed by the stage would be copied to scratch
 struct SpecPlan {
   int n, nst, direct; unsigned long long radices;
   __host__ __device__ inline int radix(int st) const { return (int)((radices >> (4 * st)) & 15ull); }
 };
-// rows: rows of a plane per block (x) | chunks: 16-byte chunks per row (x) or per tile row (y) | nl: complex lines in LDS | nh: n/2+1 | nb: blocks per plane
-struct SpecGeom { int rows, chunks, nl, nh, nb; };
 
 __host__ __device__ inline real2 cadd(real2 a, real2 b) { return make_real2(a.x + b.x, a.y + b.y); }
 __host__ __device__ inline real2 csub(real2 a, real2 b) { return make_real2(a.x - b.x, a.y - b.y); }
@@ -128,12 +155,6 @@ static SpecPlan spec_plan(int n) {
   if (m != 1) { pl.nst = 0; pl.direct = 1; pl.radices = 0ull; }
   return pl;
 }
-// complex lines of N points a block keeps in LDS (see the head of the file)
-static int spec_nl(int N) {
-  int nl = 8;
-  while (nl > 2 && 2 * (size_t)nl * N * sizeof(real2) > SPEC_LDS_SOFT) nl /= 2;
-  return nl;
-}
 static size_t spec_lds_bytes(int nl, int N) { return 2 * (size_t)nl * N * sizeof(real2); }
 // a kernel that asks for more than 64 KB of dynamic LDS has to say so once
 template <class K> static int spec_lds_attr(cales_ctx *c, K kernel, size_t lds) {
@@ -141,14 +162,8 @@ template <class K> static int spec_lds_attr(cales_ctx *c, K kernel, size_t lds) 
   if (lds > SPEC_LDS_SOFT) HIPCHK(c, hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SPEC_LDS_MAX));
   return 0;
 }
-// runs of rows per block of the x kernel (row_runs, readout.hpp): whole batches of 2 nl rows
-static void spec_x_geom(const cales_ctx *c, int nplanes, SpecGeom *sg) {
-  const int n1 = c->n[0];
-  sg->nl = spec_nl(n1); sg->nh = n1 / 2 + 1; sg->chunks = (n1 + REALV - 1) / REALV;
-  const RowRuns rr = row_runs(c->n[1], nplanes, 1, 2 * sg->nl);
-  sg->rows = rr.rows; sg->nb = rr.per_plane;
-}
 static int spec_line_ok(cales_ctx *c, int n, const char *who) {
   if (n > CALES_SPECTRA_MAX_LINE) { c->err = std::string(who) + ": a line of " + std::to_string(n) + " points is longer than CALES_SPECTRA_MAX_LINE = " + std::to_string(CALES_SPECTRA_MAX_LINE); return 1; }
   return 0;
 }
+#endif

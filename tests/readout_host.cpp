@@ -1,9 +1,12 @@
-// Stand-alone check of the host part of cales_amd/csrc/readout.hpp, built and run by tests/test_readout_host.py with the host compiler and
-// -fsanitize=address,undefined:
+// Stand-alone check of the host parts of cales_amd/csrc/readout.hpp and spectral_line.hpp, built and run by tests/test_readout_host.py with the host
+// compiler and -fsanitize=address,undefined:
 //   1. row_runs gives, for every input, the rows per block and the blocks per plane that the two functions it replaced gave -- pdf_geom (k_pdf.hip) and
 //      spec_x_geom (k_spectra.hip) as they stood before, restated below to the letter. n1, n2 = 1..2048, nplanes = 1..64, counters 1, 256, 4096, 16384 for
 //      the histograms; the three line counts of spec_nl (8, 4, 2) for the spectra. The histogram sweep is thinned: every n1 and n2 up to 64, and above
 //      that the values beside a step of one of the roundings (multiples of `want` for n2; powers of two and the divisors of the sample floor for n1);
+//   1b. the launch geometry of the spectra kernels (spectral_line.hpp: spec_geom_x, spec_geom_y, spec_geom_y2 of nf = 1, 2 fields) against the rules of
+//      the power spectra and of the cross-spectra as they stood when each had kernels of its own (k_spectra.hip, k_cospectra.hip), restated below to the
+//      letter: rows, chunks, nl, nh and nb for reals of 4 and 8 bytes; x over the thinned n1, n2 and every nplanes of 1, y and y2 over the thinned n1 and every n2;
 //   2. TempCarver: for every sequence of up to four parts of 4-, 8- and 16-byte elements with counts 0, 1, 3 and 7, every part starts on a 16-byte boundary, the
 //      parts do not overlap (each is filled with a tag of its own and read again) and the last ends inside the total, in reals of 4 and of 8 bytes;
 //   3. plane_list_check: the three refusals with `who` in front, and a list with repeats in any order accepted.
@@ -12,7 +15,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <vector>
-#include "readout.hpp"
+#include "spectral_line.hpp"
 
 static int fails = 0;
 #define CHECK(cond, ...) do { if (!(cond)) { if (fails++ < 20) { std::printf("FAILED %s: ", #cond); std::printf(__VA_ARGS__); std::printf("\n"); } } } while (0)
@@ -55,6 +58,73 @@ static long check_row_runs() {
       ++n;
     }
   }
+  return n;
+}
+
+// ---- 1b. the geometry of the spectra kernels as the two units had it: `real` a type of `rsz` bytes, REALV = 16 / rsz, sizeof(real2) = 2 rsz
+static int spec_nl_was(int N, size_t rsz) {
+  int nl = 8;
+  while (nl > 2 && 2 * (size_t)nl * N * (2 * rsz) > 64 * 1024) nl /= 2;
+  return nl;
+}
+static void spec_x_geom_was(int n1, int n2, int nplanes, size_t rsz, SpecGeom *sg) {
+  const int REALV = 16 / (int)rsz;
+  sg->nl = spec_nl_was(n1, rsz); sg->nh = n1 / 2 + 1; sg->chunks = (n1 + REALV - 1) / REALV;
+  const RowRuns rr = row_runs(n2, nplanes, 1, 2 * sg->nl);
+  sg->rows = rr.rows; sg->nb = rr.per_plane;
+}
+static void cospec_x_geom_was(int n1, int n2, int nplanes, size_t rsz, SpecGeom *sg) {
+  const int REALV = 16 / (int)rsz;
+  sg->nl = spec_nl_was(n1, rsz); sg->nh = n1 / 2 + 1; sg->chunks = (n1 + REALV - 1) / REALV;
+  const RowRuns rr = row_runs(n2, nplanes, 1, sg->nl);
+  sg->rows = rr.rows; sg->nb = rr.per_plane;
+}
+static SpecGeom spec_y_geom_was(int n1, int N, size_t rsz) {
+  const int REALV = 16 / (int)rsz;
+  SpecGeom sg; sg.nl = spec_nl_was(N, rsz); sg.nh = N / 2 + 1; sg.rows = 0; sg.chunks = 2 * sg.nl / REALV; sg.nb = (n1 + 2 * sg.nl - 1) / (2 * sg.nl);
+  return sg;
+}
+static SpecGeom cospec_y_geom_was(int n1, int N, size_t rsz) {
+  const int REALV = 16 / (int)rsz;
+  SpecGeom sg; sg.nl = spec_nl_was(N, rsz); sg.nh = N / 2 + 1; sg.rows = 0; sg.chunks = sg.nl / REALV; sg.nb = (n1 + sg.nl - 1) / sg.nl;
+  return sg;
+}
+static SpecGeom spec_y2_geom_was(int n1, int n2, size_t rsz) {
+  const int nhx = n1 / 2 + 1, nhy = n2 / 2 + 1;
+  SpecGeom sy; sy.nl = spec_nl_was(n2, rsz); sy.nh = nhy; sy.rows = 0; sy.chunks = 0; sy.nb = (nhx + sy.nl - 1) / sy.nl;
+  return sy;
+}
+static SpecGeom cospec_y2_geom_was(int n1, int n2, size_t rsz) {
+  const int nhx = n1 / 2 + 1, nhy = n2 / 2 + 1;
+  SpecGeom sy; sy.nl = spec_nl_was(n2, rsz); sy.nh = nhy; sy.rows = 0; sy.chunks = 0; sy.nb = (nhx + sy.nl / 2 - 1) / (sy.nl / 2);
+  return sy;
+}
+static void same_geom(const char *what, const SpecGeom &g, const SpecGeom &w, int n1, int n2, int nplanes, int nf, size_t rsz) {
+  CHECK(g.rows == w.rows && g.chunks == w.chunks && g.nl == w.nl && g.nh == w.nh && g.nb == w.nb, "%s n1 %d n2 %d nplanes %d nf %d reals of %zu: %d %d %d %d %d, was %d %d %d %d %d",
+        what, n1, n2, nplanes, nf, rsz, g.rows, g.chunks, g.nl, g.nh, g.nb, w.rows, w.chunks, w.nl, w.nh, w.nb);
+}
+static long check_spec_geom() {
+  long n = 0;
+  std::vector<int> n1s;      // every n1 up to 64, and above that the values beside a step of spec_nl (powers of two) and a few others
+  for (int n1 = 1; n1 <= 2048; ++n1) if (n1 <= 64 || (n1 & (n1 - 1)) == 0 || (n1 & (n1 + 1)) == 0 || ((n1 - 1) & (n1 - 2)) == 0 || n1 % 97 == 0) n1s.push_back(n1);
+  for (size_t rsz = 4; rsz <= 8; rsz += 4) for (int nf = 1; nf <= 2; ++nf) for (int n1 : n1s) {
+    for (int nplanes = 1; nplanes <= 64; ++nplanes) {
+      const int want = (2048 + nplanes - 1) / nplanes;
+      for (int n2 = 1; n2 <= 2048; ++n2) {
+        if (n2 > 64 && !near_step(n2, want) && n2 % 101) continue;
+        SpecGeom was; if (nf == 1) spec_x_geom_was(n1, n2, nplanes, rsz, &was); else cospec_x_geom_was(n1, n2, nplanes, rsz, &was);
+        same_geom("x", spec_geom_x(n1, n2, nplanes, nf, rsz), was, n1, n2, nplanes, nf, rsz);
+        ++n;
+      }
+    }
+    for (int n2 = 1; n2 <= 2048; ++n2) {
+      same_geom("y", spec_geom_y(n1, n2, nf, rsz), nf == 1 ? spec_y_geom_was(n1, n2, rsz) : cospec_y_geom_was(n1, n2, rsz), n1, n2, 0, nf, rsz);
+      same_geom("y2", spec_geom_y2(n1, n2, nf, rsz), nf == 1 ? spec_y2_geom_was(n1, n2, rsz) : cospec_y2_geom_was(n1, n2, rsz), n1, n2, 0, nf, rsz);
+      n += 2;
+    }
+  }
+  // the one geometry without chunks: two fields in single precision at nl = 2
+  CHECK(spec_geom_y(64, 2048, 2, 4).chunks == 0 && spec_geom_y(64, 1024, 2, 4).chunks == 1 && spec_geom_y(64, 2048, 1, 4).chunks == 1 && spec_geom_y(64, 2048, 2, 8).chunks == 1, "chunks of a y tile");
   return n;
 }
 
@@ -116,8 +186,8 @@ static int check_planes() {
 }
 
 int main() {
-  const long nr = check_row_runs(), nc = check_carver();
+  const long nr = check_row_runs(), ng = check_spec_geom(), nc = check_carver();
   const int np = check_planes();
-  std::printf("%ld row rules, %ld carved temporaries, %d plane lists checked, %d failures\n", nr, nc, np, fails);
+  std::printf("%ld row rules, %ld spectra geometries, %ld carved temporaries, %d plane lists checked, %d failures\n", nr, ng, nc, np, fails);
   return fails ? 1 : 0;
 }

@@ -102,10 +102,10 @@ def test_the_package_does_not_name_the_checker_side():
     seen = []
     for dirpath, _, files in os.walk(os.path.join(ROOT, "cales_amd")):
         for f in files:
-            if f in ("cospectra.py", "k_cospectra.hip", "spectral_line.hpp"):
+            if f in ("cospectra.py", "k_spectra.hip", "spectral_line.hpp"):
                 seen.append(f)
                 assert "oracle" not in open(os.path.join(dirpath, f)).read(), f
-    assert sorted(seen) == ["cospectra.py", "k_cospectra.hip", "spectral_line.hpp"]
+    assert sorted(seen) == ["cospectra.py", "k_spectra.hip", "spectral_line.hpp"]
 
 
 # ---------------------------------------------------------------------------------------------- the checker's own properties
@@ -200,7 +200,7 @@ def hermitian_split(Z):
 
 def paired_cross(a, b, mixed, real):
     """cross_x of the plane a, b (n1, n2) from complex transforms in precision `real` that carry two real rows each: rows r, r+1 of ONE field (the rule
-    of k_cospectra.hip), or -- mixed -- row r of a with row r of b"""
+    of k_spectra.hip), or -- mixed -- row r of a with row r of b"""
     ctype = np.complex64 if real == np.float32 else np.complex128
     a, b = a.astype(real), b.astype(real)
     if mixed:

@@ -1,11 +1,11 @@
-"""include/cales_cospectra.h on the device: cales_cospectra_lines and cales_cospectra_planes (k_cospectra.hip) by value against the numpy restatement of the
+"""include/cales_cospectra.h on the device: cales_cospectra_lines and cales_cospectra_planes (k_spectra.hip, the kernels k_spec_x<2, .>, k_spec_y<2>, k_spec_y2<2>) by value against the numpy restatement of the
 header's definitions (tests/test_cospectra_host.py: cospectra_ref) within the bounds derived there (cross_line_bound, cross_plane_bound, and
 line_bounds of tests/test_spectra_host.py for the line sums: forward error of an FFT and of a sequential sum, nothing tuned), and held to the rules every
 field-reading entry of the C-ABI keeps: the lazy eddy viscosity is materialised, a pending projection is completed, nothing is allocated, one profile
 scope per call, the same bits from run to run, a refused call leaves the context usable; on one rank, on y-slabs, in single precision, and through
 cales_amd/cospectra.py into the files. Every by-value case prints its largest error / bound ratio (pytest -s shows them).
 
-Launch geometry (k_cospectra.hip; the figures are those of the double-precision library): a block keeps nl complex lines of N points twice in LDS,
+Launch geometry (spec_geom_x / _y / _y2 of spectral_line.hpp with two fields; the figures are those of the double-precision library): a block keeps nl complex lines of N points twice in LDS,
 nl = 8 for N <= 256, 4 for N = 512, 2 above, HALF of them of either field: the x kernel takes runs of rows in batches of nl rows (of both fields), the y
 kernel tiles of nl columns, the y pass of the planes nl / 2 mode columns. The grids (tests/test_gpu_spectra.py says why no other shapes exist) and
 what they reach:

@@ -1,11 +1,11 @@
-"""include/cales_spectra.h on the device: cales_spectra_lines and cales_spectra_planes (k_spectra.hip) by value against the numpy restatement of the
+"""include/cales_spectra.h on the device: cales_spectra_lines and cales_spectra_planes (k_spectra.hip, the kernels k_spec_x<1, .>, k_spec_y<1>, k_spec_y2<1>) by value against the numpy restatement of the
 header's definitions (tests/test_spectra_host.py: spectra_ref) within the bounds derived there (line_bounds, plane_bound: forward error of an FFT and
 of a sequential sum, nothing tuned), and held to the rules every field-reading entry of the C-ABI keeps: the lazy eddy viscosity is materialised, a
 pending projection is completed, nothing is allocated, one profile scope per call, the same bits from run to run, a refused call leaves the context
 usable; on one rank, on y-slabs, in single precision, and through cales_amd/spectra.py into the files. Every by-value case prints its largest
 error / bound ratio (pytest -s shows them).
 
-Launch geometry (k_spectra.hip; the figures are those of the double-precision library): a block keeps nl complex lines of N points twice in LDS,
+Launch geometry (spec_geom_x / _y / _y2 of spectral_line.hpp with one field; the figures are those of the double-precision library): a block keeps nl complex lines of N points twice in LDS,
 nl = 8 for N <= 256, 4 for N = 512, 2 above; the x kernel takes runs of rows in batches of 2 nl rows, a run being a whole number of batches and
 the plane cut into about 2048 / nplanes runs; the y kernel takes tiles of 2 nl columns. The grids and what they reach:
   (96, 12, 10)   3 2^5 x line (stages 4, 4, 2, 3); y line 3 4; six row pairs in one batch; six tiles of 16 columns

@@ -16,8 +16,16 @@ picks the library.
 times the cross-spectra of include/cales_cospectra.h instead: cospectra_lines(u, w, 1), (u, w, 2) and cospectra_planes(u, w, 8 planes), each ALTERNATED
 call by call with the two power-spectrum calls it replaces (u, then w: the same reads and the same two transforms per row pair), and once each against
 the download of the two fields with numpy.fft on top. Per case one JSON line with the wall-clock medians and extremes of both, the device times of the
-profile scopes, and the cross call's device time over the read-once bound of two fields at the calibration's read rate."""
+profile scopes, and the cross call's device time over the read-once bound of two fields at the calibration's read rate.
+
+  python tools/specbench.py --digest [--grids 96x12x10,...]
+
+times nothing: for seeded fields u and w it prints per grid one JSON line per entry -- spectra_lines along x and y (with the line sums) and
+spectra_planes of u and of w, cospectra_lines along x and y (with the line sums) and cospectra_planes of the pairs (u, w) and (u, u), the planes given out
+of order with a repeat -- with the SHA-256 of the raw bytes of every array the entry returned. Two builds of the library whose lines are equal compute
+the same bits."""
 import argparse
+import hashlib
 import json
 import os
 import statistics
@@ -35,6 +43,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--tag", default="", help="copied into every line")
     ap.add_argument("--cross", action="store_true", help="the cross-spectra of two fields against two power-spectrum calls")
+    ap.add_argument("--digest", action="store_true", help="no timing: the SHA-256 of every array the spectra and cross-spectra entries return")
     a = ap.parse_args()
     import numpy as np
     from cales_amd import capi
@@ -46,6 +55,24 @@ def main():
         if a.tag:
             r["tag"] = a.tag
         print(json.dumps(r), flush=True)
+
+    def digest_mode(h, ng, base):
+        """--digest: see the head of the file"""
+        shape = tuple(n + 2 for n in ng)
+        rng = np.random.RandomState(1)
+        for name, mean in (("u", 3.), ("w", 0.)):
+            x = np.zeros(shape, order="F", dtype=R); x[...] = (mean + rng.standard_normal(shape)).astype(R)
+            h.set(name, x)
+        kp = [ng[2], 1, 1 + ng[2] // 2, 1]
+        sha = lambda out: [hashlib.sha256(np.asfortranarray(v).tobytes(order="F")).hexdigest() for v in (out if isinstance(out, tuple) else (out,))]
+        for f in ("u", "w"):
+            for idir in (1, 2):
+                emit(dict(base, entry=f"spectra_lines({f}, {idir})", sha256=sha(h.spectra_lines(f, idir))))
+            emit(dict(base, entry=f"spectra_planes({f}, {kp})", sha256=sha(h.spectra_planes(f, kp))))
+        for fa, fb in (("u", "w"), ("u", "u")):
+            for idir in (1, 2):
+                emit(dict(base, entry=f"cospectra_lines({fa}, {fb}, {idir})", sha256=sha(h.cospectra_lines(fa, fb, idir))))
+            emit(dict(base, entry=f"cospectra_planes({fa}, {fb}, {kp})", sha256=sha(h.cospectra_planes(fa, fb, kp))))
 
     def cross_mode(h, ng, cal, base):
         """--cross: see the head of the file"""
@@ -117,8 +144,11 @@ def main():
                 st = [v for k, v in h.profile_stats().items() if scope and k.startswith(scope)]
                 st = st[0] if st else (0, 0.)
                 return out, statistics.median(ts), min(ts), max(ts), (st[1] / st[0] if st[0] else None)
-            cal = h.calibrate(3)
             base = {"ng": ng, "lib": os.path.basename(capi.LIB_PATH)}
+            if a.digest:
+                digest_mode(h, ng, base)
+                continue
+            cal = h.calibrate(3)
             if a.cross:
                 cross_mode(h, ng, cal, base)
                 emit({"calibration": {k: (round(v, 1) if isinstance(v, float) else v) for k, v in cal.items()}, "ng": ng, "device": h.device_info()[0]})
